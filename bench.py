@@ -25,6 +25,7 @@ Beside the headline value the line carries (round 2):
   north_star_global_256 N > 1: BASELINE configs[2] / the north-star's strong-scaling point - global batch 256 split over
                         the N GPUs (32 tiles per GPU at N = 8), measured after the weak-scaling run
   --north-star          N = 1: batch 256 on one GPU (the north-star's single-GPU roofline point) as the headline
+  --dump-outputs DIR    the outputs of the last timed step as DIR/<name>.npy (seeded inputs: two builds compare 1:1)
 """
 import argparse
 import ctypes
@@ -454,6 +455,53 @@ def timed(step, batches, steps, sync, device):
     return dt, out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMENTS = 1 << 20      # larger arrays are dumped as a fixed seeded sample of this many elements
+
+
+def snapshot_outputs(out):
+    """The arrays the timed step handed its caller (`out` of its last timed step), copied to host memory NOW - a graph-replayed
+    step returns its static output buffers, which later steps overwrite.  {name: float32 array, float64 for float64 and
+    integer tensors}; a list / tuple entry becomes name_0, name_1, ...; None entries are left out."""
+    import numpy as np
+    import torch
+    flat = {}
+
+    def add(name, v):
+        if isinstance(v, torch.Tensor):
+            flat[name] = v
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                add("%s_%d" % (name, i), x)
+        elif isinstance(v, (int, float)) and not isinstance(v, bool):
+            flat[name] = torch.tensor(float(v), dtype=torch.float64)
+    for k in sorted(out):
+        add(k, out[k])
+    res = {}
+    for name, t in sorted(flat.items()):
+        t = t.detach()
+        t = t.to(torch.float64) if (t.dtype == torch.float64 or not t.is_floating_point()) else t.to(torch.float32)
+        t = t.reshape(-1) if t.numel() > DUMP_MAX_ELEMENTS else t
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMENTS].sort().values
+            t = t[idx.to(t.device)]
+        res[name] = t.cpu().numpy().copy()
+    total = sum(a.nbytes for a in res.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs exceed the %d-byte budget" % (total, DUMP_BUDGET_BYTES))
+    return res
+
+
+def write_outputs(arrays, d):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    print("bench: wrote %d outputs of the last timed step (%d bytes) to %s" % (len(arrays), sum(a.nbytes for a in arrays.values()), d),
+          file=sys.stderr, flush=True)
+
+
 def launch_replicas(n, argv, timeout_s=None):
     """`python bench.py --gpus N` without a launcher: start N replica processes of this script (rank r on GPU r), wait,
     return their exit code.  Runs before torch is imported, so the parent never initialises the GPU.  Attempt 1 replays
@@ -607,7 +655,15 @@ def main():
     ap.add_argument("--trunk-only", action="store_true",
                     help="only the north-star's literal quantity: student ResNet forward + backward alone at batch 256 (profiling aid)")
     ap.add_argument("--no-trunk-block", action="store_true", help="skip `north_star_b256.trunk_fwd_bwd`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (losses, logits, features, GK-Refine "
+                         "weights) as DIR/<name>.npy, float32 / float64, rank 0's; the inputs are seeded, so two builds can be "
+                         "compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.trunk_only:
+        ap.error("--dump-outputs covers the distillation step; --trunk-only has no step outputs to write")
     if args.north_star:
         args.batch = 256
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -681,6 +737,8 @@ def main():
             out = step.step(batches[i % 2], epoch=5)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            write_outputs(snapshot_outputs(out), args.dump_outputs)
         graph = graph and bool(getattr(step, "_want_graph", False))      # (a failed capture falls back to eager launches)
         Bv = batches[0][0][0].shape[0]
         if rank == 0:
@@ -740,6 +798,8 @@ def main():
     if args.eager and not args.no_kernel_timer:
         L.ph_prof_reset(); L.ph_prof_enable(1)
     dt, out = timed(step, batches, args.steps, sync, device)
+    if args.dump_outputs and rank == 0:
+        write_outputs(snapshot_outputs(out), args.dump_outputs)
     replayed = bool(getattr(step, "_want_graph", False))      # (False after a capture that failed and fell back to eager launches)
     L.ph_prof_enable(0)
     timer_region = "the timed region (eager)"

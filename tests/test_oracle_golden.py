@@ -25,6 +25,21 @@ def _close(a, b, tol=1e-5, rel=1e-4):
     assert err <= tol + rel * a.abs().max().item(), f"max err {err} (ref max {a.abs().max().item()})"
 
 
+def _close_or_truth(ref, truth, got, tol, rel, extra=0.0):
+    """After an Adam update: within tol + rel * max|ref| of the reference's fp32 golden, or no farther from the fp64 truth
+    (tests/golden/make_fp64_truth.py) than twice the reference's own distance to it (+ `extra`, the step's trajectory noise
+    scale for scalars) - the rule of tests/test_gpu_step.py::grad_row.  Adam's sign-like first steps amplify rounding, so two
+    fp32 runs on different CPUs (another BLAS kernel, another summation order) part by up to the reference's own 1e-2."""
+    a = np.asarray(ref, np.float64)
+    b = np.asarray(got.detach() if isinstance(got, torch.Tensor) else got, np.float64)
+    t = np.asarray(truth, np.float64)
+    e_ref = np.abs(a - b).max()
+    if e_ref <= tol + rel * np.abs(a).max():
+        return
+    e_tru, d_ref = np.abs(t - b).max(), np.abs(t - a).max()
+    assert e_tru <= 2.0 * d_ref + extra, f"golden err {e_ref} | truth err {e_tru} > 2 x golden-truth {d_ref} + {extra}"
+
+
 def test_student_forward_backward(golden_dir):
     g = _ld(golden_dir, "modules_b4_h64.npz")
     bt = synthetic_batch(int(g["B"]), int(g["H"]), seed=int(g["batch_seed"]))
@@ -132,8 +147,11 @@ def test_crd_loss_sample_kd(golden_dir, mode):
 
 @pytest.mark.parametrize("faithful", [False, True])
 def test_full_step_b16_h224(golden_dir, faithful):
-    """Three consecutive steps of train_test_path_multi_distill.py:249-330 vs the reference."""
+    """Three consecutive steps of train_test_path_multi_distill.py:249-330 vs the reference.  Step 0 and the updated weights
+    at every step against the reference's golden; the logits, losses, GK-Refine weights and bank rows of steps 1-2 (after
+    Adam updates) against the golden or, within the reference's own rounding distance, the fp64 truth (_close_or_truth)."""
     g = _ld(golden_dir, "step_b16_h224.npz")
+    t64 = _ld(golden_dir, "step_b16_h224_fp64.npz")
     torch.set_num_threads(8)
     orc = DistillOracle(default_opt(), seed=int(g["seed"]), n_data=int(g["n_data"]))
     nsteps = 3 if not faithful else 1
@@ -141,14 +159,21 @@ def test_full_step_b16_h224(golden_dir, faithful):
         bt = synthetic_batch(int(g["B"]), int(g["H"]), seed=100 + it)
         out = orc.step(bt, mid_ranks=[g["ranks"][2 * it], g["ranks"][2 * it + 1]], faithful=faithful)
         tol = 2e-5 * (1 + 20 * it)      # trajectories drift apart slowly (Adam amplifies rounding)
-        _close(g[f"logit_path{it}"], out["logit_path"], tol, 1e-4)
-        _close(g[f"ema_logit{it}"], out["ema_logit"], tol, 1e-4)
+        if it == 0:
+            check = lambda key, got, a, r, scalar=False: _close(g[key], got, a, r)      # noqa: E731
+        else:
+            # trajectory noise scale of this step: twice the reference's own worst vector distance to the truth
+            nz = 2 * max(np.abs(t64[f"{k}{it}"] - g[f"{k}{it}"]).max() for k in ("logit_path", "ema_logit", "path_feat"))
+            check = lambda key, got, a, r, scalar=False: _close_or_truth(g[key], t64[key], got, a, r, nz if scalar else 0.0)  # noqa: E731
+        check(f"logit_path{it}", out["logit_path"], tol, 1e-4)
+        check(f"ema_logit{it}", out["ema_logit"], tol, 1e-4)
         _close(g[f"fuse_logit{it}"], out["fuse_logit"], tol, 1e-4)
         for k in ("loss_cls", "loss"):
-            _close(g[f"{k}{it}"], out[k], tol * 10, 1e-4)
-        for k in ("loss_div1", "loss_div2", "loss_kd1", "loss_kd2"):
-            _close(g[f"{k}_{it}"], out[k], tol * 10, 1e-4)
-        _close(g[f"scale{it}"], out["scale"], 1e-3 * (1 + 5 * it), 1e-3)
+            check(f"{k}{it}", out[k], tol * 10, 1e-4, True)
+        _close(g[f"loss_div2_{it}"], out["loss_div2"], tol * 10, 1e-4)
+        for k in ("loss_div1", "loss_kd1", "loss_kd2"):
+            check(f"{k}_{it}", out[k], tol * 10, 1e-4, True)
+        check(f"scale{it}", out["scale"], 1e-3 * (1 + 5 * it), 1e-3, True)
         if it == 0:
             _close(g["g0_conv1"], out["grads"]["student.conv1.weight"], 1e-5, 2e-3)
             _close(g["g0_fc2_w"], out["grads"]["student.fc_new2.weight"], 1e-5, 2e-3)
@@ -157,8 +182,8 @@ def test_full_step_b16_h224(golden_dir, faithful):
         _close(g[f"p_fc2_{it}"], orc.student["fc_new2.weight"], 2e-4 if it else 2e-5, 0)
         _close(g[f"ema_fc2_{it}"], orc.ema["fc_new2.weight"], 2e-4, 0)
         _close(g[f"params0_{it}"], orc.crd[0].params, 1.0, 1e-4)
-        _close(g[f"bank0_v1_rows{it}"], orc.crd[0].memory_v1[bt["index"]], 1e-4)
-        _close(g[f"bank1_v2_rows{it}"], orc.crd[1].memory_v2[bt["index"]], 1e-4)
+        check(f"bank0_v1_rows{it}", orc.crd[0].memory_v1[bt["index"]], 1e-4, 1e-4)
+        check(f"bank1_v2_rows{it}", orc.crd[1].memory_v2[bt["index"]], 1e-4, 1e-4)
 
 
 def test_eval_mode_forward(golden_dir):
@@ -177,26 +202,37 @@ def test_eval_mode_forward(golden_dir):
     _close(g["t_fuse"], t[0]); _close(g["t_h_fuse"], t[4][2]); _close(g["t_pred"], t[5]); _close(g["t_pred_omic"], t[7])
 
 
-def _teacher_bwd_check(named_grads, dx_omic, loss, g, tag, rtol):
-    """Compare gradients {name: tensor} with the (partly sampled) fixture entries of one tag."""
+def _teacher_bwd_check(named_grads, dx_omic, loss, g, tag, rtol, truth=None):
+    """Compare gradients {name: tensor} with the (partly sampled) fixture entries of one tag.  truth: {name: the same
+    gradient from the oracle in fp64}, which must meet the fixture at the tolerance itself; the fp32 gradients may then sit
+    that far again - the fixture's own rounding, which a CPU with another summation order does not reproduce."""
     import numpy as np
     assert abs(float(loss) - float(g[f"{tag}_loss"])) <= 1e-4 * abs(float(g[f"{tag}_loss"]))
     ref = g[f"{tag}_dx_omic"]
     assert np.abs(dx_omic - ref).max() <= rtol * max(np.abs(ref).max(), 1e-6)
+
+    def lim(name, ref, sample):
+        tol = rtol * np.abs(ref).max() + 2e-6
+        if truth is None:
+            return tol
+        d = np.abs(sample(truth[name]) - ref).max()
+        assert d <= tol, name + " (fp64)"
+        return tol + d
     n = 0
     for key in g.files:
         if key.startswith(f"{tag}_g_"):
             name = key[len(tag) + 3:]
             got, ref = named_grads[name], g[key]
             # (a Linear bias in front of a BatchNorm has a mathematically zero gradient: 1e-8-level rounding noise)
-            assert np.abs(got - ref).max() <= rtol * np.abs(ref).max() + 2e-6, name
+            assert np.abs(got - ref).max() <= lim(name, ref, lambda t: t), name
             n += 1
         elif key.startswith(f"{tag}_gs_"):
             name = key[len(tag) + 4:]
             flat = named_grads[name].reshape(-1)
             stride = flat.size // 4096
             ref = g[key]
-            assert np.abs(flat[::stride][:4096] - ref).max() <= rtol * np.abs(ref).max() + 2e-6, name
+            tol = lim(name, ref, lambda t: t.reshape(-1)[::stride][:4096])
+            assert np.abs(flat[::stride][:4096] - ref).max() <= tol, name
             nrm = float(g[f"{tag}_gn_{name}"])
             assert abs(float(np.linalg.norm(flat.astype(np.float64))) - nrm) <= rtol * nrm, name
             n += 1
@@ -215,17 +251,24 @@ def test_teacher_backward_vs_reference_golden(golden_dir):
     from oracle.step import synthetic_batch
     g = np.load(os.path.join(golden_dir, "teacher_bwd_b4_h64.npz"))
     bt = synthetic_batch(4, 64, seed=7)
-    for tag, cut in (("cut", True), ("nocut", False)):
-        sd = {k: (v.clone().requires_grad_(True) if (v.is_floating_point() and "running_" not in k) else v.clone())
+
+    def run(cut, dt):
+        sd = {k: (v.to(dt, copy=True).requires_grad_(True) if (v.is_floating_point() and "running_" not in k) else
+                  v.to(dt, copy=True) if v.is_floating_point() else v.clone())
               for k, v in W.make_state_dict(W.teacher_shapes(320), 3).items()}
-        x_omic = bt["x_omic"].clone().requires_grad_(True)
-        out = pathomic_forward(bt["x_path"], x_omic, sd, cut_fuse_grad=cut)
+        x_omic = bt["x_omic"].to(dt, copy=True).requires_grad_(True)
+        out = pathomic_forward(bt["x_path"].to(dt), x_omic, sd, cut_fuse_grad=cut)
         pred, pred_path, pred_omic = out[5], out[6], out[7]
         loss = F.nll_loss(pred_path, bt["grade"]) + F.nll_loss(pred_omic, bt["grade"]) + F.nll_loss(pred, bt["grade"])
         names = [k for k, v in sd.items() if v.is_floating_point() and v.requires_grad]
         grads = torch.autograd.grad(loss, [sd[k] for k in names] + [x_omic], allow_unused=True)
         named = {k: (gr.numpy() if gr is not None else np.zeros(tuple(sd[k].shape), np.float32)) for k, gr in zip(names, grads[:-1])}
-        _teacher_bwd_check(named, grads[-1].numpy(), loss.item(), g, tag, 2e-4)
+        return named, grads[-1].numpy(), loss.item()
+
+    for tag, cut in (("cut", True), ("nocut", False)):
+        named, dx_omic, loss = run(cut, torch.float32)
+        truth, _, _ = run(cut, torch.float64)
+        _teacher_bwd_check(named, dx_omic, loss, g, tag, 2e-4, truth)
 
 
 def load_midstate(g, orc):
