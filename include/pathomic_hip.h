@@ -373,6 +373,35 @@ int ph_conv2d_wgrad(const void* x, const void* dy, float* dw_oihw, int B, int Ci
  * dtheta may be NULL.  B <= 4096. */
 int ph_cox_loss_grad(const float* theta, const float* survtime, const float* censor, float* loss, float* dtheta, int B,
                      ph_stream_t stream);
+/* The survival task of the stage-1 teacher (MICCAI-2022/train_test_MT.py:149-152,180-203,340-458 with --task surv;
+ * csrc/surv.hip).
+ * ph_sigmoid_range_fwd: pred = sigmoid(hazard) * range[0] + shift[0] (networks_new.py:236-237,327-328, resnets.py:252-253),
+ * sigma = sigmoid(hazard) kept for the backward; range / shift point at the module's output_range / output_shift
+ * parameters in device memory.  ph_sigmoid_range_bwd: dhazard = dpred * range[0] * sigma * (1 - sigma).
+ * ph_ema_update_dev: ema = hyper[3] * ema + hyper[4] * p (the EMA rate record of ph_adam_ema_step_dev) for the parameters
+ * the optimiser leaves alone (output_range / output_shift: update_ema_variables, train_test_MT.py:34-38, covers them).
+ * ph_surv_stage1_loss_grad: one workgroup, B <= 4096 (else PH_EINVAL).  terms[9] = cox_fuse, cox_path, cox_omic (the Cox
+ * loss of utils.py:361-376 on pred, pred_path, pred_omic; one shared risk-set pass, S_i = sum_j [t_j >= t_i] exp(theta_j)),
+ * kd_fuse, kd_path, kd_omic (MSE consistency against the EMA predictions, CL_utils/KD_losses.py:20-22, combined for
+ * num_teachers 1 / 2 / 3 as train_test_MT.py:180-201; 0 = pred_distill off, the ema pointers may then be NULL),
+ * loss_cox = cox sum, loss_pred_KD = kd_weight * kd sum, and total = lambda_cox * loss_cox + loss_pred_KD.
+ * dgrad [3][B] = d total / d (pred, pred_path, pred_omic), or
+ * NULL for the forward-only evaluation loss.
+ * ph_cindex_counts: lifelines' concordance_index(t, -h, e) rule (utils.py:424-425) for nvec in 1..3 risk vectors h0..h2
+ * against one (survtime, event) pair: counts[v*3 + {0,1,2}] = comparable, concordant, tied pairs (exact 64-bit integers,
+ * independent of row order).  Pair (i, j) is comparable iff e_i = 1 and (t_i < t_j, or t_i == t_j and e_j = 0);
+ * concordant iff h_i > h_j, tied iff h_i == h_j.  2 <= N <= 1048576 (else PH_EINVAL). */
+int ph_sigmoid_range_fwd(const float* hazard, const float* range, const float* shift, float* pred, float* sigma, int n,
+                         ph_stream_t stream);
+int ph_sigmoid_range_bwd(const float* dpred, const float* sigma, const float* range, float* dhazard, int n,
+                         ph_stream_t stream);
+int ph_ema_update_dev(float* ema, const float* p, size_t n, const float* hyper, ph_stream_t stream);
+int ph_surv_stage1_loss_grad(const float* pred, const float* pred_path, const float* pred_omic, const float* ema_pred,
+                             const float* ema_pred_path, const float* ema_pred_omic, const float* survtime,
+                             const float* censor, int B, int num_teachers, float lambda_cox, float kd_weight, float* terms,
+                             float* dgrad, ph_stream_t stream);
+int ph_cindex_counts(const float* survtime, const float* event, const float* h0, const float* h1, const float* h2, int nvec,
+                     int N, int64_t* counts, ph_stream_t stream);
 size_t ph_pkt_workspace_bytes(int B, int D);
 int ph_pkt_loss_grad(const float* f_s, const float* f_t, float* loss, float* dx, int B, int D, void* workspace,
                      ph_stream_t stream);

@@ -1,0 +1,300 @@
+// The survival (Cox) task of the stage-1 mean-teacher trainer (MICCAI-2022/train_test_MT.py:149-152,180-203 with
+// --task surv): the sigmoid-range head of the three networks (networks_new.py:236-237,327-328, resnets.py:252-253), the
+// fused per-step survival loss (three Cox partial likelihoods sharing one risk-set pass + the MSE consistency terms of
+// CL_utils/KD_losses.py:20-22) and the concordance counts behind the evaluation's C-index (utils.py:424-425).
+#include "ph_common.h"
+#include "ph_kernels.h"
+
+namespace {
+
+constexpr int SURV_MAX_B = 4096;        // one workgroup, everything in LDS (as cox_kernel in zoo.hip)
+constexpr int SURV_THREADS = 1024;
+constexpr int CIDX_TILE = 256;          // rows per workgroup and j-tile length of the concordance counts
+constexpr int CIDX_MAX_N = 1 << 20;
+
+// fixed-tree block reduction; every thread gets the total.  red: >= blockDim.x floats
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  const int tid = threadIdx.x, n = blockDim.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int o = n >> 1; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  const float t = red[0];
+  __syncthreads();
+  return t;
+}
+
+// pred = sigmoid(h) * range[0] + shift[0]; sigma kept for the backward.  range / shift are the module's parameters
+// (device memory: the EMA update and load_state_dict change them like any other parameter).
+__global__ void sigmoid_range_fwd_kernel(const float* __restrict__ h, const float* __restrict__ range,
+                                         const float* __restrict__ shift, float* __restrict__ pred,
+                                         float* __restrict__ sigma, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float s = 1.f / (1.f + expf(-h[i]));
+  sigma[i] = s;
+  pred[i] = s * range[0] + shift[0];
+}
+
+__global__ void sigmoid_range_bwd_kernel(const float* __restrict__ dpred, const float* __restrict__ sigma,
+                                         const float* __restrict__ range, float* __restrict__ dh, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float s = sigma[i];
+  dh[i] = dpred[i] * range[0] * s * (1.f - s);
+}
+
+// One workgroup.  For each student prediction k (0 fuse, 1 path, 2 omic):
+//   S_ki = sum_j [t_j >= t_i] exp(p_kj);  cox_k = -mean_i c_i (p_ki - log S_ki)           (utils.py:361-376)
+//   d cox_k / d p_kl = -(c_l - exp(p_kl) sum_i c_i [t_l >= t_i] / S_ki) / B
+// The three risk sums share one pass over t (LDS).  The per-prediction summation order is cox_kernel's, so each Cox
+// term is bitwise the one ph_cox_loss_grad computes.  KD terms: mse(a, b) = mean_i (a_i - b_i)^2 over the EMA
+// teacher's predictions q (constants), combined as train_test_MT.py:180-201 for nt = 1 / 2 / 3 (nt = 0: off).
+__global__ __launch_bounds__(SURV_THREADS) void surv_stage1_kernel(
+    const float* __restrict__ p0, const float* __restrict__ p1, const float* __restrict__ p2, const float* __restrict__ q0,
+    const float* __restrict__ q1, const float* __restrict__ q2, const float* __restrict__ t, const float* __restrict__ c,
+    int B, int nt, float lambda_cox, float kd_weight, float* __restrict__ terms, float* __restrict__ dgrad) {
+  __shared__ float tt[SURV_MAX_B];
+  __shared__ float ex[3][SURV_MAX_B];
+  __shared__ float w[3][SURV_MAX_B];      // c_i / S_ki
+  __shared__ float red[SURV_THREADS];
+  const int tid = threadIdx.x;
+  const float* p[3] = {p0, p1, p2};
+  for (int i = tid; i < B; i += SURV_THREADS) {
+    tt[i] = t[i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ex[k][i] = expf(p[k][i]);
+  }
+  __syncthreads();
+  float l[3] = {0.f, 0.f, 0.f};
+  for (int i = tid; i < B; i += SURV_THREADS) {
+    float s[3] = {0.f, 0.f, 0.f};
+    const float ti = tt[i];
+    for (int j = 0; j < B; ++j) {
+      const bool r = tt[j] >= ti;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s[k] += r ? ex[k][j] : 0.f;
+    }
+    const float ci = c[i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      w[k][i] = ci / s[k];
+      l[k] += (p[k][i] - logf(s[k])) * ci;
+    }
+  }
+  float cox[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) cox[k] = -block_sum(l[k], red) / (float)B;     // (block_sum ends with a barrier: w is complete)
+  // consistency terms; m[a][b] = mse(p_a, q_b) for the pairs the teacher count uses
+  float kd[3] = {0.f, 0.f, 0.f};
+  if (nt > 0) {
+    const float* q[3] = {q0, q1, q2};
+    float part[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) part[a][b] = 0.f;
+    for (int i = tid; i < B; i += SURV_THREADS) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          const float d = p[a][i] - q[b][i];
+          part[a][b] += d * d;
+        }
+    }
+    float m[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) m[a][b] = 0.f;
+    m[0][0] = block_sum(part[0][0], red) / (float)B;
+    m[1][1] = block_sum(part[1][1], red) / (float)B;
+    m[2][2] = block_sum(part[2][2], red) / (float)B;
+    if (nt >= 2) {
+      m[1][0] = block_sum(part[1][0], red) / (float)B;
+      m[2][0] = block_sum(part[2][0], red) / (float)B;
+    }
+    if (nt == 3) {
+      m[1][2] = block_sum(part[1][2], red) / (float)B;
+      m[2][1] = block_sum(part[2][1], red) / (float)B;
+    }
+    kd[0] = m[0][0];
+    if (nt == 1) {
+      kd[1] = m[1][1];
+      kd[2] = m[2][2];
+    } else if (nt == 2) {
+      kd[1] = (m[1][1] + m[1][0]) / 2.f;
+      kd[2] = (m[2][2] + m[2][0]) / 2.f;
+    } else {
+      kd[1] = (m[1][1] + m[1][0] + m[1][2]) / 3.f;
+      kd[2] = (m[2][2] + m[2][0] + m[2][1]) / 3.f;
+    }
+  }
+  if (tid == 0) {
+    terms[0] = cox[0]; terms[1] = cox[1]; terms[2] = cox[2];
+    terms[3] = kd[0]; terms[4] = kd[1]; terms[5] = kd[2];
+    // train_test_MT.py:152 loss_cox = path + omic + fuse, :203 loss_pred_KD = KD_weight * (fuse + path + omic), :217
+    const float lc = (cox[1] + cox[2]) + cox[0], lk = kd_weight * ((kd[0] + kd[1]) + kd[2]);
+    terms[6] = lc;
+    terms[7] = lk;
+    terms[8] = lambda_cox * lc + lk;
+  }
+  if (!dgrad) return;
+  const float inv_b = 1.f / (float)B;
+  const float* q[3] = {q0, q1, q2};
+  for (int l0 = tid; l0 < B; l0 += SURV_THREADS) {
+    float a[3] = {0.f, 0.f, 0.f};
+    const float tl = tt[l0];
+    for (int i = 0; i < B; ++i) {
+      const bool r = tl >= tt[i];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) a[k] += r ? w[k][i] : 0.f;
+    }
+    const float cl = c[l0];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      float g = lambda_cox * (-(cl - ex[k][l0] * a[k]) * inv_b);
+      if (nt > 0) {
+        const float pk = p[k][l0];
+        float dk;
+        if (k == 0 || nt == 1) {
+          dk = 2.f * (pk - q[k][l0]) * inv_b;
+        } else {
+          const int o = 3 - k;      // the other modality's teacher
+          float s = (pk - q[k][l0]) + (pk - q[0][l0]);
+          if (nt == 3) s += pk - q[o][l0];
+          dk = 2.f * s * inv_b / (float)nt;
+        }
+        g += kd_weight * dk;
+      }
+      dgrad[(size_t)k * B + l0] = g;
+    }
+  }
+}
+
+// ema = hyper[3] * ema + hyper[4] * p over parameters the optimiser does not update (requires_grad False: output_range /
+// output_shift), with the EMA rate the fused Adam step reads (update_ema_variables, train_test_MT.py:34-38, loops over
+// every parameter)
+__global__ void ema_update_dev_kernel(float* __restrict__ ema, const float* __restrict__ p, size_t n,
+                                      const float* __restrict__ hyper) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) ema[i] = hyper[3] * ema[i] + hyper[4] * p[i];
+}
+
+// Concordance counts (lifelines' concordance_index(t, -h, e) rule).  Pair (i, j) is comparable iff e_i = 1 and
+// (t_i < t_j, or t_i == t_j and e_j = 0); concordant iff h_i > h_j; tied iff h_i == h_j.  Thread = row i, the j rows
+// stream through LDS in tiles.  Integer counts, added with 64-bit integer atomics: exact, so the result does not depend
+// on the order of the rows or of the additions.  counts[v*3 + {0,1,2}] = comparable, concordant, tied.
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(CIDX_TILE) void cindex_counts_kernel(const float* __restrict__ t, const float* __restrict__ e,
+                                                                  const float* __restrict__ h0, const float* __restrict__ h1,
+                                                                  const float* __restrict__ h2, int nvec, int N,
+                                                                  unsigned long long* __restrict__ counts) {
+  __shared__ float st[CIDX_TILE], se[CIDX_TILE], sh[3][CIDX_TILE];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * CIDX_TILE + tid;
+  const float* hv[3] = {h0, h1, h2};
+  const bool live = i < N;
+  const float ti = live ? t[i] : 0.f;
+  const bool ev = live && e[i] > 0.5f;
+  float hi[3] = {0.f, 0.f, 0.f};
+  for (int v = 0; v < nvec; ++v) hi[v] = live ? hv[v][i] : 0.f;
+  unsigned int comp = 0, conc[3] = {0u, 0u, 0u}, tie[3] = {0u, 0u, 0u};
+  for (int j0 = 0; j0 < N; j0 += CIDX_TILE) {
+    const int j = j0 + tid;
+    __syncthreads();
+    if (j < N) {
+      st[tid] = t[j];
+      se[tid] = e[j];
+      for (int v = 0; v < nvec; ++v) sh[v][tid] = hv[v][j];
+    }
+    __syncthreads();
+    const int nj = min(CIDX_TILE, N - j0);
+    if (!ev) continue;       // (no early exit: every thread takes part in the barriers)
+    for (int jj = 0; jj < nj; ++jj) {
+      const float tj = st[jj];
+      const bool cmp = ti < tj || (ti == tj && se[jj] <= 0.5f);
+      if (!cmp) continue;
+      ++comp;
+      for (int v = 0; v < nvec; ++v) {
+        const float hj = sh[v][jj];
+        conc[v] += hi[v] > hj;
+        tie[v] += hi[v] == hj;
+      }
+    }
+  }
+  const int lane = tid & 63;
+  unsigned long long r = wave_sum_u64(comp);
+  if (lane == 0 && r) {
+    for (int v = 0; v < nvec; ++v) atomicAdd(&counts[v * 3 + 0], r);
+  }
+  for (int v = 0; v < nvec; ++v) {
+    const unsigned long long a = wave_sum_u64(conc[v]), b = wave_sum_u64(tie[v]);
+    if (lane == 0) {
+      if (a) atomicAdd(&counts[v * 3 + 1], a);
+      if (b) atomicAdd(&counts[v * 3 + 2], b);
+    }
+  }
+}
+
+}  // namespace
+
+#include "pathomic_hip.h"
+
+extern "C" {
+
+int ph_sigmoid_range_fwd(const float* hazard, const float* range, const float* shift, float* pred, float* sigma, int n,
+                         hipStream_t st) {
+  if (!hazard || !range || !shift || !pred || !sigma || n < 1) return PH_EINVAL;
+  hipLaunchKernelGGL(sigmoid_range_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, st, hazard, range, shift, pred, sigma, n);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_sigmoid_range_bwd(const float* dpred, const float* sigma, const float* range, float* dhazard, int n, hipStream_t st) {
+  if (!dpred || !sigma || !range || !dhazard || n < 1) return PH_EINVAL;
+  hipLaunchKernelGGL(sigmoid_range_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dpred, sigma, range, dhazard, n);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_ema_update_dev(float* ema, const float* p, size_t n, const float* hyper, hipStream_t st) {
+  if (!ema || !p || !hyper || n < 1) return PH_EINVAL;
+  hipLaunchKernelGGL(ema_update_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ema, p, n, hyper);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_surv_stage1_loss_grad(const float* pred, const float* pred_path, const float* pred_omic, const float* ema_pred,
+                             const float* ema_pred_path, const float* ema_pred_omic, const float* survtime,
+                             const float* censor, int B, int num_teachers, float lambda_cox, float kd_weight, float* terms,
+                             float* dgrad, hipStream_t st) {
+  if (!pred || !pred_path || !pred_omic || !survtime || !censor || !terms || B < 1 || B > SURV_MAX_B) return PH_EINVAL;
+  if (num_teachers < 0 || num_teachers > 3) return PH_EINVAL;
+  if (num_teachers > 0 && (!ema_pred || !ema_pred_path || !ema_pred_omic)) return PH_EINVAL;
+  hipLaunchKernelGGL(surv_stage1_kernel, dim3(1), dim3(SURV_THREADS), 0, st, pred, pred_path, pred_omic, ema_pred,
+                     ema_pred_path, ema_pred_omic, survtime, censor, B, num_teachers, lambda_cox, kd_weight, terms, dgrad);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_cindex_counts(const float* survtime, const float* event, const float* h0, const float* h1, const float* h2, int nvec,
+                     int N, int64_t* counts, hipStream_t st) {
+  if (!survtime || !event || !h0 || !counts || nvec < 1 || nvec > 3 || N < 2 || N > CIDX_MAX_N) return PH_EINVAL;
+  if ((nvec > 1 && !h1) || (nvec > 2 && !h2)) return PH_EINVAL;
+  if (hipMemsetAsync(counts, 0, sizeof(int64_t) * 3 * nvec, st) != hipSuccess) return PH_ELAUNCH;
+  hipLaunchKernelGGL(cindex_counts_kernel, dim3((N + CIDX_TILE - 1) / CIDX_TILE), dim3(CIDX_TILE), 0, st, survtime, event,
+                     h0, h1, h2, nvec, N, reinterpret_cast<unsigned long long*>(counts));
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+}  // extern "C"

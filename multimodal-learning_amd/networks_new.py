@@ -160,9 +160,7 @@ class MaxNet(nn.Module):
         out = ops.linear_fwd(features, self.classifier[0].weight, self.classifier[0].bias)
         pred = None
         if self.act is not None:
-            if not isinstance(self.act, nn.LogSoftmax):
-                raise NotImplementedError("only act_type 'LSM' is on the hot path")
-            pred = ops.LogSoftmaxFn.apply(out)
+            pred = ops.apply_act(self.act, out, self)
         return features, out, pred, None
 
 
@@ -181,9 +179,7 @@ def _maxnet_forward_autograd(self, x):
     out = ops.LinearFn.apply(features, self.classifier[0].weight, self.classifier[0].bias)
     pred = None
     if self.act is not None:
-        if not isinstance(self.act, nn.LogSoftmax):
-            raise NotImplementedError("only act_type 'LSM' is on the hot path")
-        pred = ops.LogSoftmaxFn.apply(out)
+        pred = ops.apply_act(self.act, out, self)
     return features, out, pred, None
 
 
@@ -233,9 +229,7 @@ class PathomicNet(nn.Module):
         hazard = ops.LinearFn.apply(features, self.classifier[0].weight, self.classifier[0].bias)
         pred = None
         if self.act is not None:
-            if not isinstance(self.act, nn.LogSoftmax):
-                raise NotImplementedError("only act_type 'LSM' is on the hot path")
-            pred = ops.LogSoftmaxFn.apply(hazard)
+            pred = ops.apply_act(self.act, hazard, self)
         logits = [hazard_path, hazard_omic, hazard]
         return features, path_vec, omic_vec, path_vec_f3, logits, pred, pred_path, pred_omic, None, path_grads, omic_grads
 

@@ -374,6 +374,98 @@ class KLFn(torch.autograd.Function):
         return d, None, None, None
 
 
+class SigmoidRangeFn(torch.autograd.Function):
+    """The survival head (networks_new.py:236-237,327-328, resnets.py:252-253): sigmoid(hazard) * output_range +
+    output_shift, the two read from the module's parameters in device memory (they carry no gradient: requires_grad=False
+    in the reference)."""
+
+    @staticmethod
+    def forward(ctx, hazard, output_range, output_shift):
+        h = _f32(hazard)
+        r, s = _f32(output_range.detach()), _f32(output_shift.detach())
+        pred = torch.empty_like(h)
+        sigma = torch.empty_like(h)
+        check(lib().ph_sigmoid_range_fwd(ptr(h), ptr(r), ptr(s), ptr(pred), ptr(sigma), h.numel(), stream()),
+              "ph_sigmoid_range_fwd")
+        ctx.save_for_backward(sigma, r)
+        return pred
+
+    @staticmethod
+    def backward(ctx, g):
+        sigma, r = ctx.saved_tensors
+        g = _f32(g)
+        dh = torch.empty_like(sigma)
+        check(lib().ph_sigmoid_range_bwd(ptr(g), ptr(sigma), ptr(r), ptr(dh), sigma.numel(), stream()), "ph_sigmoid_range_bwd")
+        return dh, None, None
+
+
+def apply_act(act, hazard, owner):
+    """The head of the three networks: log-softmax (grading) or the sigmoid range head of the survival task, whose range and
+    shift are `owner`'s output_range / output_shift parameters.  Any other activation raises."""
+    if isinstance(act, torch.nn.LogSoftmax):
+        return LogSoftmaxFn.apply(hazard)
+    if isinstance(act, torch.nn.Sigmoid):
+        return SigmoidRangeFn.apply(hazard, owner.output_range, owner.output_shift)
+    raise NotImplementedError("act %r: the log-softmax (grading) and sigmoid-range (survival) heads are built"
+                              % type(act).__name__)
+
+
+class SurvStage1LossFn(torch.autograd.Function):
+    """The survival block of the stage-1 teacher step in one launch (ph_surv_stage1_loss_grad): the three Cox terms
+    (train_test_MT.py:149-152) and the MSE consistency terms (:180-201, KD_losses.py:20-22).  Returns (total, terms[6]) with
+    total = lambda_cox * (cox terms) + kd_weight * (kd terms); the gradient of `total` is computed in the forward, the
+    backward scales it by the incoming gradient (as utils._CoxFn).  num_teachers 0: no consistency terms.  `terms`: cox_fuse,
+    cox_path, cox_omic, kd_fuse, kd_path, kd_omic, loss_cox (their sum), loss_pred_KD (kd_weight x the kd sum)."""
+
+    @staticmethod
+    def forward(ctx, pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic, survtime, censor, num_teachers,
+                lambda_cox, kd_weight):
+        ps = [_f32(p).reshape(-1) for p in (pred, pred_path, pred_omic)]
+        qs = [None if q is None else _f32(q.detach()).reshape(-1) for q in (ema_pred, ema_pred_path, ema_pred_omic)]
+        B = ps[0].shape[0]
+        t, c = _f32(survtime).reshape(-1), _f32(censor).reshape(-1)
+        out = torch.empty(9, device=ps[0].device, dtype=torch.float32)
+        d = torch.empty(3, B, device=ps[0].device, dtype=torch.float32)
+        check(lib().ph_surv_stage1_loss_grad(ptr(ps[0]), ptr(ps[1]), ptr(ps[2]), ptr(qs[0]), ptr(qs[1]), ptr(qs[2]), ptr(t),
+                                             ptr(c), B, int(num_teachers), float(lambda_cox), float(kd_weight), ptr(out),
+                                             ptr(d), stream()), "ph_surv_stage1_loss_grad")
+        ctx.save_for_backward(d)
+        ctx.shapes = (pred.shape, pred_path.shape, pred_omic.shape)
+        terms = out[:8]
+        ctx.mark_non_differentiable(terms)
+        return out[8], terms
+
+    @staticmethod
+    def backward(ctx, g, g_terms):
+        d, = ctx.saved_tensors
+        return ((d[0] * g).reshape(ctx.shapes[0]), (d[1] * g).reshape(ctx.shapes[1]), (d[2] * g).reshape(ctx.shapes[2]),
+                None, None, None, None, None, None, None, None)
+
+
+def surv_loss_terms(pred, pred_path, pred_omic, survtime, censor):
+    """Forward-only Cox terms (fuse, path, omic) of one batch: the evaluation's per-batch loss, as a [3] device tensor."""
+    ps = [_f32(p).reshape(-1) for p in (pred, pred_path, pred_omic)]
+    t, c = _f32(survtime).reshape(-1), _f32(censor).reshape(-1)
+    out = torch.empty(9, device=ps[0].device, dtype=torch.float32)
+    check(lib().ph_surv_stage1_loss_grad(ptr(ps[0]), ptr(ps[1]), ptr(ps[2]), None, None, None, ptr(t), ptr(c), ps[0].shape[0],
+                                         0, 1.0, 0.0, ptr(out), None, stream()), "ph_surv_stage1_loss_grad")
+    return out[:3]
+
+
+def cindex_counts(survtime, event, hazards):
+    """Concordance counts of up to three risk vectors against one (survtime, event) pair (ph_cindex_counts): an int64
+    [len(hazards), 3] device tensor of comparable, concordant and tied pairs."""
+    t, e = _f32(survtime).reshape(-1), _f32(event).reshape(-1)
+    hs = [_f32(h).reshape(-1) for h in hazards]
+    if not 1 <= len(hs) <= 3 or any(h.shape[0] != t.shape[0] for h in hs) or e.shape[0] != t.shape[0]:
+        raise ValueError("cindex_counts: 1 to 3 risk vectors, each as long as survtime and event")
+    out = torch.empty(len(hs), 3, device=t.device, dtype=torch.int64)
+    hp = [ptr(h) for h in hs] + [None] * (3 - len(hs))
+    check(lib().ph_cindex_counts(ptr(t), ptr(e), hp[0], hp[1], hp[2], len(hs), t.shape[0], ptr(out), stream()),
+          "ph_cindex_counts")
+    return out
+
+
 class L2NormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -375,9 +375,7 @@ class ResNet(nn.Module):
             hazard = ops.LinearFn.apply(features, self.fc_new2.weight, self.fc_new2.bias)
             pred = None
             if self.act is not None:
-                if not isinstance(self.act, nn.LogSoftmax):
-                    raise NotImplementedError("only act_type 'LSM' (grading task) is on the hot path")
-                pred = ops.LogSoftmaxFn.apply(hazard)
+                pred = ops.apply_act(self.act, hazard, self)
             return f3, features, hazard, pred, None
         if not self.training:
             # eval mode (the reference's test(), train_test_path_multi_distill.py:409-431): BatchNorm uses the running
@@ -389,9 +387,7 @@ class ResNet(nn.Module):
                 hazard = ops.linear_fwd(features, self.fc_new2.weight, self.fc_new2.bias)
                 pred = None
                 if self.act is not None:
-                    if not isinstance(self.act, nn.LogSoftmax):
-                        raise NotImplementedError("only act_type 'LSM' (grading task) is on the hot path")
-                    pred = ops.LogSoftmaxFn.apply(hazard)
+                    pred = ops.apply_act(self.act, hazard, self)
             return f3, features, hazard, pred, None
         f3, f4 = _TrunkFn.apply(x, self, *self._trunk_params())
         h = ops.LinearFn.apply(f4, lin.weight, lin.bias)
@@ -400,10 +396,7 @@ class ResNet(nn.Module):
         hazard = ops.LinearFn.apply(features, self.fc_new2.weight, self.fc_new2.bias)
         pred = None
         if self.act is not None:
-            if isinstance(self.act, nn.LogSoftmax):
-                pred = ops.LogSoftmaxFn.apply(hazard)
-            else:
-                raise NotImplementedError("only act_type 'LSM' (grading task) is on the hot path")
+            pred = ops.apply_act(self.act, hazard, self)
         return f3, features, hazard, pred, None
 
     def forward(self, **kwargs):

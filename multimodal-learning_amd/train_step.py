@@ -373,12 +373,28 @@ def momentum_AEKD_loss(opt, optimizer, main_loss, feat_s, loss_t_list, mo_scale,
     return state, total_KD_loss
 
 
-def _validate_opt(opt, who):
+def _validate_task(opt, who, surv_ok=False):
+    """The task / head pairing.  Grading: the log-softmax head.  Survival (`surv_ok`, the stage-1 teacher only): exactly
+    act_type Sigmoid with label_dim 1 - the reference crashes on surv with LSM (CoxLoss reshapes a [B, 3] prediction against
+    B times), and its stage-2 trainers cannot run surv at all (`loss_cls.item()` on the int 0,
+    train_test_path_multi_distill.py:318)."""
+    task, act = getattr(opt, "task", "grad"), getattr(opt, "act_type", "LSM")
+    if task == "surv" and surv_ok:
+        if act != "Sigmoid" or getattr(opt, "label_dim", 1) != 1:
+            raise NotImplementedError("%s: task 'surv' needs act_type 'Sigmoid' and label_dim 1 (got %r, %r)"
+                                      % (who, act, getattr(opt, "label_dim", None)))
+        return
+    if task != "grad":
+        raise NotImplementedError("%s: task %r - the survival (Cox) task is built for the stage-1 teacher only; "
+                                  "this trainer runs the grading task" % (who, task))
+    if act != "LSM":
+        raise NotImplementedError("%s: act_type %r (the grading task uses the log-softmax head)" % (who, act))
+
+
+def _validate_opt(opt, who, surv_ok=False):
     """A drop-in must fail loudly where it diverges: option values the reference's batch body would honour and this
     package does not implement raise here instead of silently training another objective."""
-    if getattr(opt, "task", "grad") != "grad":
-        raise NotImplementedError("%s: task %r - the survival (Cox) branch of the trainers is out of scope (SURVEY 2.1 #8); "
-                                  "only the grading task is built" % (who, opt.task))
+    _validate_task(opt, who, surv_ok)
     if getattr(opt, "reg_type", "none") not in ("none", "path", "mm", "all", "omic"):
         raise NotImplementedError("reg method [%s] is not implemented" % opt.reg_type)      # networks_new.py:106-107
     if getattr(opt, "mode", "pathomic") != "pathomic":
@@ -387,8 +403,6 @@ def _validate_opt(opt, who):
     if getattr(opt, "optimizer_type", "adam") not in ("adam", "adagrad"):
         raise NotImplementedError("%s: optimizer_type %r (adam and adagrad are built; adabound needs the absent `adabound` "
                                   "package, networks_new.py:82-83)" % (who, opt.optimizer_type))
-    if getattr(opt, "act_type", "LSM") != "LSM":
-        raise NotImplementedError("%s: act_type %r (the grading task uses the log-softmax head)" % (who, opt.act_type))
     if getattr(opt, "fusion_type", "pofusion") != "pofusion":
         raise NotImplementedError("%s: fusion_type %r (pofusion is built)" % (who, opt.fusion_type))
     if getattr(opt, "return_grad", "False") != "False":
@@ -1207,7 +1221,23 @@ class TeacherStage1Step:
         self.opt = opt
         self.device = torch.device(device)
         self.sync = sync
-        _validate_opt(opt, "TeacherStage1Step")
+        _validate_opt(opt, "TeacherStage1Step", surv_ok=True)
+        # survival task (--task surv --act_type Sigmoid --label_dim 1, train_test_MT.py:149-152): the three Cox terms and
+        # MSE consistency terms in one launch (ops.SurvStage1LossFn); survtime / censor become step inputs
+        self.surv = getattr(opt, "task", "grad") == "surv"
+        if self.surv:
+            if sync is not None:
+                raise NotImplementedError("TeacherStage1Step: task 'surv' with data parallelism - the Cox risk sets span the "
+                                          "global batch (the reference's DataParallel computes the loss on the gathered "
+                                          "outputs); a row all-gather is not built")
+            if getattr(opt, "tSVD_loss", "False") == "True":
+                raise NotImplementedError("TeacherStage1Step: task 'surv' with tSVD_loss (no reference vectors pin it)")
+            if getattr(opt, "masking", 0):
+                raise NotImplementedError("TeacherStage1Step: task 'surv' with masking (no reference vectors pin it)")
+            if getattr(opt, "pred_distill", 1) == 1 and opt.num_teachers not in (1, 2, 3):
+                raise NotImplementedError("TeacherStage1Step: task 'surv' with num_teachers %r (train_test_MT.py:180-201 "
+                                          "builds 1, 2 or 3)" % (opt.num_teachers,))
+            self._IN_NAMES = TeacherStage1Step._IN_NAMES + ("survtime", "censor")
         if models is None:
             self.model = define_net(opt, k).to(self.device)
             self.ema_model = define_net(opt, k).to(self.device)
@@ -1270,6 +1300,36 @@ class TeacherStage1Step:
             if self.orth_on:
                 self.Orth_loss.sync = sync
 
+    def _as_f32(self, name, t):
+        """survtime / censor as float32 (the survival kernel's type).  A float32 tensor passes as it is; a device tensor of
+        another dtype is converted into a persistent buffer, so that its pointer stays put and a captured graph can adopt it
+        (a fresh temporary every step would fill the adopted input sets with throwaway copies); a host tensor is converted
+        on the host (it is staged or uploaded anyway)."""
+        if t.dtype == torch.float32:
+            return t
+        if not t.is_cuda:
+            return t.float()
+        bufs = self.__dict__.setdefault("_f32_bufs", {})
+        b = bufs.get(name)
+        if b is None or b.shape != t.shape or b.device != t.device:
+            b = bufs[name] = torch.empty(t.shape, device=t.device, dtype=torch.float32)
+        b.copy_(t)
+        return b
+
+    def _ema_frozen(self):
+        """update_ema_variables (:34-38, :229) covers EVERY parameter, output_range / output_shift included; the fused Adam step
+        updates the EMA copy of the trained ones only.  Under surv the sigmoid head reads those two, so their EMA copies
+        follow here (rate from the optimiser's device record: graph-replayable).  Grading leaves them alone: its head never
+        reads them."""
+        opt_ = self.optimizer
+        if getattr(self, "_frozen_segs", None) is None:
+            f, hi = opt_.flat, opt_.ema_range[1]
+            self._frozen_segs = [(s, min(e, hi)) for s, e in f.segments(lambda t: not t.requires_grad) if s < hi]
+        f = opt_.flat
+        for s, e in self._frozen_segs:
+            check(lib().ph_ema_update_dev(ptr(self.ema_flat.flat[s:e]), ptr(f.flat[s:e]), e - s, ptr(opt_._hyper), stream()),
+                  "ph_ema_update_dev")
+
     @staticmethod
     def pred_KD_loss(p_s, p_t, bnorm=None):
         """KD_losses.py:27-29 (grading, sample_KD False): sum(kl_div(p_s, exp(p_t))) / B on log-probabilities - the KL
@@ -1314,6 +1374,9 @@ class TeacherStage1Step:
             tau = opt.Lambda_global / self.mu
             mu_pen = min(self.mu * opt.pho, opt.max_mu) if do_aux else self.mu
         given = dict(x_path=x_path, ema_x_path=ema_x_path, x_omic=x_omic, grade=grade, index=index, sample_idx=sample_idx)
+        if self.surv:
+            given["survtime"] = self._as_f32("survtime", survtime)
+            given["censor"] = self._as_f32("censor", censor)
         use_graph = (getattr(self, "_want_graph", False) and not masking_on and self.iter_num - opt.global_step >= 2
                      and all(torch.is_tensor(t) for t in given.values()))
         out = None
@@ -1343,7 +1406,8 @@ class TeacherStage1Step:
                 loss_masking = self.pred_KD_loss(pred_m1, ema_m1, B) + self.pred_KD_loss(pred_m2, ema_m2, B)   # :217-220
             out = self._device_body(x_path, ema_x_path, x_omic, grade, index.to(dev) if self.crd_on else index,
                                     sample_idx.to(dev) if self.crd_on else sample_idx, B, do_aux, getattr(opt, "CRD_weight", 1.0), tau, mu_pen,
-                                    loss_masking)
+                                    loss_masking, *((given["survtime"].to(dev, non_blocking=True),
+                                                     given["censor"].to(dev, non_blocking=True)) if self.surv else ()))
         if self.tsvd_on:
             if do_aux:
                 self.mu = mu_pen                                                                 # :413
@@ -1394,7 +1458,8 @@ class TeacherStage1Step:
                 with torch.cuda.graph(g, pool=pool, capture_error_mode=_capture_mode(self.sync)):
                     self.optimizer._prepared = True       # the step scalars are read from device memory at replay
                     out = self._device_body(bf["x_path"], bf["ema_x_path"], bf["x_omic"], bf["grade"], bf["index"],
-                                            bf["sample_idx"], B, do_aux, self._g_scal[0], self._g_scal[1], self._g_scal[2], None)
+                                            bf["sample_idx"], B, do_aux, self._g_scal[0], self._g_scal[1], self._g_scal[2], None,
+                                            bf.get("survtime"), bf.get("censor"))
                 # the graph holds raw pointers into the trunk workspaces it was captured with: keep them alive with it
                 refs = [ws for net in (self.model, self.ema_model) for mod in net.modules() if hasattr(mod, "pinned_workspaces")
                         for ws in mod.pinned_workspaces()]
@@ -1419,9 +1484,10 @@ class TeacherStage1Step:
         g.replay()
         return out
 
-    def _device_body(self, x_path, ema_x_path, x_omic, grade, index, sample_idx, B, do_aux, crd_w, tau, mu_pen, loss_masking):
+    def _device_body(self, x_path, ema_x_path, x_omic, grade, index, sample_idx, B, do_aux, crd_w, tau, mu_pen, loss_masking,
+                     survtime=None, censor=None):
         """Everything of the step that runs on the device (capturable in one HIP graph).  `crd_w`, `tau`, `mu_pen`: floats on
-        the eager path, 1-element device tensors under capture."""
+        the eager path, 1-element device tensors under capture.  `survtime`, `censor`: device tensors of the survival task."""
         opt = self.opt
         dev = self.device
         if loss_masking is None:
@@ -1447,7 +1513,18 @@ class TeacherStage1Step:
             loss_CRD = crd_w * self.CRD_criterion_fuse(
                 fuse_feat, ema_fuse_feat.detach(), index, sample_idx).reshape(())
         kd = lambda p_s, p_t: self.pred_KD_loss(p_s, p_t, B)      # noqa: E731
-        if getattr(opt, "pred_distill", 1) == 1:
+        surv_terms = None
+        if self.surv:
+            # :149-152 + :180-203 with opt.task == "surv": lambda_cox * (three Cox terms) + KD_weight * (MSE consistency
+            # terms) and its gradient with respect to the three predictions, one launch; NLL is absent (zero)
+            nt = opt.num_teachers if getattr(opt, "pred_distill", 1) == 1 else 0
+            loss_surv, surv_terms = ops.SurvStage1LossFn.apply(pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic,
+                                                               survtime, censor, nt, float(opt.lambda_cox),
+                                                               float(getattr(opt, "KD_weight", 1.0)))
+            loss_pred_KD = surv_terms[7] if nt > 0 else torch.zeros((), device=dev)
+            loss_nll = torch.zeros((), device=dev)
+            loss = loss_surv + loss_CRD + loss_masking
+        elif getattr(opt, "pred_distill", 1) == 1:
             nt = opt.num_teachers
             kd_fuse = kd(pred, ema_pred)
             if nt == 1:
@@ -1463,9 +1540,10 @@ class TeacherStage1Step:
             loss_pred_KD = getattr(opt, "KD_weight", 1.0) * (kd_fuse + kd_path + kd_omic)       # :203
         else:
             loss_pred_KD = torch.zeros((), device=dev)
-        nll = lambda p: ops.NLLFn.apply(p, grade, B)
-        loss_nll = nll(pred_path) + nll(pred_omic) + nll(pred)                                  # :208-212
-        loss = opt.lambda_nll * loss_nll + loss_CRD + loss_pred_KD + loss_masking               # :217-218; MIA-2023 :303-304
+        if not self.surv:
+            nll = lambda p: ops.NLLFn.apply(p, grade, B)      # noqa: E731
+            loss_nll = nll(pred_path) + nll(pred_omic) + nll(pred)                              # :208-212
+            loss = opt.lambda_nll * loss_nll + loss_CRD + loss_pred_KD + loss_masking           # :217-218; MIA-2023 :303-304
         loss_reg = torch.zeros((), device=dev)
         if opt.reg_type != "none":      # :209 - the shipped stage-1 command keeps the default `omic` (options.py:132)
             from .networks_new import define_reg
@@ -1531,13 +1609,20 @@ class TeacherStage1Step:
         if self.sync is not None:
             self.sync.all_reduce_grads(self.optimizer.flat)
         self.optimizer.step()                                                                   # + EMA (:229) fused
+        if self.surv:
+            self._ema_frozen()
         if self.tsvd_on:
             # the adjacency tensors are kept as VALUES: with their grad_fn they would keep this step's autograd graph - and the
             # AccumulateGrad nodes of every parameter, bound to the stream of this step - alive into the next one (a capture of
             # the next step then runs them on the wrong stream: the runtime crashes in hipStreamEndCapture)
             self.adj_tensor1 = [a.detach() for a in self.adj_tensor1]
             self.adj_tensor2 = [a.detach() for a in self.adj_tensor2]
-        return dict(loss=loss.detach(), loss_nll=loss_nll.detach(), loss_pred_KD=loss_pred_KD.detach(),
-                    loss_CRD=loss_CRD.detach(), loss_orth=loss_orth.detach(), loss_tsvd=loss_tsvd.detach(),
-                    loss_pred_KD_masking=loss_masking.detach(), loss_reg=loss_reg.detach(),
-                    pred=pred.detach(), pred_path=pred_path.detach(), pred_omic=pred_omic.detach())
+        out = dict(loss=loss.detach(), loss_nll=loss_nll.detach(), loss_pred_KD=loss_pred_KD.detach(),
+                   loss_CRD=loss_CRD.detach(), loss_orth=loss_orth.detach(), loss_tsvd=loss_tsvd.detach(),
+                   loss_pred_KD_masking=loss_masking.detach(), loss_reg=loss_reg.detach(),
+                   pred=pred.detach(), pred_path=pred_path.detach(), pred_omic=pred_omic.detach())
+        if surv_terms is not None:
+            out.update(loss_cox=surv_terms[6], loss_cox_fuse=surv_terms[0], loss_cox_path=surv_terms[1],
+                       loss_cox_omic=surv_terms[2], loss_kd_fuse=surv_terms[3], loss_kd_path=surv_terms[4],
+                       loss_kd_omic=surv_terms[5])
+        return out

@@ -1,7 +1,8 @@
-"""The three helpers of the reference's MICCAI-2022/utils.py that are on the hot path
-(init_max_weights :239-244, init_net :247-270, count_parameters :542)."""
+"""The helpers of the reference's MICCAI-2022/utils.py that are on the hot path (init_max_weights :239-244, init_net
+:247-270, count_parameters :542, CoxLoss :361-376) and the survival metrics of the stage-1 evaluation (:386-425)."""
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -98,3 +99,63 @@ def CoxLoss(survtime, censor, hazard_pred, device=None):
     a B x B host loop.  The survival TRAINERS are out of scope; this is the loss function alone."""
     g = _CoxFn.apply(hazard_pred.reshape(-1), survtime, censor)
     return g
+
+
+# ---- survival metrics (utils.py:386-425), same names and argument orders as the reference
+def CIndex_lifeline(hazards, labels, survtime_all):
+    """utils.py:424-425: lifelines' concordance_index(survtime_all, -hazards, labels), from the exact integer counts of
+    ph_cindex_counts.  A pair (i, j) is comparable iff labels_i = 1 and (t_i < t_j, or t_i == t_j and labels_j = 0); it is
+    concordant iff hazards_i > hazards_j and counts 0.5 on a tie.  No comparable pair: ZeroDivisionError, as lifelines."""
+    return float(cindex_from_counts(cindex_counts_of(hazards, labels, survtime_all)[0]))
+
+
+def cindex_counts_of(hazards, labels, survtime_all):
+    """The [nvec, 3] int64 numpy counts (comparable, concordant, tied) of one risk vector or a list of up to three."""
+    from . import ops
+    dev = torch.device("cuda", torch.cuda.current_device())
+    hs = hazards if isinstance(hazards, (list, tuple)) else [hazards]
+    f = lambda a: torch.as_tensor(a).to(dev, torch.float32).reshape(-1)      # noqa: E731
+    return ops.cindex_counts(f(survtime_all), f(labels), [f(h) for h in hs]).cpu().numpy()
+
+
+def cindex_from_counts(counts):
+    comparable, concordant, tied = (int(v) for v in counts)
+    if comparable == 0:
+        raise ZeroDivisionError("No admissable pairs in the dataset.")
+    return (concordant + 0.5 * tied) / comparable
+
+
+def _dichotomize(hazardsdata):
+    h = np.asarray(hazardsdata, dtype=np.float64).reshape(-1)
+    return (h > np.median(h)).astype(np.int64)
+
+
+def accuracy_cox(hazardsdata, labels):
+    """utils.py:398-405: accuracy of the median split of the risks (above the median = group 1) against the events."""
+    labels = np.asarray(labels).reshape(-1)
+    return np.sum(_dichotomize(hazardsdata) == labels) / len(labels)
+
+
+def cox_log_rank(hazardsdata, labels, survtime_all):
+    """utils.py:408-419: p-value of the two-sample log-rank test between the median-split groups (lifelines' logrank_test in
+    the reference): chi-square with 1 degree of freedom from the hypergeometric variance n1 n2 d (n - d) / (n^2 (n - 1)),
+    p = erfc(sqrt(chi2 / 2)).  Host float64: N numbers once per epoch.  A zero variance (no event time at which both groups
+    are at risk with a spread of outcomes, e.g. every event at the last time, or one group empty) leaves the statistic
+    undefined: the p-value is nan, as lifelines' 0 / 0 gives, not an exception."""
+    g = _dichotomize(hazardsdata)
+    t = np.asarray(survtime_all, dtype=np.float64).reshape(-1)
+    e = np.asarray(labels, dtype=np.float64).reshape(-1) > 0
+    times = np.unique(t[e])
+    o_minus_e = var = 0.0
+    for s in times:
+        at_risk = t >= s
+        n, n1 = float(at_risk.sum()), float((at_risk & (g == 0)).sum())
+        died = e & (t == s)
+        d, d1 = float(died.sum()), float((died & (g == 0)).sum())
+        o_minus_e += d1 - d * n1 / n
+        if n > 1:
+            var += n1 * (n - n1) * d * (n - d) / (n * n * (n - 1))
+    if var <= 0.0:
+        return float("nan")
+    chi2 = o_minus_e * o_minus_e / var
+    return math.erfc(math.sqrt(chi2 / 2.0))
