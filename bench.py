@@ -16,14 +16,24 @@ bf16 perf mode, README stage-2 flags, dropout 0.1 (the reference default: teache
 n_data = 1024 CRD bank rows.  Weak scaling: 64 tiles per GPU at every N (the top-level `value`).  Inputs are resident
 in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
-Beside the headline value the line carries (round 2):
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs and the line,
+which beside the headline value carries
   roofline.step_frac    algorithmic FLOPs of the whole step / time / dense bf16 MFMA peak (the north-star's 70 % is a
-                        whole-path number; `frac` is the dominant kernel's)
-  roofline.hbm          achieved GB/s of the HBM-bound CRD / optimiser / BatchNorm-apply kernels against 8 TB/s
-  parity_mode           the same step in the `bf16x6` arithmetic that meets the 1e-3 logit tolerance (N = 1)
-  cpu_baseline.faithful the reference-faithful 3 forward + 6 backward CPU figure next to the 3 + 1 one
+                        whole-path number), from the timed steps alone
+  comm                  N > 1: what the communicator saw, from the timed steps and one all-reduce of ones
+Everything that takes runs of its own is measured with --full only, after the timed steps:
+  roofline.*            the dominant kernel, `all_kernels`, `step_hbm` and `hbm` (the HBM-bound CRD / optimiser /
+                        BatchNorm-apply kernels against 8 TB/s) from the in-library kernel timer in 3 one-stream eager
+                        steps after the graph-replayed timed region (an --eager run times the timed region itself and
+                        carries them without --full)
+  north_star_b256       N = 1: batch 256 on one GPU, its dominant kernel and `trunk_fwd_bwd` (the student's trunk alone)
+  parity_mode           the same step in the arithmetics that meet the 1e-3 logit tolerance (N = 1), with
+                        `value_tolerance_compliant`
+  variants              N = 1: the MIA-2022 / MIA-2023 / t-SVD stage-1 legs (BASELINE configs[3] / configs[4])
+  cpu_baseline          the CPU oracle's step; `faithful`: the reference's 3 forward + 6 backward order
   north_star_global_256 N > 1: BASELINE configs[2] / the north-star's strong-scaling point - global batch 256 split over
                         the N GPUs (32 tiles per GPU at N = 8), measured after the weak-scaling run
+The --no-* switches leave single blocks of a --full run out.
   --north-star          N = 1: batch 256 on one GPU (the north-star's single-GPU roofline point) as the headline
   --dump-outputs DIR    the outputs of the last timed step as DIR/<name>.npy (seeded inputs: two builds compare 1:1)
 """
@@ -613,13 +623,17 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--north-star", action="store_true",
                     help="N = 1: batch 256 on one GPU - the single-GPU roofline point of the north-star (BASELINE.json)")
-    ap.add_argument("--no-parity-mode", action="store_true", help="skip the extra bf16x6 (parity arithmetic) measurement")
-    ap.add_argument("--no-north-star-block", action="store_true", help="skip the extra batch-256 single-GPU measurement (`north_star_b256`)")
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the extra global-batch-256 (configs[2]) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline figure: per-kernel rooflines, "
+                         "north_star_b256, parity_mode, variants, cpu_baseline, north_star_global_256 (N > 1)")
+    ap.add_argument("--no-parity-mode", action="store_true", help="--full: skip the extra parity-arithmetic measurements")
+    ap.add_argument("--no-north-star-block", action="store_true", help="--full: skip the extra batch-256 single-GPU measurement (`north_star_b256`)")
+    ap.add_argument("--no-strong", action="store_true", help="--full, N > 1: skip the extra global-batch-256 (configs[2]) measurement")
     ap.add_argument("--strong-batch", type=int, default=0,
-                    help="testing aid: run the extra strong-scaling measurement with this many tiles per GPU whatever N is")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+                    help="testing aid (--full): run the extra strong-scaling measurement with this many tiles per GPU whatever N is")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timer", action="store_true",
+                    help="no in-library kernel timer (--full: the eager steps after the timed region; --eager: the timed region)")
     ap.add_argument("--eager", action="store_true", help="do not replay the step from a captured HIP graph")
     ap.add_argument("--generic-loss-head", action="store_true",
                     help="A/B: per-loss autograd graphs + GK-Refine by five small backward passes instead of loss_head.py")
@@ -646,9 +660,9 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the replica-sync code path even "
                     "with one rank (exercises the collectives inside graph capture on a 1-GPU box)")
     ap.add_argument("--variant", default="miccai2022", choices=["miccai2022", "mia2022", "mia2023", "tsvd"],
-                    help="run another batch body as the measured step (profiling aid; the default line already carries "
+                    help="run another batch body as the measured step (profiling aid; the --full line carries "
                          "5-step figures of all three in `variants`)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the `variants` block (configs[3] / configs[4] legs)")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the `variants` block (configs[3] / configs[4] legs)")
     ap.add_argument("--stub-step", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--grad-exchange", default="all_reduce", choices=["all_reduce", "reduce_scatter"],
                     help="N > 1: the gradient sum as bucketed all-reduce (default) or reduce-scatter + all-gather per bucket (A/B)")
@@ -794,8 +808,10 @@ def main():
         step.loader = loader
         batches = [None, None]
     L = m.lib()
+    # the kernel timer times an eager run's own timed region; after a graph-replayed one it needs eager steps of its own (--full)
+    kernel_timer = not args.no_kernel_timer and (args.eager or args.full)
     measure(step, batches, args.steps, args.warmup, sync, device, graph=not args.eager, loader=args.device_loader)
-    if args.eager and not args.no_kernel_timer:
+    if args.eager and kernel_timer:
         L.ph_prof_reset(); L.ph_prof_enable(1)
     dt, out = timed(step, batches, args.steps, sync, device)
     if args.dump_outputs and rank == 0:
@@ -803,7 +819,7 @@ def main():
     replayed = bool(getattr(step, "_want_graph", False))      # (False after a capture that failed and fell back to eager launches)
     L.ph_prof_enable(0)
     timer_region = "the timed region (eager)"
-    if not args.eager and not args.no_kernel_timer:
+    if not args.eager and kernel_timer:
         # the in-library HIP-event timer brackets individual launches, which a graph replay does not expose:
         # time the same kernels in 3 eager steps right after the timed region (same data, same shapes)
         step._want_graph = False
@@ -821,7 +837,7 @@ def main():
     else:
         prof_steps = args.steps
     main_prof = None
-    if not args.no_kernel_timer:
+    if kernel_timer:
         # read the headline step's per-class timings NOW: the extra runs below reset and reuse the in-library timer
         main_prof = (ctypes.c_double * (4 * NALL))()
         L.ph_prof_summary4(main_prof, NALL)
@@ -890,8 +906,9 @@ def main():
         finally:
             m.set_precision("bf16")
 
+    # ---- --full: the measurements beside the headline figure, each on a fresh step object after the timed steps
     strong = None
-    if args.strong_batch > 0 or (world > 1 and not args.no_strong and 256 % world == 0 and (256 // world) != args.batch):
+    if args.full and (args.strong_batch > 0 or (world > 1 and not args.no_strong and 256 % world == 0 and (256 // world) != args.batch)):
         # BASELINE configs[2] ("Batch 256 DDP across 8 x MI355X") and the north-star's ">= 6x at 8 GPUs": the GLOBAL batch
         # of the single-GPU north-star point split over the N GPUs - strong scaling against `bench.py --north-star`
         per = args.strong_batch if args.strong_batch > 0 else 256 // world
@@ -902,7 +919,7 @@ def main():
                   "ms_per_step": round(1000.0 * d2 / args.steps, 3), "tiles_per_gpu": per, "global_batch": per * world,
                   "scaling": "strong", "final_loss": round(l2, 4)}
     ns256 = None
-    if world == 1 and not args.no_north_star_block and not args.device_loader and (args.batch, args.size) == (64, 512):
+    if args.full and world == 1 and not args.no_north_star_block and not args.device_loader and (args.batch, args.size) == (64, 512):
         # the north-star's own single-GPU point in the driver-timed line: batch 256 on one MI355X, 5 graph-replayed steps,
         # the dominant kernel's roofline from this run's own launches and its own counter traffic (profiles/r04_b256_traffic.json)
         for mod in (step.model, step.ema_model, step.fix_model.path_net):
@@ -936,7 +953,7 @@ def main():
                               "traffic_note": "HBM bytes per launch at B = 256 from profiles/" + os.path.basename(tf) + " (rocprofv3 --pmc, "
                                               "separate FETCH_SIZE / WRITE_SIZE passes of `bench.py --north-star --serial`)"}}
     parity = None
-    if world == 1 and not args.no_parity_mode and not args.device_loader:
+    if args.full and world == 1 and not args.no_parity_mode and not args.device_loader:
         # the arithmetics that meet the north-star's 1e-3 tolerance (tests/test_gpu_step.py::
         # test_two_steps_from_mid_training_state_vs_reference_golden runs the same assertions against the reference's golden
         # in each of them), same step, same sizes:
@@ -966,7 +983,7 @@ def main():
         parity["tolerance_compliant"] = "fp16x3/x1"      # the cheapest arithmetic that passes every 1e-3 assertion (also: fp16x3, bf16x6/x3, bf16x6)
 
     variants = None
-    if world == 1 and not args.no_variants and not args.device_loader and (args.batch, args.size) == (64, 512):
+    if args.full and world == 1 and not args.no_variants and not args.device_loader and (args.batch, args.size) == (64, 512):
         # driver-timed legs of BASELINE configs[3] / configs[4] (VERDICT r02 missing 2) and the CRD kernels against the
         # HBM roofline at the bank size of configs[4]; the headline step's buffers are released first
         for mod in (step.model, step.ema_model, step.fix_model.path_net):
@@ -1018,7 +1035,7 @@ def main():
                           "input_pipeline": ("on-device from resident uint8 tiles, inside the timed region and the graph"
                                              if args.device_loader else "inputs resident in HBM when the timed region starts")}}
         # ---- roofline of the dominant kernel (live HIP-event timing inside the timed region)
-        if not args.no_kernel_timer:
+        if kernel_timer:
             buf4 = main_prof
             buf = [0.0] * (3 * NALL)
             byt = [0.0] * NALL
@@ -1110,7 +1127,7 @@ def main():
                                                         "1e-3 of the fp32 reference (parity_mode block)"}
         if variants is not None:
             res["variants"] = variants
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
         _flush_c_stdio()      # (RCCL prints its version banner through C stdio: without this it lands AFTER the JSON line)
         print(json.dumps(res), flush=True)

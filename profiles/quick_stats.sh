@@ -5,7 +5,7 @@ TAG=${1:-q}; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 T=gpurun_out/$TAG
 mkdir -p "$T"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$T/stats" -- python3 bench.py --serial --steps 10 --warmup 3 --no-cpu-baseline --no-parity-mode --no-variants --no-north-star-block "$@" > "$T/bench_stats.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$T/stats" -- python3 bench.py --full --serial --steps 10 --warmup 3 --no-cpu-baseline --no-parity-mode --no-variants --no-north-star-block "$@" > "$T/bench_stats.log" 2>&1
 F=$(find "$T/stats" -name "*kernel_stats.csv" | head -1)
 python3 - "$F" <<'PY' > gpurun_out/${TAG}_kernel_stats.txt
 import csv, sys
