@@ -67,6 +67,10 @@ int ph_resnet_unit_shape(const PhResnetPlan* plan, int unit, int* out4 /* Cout, 
 /* OIHW fp32 -> MFMA operand layouts (bf16 hi/lo planes, fwd [tap][O][I] and dgrad [tap][I][O]); call after
  * every optimiser step */
 int ph_resnet_pack_weights(const PhResnetPlan* plan, const void* const* params, void* packed, ph_stream_t stream);
+/* Signature of the packed-weight layout `plan` reads under the current kernel switches (half-pair mode: which units' weights are
+ * fragment-major).  A packed buffer is valid for every plan of the same precision whose signature equals the one of the plan
+ * that packed it; re-pack when it differs.  The call refreshes the plan's layout to the current switches. */
+unsigned long long ph_resnet_plan_layout_sig(const PhResnetPlan* plan);
 /* x_nchw [B,3,H,W] f32 -> f3 [B,256], f4 [B,512] f32 (either may be NULL).  flags bit0: train mode, update the running
  * statistics; bit1: eval mode (normalise with the running statistics; no backward); bit2: forward only - no
  * ph_resnet_backward will read this workspace (the no_grad EMA / teacher forwards of train_test_path_multi_distill.py:
@@ -319,6 +323,10 @@ int ph_l1_sign_axpy(const float* w, float* g, size_t n, const float* coef_dev, f
 /* ------------------------------------------------------------------------------------------------
  * Fine-grained convolution entry points (unit tests / other callers).  Activations NHWC in the precision
  * mode's type, weights OIHW f32.  `ws` must hold ph_conv2d_workspace_bytes().
+ * Accepted by all four (fwd, dgrad, dgrad_res, wgrad): KS = 3 with pad 1 at stride 1 or 2, or pad 0 at stride 1; KS = 1 with
+ * pad 0 at stride 1 or 2; Cin, Cout multiples of 64; B >= 1 and a non-empty output.  prec: 0..3 for the forward (PH_PREC_FP16X1
+ * is a backward arithmetic), 0..4 for dgrad / dgrad_res / wgrad.  dgrad_res at 1x1 / stride 2 (output pixels no tap reaches)
+ * takes its residual in place only (res_g == dx, res_a == NULL).  Anything else returns PH_EINVAL with nothing written.
  * ---------------------------------------------------------------------------------------------- */
 size_t ph_conv2d_workspace_bytes(int B, int Cin, int IH, int IW, int Cout, int KS, int stride, int pad);
 /* PH_PREC_FP16X3: the tensors a convolution READS (x of fwd / wgrad, dy of dgrad / wgrad) are half-pair tensors - layout

@@ -1,5 +1,6 @@
 // Fine-grained convolution entry points of the C-ABI (used by the parity tests to pin each MFMA kernel
 // against the oracle's F.conv2d) + ABI version.
+#include <algorithm>
 #include "ph_common.h"
 #include "ph_kernels.h"
 #include "ph_dense.h"
@@ -44,6 +45,15 @@ __global__ void hp_unpack_kernel(const hp16* __restrict__ src, float* __restrict
   store8(dst + i * 8, v);
 }
 
+// the geometries the convolution entry points accept: KS 3 at pad 1 (stride 1 or 2) or pad 0 (stride 1 only: a stride-2 dgrad
+// at pad 0 would need taps before the first dy row), KS 1 at pad 0 (stride 1 or 2: the stride-2 view starts at pixel 0),
+// channel counts multiples of 64, a non-empty output.  Everything else is PH_EINVAL before anything is written.
+bool geometry_ok(int B, int Cin, int IH, int IW, int Cout, int KS, int stride, int pad) {
+  if (B < 1 || Cin < 64 || Cout < 64 || Cin % 64 || Cout % 64 || (stride != 1 && stride != 2)) return false;
+  if (KS == 1 ? pad != 0 : (KS != 3 || !(pad == 1 || (pad == 0 && stride == 1)))) return false;
+  return IH + 2 * pad >= KS && IW + 2 * pad >= KS;
+}
+
 int chunks_for(int B, int OH, int OW, int S, int Cout, int Cin, int* tpc) {
   const int th = ph_wgrad_tile_h(S);
   const int ntiles = B * cdiv(OH, th) * cdiv(OW, 16);
@@ -62,8 +72,10 @@ size_t ph_conv2d_workspace_bytes(int B, int Cin, int IH, int IW, int Cout, int K
   const size_t wbytes = up((size_t)PH_NPLANES * KS * KS * Cin * Cout * sizeof(bf16));
   PhTapConv t{}; t.B = B; t.Cout = Cout; t.OHt = OH; t.OWt = OW;
   // (the largest row count of any arithmetic: the split modes' small tiles, or two rows per persistent workgroup of conv_tap6.hip)
+  // (and perf mode's: conv_tap6b.hip's two rows per persistent workgroup at stride 2, the second-generation kernels' one per workgroup)
   const int nparts = ph_tapconv_stat_parts(&t, stride, PH_PREC_BF16X6), nparts_hp = ph_tapconv_stat_parts(&t, stride, PH_PREC_FP16X3);
-  const size_t parts = up((size_t)(nparts > nparts_hp ? nparts : nparts_hp) * 2 * Cout * sizeof(float));
+  const int nparts_bf = std::max(ph_tapconv_stat_parts(&t, stride, PH_PREC_BF16), ph_num_cus());
+  const size_t parts = up((size_t)std::max(std::max(nparts, nparts_hp), nparts_bf) * 2 * Cout * sizeof(float));
   int tpc; const int nc = chunks_for(B, OH, OW, stride, Cout, Cin, &tpc);
   const size_t slab = up((size_t)nc * KS * KS * Cin * Cout * sizeof(float));
   return wbytes + (parts > slab ? parts : slab) + 256;
@@ -71,14 +83,12 @@ size_t ph_conv2d_workspace_bytes(int B, int Cin, int IH, int IW, int Cout, int K
 
 int ph_conv2d_fwd(const void* x, const float* w, void* y, float* ch_sum, float* ch_sumsq, int B, int Cin, int IH,
                   int IW, int Cout, int KS, int stride, int pad, int prec, void* ws_, hipStream_t st) {
-  if ((KS != 1 && KS != 3) || Cin % 64 || Cout % 64) return PH_EINVAL;
+  // (PH_PREC_FP16X1 is a backward arithmetic)
+  if (!geometry_ok(B, Cin, IH, IW, Cout, KS, stride, pad) || prec < PH_PREC_BF16 || prec > PH_PREC_FP16X3 || !x || !w || !y || !ws_)
+    return PH_EINVAL;
   unsigned char* ws = reinterpret_cast<unsigned char*>(ws_);
   const size_t plane = (size_t)KS * KS * Cin * Cout;
   bf16* hi = reinterpret_cast<bf16*>(ws);
-  int rc = prec == PH_PREC_FP16X3 ? ph_pack_w_hp_launch(w, hi, Cout, Cin, KS, 0, st) : ph_pack_w_fwd_launch(w, hi, Cout, Cin, KS, st);
-  if (rc) return rc;
-  // perf mode, what conv_tap7.hip takes: the fragment-major copy in plane 1 (a split plane this mode does not read)
-  if (prec == PH_PREC_BF16 && KS == 3 && Cin == Cout && Cin >= 128 && (rc = ph_frag7_repack_launch(hi, Cout, Cin, 9, st))) return rc;
   const int OH = (IH + 2 * pad - KS) / stride + 1, OW = (IW + 2 * pad - KS) / stride + 1;
   PhTapConv t{};
   t.in = x; t.w = hi; t.wplane = plane; t.out = y;
@@ -86,6 +96,12 @@ int ph_conv2d_fwd(const void* x, const float* w, void* y, float* ch_sum, float* 
   t.B = B; t.IH = IH; t.IW = IW; t.Cin = Cin; t.Cout = Cout; t.OHt = OH; t.OWt = OW; t.OH = OH; t.OW = OW;
   t.os = 1; t.iy0 = -pad; t.ix0 = -pad; t.ntaps = KS * KS;
   for (int k = 0; k < t.ntaps; ++k) { t.dy[k] = k / KS; t.dx[k] = k % KS; t.wtap[k] = k; }
+  // half-pair mode: the weight layout of the kernel this descriptor reaches
+  t.w_frag = ph_tapconv_hp_wfrag(&t, stride, prec);
+  int rc = prec == PH_PREC_FP16X3 ? ph_pack_w_hp_launch(w, hi, Cout, Cin, KS, 0, t.w_frag, st) : ph_pack_w_fwd_launch(w, hi, Cout, Cin, KS, st);
+  if (rc) return rc;
+  // perf mode, what conv_tap7.hip takes: the fragment-major copy in plane 1 (a split plane this mode does not read)
+  if (prec == PH_PREC_BF16 && KS == 3 && Cin == Cout && Cin >= 128 && (rc = ph_frag7_repack_launch(hi, Cout, Cin, 9, st))) return rc;
   const bool tap6b = prec == PH_PREC_BF16 && KS == 3 && stride == 2 && pad == 1 && ph_tap6b_switch(-1) && ph_tapconv6b_eligible(&t);
   if (tap6b && (rc = ph_frag7_repack_launch(hi, Cout, Cin, 9, st))) return rc;      // the fragment-major copy in plane 1
   if (!tap6b && KS == 3 && stride == 2 && pad == 1 && ph_tapconv2_setup_s2_fwd(&t, Cin, Cout, IH, IW, prec)) stride = 1;
@@ -102,14 +118,25 @@ int ph_conv2d_fwd(const void* x, const float* w, void* y, float* ch_sum, float* 
   return PH_OK;
 }
 
-int ph_conv2d_dgrad_res(const void* dy, const float* w, void* dx, const void* res_g, const void* res_a, int B, int Cin,
-                        int IH, int IW, int Cout, int KS, int stride, int pad, int prec, void* ws_, hipStream_t st) {
-  if ((KS != 1 && KS != 3) || Cin % 64 || Cout % 64 || (stride != 1 && stride != 2)) return PH_EINVAL;
-  const size_t plane = (size_t)KS * KS * Cin * Cout;
-  bf16* hi = reinterpret_cast<bf16*>(ws_);
-  int rc = (prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1) ? ph_pack_w_hp_launch(w, hi, Cout, Cin, KS, 1, st) : ph_pack_w_dgrad_launch(w, hi, Cout, Cin, KS, st);
+namespace {
+// the layout and the descriptor's weight fields of a dgrad over `t` (stride-1 geometry filled in; stride-2 launches: row-major)
+int pack_dgrad(const float* w, bf16* hi, PhTapConv* t, int Cin, int Cout, int KS, int stride, int prec, hipStream_t st) {
+  const bool hp = prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1;
+  t->w_frag = stride == 1 ? ph_tapconv_hp_wfrag(t, 1, prec) : PH_WFRAG_ROW;
+  int rc = hp ? ph_pack_w_hp_launch(w, hi, Cout, Cin, KS, 1, t->w_frag, st) : ph_pack_w_dgrad_launch(w, hi, Cout, Cin, KS, st);
   if (rc) return rc;
   if (prec == PH_PREC_BF16 && KS == 3 && Cin == Cout && Cin >= 128 && (rc = ph_frag7_repack_launch(hi, Cin, Cout, 9, st))) return rc;
+  return PH_OK;
+}
+
+// dgrad (+ residual) of a stride-1 or stride-2 convolution.  Stride 2: one launch per output parity class; a class no tap
+// reaches (1x1) receives res_g in place (res_g == dx, no res_a), zeros (no residual), or the call is PH_EINVAL
+int dgrad_common(const void* dy, const float* w, void* dx, const void* res_g, const void* res_a, int B, int Cin, int IH, int IW,
+                 int Cout, int KS, int stride, int pad, int prec, void* ws_, hipStream_t st) {
+  if (!geometry_ok(B, Cin, IH, IW, Cout, KS, stride, pad) || prec < PH_PREC_BF16 || prec > PH_PREC_FP16X1 || !dy || !w || !dx || !ws_)
+    return PH_EINVAL;
+  const size_t plane = (size_t)KS * KS * Cin * Cout;
+  bf16* hi = reinterpret_cast<bf16*>(ws_);
   const int OH = (IH + 2 * pad - KS) / stride + 1, OW = (IW + 2 * pad - KS) / stride + 1;
   PhTapConv t{};
   t.in = dy; t.w = hi; t.wplane = plane; t.out = dx; t.res_g = res_g; t.res_a = res_a;
@@ -119,10 +146,13 @@ int ph_conv2d_dgrad_res(const void* dy, const float* w, void* dx, const void* re
     for (int k = 0; k < t.ntaps; ++k) {
       t.dy[k] = k / KS; t.dx[k] = k % KS; t.wtap[k] = (KS - 1 - k / KS) * KS + (KS - 1 - k % KS);
     }
-    return ph_tapconv_launch(&t, 1, prec, st);
+    const int rc = pack_dgrad(w, hi, &t, Cin, Cout, KS, 1, prec, st);
+    return rc ? rc : ph_tapconv_launch(&t, 1, prec, st);
   }
-  // stride 2, as resnet_plan.hip:conv_dgrad: one launch per output parity class; a class no tap reaches keeps what
-  // dx already holds (the in-place residual res_g == dx of the downsample path)
+  // stride 2, as resnet_plan.hip:conv_dgrad.  Every class is planned (and the call checked) before anything is written.
+  PhTapConv cls[4];
+  int ncls = 0;
+  bool tapless = false;
   for (int a = 0; a < 2; ++a)
     for (int b = 0; b < 2; ++b) {
       int nk = 0, khs[3], dhs[3], nw = 0, kws[3], dws[3];
@@ -130,19 +160,37 @@ int ph_conv2d_dgrad_res(const void* dy, const float* w, void* dx, const void* re
         if (((a + pad - kh) & 1) == 0) { khs[nk] = kh; dhs[nk] = (a + pad - kh) / 2; ++nk; }
       for (int kw = 0; kw < KS; ++kw)
         if (((b + pad - kw) & 1) == 0) { kws[nw] = kw; dws[nw] = (b + pad - kw) / 2; ++nw; }
-      t.OHt = (IH - a + 1) / 2; t.OWt = (IW - b + 1) / 2;
-      if (t.OHt <= 0 || t.OWt <= 0) continue;
-      t.os = 2; t.oa_h = a; t.oa_w = b; t.iy0 = 0; t.ix0 = 0; t.ntaps = nk * nw;
-      if (t.ntaps == 0) continue;
+      PhTapConv c = t;
+      c.OHt = (IH - a + 1) / 2; c.OWt = (IW - b + 1) / 2;
+      if (c.OHt <= 0 || c.OWt <= 0) continue;
+      c.os = 2; c.oa_h = a; c.oa_w = b; c.iy0 = 0; c.ix0 = 0; c.ntaps = nk * nw;
+      if (c.ntaps == 0) { tapless = true; continue; }
       int q = 0;
       for (int i = 0; i < nk; ++i)
         for (int j = 0; j < nw; ++j) {
           if (dhs[i] < 0 || dws[j] < 0 || dhs[i] > 2 || dws[j] > 2) return PH_EINVAL;
-          t.dy[q] = dhs[i]; t.dx[q] = dws[j]; t.wtap[q] = khs[i] * KS + kws[j]; ++q;
+          c.dy[q] = dhs[i]; c.dx[q] = dws[j]; c.wtap[q] = khs[i] * KS + kws[j]; ++q;
         }
-      if ((rc = ph_tapconv_launch(&t, 1, prec, st))) return rc;
+      cls[ncls++] = c;
     }
+  if (tapless && res_g && (res_g != dx || res_a)) return PH_EINVAL;
+  int rc = pack_dgrad(w, hi, &t, Cin, Cout, KS, 2, prec, st);
+  if (rc) return rc;
+  if (tapless && !res_g) {
+    const size_t es = prec == PH_PREC_BF16 ? 2 : 4;
+    if (hipMemsetAsync(dx, 0, (size_t)B * IH * IW * Cin * es, st) != hipSuccess) return PH_ELAUNCH;
+  }
+  for (int k = 0; k < ncls; ++k) {
+    cls[k].w_frag = t.w_frag;
+    if ((rc = ph_tapconv_launch(&cls[k], 1, prec, st))) return rc;
+  }
   return PH_OK;
+}
+}  // namespace
+
+int ph_conv2d_dgrad_res(const void* dy, const float* w, void* dx, const void* res_g, const void* res_a, int B, int Cin,
+                        int IH, int IW, int Cout, int KS, int stride, int pad, int prec, void* ws_, hipStream_t st) {
+  return dgrad_common(dy, w, dx, res_g, res_a, B, Cin, IH, IW, Cout, KS, stride, pad, prec, ws_, st);
 }
 
 // test access to the in-LDS BatchNorm + ReLU of a 3x3 stride-1 perf-mode forward launch (PhTapConv::in_scale): y = conv(relu(x *
@@ -201,46 +249,13 @@ int ph_conv2d_dgrad_bnstat(const void* dy, const float* w, void* dx, const void*
 
 int ph_conv2d_dgrad(const void* dy, const float* w, void* dx, int B, int Cin, int IH, int IW, int Cout, int KS,
                     int stride, int pad, int prec, void* ws_, hipStream_t st) {
-  if ((KS != 1 && KS != 3) || Cin % 64 || Cout % 64) return PH_EINVAL;
-  const size_t plane = (size_t)KS * KS * Cin * Cout;
-  bf16* hi = reinterpret_cast<bf16*>(ws_);
-  int rc = (prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1) ? ph_pack_w_hp_launch(w, hi, Cout, Cin, KS, 1, st) : ph_pack_w_dgrad_launch(w, hi, Cout, Cin, KS, st);
-  if (rc) return rc;
-  if (prec == PH_PREC_BF16 && KS == 3 && Cin == Cout && Cin >= 128 && (rc = ph_frag7_repack_launch(hi, Cin, Cout, 9, st))) return rc;
-  const int OH = (IH + 2 * pad - KS) / stride + 1, OW = (IW + 2 * pad - KS) / stride + 1;
-  PhTapConv t{};
-  t.in = dy; t.w = hi; t.wplane = plane; t.out = dx;
-  t.B = B; t.IH = OH; t.IW = OW; t.Cin = Cout; t.Cout = Cin; t.OH = IH; t.OW = IW;
-  if (stride == 1) {
-    t.OHt = IH; t.OWt = IW; t.os = 1; t.iy0 = -(KS - 1 - pad); t.ix0 = t.iy0; t.ntaps = KS * KS;
-    for (int k = 0; k < t.ntaps; ++k) {
-      t.dy[k] = k / KS; t.dx[k] = k % KS; t.wtap[k] = (KS - 1 - k / KS) * KS + (KS - 1 - k % KS);
-    }
-    return ph_tapconv_launch(&t, 1, prec, st);
-  }
-  const size_t es = prec == PH_PREC_BF16 ? 2 : 4;
-  if (hipMemsetAsync(dx, 0, (size_t)B * IH * IW * Cin * es, st) != hipSuccess) return PH_ELAUNCH;
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      int nk = 0, khs[3], dhs[3], nw = 0, kws[3], dws[3];
-      for (int kh = 0; kh < KS; ++kh)
-        if (((a + pad - kh) & 1) == 0 && a + pad - kh >= 0) { khs[nk] = kh; dhs[nk] = (a + pad - kh) / 2; ++nk; }
-      for (int kw = 0; kw < KS; ++kw)
-        if (((b + pad - kw) & 1) == 0 && b + pad - kw >= 0) { kws[nw] = kw; dws[nw] = (b + pad - kw) / 2; ++nw; }
-      t.OHt = (IH - a + 1) / 2; t.OWt = (IW - b + 1) / 2;
-      t.os = 2; t.oa_h = a; t.oa_w = b; t.iy0 = 0; t.ix0 = 0; t.ntaps = nk * nw;
-      if (t.ntaps == 0 || t.OHt <= 0 || t.OWt <= 0) continue;
-      int q = 0;
-      for (int i = 0; i < nk; ++i)
-        for (int j = 0; j < nw; ++j) { t.dy[q] = dhs[i]; t.dx[q] = dws[j]; t.wtap[q] = khs[i] * KS + kws[j]; ++q; }
-      if ((rc = ph_tapconv_launch(&t, 1, prec, st))) return rc;
-    }
-  return PH_OK;
+  return dgrad_common(dy, w, dx, nullptr, nullptr, B, Cin, IH, IW, Cout, KS, stride, pad, prec, ws_, st);
 }
 
 int ph_conv2d_wgrad(const void* x, const void* dy, float* dw, int B, int Cin, int IH, int IW, int Cout, int KS,
                     int stride, int pad, int prec, void* ws_, hipStream_t st) {
-  if ((KS != 1 && KS != 3) || Cin % 64 || Cout % 64) return PH_EINVAL;
+  if (!geometry_ok(B, Cin, IH, IW, Cout, KS, stride, pad) || prec < PH_PREC_BF16 || prec > PH_PREC_FP16X1 || !x || !dy || !dw || !ws_)
+    return PH_EINVAL;
   unsigned char* ws = reinterpret_cast<unsigned char*>(ws_);
   const size_t plane = (size_t)KS * KS * Cin * Cout;
   const int OH = (IH + 2 * pad - KS) / stride + 1, OW = (IW + 2 * pad - KS) / stride + 1;

@@ -1293,18 +1293,25 @@ int ph_tapconv2_stat_parts(const PhTapConv* p) {
 
 int ph_tapconv2_launch(const PhTapConv* p, hipStream_t st) {
   if (p->in_scale && (!p->in_shift || p->Cin > 512)) return PH_EINVAL;
-  if (p->m_groups) return (p->Cout % 128 == 0 && !p->in_scale) ? launch2<2, 2, 4, false, true>(*p, st) : PH_EINVAL;
+  if (p->m_groups) {
+    if (p->Cout % 128 || p->in_scale) return PH_EINVAL;
+    ph_dispatch_note(PH_DK_TAP2_MASKED);
+    return launch2<2, 2, 4, false, true>(*p, st);
+  }
   if (p->Cout % 128 == 0) {
     if (ph_tap3_switch(-1) && ph_tapconv3_eligible(p)) {
       // every form but the in-LDS input BatchNorm, Cin = Cout: conv_tap7.hip, same outputs
-      if (ph_tap7_switch(-1) && ph_tapconv7_eligible(p)) return ph_tapconv7_launch(p, st);
+      if (ph_tap7_switch(-1) && ph_tapconv7_eligible(p)) { ph_dispatch_note(PH_DK_TAP7); return ph_tapconv7_launch(p, st); }
+      ph_dispatch_note(PH_DK_TAP3);
       return ph_tapconv3_launch(p, st);
     }
     if (p->bst_y) return PH_EINVAL;      // (the fused BatchNorm-backward sums exist in conv_tap3.hip / conv_tap4.hip only)
+    ph_dispatch_note(PH_DK_TAP2);
     return launch2<2, 2, 4, false>(*p, st);
   }
-  if (ph_tap4_switch(-1) && ph_tapconv4_eligible(p)) return ph_tapconv4_launch(p, st);
+  if (ph_tap4_switch(-1) && ph_tapconv4_eligible(p)) { ph_dispatch_note(PH_DK_TAP4); return ph_tapconv4_launch(p, st); }
   if (p->bst_y) return PH_EINVAL;      // (the fused BatchNorm-backward sums exist in conv_tap4.hip only)
+  ph_dispatch_note(PH_DK_TAP2_L1);
 #ifdef PH_L1_ONE_GROUP   // A/B build: the one-wave-per-SIMD resident-weights configuration
   return launch2<4, 1, 2, true>(*p, st);
 #else

@@ -516,16 +516,17 @@ __device__ __forceinline__ void hp_w3(float v, f16& b0, f16& b1, f16& b2) {
   b0 = (f16)((float)b2 * PH_HP_LO);
 }
 // conv_tap5.hip's layout of a 64 x 64 x 9 slab set: per tap [block 3][k-step 2][N tile 4][lane 64][8]: row r = 4 li + n, k = 32 ks + 8 lg + j,
-// lane = 16 lg + li -> element index inside the tap (block 0); blocks are 4096 elements apart.  frag5: bit 0 = conv_tap5.hip's
-// switch, bit 1 = conv_tap6.hip's (host: ph_tap5_switch / ph_tap6_switch at pack time)
+// lane = 16 lg + li -> element index inside the tap (block 0); blocks are 4096 elements apart.  The layout of each unit is the host's
+// decision (PhPackAll::frag, PH_WFRAG_*: the same eligibility and switch state that picks the kernel, ph_tapconv_hp_wfrag)
 __device__ __forceinline__ size_t ph5_frag_index(int r, int k) { return frag64_index(r, k); }
 template <bool ONE>
-__global__ __launch_bounds__(256) void pack_all_tiled_hp_kernel(PhPackAll t, PackTiles pt, f16* __restrict__ packed, int dgrad_only, int frag5) {
+__global__ __launch_bounds__(256) void pack_all_tiled_hp_kernel(PhPackAll t, PackTiles pt, f16* __restrict__ packed, int dgrad_only) {
   __shared__ float sh[32][32 * 9 + 1];
   int u = 0;
 #pragma unroll 1
   while (u + 1 < t.n && (int)blockIdx.x >= pt.tstart[u + 1]) ++u;
   const int O = t.O[u], I = t.I[u], NT = t.NT[u];
+  const int ffwd = t.frag[u] & 3, fdg = (t.frag[u] >> 2) & 3;
   const int tile = (int)blockIdx.x - pt.tstart[u];
   const int itiles = I >> 5;
   const int o0 = (tile / itiles) << 5, i0 = (tile % itiles) << 5;
@@ -540,10 +541,10 @@ __global__ __launch_bounds__(256) void pack_all_tiled_hp_kernel(PhPackAll t, Pac
     f16 b0, b1, b2;
     if (!ONE || dgrad_only == 0) {   // forward layout [tap][O][3 I]: x = input channel (fastest), y = output channel
       hp_w3(sh[y][x * NT + tp], b0, b1, b2);
-      if ((frag5 & 1) && O == 64 && I == 64 && NT == 9) {
+      if (ffwd == PH_WFRAG_TAP5) {
         f16* d = packed + t.dst_fwd[u] + (size_t)tp * 12288 + ph5_frag_index(o0 + y, i0 + x);
         d[0] = b0; d[4096] = b1; d[8192] = b2;
-      } else if ((frag5 & 2) && O == 2 * I && NT == 9) {
+      } else if (ffwd == PH_WFRAG_TAP6) {
         // conv_tap6.hip (the stride-2 convolutions, forward orientation only): [tap][O / 64][I / 64][block 3] x 4096 elements
         const int o = o0 + y, i = i0 + x;
         f16* d = packed + t.dst_fwd[u] + (size_t)tp * O * 3 * I + (size_t)(((o >> 6) * (I >> 6) + (i >> 6)) * 3) * 4096 + ph5_frag_index(o & 63, i & 63);
@@ -555,7 +556,7 @@ __global__ __launch_bounds__(256) void pack_all_tiled_hp_kernel(PhPackAll t, Pac
     }
     if (!ONE || dgrad_only == 1) {   // dgrad layout [tap][I][3 O]: x = output channel (fastest), y = input channel
       hp_w3(sh[x][y * NT + tp], b0, b1, b2);
-      if ((frag5 & 1) && O == 64 && I == 64 && NT == 9) {
+      if (fdg == PH_WFRAG_TAP5) {
         f16* d = packed + t.dst_dg[u] + (size_t)tp * 12288 + ph5_frag_index(i0 + y, o0 + x);
         d[0] = b0; d[4096] = b1; d[8192] = b2;
       } else {
@@ -589,14 +590,19 @@ int ph_pack_w_stem_hp_launch(const float* w, void* packed, hipStream_t st) {
 }
 
 // one convolution in the PH_PREC_FP16X3 layout (forward or dgrad orientation) at the start of `packed` (test hooks)
-int ph_pack_w_hp_launch(const float* w, void* packed, int O, int I, int KS, int dgrad, hipStream_t st) {
+int ph_pack_w_hp_launch(const float* w, void* packed, int O, int I, int KS, int dgrad, int wfrag, hipStream_t st) {
   if ((O & 31) || (I & 31) || (KS != 1 && KS != 3)) return PH_EINVAL;
+  // (the fragment-major layouts exist for the shapes of their kernels only)
+  if (wfrag == PH_WFRAG_TAP5 && !(O == 64 && I == 64 && KS == 3)) return PH_EINVAL;
+  if (wfrag == PH_WFRAG_TAP6 && !(O == 2 * I && KS == 3 && !dgrad)) return PH_EINVAL;
+  if (wfrag < 0 || wfrag > PH_WFRAG_TAP6) return PH_EINVAL;
   PhPackAll t{};
   t.n = 1; t.w[0] = w; t.O[0] = O; t.I[0] = I; t.NT[0] = KS * KS; t.dst_fwd[0] = 0; t.dst_dg[0] = 0;
+  t.frag[0] = dgrad ? wfrag << 2 : wfrag;
   t.start[0] = 0; t.start[1] = t.total = (size_t)KS * KS * O * I;
   PackTiles pt;
   pt.tstart[0] = 0; pt.tstart[1] = (O >> 5) * (I >> 5);
-  hipLaunchKernelGGL(pack_all_tiled_hp_kernel<true>, dim3(pt.tstart[1]), dim3(256), 0, st, t, pt, (f16*)packed, dgrad ? 1 : 0, ph_tap5_switch(-1) | (ph_tap6_switch(-1) << 1));
+  hipLaunchKernelGGL(pack_all_tiled_hp_kernel<true>, dim3(pt.tstart[1]), dim3(256), 0, st, t, pt, (f16*)packed, dgrad ? 1 : 0);
   PH_LAUNCH_CHECK();
   return PH_OK;
 }
@@ -611,7 +617,13 @@ int ph_pack_all_launch(const PhPackAll* t, void* packed, int nplanes, hipStream_
   }
   if (nplanes == -3) {
     if (!tiled) return PH_EINVAL;
-    hipLaunchKernelGGL(pack_all_tiled_hp_kernel<false>, dim3(pt.tstart[t->n]), dim3(256), 0, st, *t, pt, (f16*)packed, 0, ph_tap5_switch(-1) | (ph_tap6_switch(-1) << 1));
+    for (int u = 0; u < t->n; ++u) {      // (the fragment-major layouts exist for the shapes of their kernels only)
+      const int ff = t->frag[u] & 3, fd = (t->frag[u] >> 2) & 3;
+      if ((ff == PH_WFRAG_TAP5 || fd == PH_WFRAG_TAP5) && !(t->O[u] == 64 && t->I[u] == 64 && t->NT[u] == 9)) return PH_EINVAL;
+      if (ff == PH_WFRAG_TAP6 && !(t->O[u] == 2 * t->I[u] && t->NT[u] == 9)) return PH_EINVAL;
+      if (ff == 3 || fd == 3 || fd == PH_WFRAG_TAP6) return PH_EINVAL;
+    }
+    hipLaunchKernelGGL(pack_all_tiled_hp_kernel<false>, dim3(pt.tstart[t->n]), dim3(256), 0, st, *t, pt, (f16*)packed, 0);
   } else if (tiled && nplanes == 1)
     hipLaunchKernelGGL(pack_all_tiled_kernel<1>, dim3(pt.tstart[t->n]), dim3(256), 0, st, *t, pt, (bf16*)packed);
   else if (tiled && nplanes == 3)
@@ -627,15 +639,17 @@ int ph_wgrad_tile_h(int S) { return S == 1 ? 8 : 4; }
 
 int ph_wgrad_launch(const PhWgrad* p, int prec, hipStream_t st) {
   if (p->Cin % 64 || p->Cout % 64 || p->nchunks < 1) return PH_EINVAL;
-  if (prec == PH_PREC_BF16) return launch_wg_T<bf16>(*p, st);
+  if (prec == PH_PREC_BF16) { ph_dispatch_note(PH_DK_WGRAD_BF16); return launch_wg_T<bf16>(*p, st); }
   if (prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1) {
     PhWgrad q = *p;
     q.hp_hi_only = prec == PH_PREC_FP16X1;
+    ph_dispatch_note(PH_DK_WGRAD_HP16);
     return launch_wg_T<hp16>(q, st);
   }
   if (PH_IS_SPLIT_PREC(prec)) {
     PhWgrad q = *p;
     q.prod6 = prec == PH_PREC_BF16X6;
+    ph_dispatch_note(PH_DK_WGRAD_F32);
     return launch_wg_T<float>(q, st);
   }
   return PH_EINVAL;

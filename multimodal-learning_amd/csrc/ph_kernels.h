@@ -87,7 +87,36 @@ struct PhTapConv {
   int ncls;
   int c_ntaps[4], c_oa_h[4], c_oa_w[4], c_OHt[4], c_OWt[4];
   int c_dy[4][4], c_dx[4][4], c_wtap[4][4];
+  // half-pair modes: the layout the weights were packed in (PH_WFRAG_*, chosen by whoever packed them from the same eligibility
+  // and switch state that picks the kernel).  conv_tap5.hip / conv_tap6.hip run only on their fragment-major layout, every other
+  // kernel only on the row-major one: a mismatch is PH_EINVAL, never a read of a layout the kernel does not understand
+  int w_frag;
+  int no_tap6b;          // perf mode: keep a stride-2 forward off conv_tap6b.hip (the plan's no_masked A/B and test switch)
 };
+#define PH_WFRAG_ROW 0       // [tap][O][3 I] (forward) / [tap][I][3 O] (dgrad)
+#define PH_WFRAG_TAP5 1      // conv_tap5.hip's 64 x 64 x 9 fragment-major slabs (3x3 stride-1, Cin = Cout = 64)
+#define PH_WFRAG_TAP6 2      // conv_tap6.hip's [tap][O / 64][I / 64][block 3] slabs (3x3 / stride 2 forward, Cout = 2 Cin)
+// the layout a half-pair convolution over descriptor p (S, prec as for ph_tapconv_launch) needs under the current switches
+int ph_tapconv_hp_wfrag(const PhTapConv* p, int S, int prec);
+// kernel-family dispatch record for the tests (host side, not part of the public C-ABI): every launcher ORs the bit of the
+// family it runs; ph_debug_dispatch_mask() reads and ph_debug_dispatch_reset() clears it (conv_tap.hip)
+#define PH_DK_GEN1_BF16 (1u << 0)     // first-generation tapconv_kernel, T = bf16 (launch_T)
+#define PH_DK_GEN1_HP16 (1u << 1)     // ... T = hp16 (half-pair modes)
+#define PH_DK_GEN1_F32 (1u << 2)      // ... T = float (split-plane modes)
+#define PH_DK_TAP2 (1u << 3)          // conv_tap2.hip <2,2,4> dense stride-1
+#define PH_DK_TAP2_MASKED (1u << 4)   // conv_tap2.hip <2,2,4> masked stride-2 grid
+#define PH_DK_TAP2_L1 (1u << 5)       // conv_tap2.hip two-group layer-1 kernel (Cin = Cout = 64)
+#define PH_DK_TAP3 (1u << 6)          // conv_tap3.hip perf form
+#define PH_DK_TAP3_HP (1u << 7)       // conv_tap3.hip half-pair form
+#define PH_DK_TAP4 (1u << 8)
+#define PH_DK_TAP5 (1u << 9)
+#define PH_DK_TAP6 (1u << 10)
+#define PH_DK_TAP6B (1u << 11)
+#define PH_DK_TAP7 (1u << 12)
+#define PH_DK_WGRAD_BF16 (1u << 13)   // conv_wgrad.hip, per activation type
+#define PH_DK_WGRAD_HP16 (1u << 14)
+#define PH_DK_WGRAD_F32 (1u << 15)
+void ph_dispatch_note(unsigned bits);
 int ph_tapconv_launch(const PhTapConv* p, int S, int prec, hipStream_t st);
 double ph_tapconv_bytes(const PhTapConv& p, int S, int es);
 int ph_tapconv_stat_parts(const PhTapConv* p, int S, int prec);
@@ -205,12 +234,13 @@ struct PhPackAll {
   const float* w[20];
   size_t dst_fwd[20], dst_dg[20], start[21];
   int O[20], I[20], NT[20];
+  int frag[20];          // nplanes = -3: PH_WFRAG_* of the forward layout (bits 0-1) | (PH_WFRAG_* of the dgrad layout) << 2
   int n;
   size_t total;
 };
 // nplanes: 1 (bf16), 3 (three bf16 split planes), -3 (PH_PREC_FP16X3: fp16 [hi 2^11 | lo | hi] per 64-channel K slice, (hi, lo) = the half-pair split)
 int ph_pack_all_launch(const PhPackAll* t, void* packed, int nplanes, hipStream_t st);
-int ph_pack_w_hp_launch(const float* w, void* packed, int O, int I, int KS, int dgrad, hipStream_t st);   // one conv, same layout
+int ph_pack_w_hp_launch(const float* w, void* packed, int O, int I, int KS, int dgrad, int wfrag, hipStream_t st);   // one conv, layout PH_WFRAG_*
 int ph_pack_w_stem_hp_launch(const float* w, void* packed, hipStream_t st);
 
 // ---- BatchNorm / elementwise (bn_act.hip).  `prec` selects the activation type (bf16 | float).

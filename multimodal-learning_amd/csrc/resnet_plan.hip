@@ -26,7 +26,27 @@ struct Unit {
   size_t wplane;           // elements per plane (lo plane follows hi)
   size_t y_off;            // byte offset of raw conv output in ws
   size_t st_off;           // byte offset of [mean, invstd, scale, shift] (4*C floats)
+  // PH_PREC_FP16X3: layouts (PH_WFRAG_*) of the fwd / dgrad weights, chosen at pack time from the descriptors below
+  mutable int wfrag_f = 0, wfrag_d = 0;
 };
+
+// geometry of unit u's forward and stride-1 dgrad descriptors (tensors, statistics and fused fields are the caller's)
+void fwd_geometry(const Unit& u, PhTapConv& t) {
+  t.IH = u.IH; t.IW = u.IW; t.Cin = u.Cin; t.Cout = u.Cout;
+  t.OHt = u.OH; t.OWt = u.OW; t.OH = u.OH; t.OW = u.OW; t.os = 1; t.oa_h = 0; t.oa_w = 0;
+  t.iy0 = -u.pad; t.ix0 = -u.pad; t.ntaps = u.KS * u.KS;
+  for (int k = 0; k < t.ntaps; ++k) { t.dy[k] = k / u.KS; t.dx[k] = k % u.KS; t.wtap[k] = k; }
+}
+void dgrad_s1_geometry(const Unit& u, PhTapConv& t) {
+  t.IH = u.OH; t.IW = u.OW; t.Cin = u.Cout; t.Cout = u.Cin;
+  t.OH = u.IH; t.OW = u.IW;
+  t.OHt = u.IH; t.OWt = u.IW; t.os = 1; t.oa_h = 0; t.oa_w = 0;
+  t.iy0 = -(u.KS - 1 - u.pad); t.ix0 = t.iy0; t.ntaps = u.KS * u.KS;
+  for (int k = 0; k < t.ntaps; ++k) {
+    const int dyy = k / u.KS, dxx = k % u.KS;
+    t.dy[k] = dyy; t.dx[k] = dxx; t.wtap[k] = (u.KS - 1 - dyy) * u.KS + (u.KS - 1 - dxx);
+  }
+}
 struct Block {
   int u1, u2, uds;
   size_t in_off, a1_off, out_off;   // byte offsets of the block input / post-bn1-relu / output activations
@@ -93,6 +113,25 @@ int stem_chunks(int B, int OH, int OW, int* tpc) {
   int want = ntiles < 1024 ? ntiles : 1024;   // 4 workgroups per CU: the per-tile staging latency is hidden by occupancy
   *tpc = cdiv(ntiles, want);
   return cdiv(ntiles, *tpc);
+}
+
+// the half-pair weight layout of every unit (Unit::wfrag_f / wfrag_d) under the current switches, and its signature: a packed
+// buffer is valid for every plan whose signature equals the one it was packed under (ph_resnet_plan_layout_sig)
+unsigned long long refresh_layouts(const PhResnetPlan* P) {
+  unsigned long long sig = 1469598103934665603ull;      // FNV-1a over (unit, fwd layout, dgrad layout)
+  for (size_t i = 1; i < P->units.size(); ++i) {
+    const Unit& u = P->units[i];
+    PhTapConv f{}, d{};
+    fwd_geometry(u, f);
+    u.wfrag_f = ph_tapconv_hp_wfrag(&f, u.S, P->prec);
+    u.wfrag_d = PH_WFRAG_ROW;
+    if (u.S == 1) { dgrad_s1_geometry(u, d); u.wfrag_d = ph_tapconv_hp_wfrag(&d, 1, P->prec); }
+    for (unsigned long long v : {(unsigned long long)i, (unsigned long long)u.wfrag_f, (unsigned long long)u.wfrag_d}) {
+      sig ^= v;
+      sig *= 1099511628211ull;
+    }
+  }
+  return sig;
 }
 
 }  // namespace
@@ -191,6 +230,7 @@ PhResnetPlan* ph_resnet_plan_create(int B, int H, int W, int prec) {
   P->cc2_off = take(2 * 512 * sizeof(float));
   P->ws_bytes = off;
   P->packed_bytes = woff * sizeof(bf16);
+  refresh_layouts(P);
   return P;
 }
 
@@ -208,6 +248,7 @@ int ph_resnet_unit_shape(const PhResnetPlan* P, int u, int* out4) {
 // params: per unit 6 pointers [w (OIHW f32), gamma, beta, running_mean, running_var, num_batches_tracked(i64)]
 int ph_resnet_pack_weights(const PhResnetPlan* P, const void* const* params, void* packed, hipStream_t st) {
   if (!P || !params || !packed) return PH_EINVAL;
+  refresh_layouts(P);
   bf16* pk = reinterpret_cast<bf16*>(packed);
   int rc = P->prec == PH_PREC_FP16X3
                ? ph_pack_w_stem_hp_launch(reinterpret_cast<const float*>(params[0]), pk + P->units[0].wf_off, st)
@@ -221,6 +262,8 @@ int ph_resnet_pack_weights(const PhResnetPlan* P, const void* const* params, voi
     t.w[k] = reinterpret_cast<const float*>(params[i * 6 + 0]);
     t.dst_fwd[k] = u.wf_off; t.dst_dg[k] = u.wd_off;
     t.O[k] = u.Cout; t.I[k] = u.Cin; t.NT[k] = u.KS * u.KS;
+    // the layouts the kernels of this unit's launches read (refresh_layouts above: the eligibility and switch state that picks them)
+    t.frag[k] = u.wfrag_f | (u.wfrag_d << 2);
     t.start[k] = acc;
     acc += u.wplane;
   }
@@ -259,10 +302,9 @@ int conv_fwd(const Ctx& c, int ui, const void* in, const float* in_scale = nullp
   t.in = in; t.w = c.pk + u.wf_off; t.wplane = u.wplane;
   t.in_scale = in_scale; t.in_shift = in_shift;
   t.out = c.ws + u.y_off; t.stats = c.eval ? nullptr : reinterpret_cast<float*>(c.ws + P->parts_off);
-  t.B = P->B; t.IH = u.IH; t.IW = u.IW; t.Cin = u.Cin; t.Cout = u.Cout;
-  t.OHt = u.OH; t.OWt = u.OW; t.OH = u.OH; t.OW = u.OW; t.os = 1; t.oa_h = 0; t.oa_w = 0;
-  t.iy0 = -u.pad; t.ix0 = -u.pad; t.ntaps = u.KS * u.KS;
-  for (int k = 0; k < t.ntaps; ++k) { t.dy[k] = k / u.KS; t.dx[k] = k % u.KS; t.wtap[k] = k; }
+  t.B = P->B;
+  fwd_geometry(u, t);
+  t.w_frag = u.wfrag_f; t.no_tap6b = c.no_masked;
   int S = u.S;
   // 3x3 / stride 2 in perf mode: a stride-1 MASKED tap grid over the four pixel-parity planes of the input (conv_tap2.hip)
   // (round 6: conv_tap6b.hip takes the un-masked stride-2 descriptor itself)
@@ -305,14 +347,10 @@ int conv_dgrad(const Ctx& c, int ui, const void* dy, void* dx, const void* res_g
   t.out = dx; t.stats = nullptr; t.res_g = res_g; t.res_a = res_a;
   t.B = P->B; t.IH = u.OH; t.IW = u.OW; t.Cin = u.Cout; t.Cout = u.Cin;
   t.OH = u.IH; t.OW = u.IW;
+  t.w_frag = u.wfrag_d;
   if (fused_parts) *fused_parts = 0;
   if (u.S == 1) {
-    t.OHt = u.IH; t.OWt = u.IW; t.os = 1; t.oa_h = 0; t.oa_w = 0;
-    t.iy0 = -(u.KS - 1 - u.pad); t.ix0 = t.iy0; t.ntaps = u.KS * u.KS;
-    for (int k = 0; k < t.ntaps; ++k) {
-      const int dyy = k / u.KS, dxx = k % u.KS;
-      t.dy[k] = dyy; t.dx[k] = dxx; t.wtap[k] = (u.KS - 1 - dyy) * u.KS + (u.KS - 1 - dxx);
-    }
+    dgrad_s1_geometry(u, t);
     if (bst && fused_parts && bst->u >= 0 && P->prec == PH_PREC_BF16 && bst_switch(-1)) {
       const Unit& bu = P->units[bst->u];
       PhTapConv f = t;
@@ -879,6 +917,8 @@ extern "C" {
 // PH_PREC_BF16X6 plan = six-product forward (logits, losses and GK-Refine weights at parity-mode accuracy), three-product
 // backward (gradients at ~1e-3 relative); -1 = follow the plan.  Both arithmetics read the same fp32 activations and the
 // same packed weight planes.
+unsigned long long ph_resnet_plan_layout_sig(const PhResnetPlan* P) { return P ? refresh_layouts(P) : 0; }
+
 int ph_resnet_plan_set_backward_prec(const PhResnetPlan* P, int prec) {
   // (a half-pair plan admits PH_PREC_FP16X1 - the hi planes' product alone in dgrad / wgrad - a split-plane plan the other
   // split-plane arithmetic)

@@ -290,8 +290,10 @@ class ResNet(nn.Module):
         follow = getattr(self, "_follow_epoch", None)
         if follow is None:
             follow = any(c.weight.requires_grad for c, _ in self._units())
-        vers = (ops.weight_epoch() if follow else -1, plan.key[3]) + tuple((c.weight._version, c.weight.data_ptr())
-                                                                for c, _ in self._units())
+        # (+ the plan's packed-weight layout: in half-pair mode which units are fragment-major follows the kernel switches; every
+        # plan of one precision shares this buffer, so a plan whose layout differs re-packs instead of misreading it)
+        vers = (ops.weight_epoch() if follow else -1, plan.key[3], lib().ph_resnet_plan_layout_sig(plan.h)) + \
+            tuple((c.weight._version, c.weight.data_ptr()) for c, _ in self._units())
         if self._packed is None or self._packed_versions != vers or self._packed.numel() != plan.packed_bytes:
             dev = self.conv1.weight.device
             if self._packed is None or self._packed.numel() != plan.packed_bytes:

@@ -1,7 +1,30 @@
 """Helpers shared by the -m gpu parity tests (they call the product through its C-ABI / module API and
 compare with the CPU oracle)."""
+import ctypes
+
 import numpy as np
 import torch
+
+# kernel families of the tap-conv / weight-gradient launchers, in the bit order of ph_debug_dispatch_mask (csrc/ph_kernels.h PH_DK_*)
+DISPATCH_FAMILIES = ["gen1_bf16", "gen1_hp16", "gen1_f32", "tap2", "tap2_masked", "tap2_l1", "tap3", "tap3_hp", "tap4", "tap5",
+                     "tap6", "tap6b", "tap7", "wgrad_bf16", "wgrad_hp16", "wgrad_f32"]
+
+
+def dispatch_lib():
+    """The library with its (non-public) dispatch-record hooks bound: ph_debug_dispatch_mask / ph_debug_dispatch_reset."""
+    from multimodal_learning_amd._lib import lib
+    L = lib()
+    L.ph_debug_dispatch_mask.restype = ctypes.c_uint
+    L.ph_debug_dispatch_mask.argtypes = []
+    L.ph_debug_dispatch_reset.restype = None
+    L.ph_debug_dispatch_reset.argtypes = []
+    return L
+
+
+def dispatched(L):
+    """The kernel families launched since the last ph_debug_dispatch_reset()."""
+    m = L.ph_debug_dispatch_mask()
+    return {f for i, f in enumerate(DISPATCH_FAMILIES) if m >> i & 1}
 
 
 def nhwc(x, dtype):

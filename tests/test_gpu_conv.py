@@ -82,6 +82,37 @@ def test_half_pair_storage_round_trip():
     assert ((y - x).abs()[small] <= 2.0 ** -24).all()  # fp16 subnormal spacing of the hi half, absolute
     z = hp_unpack(hp_pack(x * 2.0 ** -20, scale=2.0 ** 20))
     assert torch.equal(z, y)
+    # non-finite inputs (ph_common.h hp_split): a NaN stays a NaN, +-Inf and values beyond the fp16 range saturate to +-65504
+    s = torch.zeros(64, device="cuda")
+    s[:6] = torch.tensor([float("nan"), float("inf"), -float("inf"), 1e6, -1e6, 65504.0]).cuda()
+    u = hp_unpack(hp_pack(s)).cpu()
+    assert torch.isnan(u[0])
+    assert u[1:6].tolist() == [65504.0, -65504.0, 65504.0, -65504.0, 65504.0]
+    assert torch.equal(u[6:], torch.zeros(58))
+
+
+def test_nan_in_half_pair_forward_input_reaches_its_receptive_field():
+    """A NaN in a PH_PREC_FP16X3 forward input propagates to exactly the outputs whose 3x3 window holds it (the layer-1 kernel,
+    conv_tap5.hip, and the stride-2 one, conv_tap6.hip): no NaN is lost to the saturating split or spread by a stale tile."""
+    from tests.gpu_util import nhwc, hp_pack
+    m, L, ptr, stream, check = _setup()
+    for Cin, Cout, S, H, W in ((64, 64, 1, 10, 13), (64, 128, 2, 11, 14)):
+        B = 2
+        g = torch.Generator().manual_seed(3)
+        x = torch.randn(B, Cin, H, W, generator=g)
+        x[1, 5, 4, 7] = float("nan")
+        w = torch.randn(Cout, Cin, 3, 3, generator=g) * 0.05
+        OH, OW = (H - 1) // S + 1, (W - 1) // S + 1
+        ws = torch.empty(L.ph_conv2d_workspace_bytes(B, Cin, H, W, Cout, 3, S, 1), device="cuda", dtype=torch.uint8)
+        y = torch.zeros(B, OH, OW, Cout, device="cuda")
+        xd, wd = hp_pack(nhwc(x, torch.float32)), w.cuda()
+        check(L.ph_conv2d_fwd(ptr(xd), ptr(wd), ptr(y), None, None, B, Cin, H, W, Cout, 3, S, 1, 3, ptr(ws), stream()), "fwd")
+        want = torch.zeros(B, OH, OW, dtype=torch.bool)
+        for r in range(OH):
+            for c in range(OW):
+                want[1, r, c] = abs(r * S - 4) <= 1 and abs(c * S - 7) <= 1
+        got = torch.isnan(y.cpu())
+        assert torch.equal(got.all(dim=3), want) and torch.equal(got.any(dim=3), want)
 
 
 @pytest.mark.parametrize("case", CASES)

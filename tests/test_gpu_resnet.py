@@ -60,6 +60,46 @@ def test_student_forward_backward_parity_mode(golden_dir, pmode):
         m.set_precision("bf16")
 
 
+@pytest.mark.parametrize("pmode", ["bf16x6", "fp16x3"])
+def test_student_non_square_maps_two_shapes(pmode):
+    """Non-square maps through the whole network: a student forward and backward at B = 3, 72 x 120 and then 120 x 72 ON THE SAME
+    NET (no weight update in between: the second plan reuses the packed weights of the first) against oracle.resnet_forward in
+    float64, at the tolerances of test_student_forward_backward_parity_mode.  In half-pair mode the packed weights carry
+    fragment-major layouts for some units: a plan that read them with another layout would be off by O(1)."""
+    import multimodal_learning_amd as m
+    import oracle
+    from oracle import weights as W
+    from tests.gpu_util import Report
+    m.set_precision(pmode)
+    R = Report(f"student fwd/bwd, {pmode}, non-square maps vs float64 oracle (B=3)")
+    try:
+        net = _student()
+        for H, Wd in ((72, 120), (120, 72)):
+            g = torch.Generator().manual_seed(H)
+            x = torch.rand(3, 3, H, Wd, generator=g) * 2 - 1
+            for p in net.parameters():
+                p.grad = None
+            f3, feat, hazard, pred, _ = net(x_path=x.cuda())
+            wf, wh = torch.linspace(0.5, 1.5, 128), torch.tensor([1.0, -2.0, 0.5])
+            ((feat * wf.cuda()).sum() + (hazard * wh.cuda()).sum() + 0.1 * f3.sum()).backward()
+            sd = {k: v.double() for k, v in W.make_state_dict(W.student_shapes(), 1).items()}
+            names = ["fc_new2.weight", "fc_new1.0.weight", "layer4.1.bn2.weight", "layer3.1.conv2.weight",
+                     "layer2.0.downsample.0.weight", "layer1.0.conv1.weight", "layer1.1.conv2.weight", "bn1.weight", "conv1.weight"]
+            for k in names:
+                sd[k].requires_grad_(True)
+            rf3, rfeat, rhaz, rpred, _ = oracle.resnet_forward(x.double(), sd)
+            ((rfeat * wf.double()).sum() + (rhaz * wh.double()).sum() + 0.1 * rf3.sum()).backward()
+            tag = f"{H}x{Wd}"
+            R.close(rf3.detach(), f3, 1e-3, 0, f"f3 {tag}"); R.close(rfeat.detach(), feat, 1e-3, 0, f"features {tag}")
+            R.close(rhaz.detach(), hazard, 1e-3, 0, f"hazard {tag}"); R.close(rpred.detach(), pred, 1e-3, 0, f"pred {tag}")
+            P = dict(net.named_parameters())
+            for k in names:
+                R.close(sd[k].grad, P[k].grad, 1e-4, 1e-2, f"g {k} {tag}")
+        R.finish()
+    finally:
+        m.set_precision("bf16")
+
+
 def test_student_forward_perf_mode_noise_floor():
     """Perf mode (single-pass bf16) cannot meet 1e-3 on an untrained BN network - nor can ANY bf16 arithmetic:
     one bf16 ulp flipped by a different fp32 summation order is amplified by the 17 train-mode BN layers.
@@ -564,14 +604,23 @@ def test_masked_stride2_grid_vs_first_generation_kernel(B, H):
     from oracle.step import synthetic_batch
     m.set_precision("bf16")
     x = synthetic_batch(B, H, seed=33)["x_path"].cuda()
-    res = {}
+    from tests.gpu_util import dispatch_lib, dispatched
+    L = dispatch_lib()
+    res, fams = {}, {}
     for no_masked in (True, False):
         net = _student()
         net.train()
         net._no_masked = no_masked
+        torch.cuda.synchronize()
+        L.ph_debug_dispatch_reset()
         f3, feat, hazard, pred, _ = net(x_path=x)
+        torch.cuda.synchronize()
+        fams[no_masked] = dispatched(L)
         (feat.square().mean() + hazard.sum()).backward()
         res[no_masked] = (f3.detach(), feat.detach(), torch.cat([p.grad.flatten() for p in net.parameters() if p.grad is not None]))
+    # the two forwards ran different kernels for the stride-2 convolutions (no_masked: the first-generation kernel)
+    assert "tap6b" in fams[False], fams
+    assert "tap6b" not in fams[True] and "tap2_masked" not in fams[True], fams
     for (a, b), tol in zip(zip(res[True][:2], res[False][:2]), (2e-2, 6e-2)):   # trunk; head behind a small-batch BatchNorm1d
         assert torch.isfinite(b).all()
         assert (a - b).norm() <= tol * a.norm(), ((a - b).norm() / a.norm()).item()
