@@ -395,6 +395,17 @@ int ph_cox_loss_grad(const float* theta, const float* survtime, const float* cen
  * loss_cox = cox sum, loss_pred_KD = kd_weight * kd sum, and total = lambda_cox * loss_cox + loss_pred_KD.
  * dgrad [3][B] = d total / d (pred, pred_path, pred_omic), or
  * NULL for the forward-only evaluation loss.
+ * Data parallelism (the reference's nn.DataParallel computes these losses on the outputs gathered over every replica,
+ * train_test_MT.py:63-64, so every risk set spans the global batch B = world * n):
+ * ph_surv_pack_rows writes this replica's n rows into ONE staging block rows [8][n], quantity-major in this order:
+ *   0 pred, 1 pred_path, 2 pred_omic, 3 ema_pred, 4 ema_pred_path, 5 ema_pred_omic, 6 survtime, 7 censor
+ * (num_teachers 0: rows 3..5 are written as zeros and the ema pointers may be NULL).  1 <= n <= 4096.  One all-gather of
+ * the block then lands the replicas' blocks rank by rank: gathered [world][8][n], global row i = row i % n of block i / n.
+ * ph_surv_stage1_loss_grad_gathered reads that gathered buffer as it lands and computes the nine `terms` over the global
+ * batch, and dgrad_local [3][n] = the rows rank*n .. rank*n + n - 1 of d total / d (pred, pred_path, pred_omic) (NULL:
+ * forward only).  terms and dgrad_local are BITWISE what ph_surv_stage1_loss_grad computes on the concatenated vectors
+ * (one shared device body, same summation order).  world >= 1, 0 <= rank < world, n >= 1, world * n <= 4096,
+ * num_teachers 0..3; anything else returns PH_EINVAL before any HIP call.
  * ph_cindex_counts: lifelines' concordance_index(t, -h, e) rule (utils.py:424-425) for nvec in 1..3 risk vectors h0..h2
  * against one (survtime, event) pair: counts[v*3 + {0,1,2}] = comparable, concordant, tied pairs (exact 64-bit integers,
  * independent of row order).  Pair (i, j) is comparable iff e_i = 1 and (t_i < t_j, or t_i == t_j and e_j = 0);
@@ -408,6 +419,11 @@ int ph_surv_stage1_loss_grad(const float* pred, const float* pred_path, const fl
                              const float* ema_pred_path, const float* ema_pred_omic, const float* survtime,
                              const float* censor, int B, int num_teachers, float lambda_cox, float kd_weight, float* terms,
                              float* dgrad, ph_stream_t stream);
+int ph_surv_pack_rows(const float* pred, const float* pred_path, const float* pred_omic, const float* ema_pred,
+                      const float* ema_pred_path, const float* ema_pred_omic, const float* survtime, const float* censor, int n,
+                      int num_teachers, float* rows, ph_stream_t stream);
+int ph_surv_stage1_loss_grad_gathered(const float* rows, int world, int n, int rank, int num_teachers, float lambda_cox,
+                                      float kd_weight, float* terms, float* dgrad_local, ph_stream_t stream);
 int ph_cindex_counts(const float* survtime, const float* event, const float* h0, const float* h1, const float* h2, int nvec,
                      int N, int64_t* counts, ph_stream_t stream);
 size_t ph_pkt_workspace_bytes(int B, int D);

@@ -70,6 +70,8 @@ SIGNATURES = {
     "ph_sigmoid_range_bwd": (i32, [vp, vp, vp, vp, i32, vp]),
     "ph_ema_update_dev": (i32, [vp, vp, sz, vp, vp]),
     "ph_surv_stage1_loss_grad": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp]),
+    "ph_surv_pack_rows": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ph_surv_stage1_loss_grad_gathered": (i32, [vp, i32, i32, i32, i32, f32, f32, vp, vp, vp]),
     "ph_cindex_counts": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "ph_pkt_workspace_bytes": (sz, [i32, i32]),
     "ph_pkt_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),

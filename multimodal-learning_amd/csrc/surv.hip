@@ -46,26 +46,49 @@ __global__ void sigmoid_range_bwd_kernel(const float* __restrict__ dpred, const 
   dh[i] = dpred[i] * range[0] * s * (1.f - s);
 }
 
+// Addressing of the survival rows: quantity k (SURV_Q_* below, the order of the packed staging block) of global row i.
+// SurvPtrRows: one device vector per quantity (ph_surv_stage1_loss_grad).  SurvGatheredRows: the all-gathered staging
+// blocks [world][8][n], rank-blocked as the collective lands them (ph_surv_stage1_loss_grad_gathered): global row i is row
+// i % n of rank i / n's block.
+enum { SURV_Q_P0 = 0, SURV_Q_Q0 = 3, SURV_Q_T = 6, SURV_Q_C = 7, SURV_NQ = 8 };
+
+struct SurvPtrRows {
+  const float* q[SURV_NQ];
+  __device__ __forceinline__ float operator()(int k, int i) const { return q[k][i]; }
+};
+
+struct SurvGatheredRows {
+  const float* rows;
+  int n;
+  __device__ __forceinline__ float operator()(int k, int i) const {
+    const int r = i / n;
+    return rows[((size_t)r * SURV_NQ + k) * n + (i - r * n)];
+  }
+};
+
 // One workgroup.  For each student prediction k (0 fuse, 1 path, 2 omic):
 //   S_ki = sum_j [t_j >= t_i] exp(p_kj);  cox_k = -mean_i c_i (p_ki - log S_ki)           (utils.py:361-376)
 //   d cox_k / d p_kl = -(c_l - exp(p_kl) sum_i c_i [t_l >= t_i] / S_ki) / B
 // The three risk sums share one pass over t (LDS).  The per-prediction summation order is cox_kernel's, so each Cox
 // term is bitwise the one ph_cox_loss_grad computes.  KD terms: mse(a, b) = mean_i (a_i - b_i)^2 over the EMA
 // teacher's predictions q (constants), combined as train_test_MT.py:180-201 for nt = 1 / 2 / 3 (nt = 0: off).
-__global__ __launch_bounds__(SURV_THREADS) void surv_stage1_kernel(
-    const float* __restrict__ p0, const float* __restrict__ p1, const float* __restrict__ p2, const float* __restrict__ q0,
-    const float* __restrict__ q1, const float* __restrict__ q2, const float* __restrict__ t, const float* __restrict__ c,
-    int B, int nt, float lambda_cox, float kd_weight, float* __restrict__ terms, float* __restrict__ dgrad) {
+// The body is shared by both addressing forms: every sum runs over the B global rows in the same order whatever the
+// addressing, so the gathered form is bitwise the form on the concatenated vectors.  dgrad [3][nout] receives the rows
+// lo .. lo + nout - 1 (each row's gradient is computed on its own: the range changes no value).
+template <class Rows>
+__device__ __forceinline__ void surv_stage1_body(const Rows& rows, int B, int nt, float lambda_cox, float kd_weight,
+                                                 float* __restrict__ terms, float* __restrict__ dgrad, int lo, int nout) {
   __shared__ float tt[SURV_MAX_B];
   __shared__ float ex[3][SURV_MAX_B];
   __shared__ float w[3][SURV_MAX_B];      // c_i / S_ki
   __shared__ float red[SURV_THREADS];
   const int tid = threadIdx.x;
-  const float* p[3] = {p0, p1, p2};
+  auto p = [&](int k, int i) { return rows(SURV_Q_P0 + k, i); };
+  auto q = [&](int k, int i) { return rows(SURV_Q_Q0 + k, i); };
   for (int i = tid; i < B; i += SURV_THREADS) {
-    tt[i] = t[i];
+    tt[i] = rows(SURV_Q_T, i);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) ex[k][i] = expf(p[k][i]);
+    for (int k = 0; k < 3; ++k) ex[k][i] = expf(p(k, i));
   }
   __syncthreads();
   float l[3] = {0.f, 0.f, 0.f};
@@ -77,11 +100,11 @@ __global__ __launch_bounds__(SURV_THREADS) void surv_stage1_kernel(
 #pragma unroll
       for (int k = 0; k < 3; ++k) s[k] += r ? ex[k][j] : 0.f;
     }
-    const float ci = c[i];
+    const float ci = rows(SURV_Q_C, i);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       w[k][i] = ci / s[k];
-      l[k] += (p[k][i] - logf(s[k])) * ci;
+      l[k] += (p(k, i) - logf(s[k])) * ci;
     }
   }
   float cox[3];
@@ -90,7 +113,6 @@ __global__ __launch_bounds__(SURV_THREADS) void surv_stage1_kernel(
   // consistency terms; m[a][b] = mse(p_a, q_b) for the pairs the teacher count uses
   float kd[3] = {0.f, 0.f, 0.f};
   if (nt > 0) {
-    const float* q[3] = {q0, q1, q2};
     float part[3][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -101,7 +123,7 @@ __global__ __launch_bounds__(SURV_THREADS) void surv_stage1_kernel(
       for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 3; ++b) {
-          const float d = p[a][i] - q[b][i];
+          const float d = p(a, i) - q(b, i);
           part[a][b] += d * d;
         }
     }
@@ -144,8 +166,8 @@ __global__ __launch_bounds__(SURV_THREADS) void surv_stage1_kernel(
   }
   if (!dgrad) return;
   const float inv_b = 1.f / (float)B;
-  const float* q[3] = {q0, q1, q2};
-  for (int l0 = tid; l0 < B; l0 += SURV_THREADS) {
+  for (int lr = tid; lr < nout; lr += SURV_THREADS) {
+    const int l0 = lo + lr;
     float a[3] = {0.f, 0.f, 0.f};
     const float tl = tt[l0];
     for (int i = 0; i < B; ++i) {
@@ -153,26 +175,58 @@ __global__ __launch_bounds__(SURV_THREADS) void surv_stage1_kernel(
 #pragma unroll
       for (int k = 0; k < 3; ++k) a[k] += r ? w[k][i] : 0.f;
     }
-    const float cl = c[l0];
+    const float cl = rows(SURV_Q_C, l0);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       float g = lambda_cox * (-(cl - ex[k][l0] * a[k]) * inv_b);
       if (nt > 0) {
-        const float pk = p[k][l0];
+        const float pk = p(k, l0);
         float dk;
         if (k == 0 || nt == 1) {
-          dk = 2.f * (pk - q[k][l0]) * inv_b;
+          dk = 2.f * (pk - q(k, l0)) * inv_b;
         } else {
           const int o = 3 - k;      // the other modality's teacher
-          float s = (pk - q[k][l0]) + (pk - q[0][l0]);
-          if (nt == 3) s += pk - q[o][l0];
+          float s = (pk - q(k, l0)) + (pk - q(0, l0));
+          if (nt == 3) s += pk - q(o, l0);
           dk = 2.f * s * inv_b / (float)nt;
         }
         g += kd_weight * dk;
       }
-      dgrad[(size_t)k * B + l0] = g;
+      dgrad[(size_t)k * nout + lr] = g;
     }
   }
+}
+
+__global__ __launch_bounds__(SURV_THREADS) void surv_stage1_kernel(
+    const float* __restrict__ p0, const float* __restrict__ p1, const float* __restrict__ p2, const float* __restrict__ q0,
+    const float* __restrict__ q1, const float* __restrict__ q2, const float* __restrict__ t, const float* __restrict__ c,
+    int B, int nt, float lambda_cox, float kd_weight, float* __restrict__ terms, float* __restrict__ dgrad) {
+  const SurvPtrRows rows = {{p0, p1, p2, q0, q1, q2, t, c}};
+  surv_stage1_body(rows, B, nt, lambda_cox, kd_weight, terms, dgrad, 0, B);
+}
+
+// The same over the all-gathered staging blocks [world][8][n] (B = world * n); dgrad [3][n] = this rank's rows.
+__global__ __launch_bounds__(SURV_THREADS) void surv_stage1_gathered_kernel(const float* __restrict__ gathered, int world,
+                                                                            int n, int rank, int nt, float lambda_cox,
+                                                                            float kd_weight, float* __restrict__ terms,
+                                                                            float* __restrict__ dgrad) {
+  const SurvGatheredRows rows = {gathered, n};
+  surv_stage1_body(rows, world * n, nt, lambda_cox, kd_weight, terms, dgrad, rank * n, n);
+}
+
+// This replica's survival rows into one staging block [8][n] (quantity-major, SURV_Q_* order), the one buffer the
+// all-gather carries.  nt = 0: the three teacher rows are written as zeros (their pointers may be NULL).
+__global__ void surv_pack_rows_kernel(const float* __restrict__ p0, const float* __restrict__ p1,
+                                      const float* __restrict__ p2, const float* __restrict__ q0,
+                                      const float* __restrict__ q1, const float* __restrict__ q2,
+                                      const float* __restrict__ t, const float* __restrict__ c, int n, int nt,
+                                      float* __restrict__ rows) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = blockIdx.y;
+  if (i >= n) return;
+  const float* src = k == 0 ? p0 : k == 1 ? p1 : k == 2 ? p2 : k == 3 ? q0 : k == 4 ? q1 : k == 5 ? q2 : k == 6 ? t : c;
+  const bool zero = nt == 0 && k >= SURV_Q_Q0 && k < SURV_Q_T;
+  rows[(size_t)k * n + i] = zero ? 0.f : src[i];
 }
 
 // ema = hyper[3] * ema + hyper[4] * p over parameters the optimiser does not update (requires_grad False: output_range /
@@ -282,6 +336,28 @@ int ph_surv_stage1_loss_grad(const float* pred, const float* pred_path, const fl
   if (num_teachers > 0 && (!ema_pred || !ema_pred_path || !ema_pred_omic)) return PH_EINVAL;
   hipLaunchKernelGGL(surv_stage1_kernel, dim3(1), dim3(SURV_THREADS), 0, st, pred, pred_path, pred_omic, ema_pred,
                      ema_pred_path, ema_pred_omic, survtime, censor, B, num_teachers, lambda_cox, kd_weight, terms, dgrad);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_surv_pack_rows(const float* pred, const float* pred_path, const float* pred_omic, const float* ema_pred,
+                      const float* ema_pred_path, const float* ema_pred_omic, const float* survtime, const float* censor, int n,
+                      int num_teachers, float* rows, hipStream_t st) {
+  if (!pred || !pred_path || !pred_omic || !survtime || !censor || !rows || n < 1 || n > SURV_MAX_B) return PH_EINVAL;
+  if (num_teachers < 0 || num_teachers > 3) return PH_EINVAL;
+  if (num_teachers > 0 && (!ema_pred || !ema_pred_path || !ema_pred_omic)) return PH_EINVAL;
+  hipLaunchKernelGGL(surv_pack_rows_kernel, dim3((n + 255) / 256, SURV_NQ), dim3(256), 0, st, pred, pred_path, pred_omic,
+                     ema_pred, ema_pred_path, ema_pred_omic, survtime, censor, n, num_teachers, rows);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_surv_stage1_loss_grad_gathered(const float* rows, int world, int n, int rank, int num_teachers, float lambda_cox,
+                                      float kd_weight, float* terms, float* dgrad_local, hipStream_t st) {
+  if (!rows || !terms || world < 1 || n < 1 || rank < 0 || rank >= world) return PH_EINVAL;
+  if ((int64_t)world * n > SURV_MAX_B || num_teachers < 0 || num_teachers > 3) return PH_EINVAL;
+  hipLaunchKernelGGL(surv_stage1_gathered_kernel, dim3(1), dim3(SURV_THREADS), 0, st, rows, world, n, rank, num_teachers,
+                     lambda_cox, kd_weight, terms, dgrad_local);
   PH_LAUNCH_CHECK();
   return PH_OK;
 }

@@ -7,6 +7,8 @@ there are exactly four exchanges:
   2. all-gather of (index, embed_s(f_s), embed_t(f_t)) rows -> identical CRD bank updates on every replica
   3. all-reduce of the 5x5 GK-Refine Gram matrix (global-batch gradient cosine)
   4. one-off all-reduce of the CRD normalisation sums (first batch only)
+The stage-1 teacher step under the survival task adds one all-gather of its packed survival rows (all_gather_into): the
+Cox risk sets span the global batch.
 BatchNorm keeps per-replica statistics - that IS the DataParallel semantics of the reference.
 Loss normalisers use the GLOBAL batch so summed gradients equal the single-process result."""
 import torch
@@ -103,6 +105,17 @@ class ReplicaSync:
         parts = [torch.empty_like(t) for _ in range(self.world_size)]
         dist.all_gather(parts, t.contiguous(), group=self.group)
         return torch.cat(parts, dim=0)
+
+    def all_gather_into(self, out, inp):
+        """One all-gather of `inp` into the caller's persistent buffer `out` [world, *inp.shape], rank-ordered as it lands
+        (no list, no concatenation): the caller keeps `out` across steps, so a captured graph reuses its address (the survival
+        rows of the stage-1 step, ops.SurvStage1GatheredFn).  Returns `out`."""
+        if tuple(out.shape) != (self.world_size,) + tuple(inp.shape) or out.dtype != inp.dtype or not out.is_contiguous():
+            raise ValueError("all_gather_into: out must be a contiguous [%d, %s] %s buffer, got %s %s"
+                             % (self.world_size, ", ".join(map(str, inp.shape)), inp.dtype, tuple(out.shape), out.dtype))
+        # as flat vectors: gloo takes the output only as the inputs' concatenation along dim 0, RCCL either form
+        dist.all_gather_into_tensor(out.view(-1), inp.contiguous().view(-1), group=self.group)
+        return out
 
     def attach(self, step):
         """Wire the CRD memories of a DistillStep to this group and make every replica start identical."""

@@ -442,6 +442,55 @@ class SurvStage1LossFn(torch.autograd.Function):
                 None, None, None, None, None, None, None, None)
 
 
+def surv_gather_buffers(n, world, device):
+    """The persistent buffers of SurvStage1GatheredFn: this replica's staging block [8, n] and the all-gathered blocks
+    [world, 8, n] (layout: include/pathomic_hip.h, ph_surv_pack_rows)."""
+    return (torch.empty(8, n, device=device, dtype=torch.float32),
+            torch.empty(world, 8, n, device=device, dtype=torch.float32))
+
+
+class SurvStage1GatheredFn(torch.autograd.Function):
+    """SurvStage1LossFn under data parallelism, over the GLOBAL batch: the reference's nn.DataParallel computes the Cox and
+    consistency terms on the outputs gathered from every replica (train_test_MT.py:63-64), so every risk set spans all
+    replicas' rows.  Forward: pack this replica's eight survival rows into `staging` (ph_surv_pack_rows), ONE all-gather
+    into `gathered` (sync.all_gather_into, rank-ordered), then the gathered kernel (ph_surv_stage1_loss_grad_gathered).
+    Returns the same (total, terms[8]) as SurvStage1LossFn on the concatenated batch, bitwise, identical on every replica.
+    Backward: d total / d (this replica's rows) x the incoming gradient, no collective - every replica evaluates the same
+    function of the gathered rows, so the partial derivative with respect to its own rows is complete, and the gradient
+    all-reduce adds the replicas' parameter gradients up (as train_step._GatherRowsFn for the t-SVD term).  `staging`,
+    `gathered`: surv_gather_buffers(n, world); the caller keeps them so that a captured graph reuses their addresses."""
+
+    @staticmethod
+    def forward(ctx, pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic, survtime, censor, num_teachers,
+                lambda_cox, kd_weight, sync, staging, gathered):
+        ps = [_f32(p).reshape(-1) for p in (pred, pred_path, pred_omic)]
+        qs = [None if q is None else _f32(q.detach()).reshape(-1) for q in (ema_pred, ema_pred_path, ema_pred_omic)]
+        n = ps[0].shape[0]
+        t, c = _f32(survtime).reshape(-1), _f32(censor).reshape(-1)
+        W, nt = sync.world_size, int(num_teachers)
+        if tuple(staging.shape) != (8, n) or tuple(gathered.shape) != (W, 8, n):
+            raise ValueError("SurvStage1GatheredFn: staging must be [8, %d] and gathered [%d, 8, %d], got %s and %s"
+                             % (n, W, n, tuple(staging.shape), tuple(gathered.shape)))
+        check(lib().ph_surv_pack_rows(ptr(ps[0]), ptr(ps[1]), ptr(ps[2]), ptr(qs[0]), ptr(qs[1]), ptr(qs[2]), ptr(t), ptr(c),
+                                      n, nt, ptr(staging), stream()), "ph_surv_pack_rows")
+        sync.all_gather_into(gathered, staging)
+        out = torch.empty(9, device=ps[0].device, dtype=torch.float32)
+        d = torch.empty(3, n, device=ps[0].device, dtype=torch.float32)
+        check(lib().ph_surv_stage1_loss_grad_gathered(ptr(gathered), W, n, sync.rank, nt, float(lambda_cox), float(kd_weight),
+                                                      ptr(out), ptr(d), stream()), "ph_surv_stage1_loss_grad_gathered")
+        ctx.save_for_backward(d)
+        ctx.shapes = (pred.shape, pred_path.shape, pred_omic.shape)
+        terms = out[:8]
+        ctx.mark_non_differentiable(terms)
+        return out[8], terms
+
+    @staticmethod
+    def backward(ctx, g, g_terms):
+        d, = ctx.saved_tensors
+        return ((d[0] * g).reshape(ctx.shapes[0]), (d[1] * g).reshape(ctx.shapes[1]), (d[2] * g).reshape(ctx.shapes[2]),
+                None, None, None, None, None, None, None, None, None, None, None)
+
+
 def surv_loss_terms(pred, pred_path, pred_omic, survtime, censor):
     """Forward-only Cox terms (fuse, path, omic) of one batch: the evaluation's per-batch loss, as a [3] device tensor."""
     ps = [_f32(p).reshape(-1) for p in (pred, pred_path, pred_omic)]

@@ -1204,6 +1204,9 @@ class _GatherRowsFn(torch.autograd.Function):
         return g[ctx.lo:ctx.lo + ctx.n].contiguous(), None
 
 
+SURV_MAX_GLOBAL_BATCH = 4096      # one workgroup of ph_surv_stage1_loss_grad(_gathered), every row in LDS
+
+
 class TeacherStage1Step:
     """The batch body of the stage-1 mean-teacher trainer (MICCAI-2022/train_test_MT.py:121-230) for the
     grading task: student PathomicNet forward/backward, EMA PathomicNet forward, three-branch NLL (:208-212),
@@ -1216,7 +1219,13 @@ class TeacherStage1Step:
         normalisers use the global batch, the vanilla CRD bank is updated identically on every replica, the
         cross-correlation of the orthogonality loss is all-reduced, and the t-SVD adjacency tensors are built over the
         global batch from all-gathered feature views (every replica computes the same auxiliary tensors; the penalty's
-        gradient reaches this replica's rows only, the gradient all-reduce adds the replicas up)."""
+        gradient reaches this replica's rows only, the gradient all-reduce adds the replicas up).
+        Under the survival task `sync` must provide `all_gather_into` (else NotImplementedError), and the global batch
+        opt.batch_size x world_size is at most 4096 (the one-workgroup survival kernel, else ValueError): each step packs
+        this replica's survival rows into one block, all-gathers it, and computes the Cox and consistency terms over the
+        global batch (ops.SurvStage1GatheredFn), as the reference's nn.DataParallel does on its gathered outputs.  The
+        survival outputs (`loss_cox*`, `loss_kd_*` and the survival part of `loss`) are then global-batch values, the same
+        on every replica (like `loss_tsvd`); the CRD, masking and regulariser parts of `loss` stay partial per replica."""
         from .networks_new import define_net, define_optimizer, define_scheduler
         self.opt = opt
         self.device = torch.device(device)
@@ -1227,9 +1236,12 @@ class TeacherStage1Step:
         self.surv = getattr(opt, "task", "grad") == "surv"
         if self.surv:
             if sync is not None:
-                raise NotImplementedError("TeacherStage1Step: task 'surv' with data parallelism - the Cox risk sets span the "
-                                          "global batch (the reference's DataParallel computes the loss on the gathered "
-                                          "outputs); a row all-gather is not built")
+                if not callable(getattr(sync, "all_gather_into", None)):
+                    raise NotImplementedError("TeacherStage1Step: task 'surv' with data parallelism - the Cox risk sets span "
+                                              "the global batch: the sync object must provide all_gather_into")
+                if opt.batch_size * sync.world_size > SURV_MAX_GLOBAL_BATCH:
+                    raise ValueError("TeacherStage1Step: task 'surv' with a global batch of %d x %d: the survival loss "
+                                     "kernel holds at most %d rows" % (opt.batch_size, sync.world_size, SURV_MAX_GLOBAL_BATCH))
             if getattr(opt, "tSVD_loss", "False") == "True":
                 raise NotImplementedError("TeacherStage1Step: task 'surv' with tSVD_loss (no reference vectors pin it)")
             if getattr(opt, "masking", 0):
@@ -1329,6 +1341,15 @@ class TeacherStage1Step:
         for s, e in self._frozen_segs:
             check(lib().ph_ema_update_dev(ptr(self.ema_flat.flat[s:e]), ptr(f.flat[s:e]), e - s, ptr(opt_._hyper), stream()),
                   "ph_ema_update_dev")
+
+    def _surv_gather_bufs(self, input_set, n):
+        """The staging / gathered buffers of the survival all-gather (ops.surv_gather_buffers), allocated once per graph input
+        set (captured graphs keep their addresses) and once for the eager steps; a new batch size replaces them."""
+        holder = input_set if input_set is not None else self.__dict__
+        bufs = holder.get("_surv_gather")
+        if bufs is None or bufs[0].shape[1] != n:
+            bufs = holder["_surv_gather"] = ops.surv_gather_buffers(n, self.sync.world_size, self.device)
+        return bufs
 
     @staticmethod
     def pred_KD_loss(p_s, p_t, bnorm=None):
@@ -1455,11 +1476,13 @@ class TeacherStage1Step:
             was_prepared = self.optimizer._prepared
             try:
                 bf = st["bufs"]
+                if self.surv and self.sync is not None:
+                    self._surv_gather_bufs(st, bf["x_path"].shape[0])      # (allocated outside the capture)
                 with torch.cuda.graph(g, pool=pool, capture_error_mode=_capture_mode(self.sync)):
                     self.optimizer._prepared = True       # the step scalars are read from device memory at replay
                     out = self._device_body(bf["x_path"], bf["ema_x_path"], bf["x_omic"], bf["grade"], bf["index"],
                                             bf["sample_idx"], B, do_aux, self._g_scal[0], self._g_scal[1], self._g_scal[2], None,
-                                            bf.get("survtime"), bf.get("censor"))
+                                            bf.get("survtime"), bf.get("censor"), st)
                 # the graph holds raw pointers into the trunk workspaces it was captured with: keep them alive with it
                 refs = [ws for net in (self.model, self.ema_model) for mod in net.modules() if hasattr(mod, "pinned_workspaces")
                         for ws in mod.pinned_workspaces()]
@@ -1485,9 +1508,10 @@ class TeacherStage1Step:
         return out
 
     def _device_body(self, x_path, ema_x_path, x_omic, grade, index, sample_idx, B, do_aux, crd_w, tau, mu_pen, loss_masking,
-                     survtime=None, censor=None):
+                     survtime=None, censor=None, input_set=None):
         """Everything of the step that runs on the device (capturable in one HIP graph).  `crd_w`, `tau`, `mu_pen`: floats on
-        the eager path, 1-element device tensors under capture.  `survtime`, `censor`: device tensors of the survival task."""
+        the eager path, 1-element device tensors under capture.  `survtime`, `censor`: device tensors of the survival task.
+        `input_set`: the graph input set being captured (None: eager), which owns its survival gather buffers."""
         opt = self.opt
         dev = self.device
         if loss_masking is None:
@@ -1518,9 +1542,17 @@ class TeacherStage1Step:
             # :149-152 + :180-203 with opt.task == "surv": lambda_cox * (three Cox terms) + KD_weight * (MSE consistency
             # terms) and its gradient with respect to the three predictions, one launch; NLL is absent (zero)
             nt = opt.num_teachers if getattr(opt, "pred_distill", 1) == 1 else 0
-            loss_surv, surv_terms = ops.SurvStage1LossFn.apply(pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic,
-                                                               survtime, censor, nt, float(opt.lambda_cox),
-                                                               float(getattr(opt, "KD_weight", 1.0)))
+            if self.sync is None:
+                loss_surv, surv_terms = ops.SurvStage1LossFn.apply(pred, pred_path, pred_omic, ema_pred, ema_pred_path,
+                                                                   ema_pred_omic, survtime, censor, nt, float(opt.lambda_cox),
+                                                                   float(getattr(opt, "KD_weight", 1.0)))
+            else:
+                # the risk sets span the global batch: pack, one all-gather, the gathered kernel (the values are those of
+                # the concatenated batch, the same on every replica; the gradient reaches this replica's rows)
+                loss_surv, surv_terms = ops.SurvStage1GatheredFn.apply(
+                    pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic, survtime, censor, nt,
+                    float(opt.lambda_cox), float(getattr(opt, "KD_weight", 1.0)), self.sync,
+                    *self._surv_gather_bufs(input_set, pred.shape[0]))
             loss_pred_KD = surv_terms[7] if nt > 0 else torch.zeros((), device=dev)
             loss_nll = torch.zeros((), device=dev)
             loss = loss_surv + loss_CRD + loss_masking
