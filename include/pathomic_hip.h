@@ -376,7 +376,15 @@ int ph_conv2d_wgrad(const void* x, const void* dy, float* dw_oihw, int B, int Ci
  * to the student rows f_s [B, D] (the teacher rows f_t are constants), fixed summation order.
  * ph_pkt_loss_grad: "MIA 2022/distiller_zoo/PKT.py":17-46 (cosine-similarity probabilities, KL, eps 1e-7).
  * ph_rkd_loss_grad: "MIA 2022/distiller_zoo/RKD.py":15-58 (w_d * smooth-L1 of mean-normalised pairwise distances +
- * w_a * smooth-L1 of the B^3 angles); B <= 128, D <= 512. */
+ * w_a * smooth-L1 of the B^3 angles); B <= 128, D <= 512.
+ * ph_rkd_loss_grad_part (csrc/zoo_rkd.hip): the same loss, RKD.py:15-58, on Bg gathered rows (2 <= Bg <= 1024,
+ * 1 <= D <= 512), restricted to the anchors [anchor_lo, anchor_lo + n_anchors) of the angle term (RKD.py:33-43) and to the
+ * same rows of the distance matrix (RKD.py:21-31).  loss_part [1] and dx_part [Bg][D] (the gradient with respect to EVERY
+ * student row) of the parts of any partition of [0, Bg) into contiguous ranges add up to the loss and gradient of the whole
+ * batch; anchor_lo = 0, n_anchors = Bg is the complete loss.  The mean distances and the normalisers Bg^2 / Bg^3 are those
+ * of all Bg rows; unit vectors take their norm from the row difference itself (F.normalize, eps 1e-12), so coinciding rows
+ * give exact zeros and no NaN.  Fixed summation order, no atomics.  Anything outside the ranges above, anchor_lo < 0,
+ * n_anchors < 1, anchor_lo + n_anchors > Bg or a NULL pointer returns PH_EINVAL before any HIP call. */
 /* Cox negative partial log-likelihood of the survival task (MICCAI-2022/utils.py:361-376): loss and d loss / d theta;
  * dtheta may be NULL.  B <= 4096. */
 int ph_cox_loss_grad(const float* theta, const float* survtime, const float* censor, float* loss, float* dtheta, int B,
@@ -432,6 +440,9 @@ int ph_pkt_loss_grad(const float* f_s, const float* f_t, float* loss, float* dx,
 size_t ph_rkd_workspace_bytes(int B, int D);
 int ph_rkd_loss_grad(const float* f_s, const float* f_t, float* loss, float* dx, int B, int D, float w_d, float w_a,
                      void* workspace, ph_stream_t stream);
+size_t ph_rkd_part_workspace_bytes(int Bg, int D, int n_anchors);
+int ph_rkd_loss_grad_part(const float* f_s, const float* f_t, int Bg, int D, int anchor_lo, int n_anchors, float w_d,
+                          float w_a, float* loss_part, float* dx_part, void* workspace, ph_stream_t stream);
 
 /* Superpixel attention masks of the MIA-2023 stage-1 trainer (SURVEY row f-4;
  * "MIA 2023/stage1_multi_modal_teacher/train_test_MT_SP_Masking.py":77-98), the part after the input gradients exist:

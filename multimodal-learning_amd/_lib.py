@@ -77,6 +77,8 @@ SIGNATURES = {
     "ph_pkt_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
     "ph_rkd_workspace_bytes": (sz, [i32, i32]),
     "ph_rkd_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp]),
+    "ph_rkd_part_workspace_bytes": (sz, [i32, i32, i32]),
+    "ph_rkd_loss_grad_part": (i32, [vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp]),
     "ph_superpixel_mask": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "ph_shuffle_indices": (i32, [vp, i32, i32, u64, vp, vp]),
     "ph_alias_uniform_draw": (i32, [vp, vp, i32, i32, i32, u64, vp, vp]),

@@ -473,9 +473,19 @@ class DistillStep:
             if opt.distill not in zoo:
                 raise NotImplementedError("--distill %s (built: crd, kd, feats_KL, rkd, pkt, similarity)" % opt.distill)
             if sync is not None and opt.distill in ("rkd", "pkt", "similarity"):
-                raise NotImplementedError("--distill %s relates the rows of ONE batch to each other: per-replica batches "
-                                          "would change the loss (single GPU only)" % opt.distill)
-            self.zoo_kd = zoo[opt.distill]() if zoo[opt.distill] is not None else False
+                # these relate every row of the batch to every other row: under data parallelism the criterion sees the
+                # GLOBAL batch (the reference's nn.DataParallel gathers the outputs, :286, :307-308)
+                need = ("all_gather_cat", "all_reduce_sum") if opt.distill == "rkd" else ("all_gather_cat",)
+                lack = [c for c in need if not callable(getattr(sync, c, None))]
+                if lack:
+                    raise NotImplementedError("--distill %s with data parallelism spans the global batch: the sync object "
+                                              "must provide %s" % (opt.distill, ", ".join(lack)))
+                if opt.distill == "rkd" and opt.batch_size * sync.world_size > Z.RKD_MAX_ROWS:
+                    raise ValueError("--distill rkd: global batch %d x %d exceeds the %d rows of the partitioned RKD kernel"
+                                     % (opt.batch_size, sync.world_size, Z.RKD_MAX_ROWS))
+                self.zoo_kd = zoo[opt.distill](sync=sync)
+            else:
+                self.zoo_kd = zoo[opt.distill]() if zoo[opt.distill] is not None else False
             self.module_list = nn.ModuleList([self.model])
         self.optimizer = define_optimizer(opt, self.module_list)                   # :211
         self.scheduler = define_scheduler(opt, self.optimizer)                     # :212
@@ -683,7 +693,14 @@ class DistillStep:
         """The `--distill kd | feats_KL | rkd | pkt | similarity` baselines of the MIA-2022 trainer
         ("MIA 2022/train_test_path_multi_distill_v2.py":419-483): KL to one or two teachers plus one feature-level
         criterion between the student feature and the fused teacher feature, summed with fixed weights alpha / beta
-        (GK-Refine needs the per-loss list, which the trainer only builds for crd and kd with two teachers)."""
+        (GK-Refine needs the per-loss list, which the trainer only builds for crd and kd with two teachers).
+
+        Under data parallelism `rkd | pkt | similarity` are losses of the GLOBAL batch (distiller_zoo).  The value that enters
+        backward() is what the criterion returns - this replica's part of the global loss with the summed gradient behind it
+        (rkd), or the global loss itself (pkt, similarity: every replica evaluates it, the backward keeps its own rows) - so
+        that the replicas' parameter gradients add up to the single-process gradient.  The REPORTED `loss_kd1` and `loss`
+        follow the step's convention that the replicas' values add up to the single-process ones: this replica's part
+        (rkd), the global value / world_size (pkt, similarity)."""
         opt = self.opt
         z = torch.zeros((), device=self.device)
         loss_div1 = loss_div2 = z
@@ -715,7 +732,13 @@ class DistillStep:
         if self.sync is not None:
             self.sync.all_reduce_grads(self.optimizer.flat)
         self.optimizer.step()
-        return dict(loss=loss.detach(), loss_cls=loss_cls.detach(), loss_div1=loss_div1.detach(), loss_div2=loss_div2.detach(),
+        loss, loss_kd = loss.detach(), loss_kd.detach()
+        if self.sync is not None and opt.distill in ("pkt", "similarity"):
+            # every replica holds the global value: report 1 / world of it (the replicas' reports add up)
+            w = float(self.sync.world_size)
+            loss = loss - opt.beta * (loss_kd - loss_kd / w)
+            loss_kd = loss_kd / w
+        return dict(loss=loss, loss_cls=loss_cls.detach(), loss_div1=loss_div1.detach(), loss_div2=loss_div2.detach(),
                     loss_kd1=(opt.beta * loss_kd).detach(), loss_kd2=z, scale=scale, logit_path=logit_path.detach(),
                     pred_path=pred_path.detach(), path_feat=path_feat.detach(), ema_logit=ema_logit_path,
                     fuse_logit=logits[-1], fuse_feat=fuse_feat, ema_feat=ema_path_feat)
