@@ -472,6 +472,37 @@ int ph_augment_params(float* params, int B, uint64_t seed, const uint64_t* step 
                       int S, float brightness, float contrast, float saturation, float hue, ph_stream_t stream);
 int ph_augment_apply(const uint8_t* src, const int64_t* rows /* NULL - image b of the batch is src[b] - or src[rows[b]] */,
                      float* params, float* out0, float* out1, int B, int SH, int SW, int S, ph_stream_t stream);
+/* The same pipeline with V <= 4 views per image and label maps (the loader of the MIA-2023 masking trainer,
+ * "MIA 2023/stage1_multi_modal_teacher/data_loaders_MT_SP.py":352-388, :446-453: four independent views of a tile, the
+ * superpixel label map carried through the flip and crop of its view).  params: [B][V][16], the row layout above.
+ * ph_augment_params_v draws views 0 and 1 exactly as ph_augment_params does for the same seed and *step; views 2 and 3
+ * extend the same keyed counter RNG under a key no (image, view < 2) pair of that step has.  ph_augment_apply_v: outs =
+ * HOST array of V device pointers, each f32 [B][3][S][S]; label_outs = NULL or a HOST array of V device pointers (entries
+ * may be NULL), each int64 [B][S][S] := sp[tile][sy][sx] under that view's flip and crop (nearest, no colour step);
+ * sp: int16 [n][SH][SW] label maps next to the tiles (required where a label output is asked for).  PH_EINVAL for V
+ * outside 1..4 or a crop larger than the tile, before any launch. */
+int ph_augment_params_v(float* params, int B, int V, uint64_t seed, const uint64_t* step /* device pointer or NULL */, int SH,
+                        int SW, int S, float brightness, float contrast, float saturation, float hue, ph_stream_t stream);
+int ph_augment_apply_v(const uint8_t* src, const int16_t* sp, const int64_t* rows, float* params, float* const* outs,
+                       int64_t* const* label_outs, int B, int V, int SH, int SW, int S, ph_stream_t stream);
+
+/* SLIC superpixel segmentation on the device (the role of fast_slic in the reference,
+ * data_loaders_MT_SP.py:303-304 - same interface, NOT bit parity: its source is not available).  All-integer definition
+ * (table-driven 8-bit CIELAB, 64-bit distances, lowest label on a tie, integer sums): exactly reproducible, equal to
+ * tests/slic_emulation.py on every pixel.  Grid gy = floor(sqrt(K H / W)), gx = K / gy, N = gy gx <= K labels.
+ * ph_slic_num_labels: N, or PH_EINVAL for K < 1, an empty image, H or W > 8192, a grid finer than the pixels or
+ * N > 2048 (the limit of ph_superpixel_mask).  Host only.
+ * ph_slic_workspace_bytes: bytes of workspace ph_slic needs for n tiles (0 for invalid arguments).  Host only.
+ * ph_slic_lab: rgb uint8 [npix][3] -> packed 8-bit Lab words L | a << 8 | b << 16 (L * 255 / 100, a + 128, b + 128);
+ * workspace: at least the bytes ph_slic_workspace_bytes gives for one 1 x 1 tile (the two conversion tables are
+ * uploaded into it).
+ * ph_slic: tiles uint8 [n][H][W][3] -> labels int16 [n][H][W] in [0, N) after `iters` iterations at the given
+ * compactness (0..1024); one fixed launch sequence on `stream`, no host synchronisation. */
+int ph_slic_num_labels(int H, int W, int K);
+size_t ph_slic_workspace_bytes(int n, int H, int W, int K);
+int ph_slic_lab(const uint8_t* rgb, uint32_t* lab, size_t npix, void* workspace, ph_stream_t stream);
+int ph_slic(const uint8_t* tiles, int16_t* labels, int n, int H, int W, int K, int compactness, int iters, void* workspace,
+            ph_stream_t stream);
 
 /* On-device contrast-index sampler (reference MICCAI-2022/data_loaders_MT.py:229-249 and the neg_mode
  * variants of "MIA 2023/stage2_unimodal_student/data_loaders_MT.py":205-238).  out[b] = [positives | K negatives]:

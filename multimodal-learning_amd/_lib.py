@@ -84,6 +84,12 @@ SIGNATURES = {
     "ph_alias_uniform_draw": (i32, [vp, vp, i32, i32, i32, u64, vp, vp]),
     "ph_augment_params": (i32, [vp, i32, u64, vp, i32, i32, i32, f32, f32, f32, f32, vp]),
     "ph_augment_apply": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ph_augment_params_v": (i32, [vp, i32, i32, u64, vp, i32, i32, i32, f32, f32, f32, f32, vp]),
+    "ph_augment_apply_v": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "ph_slic_num_labels": (i32, [i32, i32, i32]),
+    "ph_slic_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "ph_slic_lab": (i32, [vp, vp, sz, vp, vp]),
+    "ph_slic": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "ph_apply_mask": (i32, [vp, vp, vp, i32, i32, sz, vp]),
     "ph_topk_threshold_mask": (i32, [vp, vp, i32, i32, i32, vp]),
     "ph_maxnorm_mix": (i32, [vp, vp, vp, sz, f32, f32, vp]),

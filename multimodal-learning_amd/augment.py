@@ -5,6 +5,8 @@ HBM - at the step rates of this package the PIL pipeline in four DataLoader work
     aug = DeviceAugment(opt, device)                    # opt.input_size_path = crop size
     x_path, ema_x_path = aug(src_u8)                    # src_u8 [B, SH, SW, 3] uint8 (device) -> two f32 [B, 3, S, S] views
 
+`DeviceAugmentSP` / `ResidentSuperpixelLoader`: the four views and superpixel label maps of the MIA-2023 masking loader.
+
 The draws come from a counter RNG keyed by (seed, step, image, view) - reproducible, not numpy's stream.  The colour
 arithmetic is Pillow's as torchvision drives it, pinned bit for bit against Pillow (tests/golden/colorjitter_pil.npz)."""
 import torch
@@ -66,6 +68,68 @@ class DeviceAugment:
         return out0, out1
 
 
+class DeviceAugmentSP(DeviceAugment):
+    """The transform of the MIA-2023 masking loader (data_loaders_MT_SP.py:352-388, called four times per tile, :446-450):
+    four independently drawn views, the superpixel label map carried through the flip and crop of views 0 and 1.
+
+        aug = DeviceAugmentSP(opt, device, seed)
+        x_path, sp_mask, ema_x_path, ema_sp_mask, x_path_m_v1, x_path_m_v2 = aug(src_u8, sp_i16)
+
+    src_u8 [n, SH, SW, 3] uint8 and sp_i16 [n, SH, SW] int16 on the device; views f32 [B, 3, S, S], label maps int64
+    [B, S, S].  Views 0 and 1 are `DeviceAugment`'s two views for the same seed and step counter, bit for bit (the same
+    draws, the same colour kernels); views 2 and 3 extend the keyed counter RNG.  `ema_sp_mask` is the map under view 1 (the
+    reference crops the already cropped map a second time, :447, and nothing reads the result)."""
+    VIEWS = 4
+
+    def __call__(self, src_u8, sp_i16, params=None, rows=None, out=None):
+        import ctypes as C
+        src = require_cuda(src_u8, "src_u8")
+        if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+            raise RuntimeError("src_u8 must be uint8 [B, SH, SW, 3]")
+        src = src.contiguous()
+        sp = require_cuda(sp_i16, "sp_i16")
+        if sp.dtype != torch.int16 or tuple(sp.shape) != tuple(src.shape[:3]):
+            raise RuntimeError("sp_i16 must be int16 [B, SH, SW] label maps of the same tiles")
+        sp = sp.contiguous()
+        _, SH, SW, _ = src.shape
+        if rows is not None:
+            rows = rows.to(src.device).long().contiguous()
+        B = src.shape[0] if rows is None else rows.shape[0]
+        S, V = self.S, self.VIEWS
+        if params is None:
+            params = torch.empty(B, V, NPARAM, device=src.device, dtype=torch.float32)
+            check(lib().ph_augment_params_v(ptr(params), B, V, self.seed, ptr(self.step), SH, SW, S, *self.jitter, stream()),
+                  "ph_augment_params_v")
+            self.step += 1
+        else:
+            # caller-supplied [B, 4, NPARAM] block, the row layout and the column-13 rule of DeviceAugment
+            params = params.to(src.device).float().contiguous().clone()
+            if tuple(params.shape) != (B, V, NPARAM):
+                raise ValueError("augmentation params must be [B, 4, %d]" % NPARAM)
+            c13 = params[..., 13]
+            if not bool(((c13 >= 0) & (c13 <= 15) & (c13 == c13.round())).all().item()):
+                raise ValueError("augmentation params column 13 is the mask of disabled colour steps: integers 0..15")
+            params[..., 12] = 0
+            params[..., 14:] = 0
+        if out is not None:
+            x0, l0, x1, l1, x2, x3 = out
+            for t in (x0, x1, x2, x3):
+                if tuple(t.shape) != (B, 3, S, S) or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+                    raise RuntimeError("out views must be contiguous f32 [B, 3, S, S] device tensors")
+            for t in (l0, l1):
+                if tuple(t.shape) != (B, S, S) or t.dtype != torch.int64 or not t.is_contiguous() or not t.is_cuda:
+                    raise RuntimeError("out label maps must be contiguous int64 [B, S, S] device tensors")
+        else:
+            x0, x1, x2, x3 = (torch.empty(B, 3, S, S, device=src.device, dtype=torch.float32) for _ in range(4))
+            l0, l1 = (torch.empty(B, S, S, device=src.device, dtype=torch.int64) for _ in range(2))
+        outs = (C.c_void_p * V)(ptr(x0), ptr(x1), ptr(x2), ptr(x3))
+        labs = (C.c_void_p * V)(ptr(l0), ptr(l1), None, None)
+        check(lib().ph_augment_apply_v(ptr(src), ptr(sp), ptr(rows), ptr(params), outs, labs, B, V, SH, SW, S, stream()),
+              "ph_augment_apply_v")
+        self.last_params = params
+        return x0, l0, x1, l1, x2, x3
+
+
 class ResidentTileLoader:
     """The training loader's batch tuple (data_loaders_MT.py:256) produced on the device: uint8 tiles, omic vectors and
     labels live in HBM; a batch of row indices becomes ((x_path, ema_x_path), 0, x_omic, 0, 0, grade, index, sample_idx)
@@ -113,6 +177,40 @@ class ResidentTileLoader:
         (x_path, ema_x_path), _, x_omic, _, _, grade, idx_buf, sample_idx = into
         rows = index if getattr(self, "row_to_tile", None) is None else self.row_to_tile[index]
         self.aug(self.tiles, rows=rows, out=(x_path, ema_x_path))
+        torch.index_select(self.x_omic, 0, index, out=x_omic)
+        torch.index_select(self.grade, 0, index, out=grade)
+        if not _index_in_place:
+            idx_buf.copy_(index)
+        self.sampler(idx_buf, grade, out=sample_idx)
+        return into
+
+
+class ResidentSuperpixelLoader(ResidentTileLoader):
+    """The batch tuple of the MIA-2023 stage-1 masking trainer (data_loaders_MT_SP.py:453) produced on the device:
+    ((x_path, sp_mask, ema_x_path, ema_sp_mask, x_path_m_v1, x_path_m_v2), 0, x_omic, 0, 0, grade, index, sample_idx).
+    At construction the tile store is segmented once (`superpixel.slic_segment`, opt.num_superpixels components,
+    compactness 10, as :303-304) and the int16 maps stay next to the tiles; a batch is four augmented views with the
+    label maps of views 0 and 1 (`DeviceAugmentSP`).  `num_labels` is the number of labels N of a map; where the options
+    carry no `num_superpixels_max` it is set to N, so that the step's superpixel_attention_mask call reads nothing back."""
+
+    def __init__(self, opt, tiles_u8, x_omic, grade, device="cuda", seed=0, compactness=10, iters=10, chunk=None):
+        from .superpixel import slic_segment
+        super().__init__(opt, tiles_u8, x_omic, grade, device, seed)
+        self.aug = DeviceAugmentSP(opt, self.device, seed)
+        self.sp_maps, self.num_labels = slic_segment(self.tiles, int(opt.num_superpixels), compactness, iters, chunk=chunk)
+        if getattr(opt, "num_superpixels_max", None) is None:
+            opt.num_superpixels_max = self.num_labels
+
+    def batch(self, index, into=None, _index_in_place=False):
+        index = index.to(self.device).long().contiguous()
+        rows = index if getattr(self, "row_to_tile", None) is None else self.row_to_tile[index]
+        if into is None:
+            views = self.aug(self.tiles, self.sp_maps, rows=rows)
+            grade = self.grade[index]
+            z = torch.zeros(index.shape[0], device=self.device)
+            return (views, z, self.x_omic[index], z, z, grade, index, self.sampler(index, grade))
+        views, _, x_omic, _, _, grade, idx_buf, sample_idx = into
+        self.aug(self.tiles, self.sp_maps, rows=rows, out=views)
         torch.index_select(self.x_omic, 0, index, out=x_omic)
         torch.index_select(self.grade, 0, index, out=grade)
         if not _index_in_place:

@@ -3,7 +3,8 @@
 // ColorJitter(0.1, 0.1, 0.05, 0.01), ToTensor, Normalize(0.5, 0.5)])) run by PIL in four DataLoader workers).
 // Source images stay uint8 [B][SH][SW][3] in HBM; one launch draws the per-(image, view) parameters, one computes the
 // grey mean the contrast step needs, one writes both fp32 NCHW views.  Byte work, HBM-bound: 0.8 MB read + 3 MB written
-// per 512 x 512 view.
+// per 512 x 512 view.  The *_v entries run the same kernels for V <= 4 views per image and carry an int16 label map through a
+// view's flip and crop (the MIA-2023 masking loader, "MIA 2023/stage1_multi_modal_teacher/data_loaders_MT_SP.py":352-388).
 //
 // The colour arithmetic is Pillow's, as torchvision's PIL backend drives it, and is PINNED against Pillow itself
 // (tests/golden/colorjitter_pil.npz, produced by the real ImageEnhance / convert("HSV") calls; oracle/augment.py states
@@ -29,13 +30,10 @@ __device__ __forceinline__ uint64_t amix(uint64_t z) {
 }
 __device__ __forceinline__ float u01(uint64_t h) { return (float)(h >> 40) * (1.0f / 16777216.0f); }
 
-__global__ void augment_params_kernel(float* __restrict__ params, int n, uint64_t seed, const uint64_t* __restrict__ step,
-                                      int SH, int SW, int S, float jb, float jc, float js, float jh) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;   // (image, view)
-  if (i >= n) return;
-  const uint64_t st = step ? step[0] : 0;
-  const uint64_t base = amix(seed ^ amix(st * 0x9E3779B97F4A7C15ull + (uint64_t)i + 1));
-  float* p = params + (size_t)i * AP;
+// one parameter row from the counter RNG keyed by (seed, step, key)
+__device__ __forceinline__ void draw_row(float* p, uint64_t key, uint64_t seed, uint64_t st, int SH, int SW, int S, float jb, float jc,
+                                         float js, float jh) {
+  const uint64_t base = amix(seed ^ amix(st * 0x9E3779B97F4A7C15ull + key + 1));
   p[0] = (amix(base ^ 1) >> 63) ? 1.f : 0.f;
   p[1] = (amix(base ^ 2) >> 63) ? 1.f : 0.f;
   p[2] = (float)(amix(base ^ 3) % (uint64_t)(SH - S + 1));
@@ -53,6 +51,25 @@ __global__ void augment_params_kernel(float* __restrict__ params, int n, uint64_
   }
   p[12] = 0.f; p[14] = p[15] = 0.f;
   p[13] = (float)((jb == 0.f ? 1 : 0) | (jc == 0.f ? 2 : 0) | (js == 0.f ? 4 : 0) | (jh == 0.f ? 8 : 0));
+}
+
+__global__ void augment_params_kernel(float* __restrict__ params, int n, uint64_t seed, const uint64_t* __restrict__ step,
+                                      int SH, int SW, int S, float jb, float jc, float js, float jh) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;   // (image, view)
+  if (i >= n) return;
+  draw_row(params + (size_t)i * AP, (uint64_t)i, seed, step ? step[0] : 0, SH, SW, S, jb, jc, js, jh);
+}
+
+// V views per image, rows [image][view].  Views 0 and 1 keep the key 2 * image + view of the two-view kernel (the same
+// draws for the same seed and step); view v >= 2 takes the key of view v & 1 plus (v >> 1) << 40, which no flat index
+// 2 * image + view of the same step can reach (B < 2^31), so after the bijective mixes its stream is a different one.
+__global__ void augment_params_v_kernel(float* __restrict__ params, int n, int V, uint64_t seed, const uint64_t* __restrict__ step,
+                                        int SH, int SW, int S, float jb, float jc, float js, float jh) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;   // image * V + view
+  if (i >= n) return;
+  const int b = i / V, v = i - b * V;
+  draw_row(params + (size_t)i * AP, (uint64_t)(2 * (int64_t)b + (v & 1)) + ((uint64_t)(v >> 1) << 40), seed, step ? step[0] : 0, SH, SW,
+           S, jb, jc, js, jh);
 }
 
 __device__ __forceinline__ int luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
@@ -120,13 +137,17 @@ __device__ __forceinline__ void jitter(int& r, int& g, int& b, const float* p, i
   }
 }
 
-__device__ __forceinline__ void fetch(const uint8_t* __restrict__ src, const float* p, size_t b, int SH, int SW, int y, int x,
-                                      int& r, int& g, int& bl) {
+// source pixel of output pixel (y, x) of a view: index into a [SH][SW] plane of tile b
+__device__ __forceinline__ size_t src_pixel(const float* p, size_t b, int SH, int SW, int y, int x) {
   int sy = (int)p[2] + y, sx = (int)p[3] + x;              // crop window of the flipped image ...
   if (p[1] != 0.f) sy = SH - 1 - sy;                       // ... = mirrored coordinates of the source
   if (p[0] != 0.f) sx = SW - 1 - sx;
   sy = min(max(sy, 0), SH - 1); sx = min(max(sx, 0), SW - 1);   // caller-supplied windows cannot leave the tile
-  const uint8_t* q = src + ((b * SH + sy) * SW + sx) * 3;
+  return (b * SH + sy) * SW + sx;
+}
+__device__ __forceinline__ void fetch(const uint8_t* __restrict__ src, const float* p, size_t b, int SH, int SW, int y, int x,
+                                      int& r, int& g, int& bl) {
+  const uint8_t* q = src + src_pixel(p, b, SH, SW, y, x) * 3;
   r = q[0]; g = q[1]; bl = q[2];
 }
 
@@ -134,9 +155,9 @@ __device__ __forceinline__ void fetch(const uint8_t* __restrict__ src, const flo
 // MSPLIT workgroups per (image, view) add their exact integer partial sums to the 64-bit slot of the parameter row
 constexpr int MSPLIT = 16;
 __global__ __launch_bounds__(256) void augment_mean_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ rows,
-                                                           float* __restrict__ params, int SH, int SW, int S) {
+                                                           float* __restrict__ params, int V, int SH, int SW, int S) {
   __shared__ unsigned long long red[256];
-  const int iv = blockIdx.x, b = iv >> 1;
+  const int iv = blockIdx.x, b = iv / V;
   float* p = params + (size_t)iv * AP;
   unsigned long long s = 0;
   const int n = S * S, per = (n + MSPLIT - 1) / MSPLIT, lo = blockIdx.y * per, hi = min(n, lo + per);
@@ -160,28 +181,46 @@ __device__ __forceinline__ int grey_mean(const float* p, int S) {
   return (int)((double)sum / ((double)S * (double)S) + 0.5);
 }
 
-// both views: out_v[b][c][y][x] = (jittered / 255 - 0.5) / 0.5
-__global__ void augment_apply_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ rows,
-                                     const float* __restrict__ params, float* __restrict__ out0, float* __restrict__ out1, int B,
-                                     int SH, int SW, int S) {
+constexpr int AUG_MAXV = 4;
+struct AugOuts { float* out[AUG_MAXV]; int64_t* lab[AUG_MAXV]; };
+
+// every view: out_v[b][c][y][x] = (jittered / 255 - 0.5) / 0.5; where a view has a label output, the label map of the
+// tile under the view's flip and crop (nearest, no colour step): lab_v[b][y][x] = sp[tile][sy][sx]
+__global__ void augment_apply_kernel(const uint8_t* __restrict__ src, const int16_t* __restrict__ sp, const int64_t* __restrict__ rows,
+                                     const float* __restrict__ params, AugOuts outs, int B, int V, int SH, int SW, int S) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t per = (size_t)S * S;
-  if (i >= (size_t)B * 2 * per) return;
-  const int iv = (int)(i / per), b = iv >> 1, v = iv & 1;
+  if (i >= (size_t)B * V * per) return;
+  const int iv = (int)(i / per), b = iv / V, v = iv - b * V;
   const int e = (int)(i % per);
   const float* p = params + (size_t)iv * AP;
+  const size_t tile = rows ? (size_t)rows[b] : (size_t)b;
   int r, g, bl;
-  fetch(src, p, rows ? (size_t)rows[b] : (size_t)b, SH, SW, e / S, e % S, r, g, bl);
+  fetch(src, p, tile, SH, SW, e / S, e % S, r, g, bl);
   jitter(r, g, bl, p, grey_mean(p, S), false);
-  float* o = (v ? out1 : out0) + (size_t)b * 3 * per + e;
+  float* o = (v == 0 ? outs.out[0] : v == 1 ? outs.out[1] : v == 2 ? outs.out[2] : outs.out[3]) + (size_t)b * 3 * per + e;
   o[0] = ((float)r / 255.f - 0.5f) / 0.5f;
   o[per] = ((float)g / 255.f - 0.5f) / 0.5f;
   o[2 * per] = ((float)bl / 255.f - 0.5f) / 0.5f;
+  int64_t* lo = v == 0 ? outs.lab[0] : v == 1 ? outs.lab[1] : v == 2 ? outs.lab[2] : outs.lab[3];
+  if (lo) lo[(size_t)b * per + e] = (int64_t)sp[src_pixel(p, tile, SH, SW, e / S, e % S)];
 }
 
 __global__ void augment_publish_mean_kernel(float* __restrict__ params, int n, int S) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) params[(size_t)i * AP + 12] = (float)grey_mean(params + (size_t)i * AP, S);
+}
+
+int augment_apply_launch(const uint8_t* src, const int16_t* sp, const int64_t* rows, float* params, const AugOuts& outs, int B, int V,
+                         int SH, int SW, int S, hipStream_t st) {
+  hipLaunchKernelGGL(augment_mean_kernel, dim3(V * B, MSPLIT), dim3(256), 0, st, src, rows, params, V, SH, SW, S);
+  PH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(augment_publish_mean_kernel, dim3((V * B + 255) / 256), dim3(256), 0, st, params, V * B, S);
+  PH_LAUNCH_CHECK();
+  const size_t n = (size_t)B * V * S * S;
+  hipLaunchKernelGGL(augment_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, sp, rows, params, outs, B, V, SH, SW, S);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
 }
 
 }  // namespace
@@ -202,14 +241,31 @@ int ph_augment_params(float* params, int B, uint64_t seed, const uint64_t* step,
 int ph_augment_apply(const uint8_t* src, const int64_t* rows, float* params, float* out0, float* out1, int B, int SH, int SW,
                      int S, hipStream_t st) {
   if (!src || !params || !out0 || !out1 || B < 1 || S < 1 || S > SH || S > SW) return PH_EINVAL;
-  hipLaunchKernelGGL(augment_mean_kernel, dim3(2 * B, MSPLIT), dim3(256), 0, st, src, rows, params, SH, SW, S);
-  PH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(augment_publish_mean_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, st, params, 2 * B, S);
-  PH_LAUNCH_CHECK();
-  const size_t n = (size_t)B * 2 * S * S;
-  hipLaunchKernelGGL(augment_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, rows, params, out0, out1, B, SH, SW, S);
+  AugOuts outs = {};
+  outs.out[0] = out0; outs.out[1] = out1;
+  return augment_apply_launch(src, nullptr, rows, params, outs, B, 2, SH, SW, S, st);
+}
+
+int ph_augment_params_v(float* params, int B, int V, uint64_t seed, const uint64_t* step, int SH, int SW, int S, float brightness,
+                        float contrast, float saturation, float hue, hipStream_t st) {
+  if (!params || B < 1 || V < 1 || V > AUG_MAXV || S < 1 || S > SH || S > SW) return PH_EINVAL;
+  hipLaunchKernelGGL(augment_params_v_kernel, dim3((V * B + 255) / 256), dim3(256), 0, st, params, V * B, V, seed, step, SH, SW, S,
+                     brightness, contrast, saturation, hue);
   PH_LAUNCH_CHECK();
   return PH_OK;
+}
+
+int ph_augment_apply_v(const uint8_t* src, const int16_t* sp, const int64_t* rows, float* params, float* const* outs,
+                       int64_t* const* label_outs, int B, int V, int SH, int SW, int S, hipStream_t st) {
+  if (!src || !params || !outs || B < 1 || V < 1 || V > AUG_MAXV || S < 1 || S > SH || S > SW) return PH_EINVAL;
+  AugOuts o = {};
+  for (int v = 0; v < V; ++v) {
+    if (!outs[v]) return PH_EINVAL;
+    o.out[v] = outs[v];
+    o.lab[v] = label_outs ? label_outs[v] : nullptr;
+    if (o.lab[v] && !sp) return PH_EINVAL;
+  }
+  return augment_apply_launch(src, sp, rows, params, o, B, V, SH, SW, S, st);
 }
 
 }  // extern "C"

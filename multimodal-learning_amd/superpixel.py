@@ -4,11 +4,65 @@
 Built here: everything after the input gradients exist (:77-98) - the per-superpixel aggregation of the image gradient
 (the reference moves a one-hot [B, N, H*W] tensor to the HOST and runs the bmm there), the top-`Path_K` superpixel mask
 and the top-`Omic_K` omic mask - as two kernels (csrc/superpixel.hip).  NOT built: the gradients themselves (:45-75
-need an eval-mode backward down to the image, i.e. a stem dgrad kernel, which the distillation hot path never needs)."""
+need an eval-mode backward down to the image, i.e. a stem dgrad kernel, which the distillation hot path never needs).
+
+The label maps themselves: `slic_segment` (csrc/slic.hip), the role of the reference loader's `fast_slic` call."""
 import torch
 
 from . import ops
 from ._lib import lib, check, ptr, stream, require_cuda
+
+
+def slic_num_labels(H, W, num_components):
+    """N = gy * gx <= num_components, the number of labels `slic_segment` produces for H x W tiles (host only)."""
+    N = lib().ph_slic_num_labels(int(H), int(W), int(num_components))
+    if N < 1:
+        raise ValueError(f"no SLIC grid for {H} x {W} tiles and num_components={num_components}: needs 1 <= K, tiles of "
+                         "1..8192 pixels a side, no more grid cells than pixels along an axis and at most 2048 labels")
+    return N
+
+
+def slic_segment(tiles_u8, num_components, compactness=10, iters=10, out=None, chunk=None):
+    """SLIC superpixels on the device (csrc/slic.hip): tiles_u8 [n, H, W, 3] uint8 (device) ->
+    (labels int16 [n, H, W] in [0, N), N).  The role of `fast_slic.Slic(num_components, compactness).iterate` in the
+    reference's loader (data_loaders_MT_SP.py:303-304) - the same interface, an all-integer definition of its own, not
+    bit parity.  The store is walked in chunks of `chunk` tiles (default: a workspace of about 256 MB); tiles are
+    segmented independently, so the result does not depend on the chunking.  `out`: int16 [n, H, W] to fill."""
+    t = require_cuda(tiles_u8, "tiles_u8")
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
+        raise RuntimeError("tiles_u8 must be uint8 [n, H, W, 3]")
+    t = t.contiguous()
+    n, H, W, _ = t.shape
+    N = slic_num_labels(H, W, num_components)
+    if not (0 <= int(compactness) <= 1024) or int(iters) < 1:
+        raise ValueError("compactness must lie in 0..1024 and iters be at least 1")
+    if out is None:
+        out = torch.empty(n, H, W, device=t.device, dtype=torch.int16)
+    elif tuple(out.shape) != (n, H, W) or out.dtype != torch.int16 or not out.is_contiguous() or out.device != t.device:
+        raise RuntimeError("out must be a contiguous int16 [n, H, W] tensor on the tiles' device")
+    if chunk is None:
+        chunk = max(1, (256 << 20) // (4 * H * W))
+    chunk = max(1, min(int(chunk), n))
+    ws = torch.empty(lib().ph_slic_workspace_bytes(chunk, H, W, int(num_components)), device=t.device, dtype=torch.uint8)
+    for lo in range(0, n, chunk):
+        m = min(chunk, n - lo)
+        check(lib().ph_slic(ptr(t[lo:]), ptr(out[lo:]), m, H, W, int(num_components), int(compactness), int(iters), ptr(ws),
+                            stream()), "ph_slic")
+    return out, N
+
+
+def rgb_to_lab8(rgb_u8):
+    """The colour step of `slic_segment` on its own: uint8 [..., 3] sRGB (device) -> uint8 [..., 3] 8-bit CIELAB
+    (L * 255 / 100, a + 128, b + 128)."""
+    t = require_cuda(rgb_u8, "rgb_u8")
+    if t.dtype != torch.uint8 or t.shape[-1] != 3 or t.numel() == 0:
+        raise RuntimeError("rgb_u8 must be uint8 [..., 3]")
+    t = t.contiguous()
+    npix = t.numel() // 3
+    words = torch.empty(npix, device=t.device, dtype=torch.int32)
+    ws = torch.empty(lib().ph_slic_workspace_bytes(1, 1, 1, 1), device=t.device, dtype=torch.uint8)
+    check(lib().ph_slic_lab(ptr(t), ptr(words), npix, ptr(ws), stream()), "ph_slic_lab")
+    return words.view(torch.uint8).view(npix, 4)[:, :3].reshape(t.shape)
 
 
 def superpixel_topk_mask(x_path_grad, sp_mask, path_k, num_superpixels=None, return_mean=False):
