@@ -124,6 +124,8 @@ int ph_resnet_tensor_info(const PhResnetPlan* plan, int what, int id, size_t* by
 /* ------------------------------------------------------------------------------------------------
  * Dense fp32 operators of the heads / SNN / fusion (resnets.py:165-169,239-250; networks_new.py:185-251;
  * fusion.py:36-63).  C[m][n] = act(sum_k A[m*sam+k*sak] * B[k*sbk+n*sbn] + bias[n]) (+C)
+ * ph_sgemm_splitk sums K in at most nsplit slabs of a multiple of 32 (fewer where K / 32 is smaller); nsplit < 1 returns
+ * PH_EINVAL before any HIP call.
  * ---------------------------------------------------------------------------------------------- */
 int ph_sgemm(const float* A, const float* B, const float* bias, float* C, int M, int N, int K, long sam, long sak,
              long sbk, long sbn, long ldc, int act, int accumulate, ph_stream_t stream);

@@ -3,6 +3,7 @@
 // correctness and low launch count, not MFMA.
 #include "ph_common.h"
 #include "ph_dense.h"
+#include "ph_kernels.h"
 
 namespace {
 
@@ -744,11 +745,13 @@ inline unsigned nblk(size_t n, int t = 256) { return (unsigned)((n + t - 1) / t)
 int ph_sgemm(const float* A, const float* B, const float* bias, float* C, int M, int N, int K, long sam, long sak,
              long sbk, long sbn, long ldc, int act, int accumulate, hipStream_t st) {
   if ((long)M * N <= 128L * 128L) {
+    ph_dispatch_note(PH_DK_SGEMM16);
     hipLaunchKernelGGL(sgemm_small_kernel, dim3(cdiv(N, ST), cdiv(M, ST)), dim3(256), 0, st, A, B, bias, C, M, N, K, sam,
                        sak, sbk, sbn, ldc, act, accumulate);
     PH_LAUNCH_CHECK();
     return PH_OK;
   }
+  ph_dispatch_note(PH_DK_SGEMM64);
   dim3 grid(cdiv(N, GT), cdiv(M, GT));
   hipLaunchKernelGGL(sgemm_kernel, grid, dim3(256), 0, st, A, B, bias, C, M, N, K, sam, sak, sbk, sbn, ldc, act,
                      accumulate);
@@ -758,8 +761,10 @@ int ph_sgemm(const float* A, const float* B, const float* bias, float* C, int M,
 
 int ph_sgemm_splitk(const float* A, const float* B, const float* bias, float* C, float* part, int nsplit, int M, int N,
                     int K, long sam, long sak, long sbk, long sbn, long ldc, int act, hipStream_t st) {
+  if (nsplit < 1) return PH_EINVAL;      // (the slab depth below divides by it)
   int kchunk = cdiv(cdiv(K, nsplit), GK) * GK;
-  nsplit = cdiv(K, kchunk);
+  nsplit = cdiv(K, kchunk);      // never more than asked for: `part` holds the caller's nsplit slabs of M x N
+  ph_dispatch_note(PH_DK_SGEMM_SPLITK);
   dim3 grid(cdiv(N, GT), cdiv(M, GT), nsplit);
   hipLaunchKernelGGL(sgemm_splitk_kernel, grid, dim3(256), 0, st, A, B, part, M, N, K, sam, sak, sbk, sbn, kchunk);
   hipLaunchKernelGGL(splitk_finish_kernel, dim3(nblk((size_t)M * N * 4)), dim3(256), 0, st, part, bias, C, M, N, ldc,

@@ -116,6 +116,9 @@ int ph_tapconv_hp_wfrag(const PhTapConv* p, int S, int prec);
 #define PH_DK_WGRAD_BF16 (1u << 13)   // conv_wgrad.hip, per activation type
 #define PH_DK_WGRAD_HP16 (1u << 14)
 #define PH_DK_WGRAD_F32 (1u << 15)
+#define PH_DK_SGEMM16 (1u << 16)      // dense.hip sgemm_small_kernel (16 x 16 tiles, M * N <= 128 * 128)
+#define PH_DK_SGEMM64 (1u << 17)      // dense.hip sgemm_kernel (64 x 64 tiles)
+#define PH_DK_SGEMM_SPLITK (1u << 18) // dense.hip sgemm_splitk_kernel + splitk_finish_kernel
 void ph_dispatch_note(unsigned bits);
 int ph_tapconv_launch(const PhTapConv* p, int S, int prec, hipStream_t st);
 double ph_tapconv_bytes(const PhTapConv& p, int S, int es);

@@ -7,7 +7,34 @@ import torch
 
 # kernel families of the tap-conv / weight-gradient launchers, in the bit order of ph_debug_dispatch_mask (csrc/ph_kernels.h PH_DK_*)
 DISPATCH_FAMILIES = ["gen1_bf16", "gen1_hp16", "gen1_f32", "tap2", "tap2_masked", "tap2_l1", "tap3", "tap3_hp", "tap4", "tap5",
-                     "tap6", "tap6b", "tap7", "wgrad_bf16", "wgrad_hp16", "wgrad_f32"]
+                     "tap6", "tap6b", "tap7", "wgrad_bf16", "wgrad_hp16", "wgrad_f32",
+                     # the dense GEMMs (dense.hip): 16 x 16 tiles, 64 x 64 tiles, split-K + finish
+                     "sgemm16", "sgemm64", "sgemm_splitk"]
+
+GUARD = 4096          # bytes of sentinel on each side of an output (a multiple of 256: the half-pair alignment is kept)
+SENTINEL = 0x5A
+
+
+class Guarded:
+    """An output tensor of `shape` / `dtype` inside a byte buffer with sentinel guard bands."""
+
+    def __init__(self, shape, dtype, fill=float("nan")):
+        n = 1
+        for s in shape:
+            n *= s
+        es = torch.empty((), dtype=dtype).element_size()
+        self.nbytes = n * es
+        self.buf = torch.full((GUARD + self.nbytes + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
+        self.t = self.buf[GUARD:GUARD + self.nbytes].view(dtype).view(shape)
+        self.t.fill_(fill)
+        assert self.t.data_ptr() % 256 == 0
+
+    def guards_intact(self):
+        g = torch.cat([self.buf[:GUARD], self.buf[GUARD + self.nbytes:]])
+        return bool((g == SENTINEL).all())
+
+    def snapshot(self):
+        return self.buf.clone()
 
 
 def dispatch_lib():
@@ -81,6 +108,11 @@ class Report:
     def close(self, ref, got, atol, rtol=0.0, what=""):
         err, mx = maxerr(ref, got)
         self.rows.append((what, err, mx, atol + rtol * mx))
+        return err
+
+    def add(self, what, err, mx, tol):
+        """A row whose error and tolerance the caller worked out."""
+        self.rows.append((what, err, mx, tol))
         return err
 
     def finish(self):

@@ -47,6 +47,14 @@ def test_plan_host_logic_without_gpu():
     assert not L.ph_resnet_plan_create(4, 512, 512, 7)
 
 
+def test_sgemm_splitk_rejects_nsplit_below_one_before_any_hip_call():
+    """The slab depth is cdiv(K, nsplit): nsplit < 1 is PH_EINVAL on the host, never a division by zero."""
+    import multimodal_learning_amd as m
+    L = m.lib()
+    for nsplit in (0, -1, -128):
+        assert L.ph_sgemm_splitk(None, None, None, None, None, nsplit, 4, 4, 40, 40, 1, 1, 40, 4, 0, None) == -22
+
+
 def test_state_dict_layout_matches_reference():
     import multimodal_learning_amd as m
     from oracle import weights as W

@@ -20,35 +20,11 @@ import torch
 
 from tests import conv_emulation as E
 from tests.conv_sweep_cases import CASES, expected_family
-from tests.gpu_util import dispatch_lib, dispatched
+from tests.gpu_util import GUARD, SENTINEL, Guarded, dispatch_lib, dispatched
 
 pytestmark = pytest.mark.gpu
 
 EINVAL = -22
-GUARD = 4096          # bytes of sentinel on each side of an output (a multiple of 256: the half-pair alignment is kept)
-SENTINEL = 0x5A
-
-
-class Guarded:
-    """An output tensor of `shape` / `dtype` inside a byte buffer with sentinel guard bands."""
-
-    def __init__(self, shape, dtype, fill=float("nan")):
-        n = 1
-        for s in shape:
-            n *= s
-        es = torch.empty((), dtype=dtype).element_size()
-        self.nbytes = n * es
-        self.buf = torch.full((GUARD + self.nbytes + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.t = self.buf[GUARD:GUARD + self.nbytes].view(dtype).view(shape)
-        self.t.fill_(fill)
-        assert self.t.data_ptr() % 256 == 0
-
-    def guards_intact(self):
-        g = torch.cat([self.buf[:GUARD], self.buf[GUARD + self.nbytes:]])
-        return bool((g == SENTINEL).all())
-
-    def snapshot(self):
-        return self.buf.clone()
 
 
 def _workspace(L, B, Cin, IH, IW, Cout, KS, S, pad):
