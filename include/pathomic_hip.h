@@ -201,6 +201,10 @@ int ph_sum(const float* x, float* out, int n, float scale, ph_stream_t stream);
  * mem1/mem2 = memory_v1/memory_v2 [n_data][128] f32, params = the module's `params` buffer
  * [K, T, Z_v1, Z_v2, momentum, P].
  * ---------------------------------------------------------------------------------------------- */
+/* Sizes are checked on the host before anything is launched; PH_EINVAL for: ph_crd_score B < 1 or PK < 1; ph_crd_select B < 1,
+ * P < 1, K < 0, P2 < 1, K2 < 0, P2 > P, K2 > K, an unranked side that does not keep every column (P2 != P / K2 != K) or a ranked
+ * list above 160 KiB of LDS ((2 P + K) * 4 bytes); ph_crd_zsum n < 1; ph_crd_update B < 1; ph_crd_loss_grad B < 1, P2 < 1, K2 < 0
+ * or P2 + K2 > PK (ph_crd_loss_grad_pos: B < 1, P < 1, m_neg < 1); feat_dim != 128 everywhere. */
 /* idx_bank2: optional second index array for memory_v2 (MIA-2023 v10: each bank has its own KNN positives); NULL = idx */
 int ph_crd_score(const float* v1, const float* v2, const int64_t* idx /* [B][P+K] */, const int64_t* idx_bank2,
                  const float* mem1, const float* mem2, float* out1, float* out2, float* diff /* each [B][P+K] */,

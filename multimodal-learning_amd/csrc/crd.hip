@@ -897,7 +897,7 @@ int ph_crd_bank_topk(const float* mem1, const float* mem2, const int* labels, co
 int ph_crd_score(const float* v1, const float* v2, const int64_t* idx, const int64_t* idx_bank2, const float* mem1,
                  const float* mem2, float* out1, float* out2, float* diff, int B, int PK, int feat_dim, float T,
                  hipStream_t st) {
-  if (feat_dim != D) return PH_EINVAL;
+  if (feat_dim != D || B < 1 || PK < 1) return PH_EINVAL;
   void* tok = nullptr;
   if (ph_prof_on())   // algorithmic bytes: one 512-B row of each bank per (sample, column) + the three [B][P+K] outputs
     ph_prof_begin(PH_CLS_CRD_SCORE, 2.0 * B * PK * D * 4 + 3.0 * B * PK * 4 + 2.0 * B * D * 4, st, &tok);
@@ -910,6 +910,7 @@ int ph_crd_score(const float* v1, const float* v2, const int64_t* idx, const int
 
 int ph_crd_select(const float* diff, const float* out1, const float* out2, const int* ranks, int* sel, float* xs,
                   float* xt, int B, int P, int K, int P2, int K2, int select_neg, int select_pos, hipStream_t st) {
+  if (B < 1 || P < 1 || K < 0 || P2 < 1 || K2 < 0) return PH_EINVAL;
   if (P2 > P || K2 > K || (!select_pos && P2 != P) || (!select_neg && K2 != K)) return PH_EINVAL;
   const bool ranked = select_pos || select_neg;
   const size_t lds = ranked ? (size_t)(P + K) * 4 + (size_t)P * 4 : 0;
@@ -923,6 +924,7 @@ int ph_crd_select(const float* diff, const float* out1, const float* out2, const
 }
 
 int ph_crd_zsum(const float* xs, const float* xt, float* sums, int n, hipStream_t st) {
+  if (n < 1) return PH_EINVAL;
   hipLaunchKernelGGL(crd_zsum_kernel, dim3(1), dim3(1024), 0, st, xs, xt, sums, n);
   PH_LAUNCH_CHECK();
   return PH_OK;
@@ -959,7 +961,7 @@ static int crd_loss_grad_impl(const float* xs, const float* xt, const int* sel, 
                               const float* posw_s, const float* posw_t, const float* mem1, const float* mem2,
                               const float* params, float* lossp, float* dv1, float* dv2, int B, int PK, int P2, int K2, int m_neg,
                               int feat_dim, float n_data, float inv_bnorm, void* workspace, hipStream_t st) {
-  if (feat_dim != D) return PH_EINVAL;
+  if (feat_dim != D || B < 1 || P2 < 1 || K2 < 0 || P2 + K2 > PK) return PH_EINVAL;
   int ns = workspace ? (P2 + K2) / 512 : 1;     // one workgroup per 512 columns of a sample, at most LG_SPLIT_MAX
   ns = ns < 1 ? 1 : (ns > LG_SPLIT_MAX ? LG_SPLIT_MAX : ns);
   void* tok = nullptr;
@@ -1008,7 +1010,7 @@ int ph_crd_scan_neg(float* S1, float* S2, const int* mult, const float* params, 
 }
 int ph_crd_update(float* mem1, float* mem2, const float* v1, const float* v2, const int64_t* y, const float* params,
                   int B, int feat_dim, hipStream_t st) {
-  if (feat_dim != D) return PH_EINVAL;
+  if (feat_dim != D || B < 1) return PH_EINVAL;
   hipLaunchKernelGGL(crd_update_kernel, dim3(cdiv(2 * B, 4)), dim3(256), 0, st, mem1, mem2, v1, v2, y, params, B);
   PH_LAUNCH_CHECK();
   return PH_OK;

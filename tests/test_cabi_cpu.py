@@ -55,6 +55,32 @@ def test_sgemm_splitk_rejects_nsplit_below_one_before_any_hip_call():
         assert L.ph_sgemm_splitk(None, None, None, None, None, nsplit, 4, 4, 40, 40, 1, 1, 40, 4, 0, None) == -22
 
 
+def test_crd_entries_reject_bad_sizes_before_any_hip_call():
+    """Non-positive sizes used to reach the launch as a zero grid dimension and came back as PH_ELAUNCH after a HIP call; they are
+    PH_EINVAL on the host (this machine has no device: anything that reached HIP would not return -22).  Also the list checks of
+    ph_crd_select: P2 > P, K2 > K, an unranked side that does not keep every column, a ranked list above 160 KiB of LDS."""
+    import multimodal_learning_amd as m
+    L = m.lib()
+    N9, N7, N13 = [None] * 9, [None] * 7, [None] * 13
+    for (B, PK) in ((0, 8), (-1, 8), (2, 0), (2, -3)):
+        assert L.ph_crd_score(*N9, B, PK, 128, 0.07, None) == -22, (B, PK)
+    sel = lambda B, P, K, P2, K2, sn, sp: L.ph_crd_select(*N7, B, P, K, P2, K2, sn, sp, None)
+    for a in ((0, 4, 8, 2, 2, 1, 1), (-2, 4, 8, 2, 2, 1, 1), (1, 0, 8, 0, 2, 1, 1), (1, 4, -1, 2, 0, 1, 1), (1, 4, 8, 0, 2, 1, 1),
+              (1, 4, 8, -1, 2, 1, 1), (1, 4, 8, 2, -1, 1, 1),
+              (1, 4, 8, 5, 2, 1, 1), (1, 4, 8, 2, 9, 1, 1), (1, 4, 8, 3, 2, 1, 0), (1, 4, 8, 2, 7, 0, 1),
+              (1, 4, 40955, 2, 8, 1, 1), (1, 20481, 4, 2, 2, 1, 0)):
+        assert sel(*a) == -22, a
+    for n in (0, -1):
+        assert L.ph_crd_zsum(None, None, None, n, None) == -22
+    for B in (0, -5):
+        assert L.ph_crd_update(None, None, None, None, None, None, B, 128, None) == -22
+    for (B, PK, P2, K2) in ((0, 40, 4, 16), (-1, 40, 4, 16), (2, 40, 0, 16), (2, 40, -2, 16), (2, 40, 4, 37), (2, 40, 4, -1)):
+        assert L.ph_crd_loss_grad(*N13, B, PK, P2, K2, 128, 257.0, 0.5, None, None) == -22, (B, PK, P2, K2)
+    assert L.ph_crd_loss_grad_pos(*N13, 0, 4, 16, 128, 257.0, 0.5, None) == -22
+    assert L.ph_crd_loss_grad_pos(*N13, 2, 0, 16, 128, 257.0, 0.5, None) == -22
+    assert L.ph_crd_loss_grad_pos(*N13, 2, 4, 0, 128, 257.0, 0.5, None) == -22
+
+
 def test_state_dict_layout_matches_reference():
     import multimodal_learning_amd as m
     from oracle import weights as W

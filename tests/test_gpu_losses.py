@@ -415,10 +415,11 @@ def test_mia2023_crd_v10_centers_golden(golden_dir):
         V10.CRDLoss(m.stage2_opt(nce_k=16, nce_p=3, pos_extra="prototypes"), n_data, class_idx)
 
 
-@pytest.mark.parametrize("n,B,NP", [(65536, 8, 6), (65536, 64, 6), (5000, 100, 8), (77, 3, 2)])
+@pytest.mark.parametrize("n,B,NP", [(65536, 8, 6), (65536, 64, 6), (5000, 100, 8), (77, 3, 2), (33, 33, 8), (257, 65, 1)])
 def test_mia2023_bank_topk_bit_exact(n, B, NP):
     """The KNN indices are integer work: identical to torch.sort of the class-masked cosine on the same bank.  (65536 rows =
-    BASELINE config 5's bank; 64 queries = the benchmark batch; 100 queries = two passes of <= 64; ragged last tile.)"""
+    BASELINE config 5's bank; 64 queries = the benchmark batch; 100 queries = two passes of <= 64; ragged last tile; 33 rows = one
+    tile plus one row with a second query block of one; 65 queries = a second pass of one.)"""
     from multimodal_learning_amd._lib import lib, ptr, stream, check
     import torch.nn.functional as F
     L = lib()
@@ -436,7 +437,9 @@ def test_mia2023_bank_topk_bit_exact(n, B, NP):
                              ptr(nb1), ptr(nb2), ptr(s1), ptr(s2), ptr(ws), stream()), "topk")
     for mem, nb, s in ((mem1, nb1, s1), (mem2, nb2, s2)):
         sim = (labels.view(1, -1) == bl.view(-1, 1)).float() * (F.normalize(mem[idx[:, 0]], dim=1) @ F.normalize(mem, dim=1).T)
-        srt = torch.sort(sim, descending=True, dim=-1)
+        # (33 rows, 8 neighbours: a class has fewer than 8 rows of positive similarity, the masked zeros fill the list in row order -
+        # the order of a stable sort, with the -0.0 of a masked negative similarity sorting like +0.0)
+        srt = torch.sort(sim + 0.0, descending=True, dim=-1, stable=True)
         assert torch.equal(nb.cpu(), srt[1][:, :NP])
         assert torch.allclose(s.cpu(), srt[0][:, :NP], atol=1e-6)
 
