@@ -375,7 +375,11 @@ int ph_conv2d_wgrad(const void* x, const void* dy, float* dw_oihw, int B, int Ci
  *   out[0] = scale * sum (a - b)^2 ;  gradient out = gscalar[0] * alpha * (a - b).
  * ph_tsvd_update_aux replaces update_aux(adj, Lambda_global / mu) called at :382-391 (its source is absent from the
  * reference: this is the tensor-nuclear-norm proximal operator, see csrc/tsvd.hip): adj, aux are [V][B][B] (view-major),
- * V in {2,4,6,8}, B <= 128 (B <= 64: Jacobi on the embedding of X^H X; above: one-sided Jacobi on the slice); tnn[0] = (1/V) sum over frequency slices of the nuclear norm of the thresholded slice.
+ * V in {2,4,6,8}, B <= 512 (B <= 64: Jacobi on the embedding of X^H X; up to 128: one-sided Jacobi on the slice, one workgroup per
+ * slice; up to 512: block one-sided Jacobi tiled over workgroups, one launch per round-robin step - a fixed number of launches
+ * for a given (V, B), no host read, capturable); above 512 PH_EINVAL.  tnn[0] = (1/V) sum over frequency slices of the nuclear
+ * norm of the thresholded slice.  ws: ph_tsvd_workspace_bytes(V, B) bytes, 16-byte aligned; its last 16 floats hold the TNN per
+ * slice (0 .. V/2) and, for B > 64, the Jacobi sweeps per slice (8 ..).
  * ---------------------------------------------------------------------------------------------- */
 /* Relational distillation baselines of the distiller zoo (`--distill pkt|rkd`,
  * "MIA 2022/train_test_path_multi_distill_v2.py":339-342).  Each entry returns the loss AND its gradient with respect

@@ -11,7 +11,8 @@
 // real symmetric 2B x 2B matrix [[Re, -Im], [Im, Re]] (every eigenvalue twice; a matrix function of the embedding
 // is the embedding of the matrix function) and diagonalised in LDS by parallel cyclic Jacobi rotations (round-robin
 // pairing: n/2 disjoint rotations per step).  One workgroup per frequency slice k = 0 .. V/2 (the others are
-// complex conjugates).  B <= 64; larger batches (up to 128) use the one-sided Jacobi kernel below.
+// complex conjugates).  B <= 64; larger batches use the one-sided Jacobi kernels below: up to 128 rows one workgroup per
+// slice, up to 512 rows (the global batch of a data-parallel run) a block Jacobi tiled over many workgroups.
 #include "ph_common.h"
 #include "ph_kernels.h"
 
@@ -488,11 +489,298 @@ __global__ void tsvd_idft_kernel(const float* __restrict__ yre, const float* __r
   aux[i] = acc / (float)V;
 }
 
+// ---- 128 < B <= 512: block one-sided Jacobi ACROSS workgroups.  A 512 x 512 complex slice is 2 MiB, so the working copy A
+// (column-major (re, im) pairs like the kernel above, column stride TT_CS(B) floats, padded with zero columns to an even
+// number nb of blocks of TT_W columns) lives in the workspace.  One launch per step of a round robin over the nb blocks:
+// workgroup (i, k) loads the two blocks of its pair of slice k into LDS (2 TT_W columns, 128 KiB at 512 rows), runs the
+// full inner round robin over those 32 columns - one wave per column pair, lane l owning the row pairs l + 64 m, m < 4,
+// i.e. the four-v4f register shape of `rotate` above - and writes the blocks back if anything rotated.  The order between
+// steps is the launch order on the stream; termination is a per-slice, per-sweep "rotated" flag in the workspace: the
+// launches of sweep s >= 1 return at once for a slice whose sweep s - 1 rotated nothing (or was itself skipped), so the
+// launch count TB_MAX_SWEEPS * (nb - 1) is a fixed function of (V, B) and nothing is read back by the host.  The flags are
+// cleared on the device at the start of every call (graph replays start clean) and are the only atomics of the path.
+constexpr int TT_MAXB = 512, TT_W = 16, TT_NC = 2 * TT_W, TT_FLAG_LD = 8;
+static_assert(TSVD_MAX_V / 2 + 1 <= TT_FLAG_LD, "one flag per frequency slice and sweep");
+struct TtLayout {
+  int S, nb, ncol, nm, CS;
+  size_t a_off, dj_off, meta_off, flag_off, tail_off;      // in floats from the start of the workspace
+};
+inline TtLayout tt_layout(int V, int B) {
+  TtLayout L;
+  L.S = V / 2 + 1;
+  L.nb = (((B + TT_W - 1) / TT_W) + 1) & ~1;
+  L.ncol = L.nb * TT_W;
+  L.nm = (B + 127) >> 7;             // row chunks of 128 (64 lanes x 2 rows) that hold data
+  L.CS = 256 * L.nm;
+  L.a_off = (size_t)L.S * 4 * B * B;
+  L.dj_off = L.a_off + (size_t)L.S * L.ncol * L.CS;
+  L.meta_off = L.dj_off + (size_t)L.S * L.ncol;
+  L.flag_off = L.meta_off + TT_FLAG_LD;
+  L.tail_off = L.flag_off + (size_t)TB_MAX_SWEEPS * TT_FLAG_LD;
+  return L;
+}
+
+// sum over the 64 lanes of a wave, the same bits in every lane (both partners of an exchange add the same two numbers)
+__device__ __forceinline__ float wave64_sum(float x) {
+  x = row16_sum(x);
+  x += __shfl_xor(x, 16);
+  x += __shfl_xor(x, 32);
+  return x;
+}
+
+// X_k (row-major planes, read by the finish) and the zero-padded column-major working copy A_k
+__global__ __launch_bounds__(256) void tsvd_tiled_stage_kernel(const float* __restrict__ adj, float* __restrict__ yre,
+                                                               float* __restrict__ yim, float* __restrict__ Aw, int V, int B,
+                                                               int ncol, int CS) {
+  const int k = blockIdx.y, rp = CS / 2;
+  const size_t bb = (size_t)B * B;
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)ncol * rp) return;
+  const int j = (int)(e / rp), r = (int)(e % rp);
+  v2f val = {0.f, 0.f};
+  if (j < B && r < B) {
+    float re, im;
+    const size_t ij = (size_t)r * B + j;
+    dft_elem(adj, V, bb, ij, k, re, im);
+    yre[(size_t)k * bb + ij] = re;
+    yim[(size_t)k * bb + ij] = im;
+    val = v2f{re, im};
+  }
+  *reinterpret_cast<v2f*>(Aw + ((size_t)k * ncol + j) * CS + 2 * r) = val;
+}
+
+// ||X_k||_F^2 -> the column floor of slice k; clears the slice's "rotated" flags
+__global__ __launch_bounds__(1024) void tsvd_tiled_norm_kernel(const float* __restrict__ yre, const float* __restrict__ yim,
+                                                               float* __restrict__ meta, int* __restrict__ flags, int B) {
+  __shared__ float red[1024];
+  const int tid = threadIdx.x, k = blockIdx.x;
+  const size_t bb = (size_t)B * B;
+  const float* xr = yre + (size_t)k * bb;
+  const float* xi = yim + (size_t)k * bb;
+  float part = 0.f;
+  for (size_t e = tid; e < bb; e += 1024) part += xr[e] * xr[e] + xi[e] * xi[e];
+  red[tid] = part;
+  if (tid < TB_MAX_SWEEPS) flags[tid * TT_FLAG_LD + k] = 0;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) meta[k] = 1e-14f * red[0];
+}
+
+// the rotation of tsvd_slice_big_kernel on the register copies of two columns, reduced over the 64 lanes of a wave
+__device__ __forceinline__ bool tt_rotate(v4f (&a)[4], v4f (&b)[4], int nm, float col_floor) {
+  v2f saa = {0.f, 0.f}, sbb = {0.f, 0.f}, sab = {0.f, 0.f}, sax = {0.f, 0.f};
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    if (m < nm) {
+      const v2f a0 = a[m].xy, a1 = a[m].zw, b0 = b[m].xy, b1 = b[m].zw;
+      saa = pk_fma(a0, a0, saa); saa = pk_fma(a1, a1, saa);
+      sbb = pk_fma(b0, b0, sbb); sbb = pk_fma(b1, b1, sbb);
+      sab = pk_fma(a0, b0, sab); sab = pk_fma(a1, b1, sab);        // (ar br, ai bi)
+      sax = pk_fma(a0, b0.yx, sax); sax = pk_fma(a1, b1.yx, sax);  // (ar bi, ai br)
+    }
+  }
+  const float al = wave64_sum(saa.x + saa.y), be = wave64_sum(sbb.x + sbb.y);
+  const float gr = wave64_sum(sab.x + sab.y);      // conj(a_p) . a_q
+  const float gi = wave64_sum(sax.x - sax.y);
+  const float g2 = gr * gr + gi * gi;
+  if (!(fminf(al, be) > col_floor && g2 > TB_TOL2 * al * be)) return false;
+  const float rg = __frsqrt_rn(g2);
+  const float ze = (be - al) * (0.5f * rg);
+  const float t = copysignf(1.f, ze) / (fabsf(ze) + sqrtf(1.f + ze * ze));
+  const float c = __frsqrt_rn(1.f + t * t), sn = c * t;
+  const float ser = sn * gr * rg, sei = sn * gi * rg;
+  const v2f c2 = {c, c}, s2 = {ser, ser}, ns2 = {-ser, -ser}, k1 = {-sei, sei};
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    if (m < nm) {
+      const v2f a0 = a[m].xy, a1 = a[m].zw, b0 = b[m].xy, b1 = b[m].zw;
+      const v2f p0 = pk_fma(c2, a0, pk_fma(ns2, b0, k1 * b0.yx));
+      const v2f p1 = pk_fma(c2, a1, pk_fma(ns2, b1, k1 * b1.yx));
+      const v2f q0 = pk_fma(c2, b0, pk_fma(s2, a0, k1 * a0.yx));
+      const v2f q1 = pk_fma(c2, b1, pk_fma(s2, a1, k1 * a1.yx));
+      a[m] = v4f{p0.x, p0.y, p1.x, p1.y};
+      b[m] = v4f{q0.x, q0.y, q1.x, q1.y};
+    }
+  }
+  return true;
+}
+
+// step t of sweep `sweep`: workgroup (i, k) rotates the columns of block pair i of slice k
+__global__ __launch_bounds__(1024) void tsvd_tiled_step_kernel(float* __restrict__ Aw, int* __restrict__ flags,
+                                                               const float* __restrict__ meta, int sweep, int t, int nb,
+                                                               int nm, int CS) {
+  const int tid = threadIdx.x, i = blockIdx.x, k = blockIdx.y;
+  if (sweep > 0 && flags[(sweep - 1) * TT_FLAG_LD + k] == 0) return;      // the slice has converged (uniform over the workgroup)
+  extern __shared__ float sm[];          // [TT_NC][CS] columns, then the workgroup's "rotated" flag
+  int& rotated = *reinterpret_cast<int*>(sm + TT_NC * CS);
+  // round robin over the blocks, as over the columns of tsvd_slice_big_kernel
+  const int bp = i == 0 ? nb - 1 : (t + i - 1) % (nb - 1);
+  const int bq = (t + nb - 2 - i) % (nb - 1);
+  const int lo = bp < bq ? bp : bq, hi = bp < bq ? bq : bp;
+  float* Ak = Aw + (size_t)k * nb * TT_W * CS;
+  v4f* g0 = reinterpret_cast<v4f*>(Ak + (size_t)lo * TT_W * CS);         // a block is TT_W * CS contiguous floats
+  v4f* g1 = reinterpret_cast<v4f*>(Ak + (size_t)hi * TT_W * CS);
+  v4f* s4 = reinterpret_cast<v4f*>(sm);
+  const int nv = TT_W * CS / 4;
+#pragma unroll 4
+  for (int e = tid; e < nv; e += 1024) { s4[e] = g0[e]; s4[nv + e] = g1[e]; }
+  if (tid == 0) rotated = 0;
+  const float col_floor = meta[k];
+  __syncthreads();
+  const int w = tid >> 6, l = tid & 63;
+  bool moved = false;
+#pragma unroll 1
+  for (int step = 0; step < TT_NC - 1; ++step) {
+    const int p = w == 0 ? TT_NC - 1 : (step + w - 1) % (TT_NC - 1);
+    const int q = (step + TT_NC - 2 - w) % (TT_NC - 1);
+    v4f* cp = reinterpret_cast<v4f*>(sm + p * CS) + l;
+    v4f* cq = reinterpret_cast<v4f*>(sm + q * CS) + l;
+    v4f a[4], b[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      if (m < nm) { a[m] = cp[64 * m]; b[m] = cq[64 * m]; }
+      else { a[m] = v4f{0.f, 0.f, 0.f, 0.f}; b[m] = a[m]; }     // (defined every step: nothing is carried round the loop)
+    }
+    if (tt_rotate(a, b, nm, col_floor)) {
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+        if (m < nm) { cp[64 * m] = a[m]; cq[64 * m] = b[m]; }
+      moved = true;
+    }
+    __syncthreads();
+  }
+  if (moved && l == 0) rotated = 1;
+  __syncthreads();
+  if (!rotated) return;
+#pragma unroll 4
+  for (int e = tid; e < nv; e += 1024) { g0[e] = s4[e]; g1[e] = s4[nv + e]; }
+  if (tid == 0) atomicOr(&flags[sweep * TT_FLAG_LD + k], 1);
+}
+
+// sigma_j = ||a_j||, d_j = f_j / sigma_j^2 with the `keep` rule of tsvd_slice_big_kernel; TNN of the slice in a fixed order
+__global__ __launch_bounds__(1024) void tsvd_tiled_sigma_kernel(const float* __restrict__ Aw, float* __restrict__ djw,
+                                                                const float* __restrict__ meta, const int* __restrict__ flags,
+                                                                float* __restrict__ tnn_k, int ncol, int nm, int CS, float tau,
+                                                                const float* __restrict__ tau_dev) {
+  if (tau_dev) tau = tau_dev[0];
+  __shared__ float part[TT_MAXB];
+  const int tid = threadIdx.x, k = blockIdx.x, w = tid >> 6, l = tid & 63;
+  const float col_floor = meta[k];
+  if (tid < TT_MAXB) part[tid] = 0.f;
+  __syncthreads();
+  for (int j = w; j < ncol; j += 16) {
+    const v4f* c = reinterpret_cast<const v4f*>(Aw + ((size_t)k * ncol + j) * CS) + l;
+    float s = 0.f;
+    for (int m = 0; m < nm; ++m) {
+      const v4f x = c[64 * m];
+      s += x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
+    }
+    const float a2 = wave64_sum(s);
+    const float sig = sqrtf(a2);
+    const bool keep = a2 > 100.f * col_floor && sig > tau;
+    if (l == 0) {
+      djw[(size_t)k * ncol + j] = keep ? (1.f - tau / sig) / a2 : 0.f;
+      part[j] = keep ? sig - tau : 0.f;
+    }
+  }
+  __syncthreads();
+  for (int o = TT_MAXB / 2; o > 0; o >>= 1) {
+    if (tid < o) part[tid] += part[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    tnn_k[k] = part[0];
+    int sweeps = 1;                      // sweep 0 always runs; sweep s + 1 runs iff sweep s rotated
+    for (int s = 0; s < TB_MAX_SWEEPS - 1; ++s) sweeps += flags[s * TT_FLAG_LD + k] != 0;
+    tnn_k[8 + k] = (float)sweeps;
+  }
+}
+
+// The two complex GEMMs of the finish, fp32 FMAs in a fixed k order: 64 x 64 outputs per workgroup, 4 x 4 per thread.
+//   SECOND = false: T = D A^H X   (left operand conj(A)^T: column j of A is row j, contiguous)
+//   SECOND = true : Y = A T
+template <bool SECOND>
+__global__ __launch_bounds__(256) void tsvd_tiled_gemm_kernel(const float* __restrict__ Aw, const float* __restrict__ djw,
+                                                              const float* __restrict__ rre, const float* __restrict__ rim,
+                                                              float* __restrict__ ore, float* __restrict__ oim, int B, int ncol,
+                                                              int CS) {
+  __shared__ v2f Ls[16][64];
+  __shared__ float Rr[16][64], Ri[16][64];
+  const int tid = threadIdx.x, k = blockIdx.z, m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+  const int tx = tid & 15, ty = tid >> 4;
+  const size_t bb = (size_t)B * B;
+  const float* Ak = Aw + (size_t)k * ncol * CS;
+  const float* Rre = rre + (size_t)k * bb;
+  const float* Rim = rim + (size_t)k * bb;
+  float cr[4][4], ci[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { cr[a][b] = 0.f; ci[a][b] = 0.f; }
+  for (int k0 = 0; k0 < B; k0 += 16) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int mm, kk;
+      if (SECOND) { mm = tid & 63; kk = (tid >> 6) + 4 * r; }
+      else        { kk = tid & 15; mm = (tid >> 4) + 16 * r; }
+      const int gm = m0 + mm, gk = k0 + kk;
+      v2f v = {0.f, 0.f};
+      if (gm < B && gk < B) {
+        if (SECOND) v = *reinterpret_cast<const v2f*>(Ak + (size_t)gk * CS + 2 * gm);
+        else { v = *reinterpret_cast<const v2f*>(Ak + (size_t)gm * CS + 2 * gk); v.y = -v.y; }
+      }
+      Ls[kk][mm] = v;
+      const int nn = tid & 63, k2 = (tid >> 6) + 4 * r;
+      const int gn = n0 + nn, gk2 = k0 + k2;
+      const bool in = gn < B && gk2 < B;
+      Rr[k2][nn] = in ? Rre[(size_t)gk2 * B + gn] : 0.f;
+      Ri[k2][nn] = in ? Rim[(size_t)gk2 * B + gn] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      v2f lv[4];
+      float rr[4], ri[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) lv[a] = Ls[kk][ty * 4 + a];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) { rr[b] = Rr[kk][tx * 4 + b]; ri[b] = Ri[kk][tx * 4 + b]; }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          cr[a][b] = fmaf(lv[a].x, rr[b], cr[a][b]); cr[a][b] = fmaf(-lv[a].y, ri[b], cr[a][b]);
+          ci[a][b] = fmaf(lv[a].x, ri[b], ci[a][b]); ci[a][b] = fmaf(lv[a].y, rr[b], ci[a][b]);
+        }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int gm = m0 + ty * 4 + a;
+    if (gm >= B) continue;
+    const float d = SECOND ? 1.f : djw[(size_t)k * ncol + gm];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int gn = n0 + tx * 4 + b;
+      if (gn >= B) continue;
+      ore[(size_t)k * bb + (size_t)gm * B + gn] = SECOND ? cr[a][b] : cr[a][b] * d;
+      oim[(size_t)k * bb + (size_t)gm * B + gn] = SECOND ? ci[a][b] : ci[a][b] * d;
+    }
+  }
+}
+
 }  // namespace
 
 #include "pathomic_hip.h"
 
-size_t ph_tsvd_workspace_bytes(int V, int B) { return ((size_t)(V / 2 + 1) * 4 * B * B + 16) * sizeof(float); }
+size_t ph_tsvd_workspace_bytes(int V, int B) {
+  if (B > TB_MAXB && B <= TT_MAXB && V >= 2 && V <= TSVD_MAX_V) return (tt_layout(V, B).tail_off + 16) * sizeof(float);
+  return ((size_t)(V / 2 + 1) * 4 * B * B + 16) * sizeof(float);
+}
 
 int ph_sqdiff_sum(const float* a, const float* b, float* out, size_t n, float scale, hipStream_t st) {
   hipLaunchKernelGGL(sqdiff_sum_kernel, dim3(1), dim3(1024), 0, st, a, b, out, n, scale);
@@ -525,9 +813,52 @@ int ph_tsvd_update_aux_dev(const float* adj, float* aux, float* tnn, int V, int 
 }
 static int tsvd_update_aux_impl(const float* adj, float* aux, float* tnn, int V, int B, float tau, const float* tau_dev, void* ws_,
                                 hipStream_t st) {
-  if (!adj || !aux || !ws_ || V < 2 || V > TSVD_MAX_V || (V & 1) || B < 1 || B > TB_MAXB) return PH_EINVAL;
+  if (!adj || !aux || !ws_ || V < 2 || V > TSVD_MAX_V || (V & 1) || B < 1 || B > TT_MAXB) return PH_EINVAL;
   float* ws = reinterpret_cast<float*>(ws_);
   const size_t bb = (size_t)B * B;
+  if (B > TB_MAXB) {
+    const TtLayout L = tt_layout(V, B);
+    float* yre = ws;
+    float* yim = yre + (size_t)L.S * bb;
+    float* tre = yim + (size_t)L.S * bb;
+    float* tim = tre + (size_t)L.S * bb;
+    float* Aw = ws + L.a_off;
+    float* djw = ws + L.dj_off;
+    float* meta = ws + L.meta_off;
+    int* flags = reinterpret_cast<int*>(ws + L.flag_off);
+    float* tk = ws + L.tail_off;
+    const int ldsb = (TT_NC * L.CS + 4) * (int)sizeof(float);
+    static bool attr_tiled = false;
+    if (!attr_tiled) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(tsvd_tiled_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (TT_NC * 2 * TT_MAXB + 4) * (int)sizeof(float)) != hipSuccess)
+        return PH_ELAUNCH;
+      attr_tiled = true;
+    }
+    const size_t na = (size_t)L.ncol * (L.CS / 2);
+    hipLaunchKernelGGL(tsvd_tiled_stage_kernel, dim3((unsigned)((na + 255) / 256), L.S), dim3(256), 0, st, adj, yre, yim, Aw, V, B,
+                       L.ncol, L.CS);
+    PH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tsvd_tiled_norm_kernel, dim3(L.S), dim3(1024), 0, st, yre, yim, meta, flags, B);
+    PH_LAUNCH_CHECK();
+    for (int sweep = 0; sweep < TB_MAX_SWEEPS; ++sweep)
+      for (int t = 0; t < L.nb - 1; ++t) {
+        hipLaunchKernelGGL(tsvd_tiled_step_kernel, dim3(L.nb / 2, L.S), dim3(1024), ldsb, st, Aw, flags, meta, sweep, t, L.nb, L.nm,
+                           L.CS);
+        PH_LAUNCH_CHECK();
+      }
+    hipLaunchKernelGGL(tsvd_tiled_sigma_kernel, dim3(L.S), dim3(1024), 0, st, Aw, djw, meta, flags, tk, L.ncol, L.nm, L.CS, tau,
+                       tau_dev);
+    PH_LAUNCH_CHECK();
+    const dim3 gg((B + 63) / 64, (B + 63) / 64, L.S);
+    hipLaunchKernelGGL(tsvd_tiled_gemm_kernel<false>, gg, dim3(256), 0, st, Aw, djw, yre, yim, tre, tim, B, L.ncol, L.CS);
+    PH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tsvd_tiled_gemm_kernel<true>, gg, dim3(256), 0, st, Aw, djw, tre, tim, yre, yim, B, L.ncol, L.CS);
+    PH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tsvd_idft_kernel, dim3((unsigned)((bb * V + 255) / 256)), dim3(256), 0, st, yre, yim, tk, aux, tnn, V, B);
+    PH_LAUNCH_CHECK();
+    return PH_OK;
+  }
   float* yre = ws;
   float* yim = ws + (size_t)(V / 2 + 1) * bb;
   float* tre = yim + (size_t)(V / 2 + 1) * bb;

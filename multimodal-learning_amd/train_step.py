@@ -1313,6 +1313,10 @@ class TeacherStage1Step:
                 raise ValueError(opt.tSVD_mode)
             self.mu = float(opt.mu)                                                              # :161 (never reset per epoch)
             gb = opt.batch_size * (sync.world_size if sync is not None else 1)
+            from .tsvd import TSVD_MAX_ROWS
+            if gb > TSVD_MAX_ROWS:
+                raise ValueError("tSVD_loss: global batch %d (batch_size %d x world size %d) exceeds TSVD_MAX_ROWS = %d of the "
+                                 "proximal update" % (gb, opt.batch_size, gb // opt.batch_size, TSVD_MAX_ROWS))
             z = lambda: [torch.zeros(gb, gb, device=self.device) for _ in range(opt.n_views)]
             self.adj_tensor1, self.aux_tensor1, self.adj_tensor2, self.aux_tensor2 = z(), z(), z(), z()   # :165-177
             self.path_TNN = self.omic_TNN = None
@@ -1632,8 +1636,9 @@ class TeacherStage1Step:
             self.adj_tensor2 = T.update_adj_tensor(self.adj_tensor2, feats2)
             if do_aux:
                 # `if opt.tSVD_mode == "path" or "pathomic":` (:378, :398) is always true: both tensors are updated.  The two
-                # proximal updates are independent and each is a launch of only n_views / 2 + 1 workgroups (one per Fourier
-                # slice, ~5 ms at B = 128): the second runs on a side stream beside the first.  The results land in the
+                # proximal updates are independent and each fills only part of the device (up to 128 rows n_views / 2 + 1
+                # workgroups, one per Fourier slice, ~5 ms at B = 128; above, (n_views / 2 + 1) x ~B / 32 workgroups per launch
+                # of the tiled Jacobi): the second runs on a side stream beside the first.  The results land in the
                 # PERSISTENT auxiliary tensors (captured graphs of other input sets / of the steps without an update read them)
                 main = torch.cuda.current_stream()
                 if getattr(self, "_tsvd_side", None) is None:

@@ -7,11 +7,14 @@ penalty (:418-431) and the mu schedule (:413).
 parity-unpinned: it implements the call contract with the standard tensor-nuclear-norm proximal operator (DFT along
 the view axis, singular-value soft-thresholding per frequency slice, inverse DFT; csrc/tsvd.hip) and is tested against
 oracle/variants.py:update_aux.  The reference returns the aux tensor through the host (`.float().cuda()`, :391); here
-everything stays on the device."""
+everything stays on the device.  Up to 128 rows a frequency slice is solved in the LDS of one workgroup; from 129 to
+TSVD_MAX_ROWS rows (the global batch of a data-parallel run) by a block Jacobi tiled over many workgroups."""
 import torch
 
 from . import ops
 from ._lib import lib, check, ptr, stream
+
+TSVD_MAX_ROWS = 512      # rows (global batch) ph_tsvd_update_aux admits (csrc/tsvd.hip: TT_MAXB)
 
 
 def update_adj_tensor(adj_tensor, feats):
@@ -35,10 +38,13 @@ def maxnorm_mix(a, b, wa, wb):
 def update_aux(adj, tau, print_bool=False):
     """adj: [B, B, n_views] detached adjacency stack, tau = Lambda_global / mu (a float, or a 1-element device tensor that a
     captured graph re-reads at every replay).  Returns (aux [B, B, n_views], TNN) like the call at train_test_tSVD.py:382;
-    TNN is a 0-d device tensor (no host sync)."""
+    TNN is a 0-d device tensor (no host sync).  B <= TSVD_MAX_ROWS (ValueError above); at every size the call is a fixed
+    sequence of launches without a host read, so it can be captured."""
     B, B2, V = adj.shape
     if B != B2:
         raise ValueError("adjacency stack must be [B, B, n_views]")
+    if B > TSVD_MAX_ROWS:
+        raise ValueError("adjacency stack of %d rows: update_aux admits at most TSVD_MAX_ROWS = %d" % (B, TSVD_MAX_ROWS))
     a = ops._f32(adj.detach()).permute(2, 0, 1).contiguous()          # view-major [V][B][B]
     aux = torch.empty_like(a)
     tnn = torch.empty(1, device=a.device, dtype=torch.float32)
