@@ -70,123 +70,131 @@ int ph_abi_version(void) { return 1; }
 size_t ph_conv2d_workspace_bytes(int B, int Cin, int IH, int IW, int Cout, int KS, int stride, int pad) {
   const int OH = (IH + 2 * pad - KS) / stride + 1, OW = (IW + 2 * pad - KS) / stride + 1;
   const size_t wbytes = up((size_t)PH_NPLANES * KS * KS * Cin * Cout * sizeof(bf16));
-  PhTapConv t{}; t.B = B; t.Cout = Cout; t.OHt = OH; t.OWt = OW;
-  // (the largest row count of any arithmetic: the split modes' small tiles, or two rows per persistent workgroup of conv_tap6.hip)
-  // (and perf mode's: conv_tap6b.hip's two rows per persistent workgroup at stride 2, the second-generation kernels' one per workgroup)
-  const int nparts = ph_tapconv_stat_parts(&t, stride, PH_PREC_BF16X6), nparts_hp = ph_tapconv_stat_parts(&t, stride, PH_PREC_FP16X3);
-  const int nparts_bf = std::max(ph_tapconv_stat_parts(&t, stride, PH_PREC_BF16), ph_num_cus());
-  const size_t parts = up((size_t)std::max(std::max(nparts, nparts_hp), nparts_bf) * 2 * Cout * sizeof(float));
+  // BatchNorm partial rows: the largest count of any arithmetic, at the convolution's stride or (the routes of ph_conv_fwd_route) 1;
+  // never fewer than one per CU (the size this call has always returned for small maps, kept for its callers)
+  int nparts = ph_num_cus();
+  for (int prec = PH_PREC_BF16; prec <= PH_PREC_FP16X3; ++prec)
+    for (int S = 1; S <= stride; ++S) nparts = std::max(nparts, ph_tapconv_stat_parts_bound(B, OH, OW, Cout, S, prec));
+  const size_t parts = up((size_t)nparts * 2 * Cout * sizeof(float));
   int tpc; const int nc = chunks_for(B, OH, OW, stride, Cout, Cin, &tpc);
   const size_t slab = up((size_t)nc * KS * KS * Cin * Cout * sizeof(float));
   return wbytes + (parts > slab ? parts : slab) + 256;
 }
 
+namespace {
+struct Conv { int B, Cin, IH, IW, Cout, KS, stride, pad; };
+
+// the forward launch of convolution v: geometry, route and weight layout of descriptor t (tensors are the caller's), *S = the stride
+// it is launched with.  PH_EINVAL before anything is written.
+int plan_fwd(const Conv& v, int prec, PhTapConv* t, int* S) {
+  // (PH_PREC_FP16X1 is a backward arithmetic)
+  if (!geometry_ok(v.B, v.Cin, v.IH, v.IW, v.Cout, v.KS, v.stride, v.pad) || prec < PH_PREC_BF16 || prec > PH_PREC_FP16X3) return PH_EINVAL;
+  t->B = v.B; t->wplane = (size_t)v.KS * v.KS * v.Cin * v.Cout;
+  ph_conv_fwd_geometry(t, v.Cin, v.IH, v.IW, v.Cout, v.KS, v.stride, v.pad);
+  *S = ph_conv_fwd_route(t, v.Cin, v.IH, v.IW, v.Cout, v.KS, v.stride, v.pad, prec, 0);
+  t->w_frag = ph_tapconv_hp_wfrag(t, *S, prec);
+  return ph_tapconv_select(t, *S, prec).kernel == PH_CK_REJECT ? PH_EINVAL : PH_OK;
+}
+
+// the dgrad launches of convolution v over descriptor t (tensors are the caller's): the stride-1 launch, or one launch per output
+// parity class of a stride-2 convolution (row-major weights).  Every class is planned, and the call checked, before anything is written.
+int plan_dgrad(const Conv& v, int prec, PhTapConv* t, PhTapConv cls[4], int* ncls, bool* tapless) {
+  if (!geometry_ok(v.B, v.Cin, v.IH, v.IW, v.Cout, v.KS, v.stride, v.pad) || prec < PH_PREC_BF16 || prec > PH_PREC_FP16X1) return PH_EINVAL;
+  t->B = v.B; t->wplane = (size_t)v.KS * v.KS * v.Cin * v.Cout;
+  *tapless = false;
+  if (v.stride == 1) {
+    ph_conv_dgrad_s1_geometry(t, v.Cin, v.IH, v.IW, v.Cout, v.KS, v.pad);
+    t->w_frag = ph_tapconv_hp_wfrag(t, 1, prec);
+    cls[0] = *t; *ncls = 1;
+  } else {
+    t->w_frag = PH_WFRAG_ROW;
+    const int rc = ph_conv_dgrad_s2_classes(t, v.Cin, v.IH, v.IW, v.Cout, v.KS, v.pad, cls, ncls, tapless);
+    if (rc) return rc;
+  }
+  for (int k = 0; k < *ncls; ++k)
+    if (ph_tapconv_select(&cls[k], 1, prec).kernel == PH_CK_REJECT) return PH_EINVAL;
+  return PH_OK;
+}
+
+// dgrad weights in layout w_frag, and the plane-1 fragment copy when launch t reads it
+int pack_dgrad(const float* w, bf16* hi, const PhTapConv* t, const Conv& v, int prec, hipStream_t st) {
+  const bool hp = prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1;
+  const int rc = hp ? ph_pack_w_hp_launch(w, hi, v.Cout, v.Cin, v.KS, 1, t->w_frag, st) : ph_pack_w_dgrad_launch(w, hi, v.Cout, v.Cin, v.KS, st);
+  if (rc || !ph_tapconv_needs_frag_copy(t, 1, prec)) return rc;
+  return ph_frag7_repack_launch(hi, v.Cin, v.Cout, 9, st);
+}
+}  // namespace
+
 int ph_conv2d_fwd(const void* x, const float* w, void* y, float* ch_sum, float* ch_sumsq, int B, int Cin, int IH,
                   int IW, int Cout, int KS, int stride, int pad, int prec, void* ws_, hipStream_t st) {
-  // (PH_PREC_FP16X1 is a backward arithmetic)
-  if (!geometry_ok(B, Cin, IH, IW, Cout, KS, stride, pad) || prec < PH_PREC_BF16 || prec > PH_PREC_FP16X3 || !x || !w || !y || !ws_)
-    return PH_EINVAL;
+  if (!x || !w || !y || !ws_) return PH_EINVAL;
   unsigned char* ws = reinterpret_cast<unsigned char*>(ws_);
-  const size_t plane = (size_t)KS * KS * Cin * Cout;
   bf16* hi = reinterpret_cast<bf16*>(ws);
-  const int OH = (IH + 2 * pad - KS) / stride + 1, OW = (IW + 2 * pad - KS) / stride + 1;
   PhTapConv t{};
-  t.in = x; t.w = hi; t.wplane = plane; t.out = y;
-  t.stats = reinterpret_cast<float*>(ws + up(PH_NPLANES * plane * sizeof(bf16)));
-  t.B = B; t.IH = IH; t.IW = IW; t.Cin = Cin; t.Cout = Cout; t.OHt = OH; t.OWt = OW; t.OH = OH; t.OW = OW;
-  t.os = 1; t.iy0 = -pad; t.ix0 = -pad; t.ntaps = KS * KS;
-  for (int k = 0; k < t.ntaps; ++k) { t.dy[k] = k / KS; t.dx[k] = k % KS; t.wtap[k] = k; }
-  // half-pair mode: the weight layout of the kernel this descriptor reaches
-  t.w_frag = ph_tapconv_hp_wfrag(&t, stride, prec);
-  int rc = prec == PH_PREC_FP16X3 ? ph_pack_w_hp_launch(w, hi, Cout, Cin, KS, 0, t.w_frag, st) : ph_pack_w_fwd_launch(w, hi, Cout, Cin, KS, st);
+  int S;
+  t.in = x; t.w = hi; t.out = y;
+  int rc = plan_fwd(Conv{B, Cin, IH, IW, Cout, KS, stride, pad}, prec, &t, &S);
   if (rc) return rc;
-  // perf mode, what conv_tap7.hip takes: the fragment-major copy in plane 1 (a split plane this mode does not read)
-  if (prec == PH_PREC_BF16 && KS == 3 && Cin == Cout && Cin >= 128 && (rc = ph_frag7_repack_launch(hi, Cout, Cin, 9, st))) return rc;
-  const bool tap6b = prec == PH_PREC_BF16 && KS == 3 && stride == 2 && pad == 1 && ph_tap6b_switch(-1) && ph_tapconv6b_eligible(&t);
-  if (tap6b && (rc = ph_frag7_repack_launch(hi, Cout, Cin, 9, st))) return rc;      // the fragment-major copy in plane 1
-  if (!tap6b && KS == 3 && stride == 2 && pad == 1 && ph_tapconv2_setup_s2_fwd(&t, Cin, Cout, IH, IW, prec)) stride = 1;
-  if (KS == 1 && stride == 2) {   // strided view (see resnet_plan.hip conv_fwd)
-    t.in_pix_stride = 2L * Cin; t.in_row_stride = 2L * IW * Cin; t.in_img_stride = (long)IH * IW * Cin;
-    t.IH = OH; t.IW = OW; stride = 1;
-  }
-  if ((rc = ph_tapconv_launch(&t, stride, prec, st))) return rc;
+  t.stats = reinterpret_cast<float*>(ws + up(PH_NPLANES * t.wplane * sizeof(bf16)));
+  rc = prec == PH_PREC_FP16X3 ? ph_pack_w_hp_launch(w, hi, Cout, Cin, KS, 0, t.w_frag, st) : ph_pack_w_fwd_launch(w, hi, Cout, Cin, KS, st);
+  if (rc) return rc;
+  // perf mode, conv_tap7.hip / conv_tap6b.hip: the fragment-major copy in plane 1 (a split plane this mode does not read)
+  if (ph_tapconv_needs_frag_copy(&t, S, prec) && (rc = ph_frag7_repack_launch(hi, Cout, Cin, 9, st))) return rc;
+  if ((rc = ph_tapconv_launch(&t, S, prec, st))) return rc;
   if (ch_sum || ch_sumsq) {
     hipLaunchKernelGGL(parts_sum_kernel, dim3(cdiv(Cout, 64)), dim3(64), 0, st, t.stats,
-                       ph_tapconv_stat_parts(&t, stride, prec), Cout, ch_sum, ch_sumsq);
+                       ph_tapconv_stat_parts(&t, S, prec), Cout, ch_sum, ch_sumsq);
     PH_LAUNCH_CHECK();
   }
   return PH_OK;
 }
 
 namespace {
-// the layout and the descriptor's weight fields of a dgrad over `t` (stride-1 geometry filled in; stride-2 launches: row-major)
-int pack_dgrad(const float* w, bf16* hi, PhTapConv* t, int Cin, int Cout, int KS, int stride, int prec, hipStream_t st) {
-  const bool hp = prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1;
-  t->w_frag = stride == 1 ? ph_tapconv_hp_wfrag(t, 1, prec) : PH_WFRAG_ROW;
-  int rc = hp ? ph_pack_w_hp_launch(w, hi, Cout, Cin, KS, 1, t->w_frag, st) : ph_pack_w_dgrad_launch(w, hi, Cout, Cin, KS, st);
-  if (rc) return rc;
-  if (prec == PH_PREC_BF16 && KS == 3 && Cin == Cout && Cin >= 128 && (rc = ph_frag7_repack_launch(hi, Cin, Cout, 9, st))) return rc;
-  return PH_OK;
-}
-
 // dgrad (+ residual) of a stride-1 or stride-2 convolution.  Stride 2: one launch per output parity class; a class no tap
 // reaches (1x1) receives res_g in place (res_g == dx, no res_a), zeros (no residual), or the call is PH_EINVAL
 int dgrad_common(const void* dy, const float* w, void* dx, const void* res_g, const void* res_a, int B, int Cin, int IH, int IW,
                  int Cout, int KS, int stride, int pad, int prec, void* ws_, hipStream_t st) {
-  if (!geometry_ok(B, Cin, IH, IW, Cout, KS, stride, pad) || prec < PH_PREC_BF16 || prec > PH_PREC_FP16X1 || !dy || !w || !dx || !ws_)
-    return PH_EINVAL;
-  const size_t plane = (size_t)KS * KS * Cin * Cout;
+  if (!dy || !w || !dx || !ws_) return PH_EINVAL;
+  const Conv v{B, Cin, IH, IW, Cout, KS, stride, pad};
   bf16* hi = reinterpret_cast<bf16*>(ws_);
-  const int OH = (IH + 2 * pad - KS) / stride + 1, OW = (IW + 2 * pad - KS) / stride + 1;
-  PhTapConv t{};
-  t.in = dy; t.w = hi; t.wplane = plane; t.out = dx; t.res_g = res_g; t.res_a = res_a;
-  t.B = B; t.IH = OH; t.IW = OW; t.Cin = Cout; t.Cout = Cin; t.OH = IH; t.OW = IW;
-  if (stride == 1) {
-    t.OHt = IH; t.OWt = IW; t.os = 1; t.iy0 = -(KS - 1 - pad); t.ix0 = t.iy0; t.ntaps = KS * KS;
-    for (int k = 0; k < t.ntaps; ++k) {
-      t.dy[k] = k / KS; t.dx[k] = k % KS; t.wtap[k] = (KS - 1 - k / KS) * KS + (KS - 1 - k % KS);
-    }
-    const int rc = pack_dgrad(w, hi, &t, Cin, Cout, KS, 1, prec, st);
-    return rc ? rc : ph_tapconv_launch(&t, 1, prec, st);
-  }
-  // stride 2, as resnet_plan.hip:conv_dgrad.  Every class is planned (and the call checked) before anything is written.
-  PhTapConv cls[4];
-  int ncls = 0;
-  bool tapless = false;
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      int nk = 0, khs[3], dhs[3], nw = 0, kws[3], dws[3];
-      for (int kh = 0; kh < KS; ++kh)
-        if (((a + pad - kh) & 1) == 0) { khs[nk] = kh; dhs[nk] = (a + pad - kh) / 2; ++nk; }
-      for (int kw = 0; kw < KS; ++kw)
-        if (((b + pad - kw) & 1) == 0) { kws[nw] = kw; dws[nw] = (b + pad - kw) / 2; ++nw; }
-      PhTapConv c = t;
-      c.OHt = (IH - a + 1) / 2; c.OWt = (IW - b + 1) / 2;
-      if (c.OHt <= 0 || c.OWt <= 0) continue;
-      c.os = 2; c.oa_h = a; c.oa_w = b; c.iy0 = 0; c.ix0 = 0; c.ntaps = nk * nw;
-      if (c.ntaps == 0) { tapless = true; continue; }
-      int q = 0;
-      for (int i = 0; i < nk; ++i)
-        for (int j = 0; j < nw; ++j) {
-          if (dhs[i] < 0 || dws[j] < 0 || dhs[i] > 2 || dws[j] > 2) return PH_EINVAL;
-          c.dy[q] = dhs[i]; c.dx[q] = dws[j]; c.wtap[q] = khs[i] * KS + kws[j]; ++q;
-        }
-      cls[ncls++] = c;
-    }
-  if (tapless && res_g && (res_g != dx || res_a)) return PH_EINVAL;
-  int rc = pack_dgrad(w, hi, &t, Cin, Cout, KS, 2, prec, st);
+  PhTapConv t{}, cls[4];
+  int ncls;
+  bool tapless;
+  t.in = dy; t.w = hi; t.out = dx; t.res_g = res_g; t.res_a = res_a;
+  int rc = plan_dgrad(v, prec, &t, cls, &ncls, &tapless);
   if (rc) return rc;
+  if (tapless && res_g && (res_g != dx || res_a)) return PH_EINVAL;
+  if ((rc = pack_dgrad(w, hi, &cls[0], v, prec, st))) return rc;
   if (tapless && !res_g) {
     const size_t es = prec == PH_PREC_BF16 ? 2 : 4;
     if (hipMemsetAsync(dx, 0, (size_t)B * IH * IW * Cin * es, st) != hipSuccess) return PH_ELAUNCH;
   }
-  for (int k = 0; k < ncls; ++k) {
-    cls[k].w_frag = t.w_frag;
+  for (int k = 0; k < ncls; ++k)
     if ((rc = ph_tapconv_launch(&cls[k], 1, prec, st))) return rc;
-  }
   return PH_OK;
 }
 }  // namespace
+
+// host-only test access to the selection (not part of the public C-ABI): the OR of the family bits (1u << PH_CK_*) the launches of
+// ph_conv2d_fwd (op 0) / ph_conv2d_dgrad (op 1) would reach, or PH_EINVAL; *stat_parts / *w_frag (optional) of the first launch.
+// Builds the descriptors as those entry points do and makes no HIP call.
+extern "C" int ph_debug_conv2d_select(int op, int B, int Cin, int IH, int IW, int Cout, int KS, int stride, int pad, int prec,
+                                      int* stat_parts, int* w_frag) {
+  const Conv v{B, Cin, IH, IW, Cout, KS, stride, pad};
+  PhTapConv cls[4] = {}, t{};
+  int ncls = 1, S = 1;
+  bool tapless;
+  const int rc = op == 0 ? plan_fwd(v, prec, &cls[0], &S) : (op == 1 ? plan_dgrad(v, prec, &t, cls, &ncls, &tapless) : PH_EINVAL);
+  if (rc) return rc;
+  int mask = 0;
+  for (int k = ncls - 1; k >= 0; --k) {
+    const PhConvChoice c = ph_tapconv_select(&cls[k], S, prec);
+    mask |= 1 << c.kernel;
+    if (stat_parts) *stat_parts = c.stat_parts;
+    if (w_frag) *w_frag = c.w_frag;
+  }
+  return mask;
+}
 
 int ph_conv2d_dgrad_res(const void* dy, const float* w, void* dx, const void* res_g, const void* res_a, int B, int Cin,
                         int IH, int IW, int Cout, int KS, int stride, int pad, int prec, void* ws_, hipStream_t st) {
@@ -206,9 +214,8 @@ int ph_conv2d_fwd_fused_in(const void* x, const float* in_scale, const float* in
   PhTapConv t{};
   t.in = x; t.w = hi; t.wplane = plane; t.out = y; t.in_scale = in_scale; t.in_shift = in_shift;
   t.stats = reinterpret_cast<float*>(ws + up(PH_NPLANES * plane * sizeof(bf16)));
-  t.B = B; t.IH = IH; t.IW = IW; t.Cin = Cin; t.Cout = Cout; t.OHt = IH; t.OWt = IW; t.OH = IH; t.OW = IW;
-  t.os = 1; t.iy0 = -1; t.ix0 = -1; t.ntaps = 9;
-  for (int k = 0; k < 9; ++k) { t.dy[k] = k / 3; t.dx[k] = k % 3; t.wtap[k] = k; }
+  t.B = B;
+  ph_conv_fwd_geometry(&t, Cin, IH, IW, Cout, 3, 1, 1);
   if ((rc = ph_tapconv_launch(&t, 1, PH_PREC_BF16, st))) return rc;
   if (ch_sum || ch_sumsq) {
     hipLaunchKernelGGL(parts_sum_kernel, dim3(cdiv(Cout, 64)), dim3(64), 0, st, t.stats, ph_tapconv_stat_parts(&t, 1, PH_PREC_BF16), Cout,
@@ -229,19 +236,17 @@ int ph_conv2d_dgrad_bnstat(const void* dy, const float* w, void* dx, const void*
   unsigned char* ws = reinterpret_cast<unsigned char*>(ws_);
   const size_t plane = (size_t)9 * Cin * Cout;
   bf16* hi = reinterpret_cast<bf16*>(ws);
-  int rc = ph_pack_w_dgrad_launch(w, hi, Cout, Cin, 3, st);
-  if (rc) return rc;
-  if (Cin == Cout && Cin >= 128 && (rc = ph_frag7_repack_launch(hi, Cin, Cout, 9, st))) return rc;
   PhTapConv t{};
   t.in = dy; t.w = hi; t.wplane = plane; t.out = dx; t.res_g = res_g; t.res_a = res_a;
-  t.B = B; t.IH = IH; t.IW = IW; t.Cin = Cout; t.Cout = Cin; t.OH = IH; t.OW = IW;
-  t.OHt = IH; t.OWt = IW; t.os = 1; t.iy0 = -1; t.ix0 = -1; t.ntaps = 9;
-  for (int k = 0; k < 9; ++k) { t.dy[k] = k / 3; t.dx[k] = k % 3; t.wtap[k] = 8 - k; }
+  t.B = B;
+  ph_conv_dgrad_s1_geometry(&t, Cin, IH, IW, Cout, 3, 1);
   t.bst_y = bst_y; t.bst_a = bst_a; t.bst_y2 = bst_y2; t.bst_scale = bst_scale; t.bst_shift = bst_shift;
   t.bst_mean = bst_mean; t.bst_mean2 = bst_mean2;
   t.stats = reinterpret_cast<float*>(ws + up(PH_NPLANES * plane * sizeof(bf16)));
+  int rc = pack_dgrad(w, hi, &t, Conv{B, Cin, IH, IW, Cout, 3, 1, 1}, PH_PREC_BF16, st);
+  if (rc) return rc;
   if ((rc = ph_tapconv_launch(&t, 1, PH_PREC_BF16, st))) return rc;
-  const int nparts = ph_tapconv2_stat_parts(&t);
+  const int nparts = ph_tapconv_stat_parts(&t, 1, PH_PREC_BF16);
   hipLaunchKernelGGL(parts3_sum_kernel, dim3(cdiv(Cin, 64)), dim3(64), 0, st, t.stats, nparts, Cin, sums);
   PH_LAUNCH_CHECK();
   return PH_OK;

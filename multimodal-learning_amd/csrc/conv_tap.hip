@@ -505,7 +505,6 @@ int launch_cfg(const PhTapConv& p, hipStream_t st) {
       return PH_ELAUNCH;
     attr_done = true;
   }
-  if (p.ncls && (S != 1 || p.ncls < 2 || p.ncls > 4 || p.stats)) return PH_EINVAL;
   dim3 grid(cdiv(p.OHt, TH) * cdiv(p.OWt, 16), p.Cout / BNT, p.B * (p.ncls ? p.ncls : 1));
   void* tok = nullptr;
   if (ph_prof_on()) {   // algorithmic FLOPs: 2 * positions * Cout * ntaps * Cin (merged classes: summed)
@@ -554,7 +553,7 @@ int launch_T(const PhTapConv& p, int S, hipStream_t st) {
     }
     return launch_cfg<T, 1, 16, 64, 4, 1, 2, 2, TG>(p, st);
   } else {
-    if (p.Cout % 128) return PH_EINVAL;   // stride-2 forward convs of ResNet-18 all have Cout >= 128
+    // (Cout % 128 == 0: ph_tapconv_select; the stride-2 forward convs of ResNet-18 all have Cout >= 128)
     if constexpr (SPLIT) return launch_cfg<T, 2, 2, 128, 1, 4, 1, 1, 1>(p, st);
     else return launch_cfg<T, 2, 8, 128, 2, 4, 2, 1, 3>(p, st);   // 128 x 128 tile, 8 waves, 121 KB LDS
   }
@@ -562,77 +561,28 @@ int launch_T(const PhTapConv& p, int S, hipStream_t st) {
 
 }  // namespace
 
-// number of statistic partial rows a launch writes: B * tiles
-int ph_tapconv_stat_parts(const PhTapConv* p, int S, int prec) {
-  if (prec == PH_PREC_BF16 && S == 2 && ph_tap6b_switch(-1)) {
-    // (ntaps == 0: a sizing query with B / OHt / OWt / Cout only - the larger of the candidates' counts)
-    if (p->ntaps == 0 && p->Cout % 128 == 0) return std::max(p->B * cdiv(p->OHt, 8) * cdiv(p->OWt, 16), ph_tapconv6b_stat_parts(p));
-    if (p->ntaps != 0 && !p->no_tap6b && ph_tapconv6b_eligible(p)) return ph_tapconv6b_stat_parts(p);
-  }
-  if (ph_tapconv2_tile_h(p, S, prec)) return ph_tapconv2_stat_parts(p);
-  // (half-pair mode on the third-generation kernel: one partial row per persistent workgroup, like the second generation)
-  if (prec == PH_PREC_FP16X3 && S == 1 && ph_tap3_switch(-1) && ph_tapconv3_eligible(p)) return ph_tapconv2_stat_parts(p);
-  if ((prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1) && S == 1 && p->w_frag == PH_WFRAG_TAP5 && ph_tapconv5_eligible(p)) return ph_tapconv5_stat_parts(p);
-  if (prec == PH_PREC_FP16X3 && S == 2) {
-    // (ntaps == 0: a sizing query with B / OHt / OWt / Cout only - resnet_plan.hip - take the larger of the two kernels' counts)
-    const int first_gen = p->B * cdiv(p->OHt, 8) * cdiv(p->OWt, 16);
-    if (p->ntaps == 0 && ph_tap6_switch(-1)) return std::max(first_gen, p->Cout % 128 == 0 ? ph_tapconv6_stat_parts(p) : 0);
-    if (p->ntaps != 0 && p->w_frag == PH_WFRAG_TAP6 && ph_tapconv6_eligible(p)) return ph_tapconv6_stat_parts(p);
-  }
-  const bool perf_cfg = prec == PH_PREC_BF16 || prec == PH_PREC_FP16X3;
-  const int TH = (S == 1) ? ((p->Cout % 128 == 0 && !perf_cfg) ? 8 : 16) : (perf_cfg ? 8 : 2);
-  return p->B * cdiv(p->OHt, TH) * cdiv(p->OWt, 16);
-}
-
+// ph_tapconv_select (conv_select.hip) has judged the descriptor and named the kernel; this only calls its launcher
 int ph_tapconv_launch(const PhTapConv* p, int S, int prec, hipStream_t st) {
-  if (p->Cin % 64 || p->Cout % 64 || p->ntaps < 1 || p->ntaps > 9 || (S != 1 && S != 2)) return PH_EINVAL;
-  // perf mode, 3x3 / stride 2 forward over the un-masked descriptor (the callers skip ph_tapconv2_setup_s2_fwd for it): conv_tap6b.hip
-  if (S == 2 && prec == PH_PREC_BF16 && !p->no_tap6b && ph_tap6b_switch(-1) && ph_tapconv6b_eligible(p)) {
-    ph_dispatch_note(PH_DK_TAP6B);
-    return ph_tapconv6b_launch(p, st);
-  }
-  if (ph_tapconv2_tile_h(p, S, prec)) return ph_tapconv2_launch(p, st);
-  if (p->in_scale || p->m_groups) return PH_EINVAL;   // in-LDS BatchNorm + ReLU / masked tap grids: second-generation kernels only
-  if (prec == PH_PREC_BF16) { ph_dispatch_note(PH_DK_GEN1_BF16); return launch_T<bf16>(*p, S, st); }
-  if (prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1) {
-    PhTapConv q = *p;
-    q.hp_hi_only = prec == PH_PREC_FP16X1;
-    // the fragment-major layouts: their kernels alone read them (the packer chose them with ph_tapconv_hp_wfrag)
-    // dense 3x3 stride-1, Cin = Cout = 64 (layer 1): conv_tap5.hip
-    if (q.w_frag == PH_WFRAG_TAP5) {
-      if (S != 1 || !ph_tapconv5_eligible(&q)) return PH_EINVAL;
-      ph_dispatch_note(PH_DK_TAP5);
-      return ph_tapconv5_launch(&q, st);
-    }
-    // 3x3 / stride 2 forward (layers 2-4 conv1): conv_tap6.hip
-    if (q.w_frag == PH_WFRAG_TAP6) {
-      if (S != 2 || prec != PH_PREC_FP16X3 || !ph_tapconv6_eligible(&q)) return PH_EINVAL;
-      ph_dispatch_note(PH_DK_TAP6);
-      return ph_tapconv6_launch(&q, st);
-    }
-    if (q.w_frag != PH_WFRAG_ROW) return PH_EINVAL;
-    // dense 3x3 stride-1, Cout % 128 == 0: the third-generation kernel's half-pair form (conv_tap3.hip)
-    if (S == 1 && ph_tap3_switch(-1) && ph_tapconv3_eligible(&q)) {
-      ph_dispatch_note(PH_DK_TAP3_HP);
-      return ph_tapconv3_launch_hp(&q, st);
-    }
-    ph_dispatch_note(PH_DK_GEN1_HP16);
-    return launch_T<hp16>(q, S, st);
-  }
-  if (PH_IS_SPLIT_PREC(prec)) {
-    PhTapConv q = *p;
-    q.prod6 = prec == PH_PREC_BF16X6;
-    ph_dispatch_note(PH_DK_GEN1_F32);
-    return launch_T<float>(q, S, st);
+  const PhConvChoice c = ph_tapconv_select(p, S, prec);
+  if (c.kernel == PH_CK_REJECT) return PH_EINVAL;
+  ph_dispatch_note(1u << c.kernel);
+  PhTapConv q = *p;      // what the half-pair / split-plane kernels read of the arithmetic
+  q.hp_hi_only = prec == PH_PREC_FP16X1;
+  q.prod6 = prec == PH_PREC_BF16X6;
+  switch (c.kernel) {
+    case PH_CK_GEN1_BF16: return launch_T<bf16>(*p, S, st);
+    case PH_CK_GEN1_HP16: return launch_T<hp16>(q, S, st);
+    case PH_CK_GEN1_F32: return launch_T<float>(q, S, st);
+    case PH_CK_TAP2: case PH_CK_TAP2_MASKED: case PH_CK_TAP2_L1: return ph_tapconv2_launch(p, c.kernel, st);
+    case PH_CK_TAP3: return ph_tapconv3_launch(p, st);
+    case PH_CK_TAP3_HP: return ph_tapconv3_launch_hp(&q, st);
+    case PH_CK_TAP4: return ph_tapconv4_launch(p, st);
+    case PH_CK_TAP5: return ph_tapconv5_launch(&q, st);
+    case PH_CK_TAP6: return ph_tapconv6_launch(&q, st);
+    case PH_CK_TAP6B: return ph_tapconv6b_launch(p, st);
+    case PH_CK_TAP7: return ph_tapconv7_launch(p, st);
   }
   return PH_EINVAL;
-}
-
-int ph_tapconv_hp_wfrag(const PhTapConv* p, int S, int prec) {
-  if (prec != PH_PREC_FP16X3 && prec != PH_PREC_FP16X1) return PH_WFRAG_ROW;
-  if (S == 1 && ph_tap5_switch(-1) && ph_tapconv5_eligible(p)) return PH_WFRAG_TAP5;
-  if (S == 2 && prec == PH_PREC_FP16X3 && ph_tap6_switch(-1) && ph_tapconv6_eligible(p)) return PH_WFRAG_TAP6;
-  return PH_WFRAG_ROW;
 }
 
 namespace {

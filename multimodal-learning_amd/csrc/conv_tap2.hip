@@ -1219,22 +1219,6 @@ int launch2(const PhTapConv& p, hipStream_t st) {
 
 }  // namespace
 
-// A/B and test switch between the second- and third-generation dense kernels: PH_TAP3=0 in the environment, or
-// ph_debug_set_tap3() at run time (not part of the public C-ABI).  set < 0: query.
-int ph_tap3_switch(int set) {
-  static int on = [] { const char* e = getenv("PH_TAP3"); return (e && e[0] == '0') ? 0 : 1; }();
-  if (set >= 0) on = set ? 1 : 0;
-  return on;
-}
-extern "C" int ph_debug_set_tap3(int on) { return ph_tap3_switch(on ? 1 : 0); }
-// ... and between tapconv2_l1_kernel and the fourth-generation layer-1 kernel (conv_tap4.hip): PH_TAP4=0 / ph_debug_set_tap4()
-int ph_tap4_switch(int set) {
-  static int on = [] { const char* e = getenv("PH_TAP4"); return (e && e[0] == '0') ? 0 : 1; }();
-  if (set >= 0) on = set ? 1 : 0;
-  return on;
-}
-extern "C" int ph_debug_set_tap4(int on) { return ph_tap4_switch(on ? 1 : 0); }
-
 // ---- stride-2 3x3 convolutions as MASKED stride-1 tap grids (PhTapConv::m_*).  Both fill the tap-grid part of a
 // descriptor whose tensors / batch / channel fields the caller has set (forward: in = x [B][IH][IW][Cin], Cin / Cout of
 // the convolution; dgrad: in = dy [B][OH][OW][Cout_fwd], t->Cin = Cout_fwd, t->Cout = Cin_fwd, OH / OW of dx) and
@@ -1291,27 +1275,11 @@ int ph_tapconv2_stat_parts(const PhTapConv* p) {
   return total < resident ? total : resident;
 }
 
-int ph_tapconv2_launch(const PhTapConv* p, hipStream_t st) {
-  if (p->in_scale && (!p->in_shift || p->Cin > 512)) return PH_EINVAL;
-  if (p->m_groups) {
-    if (p->Cout % 128 || p->in_scale) return PH_EINVAL;
-    ph_dispatch_note(PH_DK_TAP2_MASKED);
-    return launch2<2, 2, 4, false, true>(*p, st);
-  }
-  if (p->Cout % 128 == 0) {
-    if (ph_tap3_switch(-1) && ph_tapconv3_eligible(p)) {
-      // every form but the in-LDS input BatchNorm, Cin = Cout: conv_tap7.hip, same outputs
-      if (ph_tap7_switch(-1) && ph_tapconv7_eligible(p)) { ph_dispatch_note(PH_DK_TAP7); return ph_tapconv7_launch(p, st); }
-      ph_dispatch_note(PH_DK_TAP3);
-      return ph_tapconv3_launch(p, st);
-    }
-    if (p->bst_y) return PH_EINVAL;      // (the fused BatchNorm-backward sums exist in conv_tap3.hip / conv_tap4.hip only)
-    ph_dispatch_note(PH_DK_TAP2);
-    return launch2<2, 2, 4, false>(*p, st);
-  }
-  if (ph_tap4_switch(-1) && ph_tapconv4_eligible(p)) { ph_dispatch_note(PH_DK_TAP4); return ph_tapconv4_launch(p, st); }
-  if (p->bst_y) return PH_EINVAL;      // (the fused BatchNorm-backward sums exist in conv_tap4.hip only)
-  ph_dispatch_note(PH_DK_TAP2_L1);
+// the three forms of this file; which one a descriptor takes is ph_tapconv_select's answer (conv_select.hip)
+int ph_tapconv2_launch(const PhTapConv* p, int kernel, hipStream_t st) {
+  if (kernel == PH_CK_TAP2_MASKED) return launch2<2, 2, 4, false, true>(*p, st);
+  if (kernel == PH_CK_TAP2) return launch2<2, 2, 4, false>(*p, st);
+  if (kernel != PH_CK_TAP2_L1) return PH_EINVAL;
 #ifdef PH_L1_ONE_GROUP   // A/B build: the one-wave-per-SIMD resident-weights configuration
   return launch2<4, 1, 2, true>(*p, st);
 #else

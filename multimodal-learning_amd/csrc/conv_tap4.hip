@@ -697,12 +697,7 @@ int launch4(const PhTapConv& p, hipStream_t st) {
 }  // namespace
 
 // A/B and test switch: PH_TAP4_OVL=0 / ph_debug_set_tap4_ovl(0) = every launch with the epilogue after the tile
-static int ph_tap4_ovl_switch(int set) {
-  static int on = [] { const char* e = getenv("PH_TAP4_OVL"); return (e && e[0] == '0') ? 0 : 1; }();
-  if (set >= 0) on = set ? 1 : 0;
-  return on;
-}
-extern "C" int ph_debug_set_tap4_ovl(int on) { return ph_tap4_ovl_switch(on ? 1 : 0); }
+PH_SWITCH(tap4_ovl, "PH_TAP4_OVL")
 // A/B switch: PH_TAP4_OVL_OPS=0 = launches whose epilogue reads operands keep it after the tile (the round-5 first form)
 static bool ph_tap4_ovl_ops() {
   static const bool on = [] { const char* e = getenv("PH_TAP4_OVL_OPS"); return !(e && e[0] == '0'); }();

@@ -548,13 +548,6 @@ int launch5(const PhTapConv& p, hipStream_t st) {
 
 }  // namespace
 
-// PH_TAP5=0 in the environment / ph_debug_set_tap5(0) keeps the first-generation kernel (same-box A/B)
-int ph_tap5_switch(int set) {
-  static int on = [] { const char* e = getenv("PH_TAP5"); return (e && e[0] == '0') ? 0 : 1; }();
-  if (set >= 0) on = set ? 1 : 0;
-  return on;
-}
-extern "C" int ph_debug_set_tap5(int on) { return ph_tap5_switch(on ? 1 : 0); }
 #ifdef PH_TAP_TRACE
 extern "C" int ph_debug_tap5_trace(unsigned long long* host_out, int nwg) {
   if (nwg > PH_TRACE_WGS) nwg = PH_TRACE_WGS;

@@ -519,14 +519,6 @@ __global__ void frag7_repack_kernel(const bf16* __restrict__ src, bf16* __restri
 
 }  // namespace
 
-// PH_TAP7=0 in the environment / ph_debug_set_tap7(0) keeps conv_tap3.hip's plain form (same-box A/B; the fragment-major copy of the
-// weights is written either way)
-int ph_tap7_switch(int set) {
-  static int on = [] { const char* e = getenv("PH_TAP7"); return (e && e[0] == '0') ? 0 : 1; }();
-  if (set >= 0) on = set ? 1 : 0;
-  return on;
-}
-extern "C" int ph_debug_set_tap7(int on) { return ph_tap7_switch(on ? 1 : 0); }
 
 // eligible: conv_tap3.hip's perf-mode configuration without the in-LDS input BatchNorm (dense 3x3 stride-1 over the whole map,
 // Cin = Cout in 128 .. 512) on a dense NHWC tensor

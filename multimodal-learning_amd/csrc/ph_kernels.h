@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 // in-library kernel timer (prof.hip); classes are indices of ph_prof_summary()
 #define PH_CLS_TAPCONV_N64 0    // tapconv_kernel<.., S=1, BNT=64 ..>   (first generation: Cout = 64 dgrad parity classes)
@@ -87,83 +88,114 @@ struct PhTapConv {
   int ncls;
   int c_ntaps[4], c_oa_h[4], c_oa_w[4], c_OHt[4], c_OWt[4];
   int c_dy[4][4], c_dx[4][4], c_wtap[4][4];
-  // half-pair modes: the layout the weights were packed in (PH_WFRAG_*, chosen by whoever packed them from the same eligibility
-  // and switch state that picks the kernel).  conv_tap5.hip / conv_tap6.hip run only on their fragment-major layout, every other
-  // kernel only on the row-major one: a mismatch is PH_EINVAL, never a read of a layout the kernel does not understand
+  // half-pair modes: the layout the weights were packed in (PH_WFRAG_*, ph_tapconv_hp_wfrag).  ph_tapconv_select rejects a layout
+  // its kernel cannot take: PH_EINVAL, never a read of a layout the kernel does not understand
   int w_frag;
   int no_tap6b;          // perf mode: keep a stride-2 forward off conv_tap6b.hip (the plan's no_masked A/B and test switch)
 };
 #define PH_WFRAG_ROW 0       // [tap][O][3 I] (forward) / [tap][I][3 O] (dgrad)
 #define PH_WFRAG_TAP5 1      // conv_tap5.hip's 64 x 64 x 9 fragment-major slabs (3x3 stride-1, Cin = Cout = 64)
 #define PH_WFRAG_TAP6 2      // conv_tap6.hip's [tap][O / 64][I / 64][block 3] slabs (3x3 / stride 2 forward, Cout = 2 Cin)
-// the layout a half-pair convolution over descriptor p (S, prec as for ph_tapconv_launch) needs under the current switches
+
+// ---- kernel selection (conv_select.hip): the ONE place that combines the kernels' own predicates (ph_tapconvN_eligible,
+// ph_tapconv2_tile_h) with the A/B switches (PH_TAP3 .. PH_TAP7) and judges a descriptor.  The launcher, the BatchNorm row count,
+// the weight layout and the plan's fused-sums decision all read this answer.
+enum {
+  PH_CK_REJECT = -1,     // the descriptor is PH_EINVAL
+  PH_CK_GEN1_BF16 = 0,   // first-generation tapconv_kernel, T = bf16 (conv_tap.hip)
+  PH_CK_GEN1_HP16,       // ... T = hp16 (half-pair modes)
+  PH_CK_GEN1_F32,        // ... T = float (split-plane modes)
+  PH_CK_TAP2,            // conv_tap2.hip <2,2,4> dense stride-1
+  PH_CK_TAP2_MASKED,     // conv_tap2.hip <2,2,4> masked stride-2 grid
+  PH_CK_TAP2_L1,         // conv_tap2.hip two-group layer-1 kernel (Cin = Cout = 64)
+  PH_CK_TAP3,            // conv_tap3.hip perf form
+  PH_CK_TAP3_HP,         // conv_tap3.hip half-pair form
+  PH_CK_TAP4, PH_CK_TAP5, PH_CK_TAP6, PH_CK_TAP6B, PH_CK_TAP7,
+  PH_CK_COUNT
+};
+struct PhConvChoice {
+  int kernel;            // PH_CK_*
+  int stat_parts;        // BatchNorm partial rows (or fused-sums rows) the launch writes
+  int w_frag;            // PH_WFRAG_* the kernel reads
+};
+PhConvChoice ph_tapconv_select(const PhTapConv* p, int S, int prec);
+inline int ph_tapconv_stat_parts(const PhTapConv* p, int S, int prec) { return ph_tapconv_select(p, S, prec).stat_parts; }
+// the largest row count of any kernel a [B][OH][OW][Cout] output can reach at stride S in arithmetic prec under the current switches
+extern "C" int ph_tapconv_stat_parts_bound(int B, int OH, int OW, int Cout, int S, int prec);   // (C name: the host-only tests call it)
+// the layout to PACK for a half-pair convolution over descriptor p (the only reader of PH_TAP5 / PH_TAP6: after the pack the
+// descriptor's w_frag decides)
 int ph_tapconv_hp_wfrag(const PhTapConv* p, int S, int prec);
+// the launch reads the fragment-major copy of its perf-mode weights in plane 1 (conv_tap7.hip, conv_tap6b.hip: ph_frag7_repack_launch)
+bool ph_tapconv_needs_frag_copy(const PhTapConv* p, int S, int prec);
+
+// ---- descriptor builders of the convolution entry points and the ResNet plan (conv_select.hip).  A convolution is given by plain
+// ints (Cin, IH, IW -> Cout, KS, stride, pad); tensors, batch, statistics and fused fields of the descriptor are the caller's.
+void ph_conv_fwd_geometry(PhTapConv* t, int Cin, int IH, int IW, int Cout, int KS, int stride, int pad);
+// ... then the route of a stride-2 forward: 1x1 as a stride-1 launch over the even-pixel view; 3x3 on conv_tap6b.hip, else
+// (unless no_masked) conv_tap2.hip's masked grid, else the first generation.  Returns the stride to launch with.
+int ph_conv_fwd_route(PhTapConv* t, int Cin, int IH, int IW, int Cout, int KS, int stride, int pad, int prec, int no_masked);
+void ph_conv_dgrad_s1_geometry(PhTapConv* t, int Cin, int IH, int IW, int Cout, int KS, int pad);
+// the output-parity classes of a stride-2 dgrad (x row 2i + a receives kh with a + pad - kh even): cls[0 .. *ncls) are copies of
+// *t with one class's geometry each, *tapless = some class is reached by no tap.  PH_EINVAL: a tap offset outside 0..2.
+int ph_conv_dgrad_s2_classes(const PhTapConv* t, int Cin, int IH, int IW, int Cout, int KS, int pad, PhTapConv cls[4], int* ncls,
+                             bool* tapless);
+
+// A/B and test switch `ph_<name>_switch(set)`: on unless ENV=0 in the environment (read once); set >= 0 sets it at run time, set < 0
+// queries.  ph_debug_set_<name>() is the run-time setter the tests use (not part of the public C-ABI).
+#define PH_SWITCH(name, ENV)                                                                              \
+  int ph_##name##_switch(int set) {                                                                       \
+    static int on = [] { const char* e = getenv(ENV); return (e && e[0] == '0') ? 0 : 1; }();             \
+    if (set >= 0) on = set ? 1 : 0;                                                                       \
+    return on;                                                                                            \
+  }                                                                                                       \
+  extern "C" int ph_debug_set_##name(int on) { return ph_##name##_switch(on ? 1 : 0); }
+
 // kernel-family dispatch record for the tests (host side, not part of the public C-ABI): every launcher ORs the bit of the
-// family it runs; ph_debug_dispatch_mask() reads and ph_debug_dispatch_reset() clears it (conv_tap.hip)
-#define PH_DK_GEN1_BF16 (1u << 0)     // first-generation tapconv_kernel, T = bf16 (launch_T)
-#define PH_DK_GEN1_HP16 (1u << 1)     // ... T = hp16 (half-pair modes)
-#define PH_DK_GEN1_F32 (1u << 2)      // ... T = float (split-plane modes)
-#define PH_DK_TAP2 (1u << 3)          // conv_tap2.hip <2,2,4> dense stride-1
-#define PH_DK_TAP2_MASKED (1u << 4)   // conv_tap2.hip <2,2,4> masked stride-2 grid
-#define PH_DK_TAP2_L1 (1u << 5)       // conv_tap2.hip two-group layer-1 kernel (Cin = Cout = 64)
-#define PH_DK_TAP3 (1u << 6)          // conv_tap3.hip perf form
-#define PH_DK_TAP3_HP (1u << 7)       // conv_tap3.hip half-pair form
-#define PH_DK_TAP4 (1u << 8)
-#define PH_DK_TAP5 (1u << 9)
-#define PH_DK_TAP6 (1u << 10)
-#define PH_DK_TAP6B (1u << 11)
-#define PH_DK_TAP7 (1u << 12)
+// family it runs; ph_debug_dispatch_mask() reads and ph_debug_dispatch_reset() clears it (conv_tap.hip).  Bits 0 .. 12: 1u << PH_CK_*
 #define PH_DK_WGRAD_BF16 (1u << 13)   // conv_wgrad.hip, per activation type
 #define PH_DK_WGRAD_HP16 (1u << 14)
 #define PH_DK_WGRAD_F32 (1u << 15)
 #define PH_DK_SGEMM16 (1u << 16)      // dense.hip sgemm_small_kernel (16 x 16 tiles, M * N <= 128 * 128)
 #define PH_DK_SGEMM64 (1u << 17)      // dense.hip sgemm_kernel (64 x 64 tiles)
 #define PH_DK_SGEMM_SPLITK (1u << 18) // dense.hip sgemm_splitk_kernel + splitk_finish_kernel
+static_assert(PH_CK_COUNT == 13, "the weight-gradient bits follow the convolution families");
 void ph_dispatch_note(unsigned bits);
 int ph_tapconv_launch(const PhTapConv* p, int S, int prec, hipStream_t st);
 double ph_tapconv_bytes(const PhTapConv& p, int S, int es);
-int ph_tapconv_stat_parts(const PhTapConv* p, int S, int prec);
-// second-generation stride-1 perf-mode kernel (conv_tap2.hip): tile height of the configuration it would run, 0 = not eligible
+// The kernels below say what they can run (ph_tapconvN_eligible, ph_tapconv2_tile_h) and how many rows they write; only
+// ph_tapconv_select combines that with the switches.
+// second-generation stride-1 perf-mode kernels (conv_tap2.hip): tile height of the configuration, 0 = not eligible
 int ph_tapconv2_tile_h(const PhTapConv* p, int S, int prec);
-int ph_tapconv2_launch(const PhTapConv* p, hipStream_t st);
-int ph_tapconv2_stat_parts(const PhTapConv* p);   // one BatchNorm partial row per persistent workgroup
-// third-generation dense 3x3 stride-1 kernel (conv_tap3.hip: 16x16x32 fragments, 8-byte stores); PH_TAP3=0 in the environment
-// keeps the second-generation kernel (same-box A/B)
-int ph_tap3_switch(int set);
+int ph_tapconv2_launch(const PhTapConv* p, int kernel, hipStream_t st);   // kernel: PH_CK_TAP2 / _TAP2_MASKED / _TAP2_L1
+int ph_tapconv2_stat_parts(const PhTapConv* p);   // one row per persistent workgroup (conv_tap3 / 4 / 7 write the same count)
+// third-generation dense 3x3 stride-1 kernel (conv_tap3.hip: 16x16x32 fragments, 8-byte stores); PH_TAP3=0 keeps the second generation
 bool ph_tapconv3_eligible(const PhTapConv* p);
 int ph_tapconv3_launch(const PhTapConv* p, hipStream_t st);
 int ph_tapconv3_launch_hp(const PhTapConv* p, hipStream_t st);      // PH_PREC_FP16X3 form of the same kernel
 // fourth-generation kernel for Cin = Cout = 64 (conv_tap4.hip: ResNet layer 1; one wave per SIMD, 16x16x32 fragments, resident
-// weights, one barrier per tile, optional fused BatchNorm-backward sums); PH_TAP4=0 keeps tapconv2_l1_kernel (same-box A/B)
-int ph_tap4_switch(int set);
+// weights, one barrier per tile, optional fused BatchNorm-backward sums); PH_TAP4=0 keeps tapconv2_l1_kernel
 bool ph_tapconv4_eligible(const PhTapConv* p);
 int ph_tapconv4_launch(const PhTapConv* p, hipStream_t st);
 // half-pair kernel for Cin = Cout = 64 (conv_tap5.hip: both halo planes of a 32 x 16 tile resident in LDS, weight fragments from
-// global memory into a rotating register window, two barriers per tile); p->hp_hi_only selects the hi-only form; PH_TAP5=0 keeps
-// the first-generation kernel (same-box A/B)
-int ph_tap5_switch(int set);
+// global memory into a rotating register window, two barriers per tile; reads PH_WFRAG_TAP5 weights); p->hp_hi_only selects the
+// hi-only form; PH_TAP5=0 at pack time keeps the first-generation kernel
 bool ph_tapconv5_eligible(const PhTapConv* p);
 int ph_tapconv5_launch(const PhTapConv* p, hipStream_t st);
 int ph_tapconv5_stat_parts(const PhTapConv* p);
-// (its 64 x 64 x 9 weight slabs are packed fragment-major while the switch is on: pack_all_tiled_hp_kernel, conv_wgrad.hip - do not
-// change the switch between a pack and the launches that read it)
 // perf-mode kernel of the dense 3x3 stride-1 convolutions with Cin = Cout >= 128 (conv_tap7.hip: conv_tap3.hip's plain form on the
 // register-window machinery, bitwise the same outputs); reads the fragment-major copy of the weights in plane 1 of the unit's packed
-// region (p->w + p->wplane elements; pack_all_tiled_kernel<1> writes it, ph_frag7_repack_launch for a single convolution)
-int ph_tap7_switch(int set);
+// region (p->w + p->wplane elements; pack_all_tiled_kernel<1> writes it, ph_frag7_repack_launch for a single convolution);
+// PH_TAP7=0 keeps conv_tap3.hip
 bool ph_tapconv7_eligible(const PhTapConv* p);
 int ph_tapconv7_launch(const PhTapConv* p, hipStream_t st);
 int ph_frag7_repack_launch(void* packed, int R, int K, int ntaps, hipStream_t st);
 // half-pair kernel of the 3x3 / stride-2 forward convolutions (conv_tap6.hip: parity-plane images through four LDS buffers on a
-// compile-time DMA schedule, conv_tap5.hip's weight window); PH_TAP6=0 keeps the first-generation kernel; its weights are packed
-// fragment-major while the switch is on (same caveat as PH_TAP5)
-int ph_tap6_switch(int set);
+// compile-time DMA schedule, conv_tap5.hip's weight window; reads PH_WFRAG_TAP6 weights); PH_TAP6=0 at pack time keeps the first generation
 bool ph_tapconv6_eligible(const PhTapConv* p);
 int ph_tapconv6_launch(const PhTapConv* p, hipStream_t st);
 int ph_tapconv6_stat_parts(const PhTapConv* p);
 // ... and its perf-mode (bf16) form (conv_tap6b.hip); reads the fragment-major copy in plane 1 of the unit's packed region; PH_TAP6B=0
 // keeps conv_tap2.hip's masked grid
-int ph_tap6b_switch(int set);
 bool ph_tapconv6b_eligible(const PhTapConv* p);
 int ph_tapconv6b_launch(const PhTapConv* p, hipStream_t st);
 int ph_tapconv6b_stat_parts(const PhTapConv* p);

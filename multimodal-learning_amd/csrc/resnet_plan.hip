@@ -17,6 +17,9 @@
 #include "ph_kernels.h"
 #include "ph_dense.h"
 
+// A/B and test switch: PH_BST=0 in the environment / ph_debug_set_bst(0) keeps every BatchNorm-backward reduction a pass of its own
+PH_SWITCH(bst, "PH_BST")
+
 namespace {
 
 struct Unit {
@@ -30,23 +33,6 @@ struct Unit {
   mutable int wfrag_f = 0, wfrag_d = 0;
 };
 
-// geometry of unit u's forward and stride-1 dgrad descriptors (tensors, statistics and fused fields are the caller's)
-void fwd_geometry(const Unit& u, PhTapConv& t) {
-  t.IH = u.IH; t.IW = u.IW; t.Cin = u.Cin; t.Cout = u.Cout;
-  t.OHt = u.OH; t.OWt = u.OW; t.OH = u.OH; t.OW = u.OW; t.os = 1; t.oa_h = 0; t.oa_w = 0;
-  t.iy0 = -u.pad; t.ix0 = -u.pad; t.ntaps = u.KS * u.KS;
-  for (int k = 0; k < t.ntaps; ++k) { t.dy[k] = k / u.KS; t.dx[k] = k % u.KS; t.wtap[k] = k; }
-}
-void dgrad_s1_geometry(const Unit& u, PhTapConv& t) {
-  t.IH = u.OH; t.IW = u.OW; t.Cin = u.Cout; t.Cout = u.Cin;
-  t.OH = u.IH; t.OW = u.IW;
-  t.OHt = u.IH; t.OWt = u.IW; t.os = 1; t.oa_h = 0; t.oa_w = 0;
-  t.iy0 = -(u.KS - 1 - u.pad); t.ix0 = t.iy0; t.ntaps = u.KS * u.KS;
-  for (int k = 0; k < t.ntaps; ++k) {
-    const int dyy = k / u.KS, dxx = k % u.KS;
-    t.dy[k] = dyy; t.dx[k] = dxx; t.wtap[k] = (u.KS - 1 - dyy) * u.KS + (u.KS - 1 - dxx);
-  }
-}
 struct Block {
   int u1, u2, uds;
   size_t in_off, a1_off, out_off;   // byte offsets of the block input / post-bn1-relu / output activations
@@ -122,10 +108,10 @@ unsigned long long refresh_layouts(const PhResnetPlan* P) {
   for (size_t i = 1; i < P->units.size(); ++i) {
     const Unit& u = P->units[i];
     PhTapConv f{}, d{};
-    fwd_geometry(u, f);
+    ph_conv_fwd_geometry(&f, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.S, u.pad);
     u.wfrag_f = ph_tapconv_hp_wfrag(&f, u.S, P->prec);
     u.wfrag_d = PH_WFRAG_ROW;
-    if (u.S == 1) { dgrad_s1_geometry(u, d); u.wfrag_d = ph_tapconv_hp_wfrag(&d, 1, P->prec); }
+    if (u.S == 1) { ph_conv_dgrad_s1_geometry(&d, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.pad); u.wfrag_d = ph_tapconv_hp_wfrag(&d, 1, P->prec); }
     for (unsigned long long v : {(unsigned long long)i, (unsigned long long)u.wfrag_f, (unsigned long long)u.wfrag_d}) {
       sig ^= v;
       sig *= 1099511628211ull;
@@ -185,8 +171,8 @@ PhResnetPlan* ph_resnet_plan_create(int B, int H, int W, int prec) {
         u.wd_off = woff; woff += PH_NPLANES * u.wplane;
         u.y_off = take((size_t)B * u.OH * u.OW * cout * es);
         u.st_off = take(4 * (size_t)cout * sizeof(float));
-        PhTapConv tc{}; tc.B = B; tc.Cout = cout; tc.OHt = u.OH; tc.OWt = u.OW;
-        parts_max = std::max(parts_max, (size_t)ph_tapconv_stat_parts(&tc, (ks == 1 ? 1 : st), prec) * 2 * cout * sizeof(float));
+        for (int S = 1; S <= (ks == 1 ? 1 : st); ++S)      // (a 3x3 stride-2 forward may be routed to a stride-1 launch, a 1x1 always is)
+          parts_max = std::max(parts_max, (size_t)ph_tapconv_stat_parts_bound(B, u.OH, u.OW, cout, S, prec) * 2 * cout * sizeof(float));
         int tpc; int nc = wgrad_chunks(u, B, &tpc);
         slab_max = std::max(slab_max, (size_t)nc * ks * ks * cin * cout * sizeof(float));
         P->units.push_back(u);
@@ -303,17 +289,9 @@ int conv_fwd(const Ctx& c, int ui, const void* in, const float* in_scale = nullp
   t.in_scale = in_scale; t.in_shift = in_shift;
   t.out = c.ws + u.y_off; t.stats = c.eval ? nullptr : reinterpret_cast<float*>(c.ws + P->parts_off);
   t.B = P->B;
-  fwd_geometry(u, t);
-  t.w_frag = u.wfrag_f; t.no_tap6b = c.no_masked;
-  int S = u.S;
-  // 3x3 / stride 2 in perf mode: a stride-1 MASKED tap grid over the four pixel-parity planes of the input (conv_tap2.hip)
-  // (round 6: conv_tap6b.hip takes the un-masked stride-2 descriptor itself)
-  const bool tap6b = P->prec == PH_PREC_BF16 && u.KS == 3 && u.S == 2 && !c.no_masked && ph_tap6b_switch(-1) && ph_tapconv6b_eligible(&t);
-  if (!tap6b && u.KS == 3 && u.S == 2 && u.pad == 1 && !c.no_masked && ph_tapconv2_setup_s2_fwd(&t, u.Cin, u.Cout, u.IH, u.IW, P->prec)) S = 1;
-  if (u.KS == 1 && u.S == 2) {   // 1x1 / stride 2 == 1x1 / stride 1 over the even-pixel view of the input
-    t.in_pix_stride = 2L * u.Cin; t.in_row_stride = 2L * u.IW * u.Cin; t.in_img_stride = (long)u.IH * u.IW * u.Cin;
-    t.IH = u.OH; t.IW = u.OW; S = 1;
-  }
+  ph_conv_fwd_geometry(&t, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.S, u.pad);
+  t.w_frag = u.wfrag_f;
+  const int S = ph_conv_fwd_route(&t, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.S, u.pad, P->prec, c.no_masked);
   int rc = ph_tapconv_launch(&t, S, P->prec, c.st);
   if (rc || c.eval) return rc;      // (eval: scale/shift were preset from the running statistics)
   const int nparts = ph_tapconv_stat_parts(&t, S, P->prec);
@@ -328,13 +306,6 @@ int conv_fwd(const Ctx& c, int ui, const void* in, const float* in_scale = nullp
 // when a == null, else a > 0) and optionally of unit `u2` (the downsample branch reading the same dz)
 struct Bst { int u = -1, u2 = -1; const void* a = nullptr; };
 
-// A/B and test switch: PH_BST=0 in the environment / ph_debug_set_bst(0) keeps every BatchNorm-backward reduction a pass of its own
-int bst_switch(int set) {
-  static int on = [] { const char* e = getenv("PH_BST"); return (e && e[0] == '0') ? 0 : 1; }();
-  if (set >= 0) on = set ? 1 : 0;
-  return on;
-}
-
 // dgrad of unit ui: in = dY [B][OH][OW][Cout] -> out = dX [B][IH][IW][Cin] (+ residual); dzs: dY's scale record (half-pair mode).
 // bst (optional) + fused_parts: when the launch can take the sums, *fused_parts = the number of [3][C] rows it left in the plan's
 // fparts buffer (0 = not fused: the caller runs the separate reduction)
@@ -345,13 +316,12 @@ int conv_dgrad(const Ctx& c, int ui, const void* dy, void* dx, const void* res_g
   PhTapConv t{};
   t.in = dy; t.w = c.pk + u.wd_off; t.wplane = u.wplane; t.in_unscale = dzs;
   t.out = dx; t.stats = nullptr; t.res_g = res_g; t.res_a = res_a;
-  t.B = P->B; t.IH = u.OH; t.IW = u.OW; t.Cin = u.Cout; t.Cout = u.Cin;
-  t.OH = u.IH; t.OW = u.IW;
+  t.B = P->B;
   t.w_frag = u.wfrag_d;
   if (fused_parts) *fused_parts = 0;
   if (u.S == 1) {
-    dgrad_s1_geometry(u, t);
-    if (bst && fused_parts && bst->u >= 0 && P->prec == PH_PREC_BF16 && bst_switch(-1)) {
+    ph_conv_dgrad_s1_geometry(&t, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.pad);
+    if (bst && fused_parts && bst->u >= 0 && P->prec == PH_PREC_BF16 && ph_bst_switch(-1)) {
       const Unit& bu = P->units[bst->u];
       PhTapConv f = t;
       f.bst_y = c.ws + bu.y_off; f.bst_mean = c.stat(bu, 0);
@@ -370,16 +340,15 @@ int conv_dgrad(const Ctx& c, int ui, const void* dy, void* dx, const void* res_g
       // force it off / on, 1 also on conv_tap3.hip)
       static const int bst3 = [] { const char* e = getenv("PH_BST3"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
       static const int bst2 = [] { const char* e = getenv("PH_BST2"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-      const bool dense = ph_tap3_switch(-1) && ph_tapconv2_tile_h(&f, 1, P->prec) && ph_tapconv3_eligible(&f);
-      const bool on7 = dense && ph_tap7_switch(-1) && ph_tapconv7_eligible(&f);
-      const bool l1 = ph_tap4_switch(-1) && ph_tapconv4_eligible(&f);
+      const PhConvChoice ch = ph_tapconv_select(&f, 1, P->prec);      // the kernels that can take the sums: conv_tap3 / 4 / 7
+      const bool on7 = ch.kernel == PH_CK_TAP7, dense = on7 || ch.kernel == PH_CK_TAP3, l1 = ch.kernel == PH_CK_TAP4;
       const bool big = P->B >= 128;
       const bool mask_ok = !bst->a || bst2 == 1 || (bst2 == -1 && on7 && big);      // the mask-tensor forms (bn2 / downsample behind conv1's dgrad)
       const bool ok = bu.Cout == t.Cout && bu.OH == t.OH && bu.OW == t.OW && mask_ok &&
                       (l1 || (dense && (bst3 == 1 || (bst3 == -1 && on7 && big))));
       if (ok) {
         const int rc = ph_tapconv_launch(&f, 1, c.bprec(), c.st);
-        if (rc == PH_OK) *fused_parts = ph_tapconv2_stat_parts(&f);
+        if (rc == PH_OK) *fused_parts = ch.stat_parts;
         return rc;
       }
     }
@@ -390,47 +359,32 @@ int conv_dgrad(const Ctx& c, int ui, const void* dy, void* dx, const void* res_g
   // round 6: as four launches in a row layers 3.0 / 4.0 put 256 / 128 workgroups on the 256 CUs each time; PH_S2_MERGE=0
   // keeps them apart, A/B and test switch)
   static const bool merge = [] { const char* e = getenv("PH_S2_MERGE"); return !(e && e[0] == '0'); }();
-  PhTapConv mt = t;
+  PhTapConv cls[4];
+  int ncls;
+  bool tapless;      // (a class no tap reaches, 1x1 stride-2: the gradient is zero there; with an in-place residual (res_g == dx) the
+                     // existing values already are the result, otherwise the caller pre-zeroed dx)
+  int rc = ph_conv_dgrad_s2_classes(&t, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.pad, cls, &ncls, &tapless);
+  if (rc) return rc;
+  PhTapConv mt = cls[0];
   mt.ncls = 0;
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      int nk = 0, khs[3], dhs[3], nw = 0, kws[3], dws[3];
-      for (int kh = 0; kh < u.KS; ++kh)
-        if (((a + u.pad - kh) & 1) == 0) { khs[nk] = kh; dhs[nk] = (a + u.pad - kh) / 2; ++nk; }
-      for (int kw = 0; kw < u.KS; ++kw)
-        if (((b + u.pad - kw) & 1) == 0) { kws[nw] = kw; dws[nw] = (b + u.pad - kw) / 2; ++nw; }
-      t.OHt = (u.IH - a + 1) / 2; t.OWt = (u.IW - b + 1) / 2;
-      if (t.OHt <= 0 || t.OWt <= 0) continue;
-      t.os = 2; t.oa_h = a; t.oa_w = b; t.iy0 = 0; t.ix0 = 0;
-      t.ntaps = nk * nw;
-      if (t.ntaps == 0) {
-        // no tap reaches this class (1x1 stride-2): gradient is zero there; with an in-place residual
-        // (res_g == dx) the existing values already are the result, otherwise the caller pre-zeroed dx.
-        continue;
+  for (int i = 0; i < ncls; ++i) {
+    const PhTapConv& q = cls[i];
+    if (merge && u.KS == 3 && q.ntaps <= 4 && mt.ncls < 4) {
+      const int k = mt.ncls++;
+      mt.c_ntaps[k] = q.ntaps; mt.c_oa_h[k] = q.oa_h; mt.c_oa_w[k] = q.oa_w; mt.c_OHt[k] = q.OHt; mt.c_OWt[k] = q.OWt;
+      for (int e = 0; e < q.ntaps; ++e) { mt.c_dy[k][e] = q.dy[e]; mt.c_dx[k][e] = q.dx[e]; mt.c_wtap[k][e] = q.wtap[e]; }
+      for (int e = q.ntaps; e < 4; ++e) { mt.c_dy[k][e] = 0; mt.c_dx[k][e] = 0; mt.c_wtap[k][e] = 0; }
+      // the descriptor's own fields: the largest class (grid extent; profiler)
+      if (k == 0 || q.OHt * q.OWt > mt.OHt * mt.OWt) { mt.OHt = q.OHt; mt.OWt = q.OWt; }
+      if (k == 0 || q.ntaps > mt.ntaps) {
+        mt.ntaps = q.ntaps;
+        for (int e = 0; e < q.ntaps; ++e) { mt.dy[e] = q.dy[e]; mt.dx[e] = q.dx[e]; mt.wtap[e] = q.wtap[e]; }
       }
-      int q = 0;
-      for (int i = 0; i < nk; ++i)
-        for (int j = 0; j < nw; ++j) {
-          if (dhs[i] < 0 || dws[j] < 0 || dhs[i] > 2 || dws[j] > 2) return PH_EINVAL;
-          t.dy[q] = dhs[i]; t.dx[q] = dws[j]; t.wtap[q] = khs[i] * u.KS + kws[j]; ++q;
-        }
-      if (merge && u.KS == 3 && t.ntaps <= 4 && mt.ncls < 4) {
-        const int k = mt.ncls++;
-        mt.c_ntaps[k] = t.ntaps; mt.c_oa_h[k] = a; mt.c_oa_w[k] = b; mt.c_OHt[k] = t.OHt; mt.c_OWt[k] = t.OWt;
-        for (int e = 0; e < t.ntaps; ++e) { mt.c_dy[k][e] = t.dy[e]; mt.c_dx[k][e] = t.dx[e]; mt.c_wtap[k][e] = t.wtap[e]; }
-        for (int e = t.ntaps; e < 4; ++e) { mt.c_dy[k][e] = 0; mt.c_dx[k][e] = 0; mt.c_wtap[k][e] = 0; }
-        // the descriptor's own fields: the largest class (grid extent; profiler)
-        if (k == 0 || t.OHt * t.OWt > mt.OHt * mt.OWt) { mt.OHt = t.OHt; mt.OWt = t.OWt; }
-        if (k == 0 || t.ntaps > mt.ntaps) {
-          mt.ntaps = t.ntaps;
-          for (int e = 0; e < t.ntaps; ++e) { mt.dy[e] = t.dy[e]; mt.dx[e] = t.dx[e]; mt.wtap[e] = t.wtap[e]; }
-        }
-        mt.os = 2; mt.oa_h = 0; mt.oa_w = 0; mt.iy0 = 0; mt.ix0 = 0;
-        continue;
-      }
-      int rc = ph_tapconv_launch(&t, 1, c.bprec(), c.st);
-      if (rc) return rc;
+      mt.os = 2; mt.oa_h = 0; mt.oa_w = 0; mt.iy0 = 0; mt.ix0 = 0;
+      continue;
     }
+    if ((rc = ph_tapconv_launch(&q, 1, c.bprec(), c.st))) return rc;
+  }
   if (mt.ncls >= 2) return ph_tapconv_launch(&mt, 1, c.bprec(), c.st);
   if (mt.ncls == 1) {      // (a single class that qualified: an ordinary launch)
     PhTapConv one = mt;
@@ -931,7 +885,6 @@ int ph_resnet_plan_set_backward_prec(const PhResnetPlan* P, int prec) {
 // A/B and test switch: 0 = the whole backward on the caller's stream (the round-2 sequence), 1 (default) = weight
 // gradients on the side stream
 // A/B and test switch (not part of the public C-ABI): 0 = every BatchNorm-backward reduction as a pass of its own
-int ph_debug_set_bst(int on) { return bst_switch(on ? 1 : 0); }
 
 int ph_resnet_plan_set_backward_overlap(const PhResnetPlan* P, int on) {
   if (!P) return PH_EINVAL;

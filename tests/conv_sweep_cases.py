@@ -1,7 +1,7 @@
 """The shapes of the convolution dispatch sweep (tests/test_gpu_conv_sweep.py) and the kernel family each call reaches.
 
-Each case sits on or just outside an eligibility predicate of ph_tapconv_launch / ph_tapconv2_launch (conv_tap.hip,
-conv_tap2.hip, the ph_tapconv*_eligible functions).  Every map is non-square; several are odd."""
+Each case sits on or just outside an eligibility predicate of ph_tapconv_select (conv_select.hip; the ph_tapconv*_eligible
+functions beside the kernels).  Every map is non-square; several are odd."""
 from tests.conv_emulation import BF16, BF16X6, BF16X3, FP16X3, FP16X1
 
 # name: (Cin, Cout, IH, IW, KS, stride, pad, B)
