@@ -271,6 +271,21 @@ int ph_contrast_loss_v2(const float* x, float* rows, float* dx, int B, int S, in
 size_t ph_crd_class_centers_workspace_bytes(int num_classes, int max_class_rows);
 int ph_crd_class_centers(float* mem_ext, const int* members, const int* offsets, int num_classes, int max_class_rows,
                          int n_data, int feat_dim, void* workspace, ph_stream_t stream);
+/* MIA-2023 v10 clustered class centres (`--pos_extra centers --nce_p N`, N > 2, CRD_criterion_v10.py:81-101,117-137: the
+ * reference fits sklearn KMeans(n_clusters = N - 1) on every class of either bank at every call, :90-92 / :126-128).  Here a
+ * deterministic Lloyd iteration on the device: farthest-point initialisation from the member at list
+ * position 0, `iters` rounds of assignment (least direct-form distance, lowest centre index among equals) and mean update (a
+ * centre without members keeps its value).  mem*_ext = banks allocated with n_data + num_classes * k rows; row
+ * n_data + c * k + j receives centre j of class c, the n_data bank rows are only read.  Both banks go in every launch;
+ * k + 2 * iters launches, no host read, no allocation.  labels (optional) = the last assignment, per bank in list order;
+ * counts (optional) = the members of every centre after it.  A class with fewer than k members: centres j >= its size are
+ * zero rows without members.  PH_EINVAL for feat_dim != 128, k outside 2 .. 8 (k == 1 is ph_crd_class_centers), iters < 1,
+ * num_classes < 1, a NULL or not 16-byte aligned bank, a NULL list or workspace. */
+size_t ph_crd_kmeans_centers_workspace_bytes(int num_classes, int max_class_rows, int k);
+int ph_crd_kmeans_centers(float* mem1_ext, float* mem2_ext, const int* members, const int* offsets, int num_classes,
+                          int max_class_rows, int n_data, int feat_dim, int k, int iters,
+                          int* labels /* [2][offsets[num_classes]] or NULL */, int* counts /* [2][num_classes][k] or NULL */,
+                          void* workspace, ph_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GK-Refine (AEKD_loss, train_test_path_multi_distill.py:41-70) and optimiser

@@ -7,7 +7,12 @@ query every step (:72-79,110-116); here `ph_crd_bank_topk` scans the bank on the
 `pos_extra == "centers"` with nce_p == 2 (:81-101: the positives are the MEAN bank row of the query's class and the query's
 own row, the other classes' means join the negatives) is built: `ph_crd_class_centers` writes the class means behind the
 bank and the same fused kernels run over the extended column lists.  nce_p > 2 clusters every class with sklearn KMeans
-from a random initialisation at every call - not reproducible, parity-unpinned - and raises."""
+from a random initialisation at every call (:90-92, :126-128) - not reproducible, so with the default
+`opt.centers_kmeans == "sklearn"` it raises.  `opt.centers_kmeans = "device"` (3 <= nce_p <= 9) runs a deterministic k-means of
+this project's own instead, `ph_crd_kmeans_centers`: farthest-point initialisation, `opt.kmeans_iters`
+(default 16) Lloyd iterations on the device, the nce_p - 1 centres of every class behind the bank rows.  It is not sklearn's
+k-means++ and claims no draw parity; on a bank whose clustering is not in doubt it gives the reference's numbers
+(tests/golden/make_golden_mia2023_kmeans.py)."""
 import math
 
 import numpy as np
@@ -44,23 +49,24 @@ class ContrastMemory(nn.Module):
         self.batch_norm_size = None
         self.verbose = True
         self.last = None
+        self.center_k = 1          # centre rows per class behind the bank (CRDLoss sets nce_p - 1)
 
     def _load_from_state_dict(self, *a, **k):
         super()._load_from_state_dict(*a, **k)
         self._z_set = bool((self.params[2:4] > 0).all().item())
 
     def ensure_center_rows(self, dev):
-        """`pos_extra == "centers"`: re-home both banks into allocations with len(class_idx) extra rows behind the
+        """`pos_extra == "centers"`: re-home both banks into allocations with len(class_idx) * center_k extra rows behind the
         n_data bank rows (the buffers stay [n_data, D] views, so state_dict / load_state_dict are unchanged) and build
         the flat class-member lists once.  Module.to() / .cuda() replace the buffers by compact copies; the next call
         re-homes them."""
         C = len(self.class_idx)
-        n, D = self.nLem, self.memory_v1.shape[1]
+        n, D, ck = self.nLem, self.memory_v1.shape[1], self.center_k
         for name in ("memory_v1", "memory_v2"):
             ext = getattr(self, "_ext_" + name, None)
             cur = getattr(self, name)
-            if ext is None or ext.device != cur.device or cur.data_ptr() != ext.data_ptr():
-                ext = torch.zeros(n + C, D, device=cur.device, dtype=torch.float32)
+            if ext is None or ext.device != cur.device or cur.data_ptr() != ext.data_ptr() or ext.shape[0] != n + C * ck:
+                ext = torch.zeros(n + C * ck, D, device=cur.device, dtype=torch.float32)
                 ext[:n].copy_(cur)
                 setattr(self, "_ext_" + name, ext)
                 self._buffers[name] = ext[:n]
@@ -75,6 +81,10 @@ class ContrastMemory(nn.Module):
             self._center_ws = torch.empty(lib().ph_crd_class_centers_workspace_bytes(C, self._max_class), device=dev,
                                           dtype=torch.uint8)
             self._others = torch.as_tensor([[j for j in range(C) if j != c] for c in range(C)], device=dev, dtype=torch.int64)
+            self._kmeans_ws = None
+        if ck > 1 and (getattr(self, "_kmeans_ws", None) is None or self._kmeans_ws.device != dev):
+            self._kmeans_ws = torch.empty(lib().ph_crd_kmeans_centers_workspace_bytes(C, self._max_class, ck), device=dev,
+                                          dtype=torch.uint8)
 
 
 class CRDLoss(nn.Module):
@@ -90,10 +100,24 @@ class CRDLoss(nn.Module):
         self.pos_extra = opt.pos_extra
         if self.pos_extra not in ("neighbors", "centers"):
             raise NotImplementedError("pos_extra '%s' (CRD_criterion_v10.py knows 'neighbors' and 'centers')" % self.pos_extra)
+        self.centers_kmeans = getattr(opt, "centers_kmeans", "sklearn")
+        self.kmeans_iters = int(getattr(opt, "kmeans_iters", 16))
         if self.pos_extra == "centers" and self.num_pos != 2:
-            raise NotImplementedError("pos_extra 'centers' with nce_p %d: nce_p > 2 runs sklearn KMeans from a random "
-                                      "initialisation per class and call (:90-93) - not reproducible, parity-unpinned; "
-                                      "nce_p == 2 (class means) is built" % self.num_pos)
+            if self.centers_kmeans != "device":
+                raise NotImplementedError("pos_extra 'centers' with nce_p %d: nce_p > 2 runs sklearn KMeans from a random "
+                                          "initialisation per class and call (:90-93) - not reproducible, parity-unpinned; "
+                                          "nce_p == 2 (class means) is built, and centers_kmeans=\"device\" runs the "
+                                          "deterministic device k-means for 3 <= nce_p <= 9" % self.num_pos)
+            if not 3 <= self.num_pos <= 9:
+                raise NotImplementedError("pos_extra 'centers' with centers_kmeans 'device': nce_p %d outside 3 .. 9 (the "
+                                          "device k-means holds 2 .. 8 centres per class)" % self.num_pos)
+            if self.kmeans_iters < 1:
+                raise ValueError("kmeans_iters must be >= 1, got %d" % self.kmeans_iters)
+            small = [c for c, members in enumerate(train_class_idx) if len(members) < self.num_pos - 1]
+            if small:      # sklearn: "n_samples=.. should be >= n_clusters=.."
+                raise ValueError("pos_extra 'centers' with nce_p %d: class(es) %s have fewer than %d rows (n_samples should be "
+                                 ">= n_clusters)" % (self.num_pos, small, self.num_pos - 1))
+            self.contrast.center_k = self.num_pos - 1
         self.criterion_t = ContrastLoss_v2(n_data)
         self.criterion_s = ContrastLoss_v2(n_data)
         import os
@@ -170,26 +194,43 @@ class CRDLoss(nn.Module):
         return idx1, dict(nb1=nb1, nb2=nb2, sim1=sim1, sim2=sim2, _ws=ws)
 
     def _forward_centers(self, sample_weights, v1, v2, batch_label, idx, contrast_idx):
-        """:81-101 / :118-139 with num_pos == 2 and ContrastLoss (:241-277): columns = [class centre, the K + 1 sampled
-        rows (the first is the query's own), the other classes' centres]; the first two are the equally weighted
-        positives."""
+        """:81-101 / :118-139 and ContrastLoss (:241-277) for P = num_pos: columns = [the P - 1 centres of the query's class,
+        the K + 1 sampled rows (the first is the query's own), the (C - 1)(P - 1) centres of the other classes, classes
+        ascending, centres ascending]; the first P are the positives.  ContrastLoss with P > 1 is
+        -(sum_p log_D1_p) / P - sum log_D0 (:268 repeats the negatives' sum P times and divides by P): uniform weights 1 / P,
+        what the fused kernels compute for posw = None.  P == 2: the class means (ph_crd_class_centers); P > 2: the device
+        k-means (ph_crd_kmeans_centers), both banks in one call, from the PRE-update bank like the means.  Under ReplicaSync
+        the banks are replicated and the k-means is deterministic - the same bits on every replica - so no exchange is
+        needed."""
         mem = self.contrast
         K, n, dev = mem.K, mem.nLem, v1.device
         B = v1.shape[0]
         C = len(mem.class_idx)
         mem.ensure_center_rows(dev)
-        for bank in (mem.memory_v1, mem.memory_v2):
-            check(lib().ph_crd_class_centers(ptr(bank), ptr(mem._members), ptr(mem._member_off), C, mem._max_class, n,
-                                             v1.shape[1], ptr(mem._center_ws), stream()), "ph_crd_class_centers")
+        P, ck = self.num_pos, self.num_pos - 1
+        if ck == 1:
+            for bank in (mem.memory_v1, mem.memory_v2):
+                check(lib().ph_crd_class_centers(ptr(bank), ptr(mem._members), ptr(mem._member_off), C, mem._max_class, n,
+                                                 v1.shape[1], ptr(mem._center_ws), stream()), "ph_crd_class_centers")
+        else:
+            check(lib().ph_crd_kmeans_centers(ptr(mem.memory_v1), ptr(mem.memory_v2), ptr(mem._members), ptr(mem._member_off),
+                                              C, mem._max_class, n, v1.shape[1], ck, self.kmeans_iters, None, None,
+                                              ptr(mem._kmeans_ws), stream()), "ph_crd_kmeans_centers")
         # the other classes in ascending order (np.argwhere(onehot == 0)[:, 1], :63-64)
         others = mem._others[batch_label]                                          # [B, C - 1]
-        cols = torch.cat(((n + batch_label).view(B, 1), contrast_idx, n + others), 1).contiguous()
-        mem.P, mem.P2, mem.K2 = 2, 2, K + C - 1
+        if ck == 1:
+            cols = torch.cat(((n + batch_label).view(B, 1), contrast_idx, n + others), 1).contiguous()
+        else:
+            j = torch.arange(ck, device=dev)
+            own = n + batch_label.view(B, 1) * ck + j                              # [B, P - 1]
+            neg = (n + others.view(B, C - 1, 1) * ck + j).view(B, (C - 1) * ck)
+            cols = torch.cat((own, contrast_idx, neg), 1).contiguous()
+        mem.P, mem.P2, mem.K2 = P, P, K + (C - 1) * ck
         mem._idx_bank2 = None
         mem._scan_neg = None
         mem._posw_s = mem._posw_t = None                                           # ContrastLoss: 1 / P each
         K_saved = mem.K
-        mem.K = K + C - 1                                                          # crd_core reads P + K as the list width
+        mem.K = K + (C - 1) * ck                                                   # crd_core reads P + K as the list width
         try:
             rows = _CRDCoreFn.apply(v1, v2, mem, idx, cols, None, True)
         finally:

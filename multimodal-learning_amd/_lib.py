@@ -118,6 +118,8 @@ SIGNATURES = {
     "ph_contrast_loss_v2": (i32, [vp, vp, vp, i32, i32, i32, f32, vp]),
     "ph_crd_class_centers_workspace_bytes": (sz, [i32, i32]),
     "ph_crd_class_centers": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "ph_crd_kmeans_centers_workspace_bytes": (sz, [i32, i32, i32]),
+    "ph_crd_kmeans_centers": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "ph_gram": (i32, [vp, vp, i32, i32, vp]),
     "ph_gk_scale": (i32, [vp, vp, i32, i32, f32, vp, vp, vp]),
     "ph_gk_scale_momentum": (i32, [vp, i32, i32, f32, f32, vp, vp, vp]),

@@ -23,7 +23,10 @@ def stage2_opt(**overrides):
         global_step=0, batch_size=16,
         grads_m=0.9, grads_thresh="False", thresh=0.0,   # MIA-2022 momentum GK-Refine ("MIA 2022/options.py":80-82)
         pos_extra="neighbors", use_grads_thresh="True", max_discrep=1, discrep_scale=1, start_reweight=0,   # MIA-2023
-        overlap_teachers=True)     # ours: run the EMA / teacher forwards on a second HIP stream
+        overlap_teachers=True,     # ours: run the EMA / teacher forwards on a second HIP stream
+        # ours: `pos_extra centers` with nce_p > 2 - "sklearn" raises (the reference's per-call KMeans is not reproducible),
+        # "device" runs the deterministic device k-means with kmeans_iters Lloyd iterations
+        centers_kmeans="sklearn", kmeans_iters=16)
     for k, v in overrides.items():
         if not hasattr(o, k):
             raise AttributeError("unknown option %r" % k)
