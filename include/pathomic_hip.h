@@ -198,13 +198,13 @@ int ph_sum(const float* x, float* out, int n, float scale, ph_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
  * CRD memory bank (DC-Distill): ContrastMemory_v3.forward (CL_utils/memory_new.py:249-397) and
  * ContrastLoss_v2 (CL_utils/CRD_loss.py:221-244).  v1 = student embedding, v2 = teacher embedding,
- * mem1/mem2 = memory_v1/memory_v2 [n_data][128] f32, params = the module's `params` buffer
+ * mem1/mem2 = memory_v1/memory_v2 [n_data][feat_dim] f32, feat_dim (the row width) one of 64, 128, 256; params = the module's `params` buffer
  * [K, T, Z_v1, Z_v2, momentum, P].
  * ---------------------------------------------------------------------------------------------- */
 /* Sizes are checked on the host before anything is launched; PH_EINVAL for: ph_crd_score B < 1 or PK < 1; ph_crd_select B < 1,
  * P < 1, K < 0, P2 < 1, K2 < 0, P2 > P, K2 > K, an unranked side that does not keep every column (P2 != P / K2 != K) or a ranked
  * list above 160 KiB of LDS ((2 P + K) * 4 bytes); ph_crd_zsum n < 1; ph_crd_update B < 1; ph_crd_loss_grad B < 1, P2 < 1, K2 < 0
- * or P2 + K2 > PK (ph_crd_loss_grad_pos: B < 1, P < 1, m_neg < 1); feat_dim != 128 everywhere. */
+ * or P2 + K2 > PK (ph_crd_loss_grad_pos: B < 1, P < 1, m_neg < 1); feat_dim outside {64, 128, 256} everywhere, before any launch. */
 /* idx_bank2: optional second index array for memory_v2 (MIA-2023 v10: each bank has its own KNN positives); NULL = idx */
 int ph_crd_score(const float* v1, const float* v2, const int64_t* idx /* [B][P+K] */, const int64_t* idx_bank2,
                  const float* mem1, const float* mem2, float* out1, float* out2, float* diff /* each [B][P+K] */,
@@ -216,14 +216,15 @@ int ph_crd_select(const float* diff, const float* out1, const float* out2, const
                   ph_stream_t stream);
 int ph_crd_zsum(const float* xs, const float* xt, float* sums2, int n, ph_stream_t stream);
 int ph_crd_setz(float* params, const float* sums2, float count, float n_data, ph_stream_t stream);
-/* loss partials lossp[B] (sum = s_loss + t_loss) and d loss/d v1, d loss/d v2 [B][128] */
+/* loss partials lossp[B] (sum = s_loss + t_loss) and d loss/d v1, d loss/d v2 [B][feat_dim] */
 /* posw_s / posw_t: optional per-positive weights [B][P2] (MIA-2023 ContrastLoss_v2: similarity / sum similarity,
  * "MIA 2023/stage2_unimodal_student/CL_utils/CRD_criterion_v10.py":281-314); NULL = 1/P2 */
 int ph_crd_loss_grad(const float* xs, const float* xt, const int* sel, const int64_t* idx, const int64_t* idx_bank2,
                      const float* posw_s, const float* posw_t, const float* mem1, const float* mem2,
                      const float* params, float* lossp, float* dv1, float* dv2, int B, int PK, int P2, int K2,
                      int feat_dim, float n_data, float inv_bnorm, void* workspace /* may be NULL */, ph_stream_t stream);
-size_t ph_crd_loss_grad_workspace_bytes(int B);
+size_t ph_crd_loss_grad_workspace_bytes(int B);                        /* the size at feat_dim 128 */
+size_t ph_crd_loss_grad_workspace_bytes_w(int B, int feat_dim);        /* the size at any supported width */
 /* Bank-scan form of the CRD negatives: BASELINE configs[4] read as nce_k = 65536 negatives per query (SURVEY 8-e assumption (i);
  * the reference gathers them: "MIA 2023/stage2_unimodal_student/CL_utils/CRD_criterion_v10.py":68-70,106-107,140-141 index_select +
  * bmm over [B][K+1][128], and sums their terms in ContrastLoss_v2 :300-306).  With K at or above the number of bank rows the same
@@ -244,7 +245,8 @@ int ph_crd_loss_grad_pos(const float* xs, const float* xt, const int* sel, const
                          float* lossp, float* dv1, float* dv2, int B, int P, int m_neg, int feat_dim, float n_data, float inv_bnorm,
                          ph_stream_t stream);
 /* MIA-2023 v10 KNN positives (CRD_criterion_v10.py:72-79,110-116): class-masked full-bank cosine top-num_pos of each
- * query's own bank row, for both banks; labels = class of every bank row (int32 [n_data]) */
+ * query's own bank row, for both banks; labels = class of every bank row (int32 [n_data]).  The workspace size does not
+ * depend on feat_dim (a pass takes up to 64 queries at every width, through the same buffers). */
 size_t ph_crd_bank_topk_workspace_bytes(int B, int n_data);
 int ph_crd_bank_topk(const float* mem1, const float* mem2, const int* labels, const int64_t* idx, int PK,
                      const int64_t* batch_label, int B, int n_data, int num_pos, int feat_dim, int64_t* nb1,
@@ -253,7 +255,7 @@ int ph_crd_update(float* mem1, float* mem2, const float* v1, const float* v2, co
                   int B, int feat_dim, ph_stream_t stream);
 /* ContrastMemory_v3.forward as a STANDALONE call returning (out_v1, out_v2) [B][P2+K2] (memory_new.py:362-379: selected
  * scores / Z); also gathers the selected PRE-update bank rows (rows1 from memory_v1, rows2 from memory_v2, each
- * [B][P2+K2][128]) that its backward needs after the in-call momentum update (:382-395) has overwritten the bank. */
+ * [B][P2+K2][feat_dim]) that its backward needs after the in-call momentum update (:382-395) has overwritten the bank. */
 int ph_crd_outputs(const float* xs, const float* xt, const int* sel, const int64_t* idx, const int64_t* idx_bank2,
                    const float* mem1, const float* mem2, const float* params, float* out1, float* out2, float* rows1,
                    float* rows2, int B, int PK, int S2, int feat_dim, ph_stream_t stream);
@@ -268,7 +270,8 @@ int ph_contrast_loss_v2(const float* x, float* rows, float* dx, int B, int S, in
 /* MIA-2023 v10 class-centre positives (`--pos_extra centers --nce_p 2`, CRD_criterion_v10.py:84-89,121-126: the mean
  * bank row of every class, recomputed per call).  mem_ext = a bank allocated with n_data + num_classes rows; row
  * n_data + c receives the mean of rows members[offsets[c] .. offsets[c+1]).  max_class_rows = the largest class. */
-size_t ph_crd_class_centers_workspace_bytes(int num_classes, int max_class_rows);
+size_t ph_crd_class_centers_workspace_bytes(int num_classes, int max_class_rows);                 /* feat_dim 128 */
+size_t ph_crd_class_centers_workspace_bytes_w(int num_classes, int max_class_rows, int feat_dim);
 int ph_crd_class_centers(float* mem_ext, const int* members, const int* offsets, int num_classes, int max_class_rows,
                          int n_data, int feat_dim, void* workspace, ph_stream_t stream);
 /* MIA-2023 v10 clustered class centres (`--pos_extra centers --nce_p N`, N > 2, CRD_criterion_v10.py:81-101,117-137: the
@@ -316,7 +319,7 @@ int ph_gk_finish_momentum(const float* gram, const float* losses, float alpha, f
                           float mult, int use_thresh, float thresh, float momentum, float* mo_scale, int* mo_init, float* w,
                           float* total, float* scaled, float* scale_ext, ph_stream_t stream);
 /* GK_refine_thresh ("MIA 2023/stage2_unimodal_student/train_test_path_multi_distill.py":81-128): per-sample cosine
- * matrix of the ng gradients G[ng][B][128] -> all_scale[B][ng] */
+ * matrix of the ng gradients G[ng][B][D] -> all_scale[B][ng]; PH_EINVAL for D outside {64, 128, 256} or ng outside {3, 5} */
 int ph_gk_rows(const float* G, int ng, int B, int D, int use_thresh, float thresh, float* all_scale,
                ph_stream_t stream);
 int ph_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema /* may be NULL */, size_t n, double lr,

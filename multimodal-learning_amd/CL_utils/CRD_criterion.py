@@ -9,7 +9,7 @@ import torch.nn as nn
 from .. import ops
 from .CRD_loss import Normalize
 from .CRD_criterion_v3 import ContrastMemory, ContrastLoss   # noqa: F401  (:8-81, :190-217 are identical up to the weights)
-from .memory_new import _CRDCoreFn, draw_uniform_indices
+from .memory_new import _CRDCoreFn, draw_uniform_indices, check_feat_dim
 
 
 class Embed(nn.Module):
@@ -32,6 +32,7 @@ class CRDLoss(nn.Module):
 
     def __init__(self, opt):
         super().__init__()
+        check_feat_dim(opt.feat_dim)
         self.embed_s = Embed(opt.s_dim, opt.feat_dim)
         self.embed_t = Embed(opt.t_dim, opt.feat_dim)
         self.contrast = ContrastMemory(opt.feat_dim, opt.n_data, opt.nce_k, opt.nce_t, opt.nce_m)

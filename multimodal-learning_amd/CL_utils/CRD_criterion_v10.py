@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .CRD_loss import Embed, Normalize   # noqa: F401
-from .memory_new import _CRDCoreFn
+from .memory_new import _CRDCoreFn, check_feat_dim
 from .._lib import lib, check, ptr, stream
 
 eps = 1e-7
@@ -78,7 +78,7 @@ class ContrastMemory(nn.Module):
             self._members = torch.as_tensor(cat, device=dev)
             self._member_off = torch.as_tensor(off, device=dev)
             self._max_class = int(max(len(x) for x in lists))
-            self._center_ws = torch.empty(lib().ph_crd_class_centers_workspace_bytes(C, self._max_class), device=dev,
+            self._center_ws = torch.empty(lib().ph_crd_class_centers_workspace_bytes_w(C, self._max_class, D), device=dev,
                                           dtype=torch.uint8)
             self._others = torch.as_tensor([[j for j in range(C) if j != c] for c in range(C)], device=dev, dtype=torch.int64)
             self._kmeans_ws = None
@@ -93,6 +93,7 @@ class CRDLoss(nn.Module):
 
     def __init__(self, opt, n_data, train_class_idx):
         super().__init__()
+        check_feat_dim(opt.feat_dim)
         self.embed_s = Embed(opt.s_dim, opt.feat_dim)
         self.embed_t = Embed(opt.t_dim, opt.feat_dim)
         self.contrast = ContrastMemory(opt.feat_dim, n_data, train_class_idx, opt.nce_k, opt.nce_t, opt.nce_m)
@@ -108,6 +109,9 @@ class CRDLoss(nn.Module):
                                           "initialisation per class and call (:90-93) - not reproducible, parity-unpinned; "
                                           "nce_p == 2 (class means) is built, and centers_kmeans=\"device\" runs the "
                                           "deterministic device k-means for 3 <= nce_p <= 9" % self.num_pos)
+            if opt.feat_dim != 128:
+                raise NotImplementedError("centers_kmeans 'device' with feat_dim %d: the device k-means is built for feat_dim 128 "
+                                          "alone" % opt.feat_dim)
             if not 3 <= self.num_pos <= 9:
                 raise NotImplementedError("pos_extra 'centers' with centers_kmeans 'device': nce_p %d outside 3 .. 9 (the "
                                           "device k-means holds 2 .. 8 centres per class)" % self.num_pos)

@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from .CRD_loss import Embed, Normalize   # noqa: F401  (same classes as CRD_criterion_v3.py:227-250)
-from .memory_new import _CRDCoreFn, draw_uniform_indices
+from .memory_new import _CRDCoreFn, draw_uniform_indices, check_feat_dim
 
 eps = 1e-7
 
@@ -44,6 +44,7 @@ class CRDLoss(nn.Module):
 
     def __init__(self, opt, n_data):
         super().__init__()
+        check_feat_dim(opt.feat_dim)
         self.embed_s = Embed(opt.s_dim, opt.feat_dim)
         self.embed_t = Embed(opt.t_dim, opt.feat_dim)
         self.contrast = ContrastMemory(opt.feat_dim, n_data, opt.nce_k, opt.nce_t, opt.nce_m)

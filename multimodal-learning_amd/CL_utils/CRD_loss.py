@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .memory_new import ContrastMemory_v3
+from .memory_new import ContrastMemory_v3, check_feat_dim
 
 eps = 1e-7
 
@@ -16,6 +16,7 @@ class CRDLoss(nn.Module):
 
     def __init__(self, opt, n_data):
         super().__init__()
+        check_feat_dim(opt.feat_dim)
         self.P = opt.nce_p
         self.P2 = opt.nce_p2
         self.embed_s = Embed(opt.s_dim, opt.feat_dim)

@@ -13,6 +13,16 @@ from .. import ops
 from .._lib import lib, check, ptr, stream, require_cuda
 
 
+FEAT_DIMS = (64, 128, 256)      # the row widths the bank kernels are built for (csrc/crd.hip)
+
+
+def check_feat_dim(feat_dim, what="feat_dim"):
+    """The criteria call this at construction: a width the kernels refuse (PH_EINVAL) fails here, by name."""
+    if feat_dim not in FEAT_DIMS:
+        raise ValueError("%s %r: the CRD bank kernels are built for the widths %s" % (what, feat_dim, list(FEAT_DIMS)))
+    return int(feat_dim)
+
+
 def crd_core(v1, v2, mem, y, idx, ranks, per_sample=False, loss_out=None, outputs_only=False):
     """The fused CRD step on normalised embeddings: scores against the PRE-update banks, pair selection, first-call Z,
     NCE loss, analytic gradients, bank momentum update.  Returns (loss, dv1, dv2) with dv = d loss / d v for a unit
@@ -79,7 +89,7 @@ def crd_core(v1, v2, mem, y, idx, ranks, per_sample=False, loss_out=None, output
     if getattr(mem, "sample_KD", False):
         bnorm = 1.0      # ContrastLoss_v2's per-sample branch (CRD_loss.py:246-250) does not divide by the batch size
     # long column lists (nce_k = 4096 of the MIA trainers) are dealt to several workgroups per sample through a workspace
-    lg_ws = (torch.empty(L.ph_crd_loss_grad_workspace_bytes(B), device=dev, dtype=torch.uint8) if P2 + K2 >= 1024 else None)
+    lg_ws = (torch.empty(L.ph_crd_loss_grad_workspace_bytes_w(B, D), device=dev, dtype=torch.uint8) if P2 + K2 >= 1024 else None)
     check(L.ph_crd_loss_grad(ptr(xs), ptr(xt), ptr(sel), ptr(idx), ptr(idx2), ptr(posw_s), ptr(posw_t),
                              ptr(mem.memory_v1), ptr(mem.memory_v2),
                              ptr(mem.params), ptr(lossp), ptr(dv1), ptr(dv2), B, PK, P2, K2, D, float(mem.nLem),

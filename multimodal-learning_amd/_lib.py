@@ -107,6 +107,7 @@ SIGNATURES = {
     "ph_crd_zsum": (i32, [vp, vp, vp, i32, vp]),
     "ph_crd_setz": (i32, [vp, vp, f32, f32, vp]),
     "ph_crd_loss_grad_workspace_bytes": (sz, [i32]),
+    "ph_crd_loss_grad_workspace_bytes_w": (sz, [i32, i32]),
     "ph_crd_loss_grad": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp]),
     "ph_crd_neg_hist": (i32, [vp, lng, i32, i32, i32, i32, vp, vp]),
     "ph_crd_scan_neg_workspace_bytes": (sz, [i32, i32]),
@@ -117,6 +118,7 @@ SIGNATURES = {
     "ph_crd_outputs_bwd": (i32, [vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, vp]),
     "ph_contrast_loss_v2": (i32, [vp, vp, vp, i32, i32, i32, f32, vp]),
     "ph_crd_class_centers_workspace_bytes": (sz, [i32, i32]),
+    "ph_crd_class_centers_workspace_bytes_w": (sz, [i32, i32, i32]),
     "ph_crd_class_centers": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "ph_crd_kmeans_centers_workspace_bytes": (sz, [i32, i32, i32]),
     "ph_crd_kmeans_centers": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),

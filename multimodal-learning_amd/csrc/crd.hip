@@ -1,6 +1,6 @@
 // CRD memory-bank contrastive loss (DC-Distill): reference CL_utils/memory_new.py:249-397
 // (ContrastMemory_v3.forward) + CL_utils/CRD_loss.py:221-244 (ContrastLoss_v2), fused so that nothing
-// [B, P+K, 128]-sized is ever written:
+// [B, P+K, feat_dim]-sized is ever written (feat_dim = 64, 128 or 256; the numbers below are for 128):
 //   crd_score   : one coalesced 512-B read per bank row, 4 dot products + 2 norms in registers,
 //                 half-wave (32-lane) reductions -> exp scores (both directions) + cosine discrepancy
 //   crd_select  : per-sample rank-by-counting in LDS (replaces two full torch.sort calls): P2 positives at the
@@ -19,15 +19,20 @@
 
 namespace {
 
-constexpr int D = 128;   // feat_dim (options.py:83); asserted by the launcher
+// feat_dim (options.py:83) is the template parameter D of every kernel that sees a row: 64, 128 or 256, dispatched by the
+// launchers (PH_CRD_DISPATCH), anything else is PH_EINVAL.  A row is D/4 lanes of one 16-byte load each - a GROUP of 16, 32
+// (the half-wave the kernels were written for) or 64 lanes; a wave holds 64 / (D/4) groups.
+constexpr bool crd_width_ok(int d) { return d == 64 || d == 128 || d == 256; }
 
-__device__ __forceinline__ float half_sum(float v) {   // reduce within each 32-lane half of the wave
+template <int D>
+__device__ __forceinline__ float group_sum(float v) {   // reduce within each group of D/4 lanes of the wave (xor butterfly)
 #pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = D / 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 
-// grid (ceil(PK/64), B), block 256 = 8 half-waves, each half-wave walks 8 of the block's 64 columns
+// grid (ceil(PK/64), B), block 256 = 1024/D groups, each group walks D/16 of the block's 64 columns (128: 8 half-waves x 8)
+template <int D>
 __global__ __launch_bounds__(256) void crd_score_kernel(const float* __restrict__ v1, const float* __restrict__ v2,
                                                         const int64_t* __restrict__ idx,
                                                         const int64_t* __restrict__ idx_b2,
@@ -35,15 +40,16 @@ __global__ __launch_bounds__(256) void crd_score_kernel(const float* __restrict_
                                                         const float* __restrict__ mem2, float* __restrict__ out1,
                                                         float* __restrict__ out2, float* __restrict__ diff, int PK,
                                                         float invT) {
+  constexpr int G = D / 4, COLS = 64 / (256 / G);      // lanes per row, columns per group
   const int b = blockIdx.y;
-  const int hw = threadIdx.x >> 5, l = threadIdx.x & 31;
+  const int hw = threadIdx.x / G, l = threadIdx.x % G;
   const f32x4 a1 = *reinterpret_cast<const f32x4*>(v1 + (size_t)b * D + l * 4);
   const f32x4 a2 = *reinterpret_cast<const f32x4*>(v2 + (size_t)b * D + l * 4);
-  const float n1 = sqrtf(half_sum(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2] + a1[3] * a1[3]));
-  const float n2 = sqrtf(half_sum(a2[0] * a2[0] + a2[1] * a2[1] + a2[2] * a2[2] + a2[3] * a2[3]));
-  const int j0 = blockIdx.x * 64 + hw * 8;
+  const float n1 = sqrtf(group_sum<D>(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2] + a1[3] * a1[3]));
+  const float n2 = sqrtf(group_sum<D>(a2[0] * a2[0] + a2[1] * a2[1] + a2[2] * a2[2] + a2[3] * a2[3]));
+  const int j0 = blockIdx.x * 64 + hw * COLS;
 #pragma unroll 4
-  for (int jj = 0; jj < 8; ++jj) {
+  for (int jj = 0; jj < COLS; ++jj) {
     const int j = j0 + jj;
     if (j >= PK) break;
     const int64_t row = idx[(size_t)b * PK + j];
@@ -60,8 +66,8 @@ __global__ __launch_bounds__(256) void crd_score_kernel(const float* __restrict_
       q1 += m1[k] * m1[k];
       q2 += m2[k] * m2[k];
     }
-    d12 = half_sum(d12); d21 = half_sum(d21); d11 = half_sum(d11); d22 = half_sum(d22);
-    q1 = half_sum(q1); q2 = half_sum(q2);
+    d12 = group_sum<D>(d12); d21 = group_sum<D>(d21); d11 = group_sum<D>(d11); d22 = group_sum<D>(d22);
+    q1 = group_sum<D>(q1); q2 = group_sum<D>(q2);
     if (l == 0) {
       out2[(size_t)b * PK + j] = expf(d12 * invT);
       out1[(size_t)b * PK + j] = expf(d21 * invT);
@@ -170,6 +176,7 @@ __global__ void crd_setz_kernel(float* params, const float* sums, float count, f
 //   loss_s = -(1/Bn) [ sum_p log(x/(x+c)) / P2 + sum_n log(mPn/(x+c)) ],  x = xs/Z_v1, c = K2/n_data + eps
 //   d loss_s / d dot_j = -(1/(Bn P2)) (c/(x+c))/T  (positives) ;  +(1/Bn) (x/(x+c))/T  (negatives)
 //   dv1[b] = sum_j coef_s[j] mem2[idx[b][sel_j]] ; dv2[b] = sum_j coef_t[j] mem1[idx[b][sel_j]]
+template <int D>
 __global__ __launch_bounds__(1024) void crd_loss_grad_kernel(const float* __restrict__ xs,
                                                             const float* __restrict__ xt,
                                                             const int* __restrict__ sel,
@@ -185,15 +192,17 @@ __global__ __launch_bounds__(1024) void crd_loss_grad_kernel(const float* __rest
                                                             float n_data, float inv_bnorm, float* __restrict__ part) {
   // gridDim.y > 1 (long column lists, e.g. nce_k = 4096): the columns of a sample are dealt to gridDim.y workgroups whose
   // partial sums go to `part` and are added in a fixed order by crd_loss_grad_reduce_kernel
+  constexpr int G = D / 4;
   const int b = blockIdx.x, S2 = P2 + K2;
-  const int hw = threadIdx.x >> 5, l = threadIdx.x & 31;
+  const int hw = threadIdx.x / G, l = threadIdx.x % G;
   const float invT = 1.f / params[1], Z1 = params[2], Z2 = params[3];
   const float mPn = (float)m_neg / n_data, c = mPn + 1e-7f;      // m = the number of negatives of the loss (= K2 unless they are scanned)
   f32x4 g1 = {0.f, 0.f, 0.f, 0.f}, g2 = {0.f, 0.f, 0.f, 0.f};
   float ls = 0.f;
-  // 32 half-waves per sample: the loop is a chain of dependent gathers (sel -> idx -> bank row), latency-bound; with 8
-  // half-waves (256 threads) it took 54 us at B = 64, P2 + K2 = 532
-  constexpr int NHW = 32;
+  // 4096/D row groups per sample (128: 32 half-waves): the loop is a chain of dependent gathers (sel -> idx -> bank row), latency-bound; with 8
+  // half-waves (256 threads) it took 54 us at B = 64, P2 + K2 = 532.  The block stays 1024 threads at every width: 64, 32 or
+  // 16 row groups, and sh[NHW][2][D] is 32 KiB whichever
+  constexpr int NHW = 1024 / G;
   for (int j = blockIdx.y * NHW + hw; j < S2; j += NHW * gridDim.y) {
     const float x1 = xs[(size_t)b * S2 + j] / Z1, x2 = xt[(size_t)b * S2 + j] / Z2;
     float c1, c2;
@@ -223,7 +232,7 @@ __global__ __launch_bounds__(1024) void crd_loss_grad_kernel(const float* __rest
   if (l == 0) shl[hw] = ls;
   __syncthreads();
   if (threadIdx.x < 2 * D) {
-    const int which = threadIdx.x >> 7, d = threadIdx.x & 127;
+    const int which = threadIdx.x / D, d = threadIdx.x % D;
     float t = 0.f;
 #pragma unroll
     for (int q = 0; q < NHW; ++q) t += sh[q][which][d];
@@ -238,10 +247,11 @@ __global__ __launch_bounds__(1024) void crd_loss_grad_kernel(const float* __rest
   }
 }
 
-__global__ __launch_bounds__(256) void crd_loss_grad_reduce_kernel(const float* __restrict__ part, float* __restrict__ lossp,
-                                                                   float* __restrict__ dv1, float* __restrict__ dv2, int NS,
-                                                                   float inv_bnorm) {
-  const int b = blockIdx.x, which = threadIdx.x >> 7, d = threadIdx.x & 127;
+template <int D>      // block 2 D
+__global__ __launch_bounds__(2 * D) void crd_loss_grad_reduce_kernel(const float* __restrict__ part, float* __restrict__ lossp,
+                                                                     float* __restrict__ dv1, float* __restrict__ dv2, int NS,
+                                                                     float inv_bnorm) {
+  const int b = blockIdx.x, which = threadIdx.x / D, d = threadIdx.x % D;
   float t = 0.f;
   for (int y = 0; y < NS; ++y) t += part[(((size_t)b * NS + y) * 2 + which) * D + d];
   (which ? dv2 : dv1)[(size_t)b * D + d] = t;
@@ -252,7 +262,8 @@ __global__ __launch_bounds__(256) void crd_loss_grad_reduce_kernel(const float* 
   }
 }
 
-// mem[y[b]] = normalize(momentum * mem[y[b]] + (1 - momentum) * v[b]); one wave per (sample, bank)
+// mem[y[b]] = normalize(momentum * mem[y[b]] + (1 - momentum) * v[b]); one wave per (sample, bank), D/64 elements per lane
+template <int D>
 __global__ __launch_bounds__(256) void crd_update_kernel(float* __restrict__ mem1, float* __restrict__ mem2,
                                                          const float* __restrict__ v1, const float* __restrict__ v2,
                                                          const int64_t* __restrict__ y, const float* params, int B) {
@@ -263,11 +274,17 @@ __global__ __launch_bounds__(256) void crd_update_kernel(float* __restrict__ mem
   const float* v = (w & 1) ? v2 : v1;
   const float mom = params[4];
   const int64_t row = y[b];
-  float a0 = mem[row * D + lane] * mom + v[(size_t)b * D + lane] * (1.f - mom);
-  float a1 = mem[row * D + 64 + lane] * mom + v[(size_t)b * D + 64 + lane] * (1.f - mom);
-  const float n = sqrtf(wave_sum(a0 * a0 + a1 * a1));
-  mem[row * D + lane] = a0 / n;
-  mem[row * D + 64 + lane] = a1 / n;
+  constexpr int E = D / 64;
+  float a[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) a[e] = mem[row * D + e * 64 + lane] * mom + v[(size_t)b * D + e * 64 + lane] * (1.f - mom);
+  float ss;      // (written out per width: the 128 form is the expression the kernel always had)
+  if constexpr (E == 1) ss = a[0] * a[0];
+  else if constexpr (E == 2) ss = a[0] * a[0] + a[1] * a[1];
+  else ss = (a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]);
+  const float n = sqrtf(wave_sum(ss));
+#pragma unroll
+  for (int e = 0; e < E; ++e) mem[row * D + e * 64 + lane] = a[e] / n;
 }
 
 // MIA-2023 v10 positives (CL_utils/CRD_criterion_v10.py:72-79,110-116): for each query the num_pos bank rows of
@@ -328,8 +345,23 @@ __device__ __forceinline__ void knn_insert(u64 (&L)[TOPK_MAX], u64 c) {
 // row with the queries as scalar operands 120-132 us; similarity matrix [2][B][n_data] written by an MFMA kernel (59 us) and
 // re-read by a selection kernel (41 us) + merge (9 us): 136 MB of traffic for 67 MB of bank, 157-162 us per call (round 3);
 // one unseeded pass with lists 57 + 22 us; seeded, rows through registers and a half-tile LDS stage 16 + 5 + 38 + 10 us.
-constexpr int SIM_RS = 129;     // dwords per staged query row (odd: the 32 lanes of a ds_read_b32 group hit 32 different banks)
+// Width D: a tile of 32 bank rows is NG = D/32 feature groups of 32 rows x 32 features (2, 4 or 8; the description above is
+// NG = 4, "quarter" = group); the pipeline, the ring and the swizzle are per group and do not see D.  LDS of the full pass at 64
+// queries, bytes:
+//   D    waves  query image 64*(D+1)*4   ring waves x 12 KiB   norms, labels, |q|^2   total
+//   64   8      16 640                    98 304                5 376                  120 320
+//   128  8      33 024                    98 304                5 632                  136 960
+//   256  4      65 792                    49 152                3 584                  118 528
+// At D = 256 the image of 64 queries and the ring of eight waves exceed the 160 KiB of a CU.  Both ways out were built and
+// timed at 65 536 rows x 64 queries (tests/bench_crd_width_gpu.py, same device, alternated): two passes of 32 queries with
+// eight waves 116.2 - 116.3 us, one pass of 64 queries with FOUR waves (template parameter NWF) 84.3 - 85.4 us - reading the bank
+// once outweighs the second wave per SIMD.  The four-wave form is the one kept; up to 32 queries (one 32-query block, image
+// 32 896 B) run with eight waves at every width.  The result does not depend on the choice: a query's keys are selected among
+// the same rows with the same arithmetic (both forms matched the float64 sort on every case of tests/test_gpu_crd_width.py).
 constexpr int KNN_WAVES = 8, KNN_SAMPLE_WAVES = 4, KNN_NBUF = 3, KNN_MAX_GX = 128, KNN_SAMPLE_TILES = 128, KNN_MAX_B = 64;
+constexpr size_t knn_lds_bytes(int d, int nq, int nw) {
+  return (size_t)(nq * 32 * (d + 1) + nw * (KNN_NBUF * 1024 + 32 + 128) + nq * 32 * (d / 64)) * sizeof(float);
+}
 
 // DPP helpers (no LDS round trip, unlike __shfl): x of the lane N to the right inside the 16-lane row / lane 15 or 31 broadcast
 template <int CTRL, int ROW_MASK = 0xf>
@@ -371,12 +403,17 @@ __device__ __forceinline__ void knn_dma4(const void* g, unsigned lds_addr) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" : : "s"(__builtin_amdgcn_readfirstlane((int)lds_addr)), "v"(g) : "memory");
 }
 
-template <int NQ, bool SAMPLE>
-__global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : KNN_WAVES) * 64) void crd_bank_knn_kernel(
+template <int D, int NQ, bool SAMPLE, int NWF = KNN_WAVES>      // NWF: waves of the full pass
+__global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : NWF) * 64) void crd_bank_knn_kernel(
     const float* __restrict__ mem1, const float* __restrict__ mem2, const int* __restrict__ labels, const int64_t* __restrict__ idx,
     int PK, const int64_t* __restrict__ batch_label, int B, int n_data, int stiles, int tstride, u64* __restrict__ gmax,
     const u64* __restrict__ thr, u64* __restrict__ cand) {
-  constexpr int NW = SAMPLE ? KNN_SAMPLE_WAVES : KNN_WAVES;
+  constexpr int NW = SAMPLE ? KNN_SAMPLE_WAVES : NWF;
+  constexpr int NG = D / 32;          // feature groups per tile
+  constexpr int SIM_RS = D + 1;       // dwords per staged query row (odd: the 32 lanes of a ds_read_b32 group hit 32 different banks)
+  constexpr int QL = D / 4;           // lanes per query row while staging (16-byte pieces)
+  constexpr int NPART = D / 64;       // 16-lane DPP rows per query row: the parts of |q|^2
+  static_assert(NG >= 2, "the pipeline keeps two groups of a tile in flight");
   typedef __attribute__((address_space(3))) unsigned char lds_uchar;
   extern __shared__ __attribute__((aligned(16))) float sim_lds[];
   float* Qs = sim_lds;                                   // [NQ * 32][SIM_RS]
@@ -385,7 +422,7 @@ __global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : KNN_WAVES) * 64) void 
   float* Rq = sim_lds + RQ0 + wv * RQW;                  // this wave's KNN_NBUF quarter tiles [32 rows][32 features], 16-B chunks swizzled
   float* rnl = sim_lds + AUX0 + wv * AUXW;               // its 32 row norms | 2 x 64 row labels (tile parity; a 64-lane DMA each)
   int* rli = reinterpret_cast<int*>(rnl) + 32;
-  float* qpart = sim_lds + AUX0 + NW * AUXW;             // [NQ * 32][2] halves of |q|^2
+  float* qpart = sim_lds + AUX0 + NW * AUXW;             // [NQ * 32][NPART] parts of |q|^2 (128: the two halves)
   const unsigned lds0 = (unsigned)(size_t)(lds_uchar*)sim_lds;
   const unsigned rq_lds = lds0 + (RQ0 + wv * RQW) * 4, rli_lds = lds0 + (AUX0 + wv * AUXW + 32) * 4;
   const int bank = blockIdx.y;
@@ -393,7 +430,7 @@ __global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : KNN_WAVES) * 64) void 
   const float* mem = bank ? mem2 : mem1;
   const int ntiles = (n_data + 31) / 32;
   const int stride = SAMPLE ? ntiles : gridDim.x * NW;      // (a sample wave has one tile)
-  // Quarter group (tile, q) = 4 DMA instructions of 8 rows x 128 B (+ the 32 row labels in front of quarter 0): lane l carries
+  // Group (tile, q) - at 128 a quarter tile - = 4 DMA instructions of 8 rows x 128 B, whatever D (+ the 32 row labels in front of group 0): lane l carries
   // chunk position l & 7 of row 8e + (l >> 3); the LDS image is linear, the XOR swizzle of the 16-byte chunks is applied to the
   // SOURCE (chunk p of row r holds features 4 (p ^ ((r >> 1) & 7)) ..): the 32 lanes of a matrix operand read hit 16 banks
   const int drow = lane >> 3, dchunk = ((lane & 7) ^ ((drow >> 1) & 3)) * 4;      // ((8e + drow) >> 1) & 7 = 4 (e & 1) + (drow >> 1)
@@ -415,24 +452,25 @@ __global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : KNN_WAVES) * 64) void 
     issue(t, 0, 0, 0);
     issue(t, 1, 1, 0);
   }
-  {   // the queries = the bank rows of the samples themselves, idx[b][0]: NQ * 32 rows of 32 16-byte pieces, all loads of a
-      // thread in flight together; a half-wave holds one row, its |q|^2 comes from the two 16-lane DPP rows
-    constexpr int NE = NQ * 32 * 32 / (NW * 64);
+  {   // the queries = the bank rows of the samples themselves, idx[b][0]: NQ * 32 rows of QL 16-byte pieces, all loads of a
+      // thread in flight together; QL lanes (128: a half-wave) hold one row, its |q|^2 comes from their 16-lane DPP rows
+    constexpr int NE = NQ * 32 * QL / (NW * 64);
+    static_assert(NE >= 1 && NE * (NW * 64) == NQ * 32 * QL, "the block stages the query image in whole rounds");
     f32x4 qv[NE];
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
-      const int pc = e * (NW * 64) + threadIdx.x, qi = q0 + (pc >> 5);
+      const int pc = e * (NW * 64) + threadIdx.x, qi = q0 + pc / QL;
       qv[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (qi < B) qv[e] = *reinterpret_cast<const f32x4*>(mem + idx[(size_t)qi * PK] * D + (pc & 31) * 4);
+      if (qi < B) qv[e] = *reinterpret_cast<const f32x4*>(mem + idx[(size_t)qi * PK] * D + (pc % QL) * 4);
     }
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
-      const int pc = e * (NW * 64) + threadIdx.x, ql_ = pc >> 5;
+      const int pc = e * (NW * 64) + threadIdx.x, ql_ = pc / QL;
       float ps = 0.f;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) { Qs[ql_ * SIM_RS + (pc & 31) * 4 + k] = qv[e][k]; ps += qv[e][k] * qv[e][k]; }
+      for (int k = 0; k < 4; ++k) { Qs[ql_ * SIM_RS + (pc % QL) * 4 + k] = qv[e][k]; ps += qv[e][k] * qv[e][k]; }
       ps = row16_sum_hi(ps);
-      if ((lane & 15) == 15) qpart[ql_ * 2 + ((lane >> 4) & 1)] = ps;
+      if ((lane & 15) == 15) qpart[ql_ * NPART + ((lane >> 4) & (NPART - 1))] = ps;
     }
   }
   __syncthreads();
@@ -443,7 +481,10 @@ __global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : KNN_WAVES) * 64) void 
 #pragma unroll
   for (int nq = 0; nq < NQ; ++nq) {
     const int qi = q0 + nq * 32 + j;
-    qn[nq] = qi < B ? sqrtf(qpart[(nq * 32 + j) * 2] + qpart[(nq * 32 + j) * 2 + 1]) : 0.f;
+    const float* qp = qpart + (nq * 32 + j) * NPART;      // the parts in order (128: p0 + p1)
+    if constexpr (NPART == 1) qn[nq] = qi < B ? sqrtf(qp[0]) : 0.f;
+    else if constexpr (NPART == 2) qn[nq] = qi < B ? sqrtf(qp[0] + qp[1]) : 0.f;
+    else qn[nq] = qi < B ? sqrtf(((qp[0] + qp[1]) + qp[2]) + qp[3]) : 0.f;
     ql[nq] = qi < B ? (int)batch_label[qi] : -2;
     tk[nq] = (!SAMPLE && qi < B) ? thr[bank * B + qi] : 0;
     tv[nq] = tk[nq] ? knn_value(tk[nq]) : -INFINITY;
@@ -460,15 +501,27 @@ __global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : KNN_WAVES) * 64) void 
       for (int r = 0; r < 16; ++r) acc[nq][r] = 0.f;
     float nn = 0.f;       // |row j|^2 over the features of parity kk: the matrix operands themselves
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      // quarter (t, q) has landed when only the group behind it is still in flight; then the group two ahead is issued into
-      // the buffer the previous quarter was read from
-      if (q == 3) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    for (int q = 0; q < NG; ++q) {
+      // group (t, q) has landed when only the group behind it is still in flight; then the group two ahead is issued into
+      // the buffer the previous group was read from: group q + 2 of this tile, else group q + 2 - NG of the next.
+      // The wait counts.  Vector-memory instructions return in issue order; a group is its 4 row DMAs, group 0 of a tile has the
+      // label DMA in front of them (5).  At the wait of step q the wave has issued, oldest first, group q and the one behind it
+      // (everything older was waited for at step q - 1; the query loads and thr / label loads of the prologue are consumed
+      // before the loop), so vmcnt = the instruction count of the group BEHIND q:
+      //   NG   step q:  in flight (oldest first)                 behind q           vmcnt
+      //   2    0        (t,0)=5 (t,1)=4                          (t,1)   = 4        4
+      //        1        (t,1)=4 (t+1,0)=5                        (t+1,0) = 5        5
+      //   4    0,1,2    (t,q) (t,q+1)=4                          (t,q+1) = 4        4
+      //        3        (t,3)=4 (t+1,0)=5                        (t+1,0) = 5        5
+      //   8    0..6     (t,q) (t,q+1)=4                          (t,q+1) = 4        4
+      //        7        (t,7)=4 (t+1,0)=5                        (t+1,0) = 5        5
+      // i.e. 5 at the last group of a tile, 4 elsewhere, at every NG >= 2.
+      if (q == NG - 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       {
         const int b2 = bufc + 2 >= KNN_NBUF ? bufc + 2 - KNN_NBUF : bufc + 2;
-        if (q < 2) issue(t, q + 2, b2, par);
-        else issue(t + stride, q - 2, b2, par ^ 1);
+        if (q + 2 < NG) issue(t, q + 2, b2, par);
+        else issue(t + stride, q + 2 - NG, b2, par ^ 1);
       }
       const float* R = Rq + bufc * 1024 + jrow;
       // operands of 4 k-steps (8 features = two 16-byte chunks) per batch, the next batch's LDS reads in flight under this
@@ -543,7 +596,7 @@ __global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : KNN_WAVES) * 64) void 
       }
   } else {
     // the two half-waves hold disjoint rows of the same queries: fold the upper half's lists into the lower's, one list per wave
-    const int nlists = gridDim.x * KNN_WAVES;
+    const int nlists = gridDim.x * NW;
 #pragma unroll
     for (int nq = 0; nq < NQ; ++nq) {
       u64 other[TOPK_MAX];
@@ -643,19 +696,27 @@ __global__ __launch_bounds__(256) void crd_knn_merge_kernel(const u64* __restric
 // index lists.  Coalesced 512-B row reads; partial sums per (class, 256-row chunk), combined in a fixed order in
 // double: bitwise reproducible.
 constexpr int CC_ROWS = 256;
+template <int D>
 __global__ __launch_bounds__(256) void class_center_partial_kernel(const float* __restrict__ mem, const int* __restrict__ members,
                                                                    const int* __restrict__ offsets, float* __restrict__ parts,
                                                                    int nchunks) {
   const int c = blockIdx.y, chunk = blockIdx.x;
   const int lo = offsets[c] + chunk * CC_ROWS, hi = min(offsets[c + 1], lo + CC_ROWS);
-  const int f = threadIdx.x & (D - 1), rl = threadIdx.x >> 7;     // 2 row lanes x 128 features
+  constexpr int RL = 256 / D;                                     // row lanes x D features (128: 2 x 128)
+  const int f = threadIdx.x % D, rl = threadIdx.x / D;
   float s = 0.f;
-  for (int r = lo + rl; r < hi; r += 2) s += mem[(size_t)members[r] * D + f];
+  for (int r = lo + rl; r < hi; r += RL) s += mem[(size_t)members[r] * D + f];
   __shared__ float sh[256];
   sh[threadIdx.x] = s;
   __syncthreads();
-  if (threadIdx.x < D) parts[((size_t)c * nchunks + chunk) * D + f] = sh[threadIdx.x] + sh[threadIdx.x + D];
+  if (threadIdx.x < D) {
+    float t = sh[threadIdx.x];
+#pragma unroll
+    for (int q = 1; q < RL; ++q) t += sh[threadIdx.x + q * D];
+    parts[((size_t)c * nchunks + chunk) * D + f] = t;
+  }
 }
+template <int D>      // block D
 __global__ void class_center_finish_kernel(const float* __restrict__ parts, const int* __restrict__ offsets, float* __restrict__ mem,
                                            int nchunks, int n_data) {
   const int c = blockIdx.x, f = threadIdx.x;
@@ -670,7 +731,8 @@ __global__ void class_center_finish_kernel(const float* __restrict__ parts, cons
 // out1[b][j] = xs[b][j] / Z_v1, out2 = xt / Z_v2 (:378-379) and the selected PRE-update bank rows are gathered for the
 // backward (the momentum update of :382-395 happens inside the same forward call, so a later backward cannot read them
 // from the bank any more): rows2[b][j] = mem2[idx_b2[b][sel]] feeds d out_v1 / d v1, rows1 = mem1[idx[b][sel]] d out_v2 / d v2.
-// grid (ceil(S2/8), B), block 256 = 8 half-waves, one (sample, column) per half-wave.
+// grid (ceil(S2 / (1024/D)), B), block 256 = 1024/D row groups (128: 8 half-waves), one (sample, column) per group.
+template <int D>
 __global__ __launch_bounds__(256) void crd_outputs_kernel(const float* __restrict__ xs, const float* __restrict__ xt,
                                                           const int* __restrict__ sel, const int64_t* __restrict__ idx,
                                                           const int64_t* __restrict__ idx_b2,
@@ -678,8 +740,9 @@ __global__ __launch_bounds__(256) void crd_outputs_kernel(const float* __restric
                                                           const float* __restrict__ params, float* __restrict__ out1,
                                                           float* __restrict__ out2, float* __restrict__ rows1,
                                                           float* __restrict__ rows2, int PK, int S2) {
-  const int b = blockIdx.y, hw = threadIdx.x >> 5, l = threadIdx.x & 31;
-  const int j = blockIdx.x * 8 + hw;
+  constexpr int G = D / 4;
+  const int b = blockIdx.y, hw = threadIdx.x / G, l = threadIdx.x % G;
+  const int j = blockIdx.x * (256 / G) + hw;
   if (j >= S2) return;
   const size_t o = (size_t)b * S2 + j;
   const int col = sel[o];
@@ -694,32 +757,34 @@ __global__ __launch_bounds__(256) void crd_outputs_kernel(const float* __restric
 
 // dv1[b] = sum_j g1[b][j] out1[b][j] / T * rows2[b][j][:], dv2[b] = sum_j g2[b][j] out2[b][j] / T * rows1[b][j][:]
 // (out = exp(row . v / T) / Z with Z a constant: memory_new.py:270-278,378-379).  One block per (sample, side), fixed
-// summation order (8 half-waves stride the columns, then a fixed-order LDS combine).
+// summation order (the 1024/D row groups - 128: 8 half-waves - stride the columns, then a fixed-order LDS combine).
+template <int D>
 __global__ __launch_bounds__(256) void crd_outputs_bwd_kernel(const float* __restrict__ g1, const float* __restrict__ g2,
                                                               const float* __restrict__ out1, const float* __restrict__ out2,
                                                               const float* __restrict__ rows1, const float* __restrict__ rows2,
                                                               float invT, float* __restrict__ dv1, float* __restrict__ dv2,
                                                               int S2) {
-  const int b = blockIdx.x, side = blockIdx.y, hw = threadIdx.x >> 5, l = threadIdx.x & 31;
+  constexpr int G = D / 4, NGRP = 256 / G;
+  const int b = blockIdx.x, side = blockIdx.y, hw = threadIdx.x / G, l = threadIdx.x % G;
   const float* g = side ? g2 : g1;
   const float* out = side ? out2 : out1;
   const float* rows = side ? rows1 : rows2;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int j = hw; j < S2; j += 8) {
+  for (int j = hw; j < S2; j += NGRP) {
     const size_t o = (size_t)b * S2 + j;
     const float c = (g ? g[o] : 0.f) * out[o] * invT;
     const f32x4 r = *reinterpret_cast<const f32x4*>(rows + o * D + l * 4);
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[k] += c * r[k];
   }
-  __shared__ float sh[8][D];
+  __shared__ float sh[NGRP][D];
 #pragma unroll
   for (int k = 0; k < 4; ++k) sh[hw][l * 4 + k] = acc[k];
   __syncthreads();
   if (threadIdx.x < D) {
     float t = 0.f;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) t += sh[q][threadIdx.x];
+    for (int q = 0; q < NGRP; ++q) t += sh[q][threadIdx.x];
     (side ? dv2 : dv1)[(size_t)b * D + threadIdx.x] = t;
   }
 }
@@ -828,7 +893,16 @@ __global__ __launch_bounds__(64) void crd_scan_neg_finish_kernel(const float* __
 }
 }  // namespace
 
-// workspace: list keys [2][B][TOPK_MAX][nlists] u64 | group maxima [2][B][2 * stiles] | thr [2][B]  (B <= 64 per pass)
+// run `stmt` with the constant DW = feat_dim (64, 128 or 256; the caller has checked crd_width_ok)
+#define PH_CRD_DISPATCH(feat_dim, stmt)                      \
+  do {                                                       \
+    if ((feat_dim) == 64) { constexpr int DW = 64; stmt; }   \
+    else if ((feat_dim) == 128) { constexpr int DW = 128; stmt; } \
+    else { constexpr int DW = 256; stmt; }                   \
+  } while (0)
+
+// workspace: list keys [2][B][TOPK_MAX][nlists] u64 | group maxima [2][B][2 * stiles] | thr [2][B]  (B <= 64 per pass; sized for
+// eight lists per workgroup, the four-wave form of width 256 uses half of them)
 static inline int knn_gx(int n_data) {
   const int g = cdiv(cdiv(n_data, 32), KNN_WAVES);
   return g < KNN_MAX_GX ? g : KNN_MAX_GX;      // one workgroup per CU over the two banks; a wave walks its tiles
@@ -845,11 +919,11 @@ size_t ph_crd_bank_topk_workspace_bytes(int B, int n_data) {
 int ph_crd_bank_topk(const float* mem1, const float* mem2, const int* labels, const int64_t* idx, int PK,
                      const int64_t* batch_label, int B, int n_data, int num_pos, int feat_dim, int64_t* nb1,
                      int64_t* nb2, float* sim1, float* sim2, void* workspace, hipStream_t st) {
-  if (feat_dim != D || num_pos < 1 || num_pos > TOPK_MAX || !workspace || B < 1 || n_data < 1) return PH_EINVAL;
+  if (!crd_width_ok(feat_dim) || num_pos < 1 || num_pos > TOPK_MAX || !workspace || B < 1 || n_data < 1) return PH_EINVAL;
   if (B > KNN_MAX_B) {
     // a lane selects for one query per 32-query block and two blocks fill its registers (accumulators + lists): larger batches
     // (the reference has no limit; a replica batch of 256 is the north-star size) run in chunks of 64 queries through the same
-    // workspace, in stream order - the matrix work is the same, only the 67 MB bank is read once per chunk
+    // workspace, in stream order - the matrix work is the same, only the bank (2 x n_data x 4 D bytes) is read once per chunk
     for (int c0 = 0; c0 < B; c0 += KNN_MAX_B) {
       const int bc = B - c0 < KNN_MAX_B ? B - c0 : KNN_MAX_B;
       const int rc = ph_crd_bank_topk(mem1, mem2, labels, idx + (size_t)c0 * PK, PK, batch_label + c0, bc, n_data, num_pos, feat_dim,
@@ -859,34 +933,45 @@ int ph_crd_bank_topk(const float* mem1, const float* mem2, const int* labels, co
     }
     return PH_OK;
   }
-  const int gx = knn_gx(n_data), nlists = gx * KNN_WAVES, stiles = knn_stiles(n_data), tstride = cdiv(n_data, 32) / stiles;
+  const int nq = cdiv(B, 32);      // <= 2 (chunked above)
+  // waves of the full pass: four under the 64-query image of width 256 (knn_lds_bytes; the dispatch below), eight otherwise
+  const int nwf = feat_dim == 256 && nq == 2 ? 4 : KNN_WAVES;
+  const int gx = knn_gx(n_data), nlists = gx * nwf, stiles = knn_stiles(n_data), tstride = cdiv(n_data, 32) / stiles;
   u64* cand = reinterpret_cast<u64*>(workspace);
   u64* gmax = cand + (size_t)2 * B * TOPK_MAX * nlists;
   u64* thr = gmax + (size_t)2 * B * 2 * stiles;
   void* tok = nullptr;
   if (ph_prof_on())   // algorithmic bytes: every row of both banks once + the row labels + the 2 x B x num_pos results
-    ph_prof_begin(PH_CLS_CRD_TOPK, 2.0 * n_data * D * 4 + 4.0 * n_data + 2.0 * B * num_pos * 12, st, &tok);
-  const int nq = cdiv(B, 32);      // <= 2 (chunked above)
-#define PH_KNN_LAUNCH(N, SAMPLE, GX, GZ)                                                                                        \
+    ph_prof_begin(PH_CLS_CRD_TOPK, 2.0 * n_data * feat_dim * 4 + 4.0 * n_data + 2.0 * B * num_pos * 12, st, &tok);
+#define PH_KNN_LAUNCH(DW, N, SAMPLE, GX, GZ) PH_KNN_LAUNCH_W(DW, N, SAMPLE, KNN_WAVES, GX, GZ)
+#define PH_KNN_LAUNCH_W(DW, N, SAMPLE, NWF, GX, GZ)                                                                             \
   do {                                                                                                                      \
-    constexpr int NW = SAMPLE ? KNN_SAMPLE_WAVES : KNN_WAVES;                                                               \
-    const size_t lds = (size_t)(N * 32 * SIM_RS + NW * (KNN_NBUF * 1024 + 32 + 128) + N * 64) * sizeof(float);              \
+    constexpr int NW = SAMPLE ? KNN_SAMPLE_WAVES : NWF;                                                                     \
+    constexpr size_t lds = knn_lds_bytes(DW, N, NW);                                                                        \
+    static_assert(lds <= 160 * 1024, "LDS of a CU");                                                                        \
     static bool done = false;                                                                                               \
     if (!done) {                                                                                                            \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(crd_bank_knn_kernel<N, SAMPLE>),                                \
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(crd_bank_knn_kernel<DW, N, SAMPLE, NWF>),                       \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)                          \
         return PH_ELAUNCH;                                                                                                  \
       done = true;                                                                                                          \
     }                                                                                                                       \
-    hipLaunchKernelGGL((crd_bank_knn_kernel<N, SAMPLE>), dim3(GX, 2, GZ), dim3(NW * 64), lds, st, mem1, mem2, labels, idx, PK, \
-                       batch_label, B, n_data, stiles, tstride, gmax, thr, cand);                                           \
+    hipLaunchKernelGGL((crd_bank_knn_kernel<DW, N, SAMPLE, NWF>), dim3(GX, 2, GZ), dim3(NW * 64), lds, st, mem1, mem2, labels, idx, \
+                       PK, batch_label, B, n_data, stiles, tstride, gmax, thr, cand);                                       \
   } while (0)
-  PH_KNN_LAUNCH(1, true, cdiv(stiles, KNN_SAMPLE_WAVES), nq);      // one 32-query block per workgroup (grid z)
+  // one 32-query block per workgroup (grid z)
+  if (feat_dim == 64) PH_KNN_LAUNCH(64, 1, true, cdiv(stiles, KNN_SAMPLE_WAVES), nq);
+  else if (feat_dim == 128) PH_KNN_LAUNCH(128, 1, true, cdiv(stiles, KNN_SAMPLE_WAVES), nq);
+  else PH_KNN_LAUNCH(256, 1, true, cdiv(stiles, KNN_SAMPLE_WAVES), nq);
   PH_LAUNCH_CHECK();
   hipLaunchKernelGGL(crd_knn_thr_kernel, dim3(B, 2), dim3(256), 0, st, gmax, 2 * stiles, thr);
   PH_LAUNCH_CHECK();
-  if (nq == 1) PH_KNN_LAUNCH(1, false, gx, 1); else PH_KNN_LAUNCH(2, false, gx, 1);
+  if (feat_dim == 64) { if (nq == 1) PH_KNN_LAUNCH(64, 1, false, gx, 1); else PH_KNN_LAUNCH(64, 2, false, gx, 1); }
+  else if (feat_dim == 128) { if (nq == 1) PH_KNN_LAUNCH(128, 1, false, gx, 1); else PH_KNN_LAUNCH(128, 2, false, gx, 1); }
+  else if (nq == 1) PH_KNN_LAUNCH(256, 1, false, gx, 1);
+  else PH_KNN_LAUNCH_W(256, 2, false, 4, gx, 1);      // (the four-wave form: 64 queries under one image)
 #undef PH_KNN_LAUNCH
+#undef PH_KNN_LAUNCH_W
   PH_LAUNCH_CHECK();
   hipLaunchKernelGGL(crd_knn_merge_kernel, dim3(B, 2), dim3(256), 0, st, cand, nlists, num_pos, nb1, nb2, sim1, sim2);
   ph_prof_end(tok, st);
@@ -897,12 +982,13 @@ int ph_crd_bank_topk(const float* mem1, const float* mem2, const int* labels, co
 int ph_crd_score(const float* v1, const float* v2, const int64_t* idx, const int64_t* idx_bank2, const float* mem1,
                  const float* mem2, float* out1, float* out2, float* diff, int B, int PK, int feat_dim, float T,
                  hipStream_t st) {
-  if (feat_dim != D || B < 1 || PK < 1) return PH_EINVAL;
+  if (!crd_width_ok(feat_dim) || B < 1 || PK < 1) return PH_EINVAL;
+  const int D = feat_dim;
   void* tok = nullptr;
-  if (ph_prof_on())   // algorithmic bytes: one 512-B row of each bank per (sample, column) + the three [B][P+K] outputs
+  if (ph_prof_on())   // algorithmic bytes: one row of each bank per (sample, column) + the three [B][P+K] outputs
     ph_prof_begin(PH_CLS_CRD_SCORE, 2.0 * B * PK * D * 4 + 3.0 * B * PK * 4 + 2.0 * B * D * 4, st, &tok);
-  hipLaunchKernelGGL(crd_score_kernel, dim3(cdiv(PK, 64), B), dim3(256), 0, st, v1, v2, idx,
-                     idx_bank2 ? idx_bank2 : idx, mem1, mem2, out1, out2, diff, PK, 1.f / T);
+  PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(crd_score_kernel<DW>, dim3(cdiv(PK, 64), B), dim3(256), 0, st, v1, v2, idx,
+                                               idx_bank2 ? idx_bank2 : idx, mem1, mem2, out1, out2, diff, PK, 1.f / T));
   ph_prof_end(tok, st);
   PH_LAUNCH_CHECK();
   return PH_OK;
@@ -935,7 +1021,10 @@ int ph_crd_setz(float* params, const float* sums, float count, float n_data, hip
   return PH_OK;
 }
 constexpr int LG_SPLIT_MAX = 8;
-size_t ph_crd_loss_grad_workspace_bytes(int B) { return (size_t)B * LG_SPLIT_MAX * (2 * D + 1) * sizeof(float); }
+size_t ph_crd_loss_grad_workspace_bytes_w(int B, int feat_dim) {
+  return (size_t)B * LG_SPLIT_MAX * (2 * feat_dim + 1) * sizeof(float);
+}
+size_t ph_crd_loss_grad_workspace_bytes(int B) { return ph_crd_loss_grad_workspace_bytes_w(B, 128); }
 
 static int crd_loss_grad_impl(const float* xs, const float* xt, const int* sel, const int64_t* idx, const int64_t* idx_bank2,
                               const float* posw_s, const float* posw_t, const float* mem1, const float* mem2,
@@ -961,19 +1050,20 @@ static int crd_loss_grad_impl(const float* xs, const float* xt, const int* sel, 
                               const float* posw_s, const float* posw_t, const float* mem1, const float* mem2,
                               const float* params, float* lossp, float* dv1, float* dv2, int B, int PK, int P2, int K2, int m_neg,
                               int feat_dim, float n_data, float inv_bnorm, void* workspace, hipStream_t st) {
-  if (feat_dim != D || B < 1 || P2 < 1 || K2 < 0 || P2 + K2 > PK) return PH_EINVAL;
+  if (!crd_width_ok(feat_dim) || B < 1 || P2 < 1 || K2 < 0 || P2 + K2 > PK) return PH_EINVAL;
+  const int D = feat_dim;
   int ns = workspace ? (P2 + K2) / 512 : 1;     // one workgroup per 512 columns of a sample, at most LG_SPLIT_MAX
   ns = ns < 1 ? 1 : (ns > LG_SPLIT_MAX ? LG_SPLIT_MAX : ns);
   void* tok = nullptr;
   if (ph_prof_on())   // algorithmic bytes: the selected rows of both banks + the two gradient rows per sample
     ph_prof_begin(PH_CLS_CRD_LOSSGRAD, 2.0 * B * (P2 + K2) * D * 4 + 2.0 * B * D * 4 + 2.0 * B * (P2 + K2) * 4, st, &tok);
-  hipLaunchKernelGGL(crd_loss_grad_kernel, dim3(B, ns), dim3(1024), 0, st, xs, xt, sel, idx, idx_bank2 ? idx_bank2 : idx,
-                     posw_s, posw_t, mem1, mem2, params, lossp, dv1, dv2, PK, P2, K2, m_neg, n_data, inv_bnorm,
-                     reinterpret_cast<float*>(workspace));
+  PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(crd_loss_grad_kernel<DW>, dim3(B, ns), dim3(1024), 0, st, xs, xt, sel, idx,
+                                               idx_bank2 ? idx_bank2 : idx, posw_s, posw_t, mem1, mem2, params, lossp, dv1, dv2,
+                                               PK, P2, K2, m_neg, n_data, inv_bnorm, reinterpret_cast<float*>(workspace)));
   PH_LAUNCH_CHECK();
   if (ns > 1) {
-    hipLaunchKernelGGL(crd_loss_grad_reduce_kernel, dim3(B), dim3(256), 0, st, reinterpret_cast<const float*>(workspace), lossp,
-                       dv1, dv2, ns, inv_bnorm);
+    PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(crd_loss_grad_reduce_kernel<DW>, dim3(B), dim3(2 * DW), 0, st,
+                                                 reinterpret_cast<const float*>(workspace), lossp, dv1, dv2, ns, inv_bnorm));
     PH_LAUNCH_CHECK();
   }
   ph_prof_end(tok, st);
@@ -1010,25 +1100,29 @@ int ph_crd_scan_neg(float* S1, float* S2, const int* mult, const float* params, 
 }
 int ph_crd_update(float* mem1, float* mem2, const float* v1, const float* v2, const int64_t* y, const float* params,
                   int B, int feat_dim, hipStream_t st) {
-  if (feat_dim != D || B < 1) return PH_EINVAL;
-  hipLaunchKernelGGL(crd_update_kernel, dim3(cdiv(2 * B, 4)), dim3(256), 0, st, mem1, mem2, v1, v2, y, params, B);
+  if (!crd_width_ok(feat_dim) || B < 1) return PH_EINVAL;
+  PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(crd_update_kernel<DW>, dim3(cdiv(2 * B, 4)), dim3(256), 0, st, mem1, mem2, v1, v2,
+                                               y, params, B));
   PH_LAUNCH_CHECK();
   return PH_OK;
 }
 
+size_t ph_crd_class_centers_workspace_bytes_w(int num_classes, int max_class_rows, int feat_dim) {
+  return (size_t)num_classes * (size_t)cdiv(max_class_rows > 0 ? max_class_rows : 1, CC_ROWS) * feat_dim * sizeof(float);
+}
 size_t ph_crd_class_centers_workspace_bytes(int num_classes, int max_class_rows) {
-  return (size_t)num_classes * (size_t)cdiv(max_class_rows > 0 ? max_class_rows : 1, CC_ROWS) * D * sizeof(float);
+  return ph_crd_class_centers_workspace_bytes_w(num_classes, max_class_rows, 128);
 }
 
 int ph_crd_class_centers(float* mem_ext, const int* members, const int* offsets, int num_classes, int max_class_rows,
                          int n_data, int feat_dim, void* workspace, hipStream_t st) {
-  if (feat_dim != D || !mem_ext || !members || !offsets || !workspace || num_classes < 1) return PH_EINVAL;
+  if (!crd_width_ok(feat_dim) || !mem_ext || !members || !offsets || !workspace || num_classes < 1) return PH_EINVAL;
   const int nchunks = cdiv(max_class_rows > 0 ? max_class_rows : 1, CC_ROWS);
-  hipLaunchKernelGGL(class_center_partial_kernel, dim3(nchunks, num_classes), dim3(256), 0, st, mem_ext, members, offsets,
-                     reinterpret_cast<float*>(workspace), nchunks);
+  PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(class_center_partial_kernel<DW>, dim3(nchunks, num_classes), dim3(256), 0, st,
+                                               mem_ext, members, offsets, reinterpret_cast<float*>(workspace), nchunks));
   PH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(class_center_finish_kernel, dim3(num_classes), dim3(D), 0, st, reinterpret_cast<const float*>(workspace),
-                     offsets, mem_ext, nchunks, n_data);
+  PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(class_center_finish_kernel<DW>, dim3(num_classes), dim3(DW), 0, st,
+                                               reinterpret_cast<const float*>(workspace), offsets, mem_ext, nchunks, n_data));
   PH_LAUNCH_CHECK();
   return PH_OK;
 }
@@ -1036,18 +1130,19 @@ int ph_crd_class_centers(float* mem_ext, const int* members, const int* offsets,
 int ph_crd_outputs(const float* xs, const float* xt, const int* sel, const int64_t* idx, const int64_t* idx_bank2,
                    const float* mem1, const float* mem2, const float* params, float* out1, float* out2, float* rows1,
                    float* rows2, int B, int PK, int S2, int feat_dim, hipStream_t st) {
-  if (feat_dim != D || B < 1 || S2 < 1) return PH_EINVAL;
-  hipLaunchKernelGGL(crd_outputs_kernel, dim3(cdiv(S2, 8), B), dim3(256), 0, st, xs, xt, sel, idx,
-                     idx_bank2 ? idx_bank2 : idx, mem1, mem2, params, out1, out2, rows1, rows2, PK, S2);
+  if (!crd_width_ok(feat_dim) || B < 1 || S2 < 1) return PH_EINVAL;
+  PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(crd_outputs_kernel<DW>, dim3(cdiv(S2, 1024 / DW), B), dim3(256), 0, st, xs, xt,
+                                               sel, idx, idx_bank2 ? idx_bank2 : idx, mem1, mem2, params, out1, out2, rows1,
+                                               rows2, PK, S2));
   PH_LAUNCH_CHECK();
   return PH_OK;
 }
 
 int ph_crd_outputs_bwd(const float* g1, const float* g2, const float* out1, const float* out2, const float* rows1,
                        const float* rows2, float T, float* dv1, float* dv2, int B, int S2, int feat_dim, hipStream_t st) {
-  if (feat_dim != D || B < 1 || S2 < 1) return PH_EINVAL;
-  hipLaunchKernelGGL(crd_outputs_bwd_kernel, dim3(B, 2), dim3(256), 0, st, g1, g2, out1, out2, rows1, rows2, 1.f / T, dv1,
-                     dv2, S2);
+  if (!crd_width_ok(feat_dim) || B < 1 || S2 < 1) return PH_EINVAL;
+  PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(crd_outputs_bwd_kernel<DW>, dim3(B, 2), dim3(256), 0, st, g1, g2, out1, out2,
+                                               rows1, rows2, 1.f / T, dv1, dv2, S2));
   PH_LAUNCH_CHECK();
   return PH_OK;
 }

@@ -249,24 +249,28 @@ __global__ void gk_scale2_kernel(const float* __restrict__ gram, int ng, int use
 
 // MIA-2023 GK_refine_thresh (".../train_test_path_multi_distill.py":81-128): PER-SAMPLE cosine matrix of the ng
 // gradients (sklearn cosine_similarity: zero-norm rows give 0), column sums of max(cos, 0) or of (cos > thresh).
-// One wave per sample; G is [ng][B][D] with D = 128.
-template <int NG>
+// One wave per sample; G is [ng][B][D] with D = 64, 128 or 256: D/64 floats per lane.
+template <int NG, int D>
 __global__ __launch_bounds__(256) void gk_rows_kernel(const float* __restrict__ G, int B, int use_thresh, float thresh,
                                                       float* __restrict__ all_scale) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (b >= B) return;
-  float v[NG][2];
+  constexpr int E = D / 64;
+  float v[NG][E];
 #pragma unroll
-  for (int i = 0; i < NG; ++i) {
-    v[i][0] = G[((size_t)i * B + b) * 128 + lane];
-    v[i][1] = G[((size_t)i * B + b) * 128 + 64 + lane];
-  }
+  for (int i = 0; i < NG; ++i)
+#pragma unroll
+    for (int e = 0; e < E; ++e) v[i][e] = G[((size_t)i * B + b) * D + e * 64 + lane];
   float gram[NG][NG];
 #pragma unroll
   for (int i = 0; i < NG; ++i)
 #pragma unroll
     for (int j = i; j < NG; ++j) {
-      const float s = wave_sum(v[i][0] * v[j][0] + v[i][1] * v[j][1]);
+      float p;      // (written out per width: the 128 form is the expression the kernel always had)
+      if constexpr (E == 1) p = v[i][0] * v[j][0];
+      else if constexpr (E == 2) p = v[i][0] * v[j][0] + v[i][1] * v[j][1];
+      else p = (v[i][0] * v[j][0] + v[i][1] * v[j][1]) + (v[i][2] * v[j][2] + v[i][3] * v[j][3]);
+      const float s = wave_sum(p);
       gram[i][j] = s; gram[j][i] = s;
     }
   if (lane == 0) {
@@ -321,13 +325,12 @@ __global__ void l1_sign_axpy_kernel(const float* __restrict__ w, float* __restri
 }  // namespace
 
 int ph_gk_rows(const float* G, int ng, int B, int D, int use_thresh, float thresh, float* all_scale, hipStream_t st) {
-  if (D != 128) return PH_EINVAL;
+  if ((D != 64 && D != 128 && D != 256) || (ng != 3 && ng != 5)) return PH_EINVAL;
   dim3 grid(cdiv(B, 4));
-  switch (ng) {
-    case 3: hipLaunchKernelGGL(gk_rows_kernel<3>, grid, dim3(256), 0, st, G, B, use_thresh, thresh, all_scale); break;
-    case 5: hipLaunchKernelGGL(gk_rows_kernel<5>, grid, dim3(256), 0, st, G, B, use_thresh, thresh, all_scale); break;
-    default: return PH_EINVAL;
-  }
+#define PH_GK_ROWS(NGV, DW) hipLaunchKernelGGL((gk_rows_kernel<NGV, DW>), grid, dim3(256), 0, st, G, B, use_thresh, thresh, all_scale)
+  if (ng == 3) { if (D == 64) PH_GK_ROWS(3, 64); else if (D == 128) PH_GK_ROWS(3, 128); else PH_GK_ROWS(3, 256); }
+  else { if (D == 64) PH_GK_ROWS(5, 64); else if (D == 128) PH_GK_ROWS(5, 128); else PH_GK_ROWS(5, 256); }
+#undef PH_GK_ROWS
   PH_LAUNCH_CHECK();
   return PH_OK;
 }

@@ -210,6 +210,8 @@ class FusedMia2023LossFn(torch.autograd.Function):
         st = stream()
         feat = ops._f32(feat).contiguous()
         B, D = feat.shape
+        if D not in (64, 128, 256):      # before anything runs: the CRD chains below update the banks
+            raise ValueError("MIA-2023 loss head: feature rows of width %d; ph_gk_rows is built for the widths [64, 128, 256]" % D)
         dev = feat.device
         W2, b2 = model.fc_new2.weight, model.fc_new2.bias
         Cc = W2.shape[0]

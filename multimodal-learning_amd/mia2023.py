@@ -64,6 +64,8 @@ def GK_refine_thresh(opt, optimizer, main_loss, feat_s, loss_t_list, batch_norm_
     ng = len(grads)
     G = torch.stack(grads).contiguous()                       # [ng, B, D]
     B, D = G.shape[1], G.shape[2]
+    if D not in (64, 128, 256):
+        raise ValueError("GK_refine_thresh: feature rows of width %d; ph_gk_rows is built for the widths [64, 128, 256]" % D)
     all_scale = torch.empty(B, ng, device=G.device, dtype=torch.float32)
     check(lib().ph_gk_rows(ptr(G), ng, B, D, 1 if opt.use_grads_thresh == "True" else 0, float(opt.grads_thresh),
                            ptr(all_scale), stream()), "ph_gk_rows")

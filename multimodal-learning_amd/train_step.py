@@ -443,6 +443,10 @@ class DistillStep:
             raise ValueError("variant must be 'miccai2022', 'mia2022' or 'mia2023'")
         self.variant = variant
         _validate_opt(opt, "DistillStep")
+        if variant == "mia2023" and getattr(opt, "path_dim", 128) not in (64, 128, 256):
+            # the per-sample GK-Refine (ph_gk_rows) runs on the student's feature rows, path_dim wide
+            raise ValueError("DistillStep, variant 'mia2023': path_dim %r; the per-sample GK-Refine kernel is built for the "
+                             "widths [64, 128, 256]" % opt.path_dim)
         self._mo_state = None     # momentum GK-Refine weights (mia2022), updated in place on the device
         self.sampler = None       # optional ContrastIndexSampler: draws sample_idx when the batch carries None
         self._mo_init = None
