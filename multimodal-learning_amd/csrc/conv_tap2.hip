@@ -33,34 +33,10 @@ namespace {
 __device__ unsigned long long ph_tap_trace[PH_TRACE_WGS * 12];
 #endif
 
-__device__ const u32x4 ph_zero16[4] = {};   // source of out-of-image halo pixels
-// ... when the input's BatchNorm + ReLU is applied in LDS (PhTapConv::in_scale): padding must be zero AFTER that map, for
-// any scale / shift.  Quiet NaNs do it: fma(NaN, s, b) = NaN and the ReLU's v_max_f32(NaN, 0) returns the number, 0.
-__device__ const u32x4 ph_nan16[4] = {{0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}, {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u},
-                                      {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}, {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}};
 
-// relu(x * s + h) on the 8 bf16 values of one 16-byte chunk (channel 2q in the low half of dword q), result rounded to
-// bf16 like the stand-alone bn_apply pass stores it
-__device__ __forceinline__ u32x4 bn_relu_chunk(u32x4 v, const f32x4& sA, const f32x4& sB, const f32x4& hA, const f32x4& hB) {
-  u32x4 o;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float x0 = __builtin_bit_cast(float, v[q] << 16), x1 = __builtin_bit_cast(float, v[q] & 0xffff0000u);
-    const float s0 = q < 2 ? sA[2 * q] : sB[2 * q - 4], s1 = q < 2 ? sA[2 * q + 1] : sB[2 * q - 3];
-    const float h0 = q < 2 ? hA[2 * q] : hB[2 * q - 4], h1 = q < 2 ? hA[2 * q + 1] : hB[2 * q - 3];
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
-    bf2 r;
-    r[0] = (bf16)fmaxf(x0 * s0 + h0, 0.f);
-    r[1] = (bf16)fmaxf(x1 * s1 + h1, 0.f);
-    o[q] = __builtin_bit_cast(unsigned, r);
-  }
-  return o;
-}
-
-typedef __attribute__((address_space(3))) unsigned char lds_uchar;
-
-// one LDS-DMA wave-instruction: lane l copies 16 B from its global address g to LDS byte lds_addr + 16*l
-__device__ __forceinline__ void lds_dma16(const void* g, unsigned lds_addr) {
+// tap2's LDS-DMA (tap_common.h: lds_dma16) passes lds_addr to the s_mov as it is, without the readfirstlane of the common form:
+// with it the compiler schedules this file's kernels differently.  Carries the PH_ABL_NODMA ablation of this file's trace builds.
+__device__ __forceinline__ void lds_dma16_asis(const void* g, unsigned lds_addr) {
 #ifdef PH_ABL_NODMA   // timing ablation only (results are garbage)
   asm volatile("" : : "s"(lds_addr), "v"(g) : "memory");
 #else
@@ -73,8 +49,6 @@ __device__ __forceinline__ void lds_dma4(const void* g, unsigned lds_addr) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" : : "s"(lds_addr), "v"(g) : "memory");
 #endif
 }
-#define PH_WAIT_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define PH_BARRIER() asm volatile("s_barrier" ::: "memory")
 
 // Configurations: <WM, WN, FM, RES>.  Wave tile (32*FM) pixels x 64 channels, workgroup tile 16 x 16 pixels x (64*WN)
 // channels.  RES = false: weights stream through a ring of 4 taps (any Cin).  RES = true (Cin = Cout = 64, ResNet
@@ -459,14 +433,14 @@ __global__ __launch_bounds__(256) void tapconv2_kernel(PhTapConv p) {
 #pragma unroll
     for (int e = 0; e < C::NHE; ++e)
       if (wave + 4 * e < C::NHD)
-        lds_dma16(((hm_cur >> e) & 1) ? hb + h_off[e] : zero_src, lds0 + (wave + 4 * e) * 1024);
+        lds_dma16_asis(((hm_cur >> e) & 1) ? hb + h_off[e] : zero_src, lds0 + (wave + 4 * e) * 1024);
 #pragma unroll
     for (int j = 0; j < (RES ? NTAPS : C::RING - 1); ++j) {
       const unsigned char* wb = MASKED ? wq_addr() : w_base(tcur.n0, 0, 0, j);
       if constexpr (MASKED) wq_next();
 #pragma unroll
       for (int e = 0; e < C::NBE; ++e)
-        lds_dma16(wb + wb_off[e], lds0 + B_BASE + j * C::TAPB + (wave * C::NBE + e) * 1024);
+        lds_dma16_asis(wb + wb_off[e], lds0 + B_BASE + j * C::TAPB + (wave * C::NBE + e) * 1024);
     }
   }
   zero_acc();
@@ -508,7 +482,6 @@ __global__ __launch_bounds__(256) void tapconv2_kernel(PhTapConv p) {
 #else
 #define PH_LDA(AA, I, KS) (*reinterpret_cast<const bf16x8*>(smem + ((AA)[I] ^ ((KS) << 5))))
 #endif
-#define PH_SB() __builtin_amdgcn_sched_barrier(0)
 #define PH_KSTEP(CB, NB, KS, F0, F1, F2, F3, F4, F5, F6, F7)             \
   PH_MM(CB, 0, 0); fa[NB][0] = PH_LDA(aaddr, 0, KS); F0; PH_SB();         \
   PH_MM(CB, 0, 1); fb[NB][0] = PH_LDA(bxs, 0, KS); F1; PH_SB();           \
@@ -523,7 +496,6 @@ __global__ __launch_bounds__(256) void tapconv2_kernel(PhTapConv p) {
   PH_MM(CB, 0, 1); fb[NB][0] = PH_LDA(bxs, 0, KS); F1; PH_SB();           \
   PH_MM(CB, 1, 0); fb[NB][1] = PH_LDA(bxs, 1, KS); F2; PH_SB();           \
   PH_MM(CB, 1, 1); fa[NB][1] = PH_LDA(aaddr, 1, KS); F3; PH_SB()
-#define PH_NOP_ ((void)0)
   tap_addr(0, 0, 0);
 #pragma unroll
   for (int i = 0; i < FM; ++i) fa[0][i] = PH_LDA(aaddr, i, 0);
@@ -574,11 +546,11 @@ __global__ __launch_bounds__(256) void tapconv2_kernel(PhTapConv p) {
         constexpr int HT = MASKED ? 3 : C::HALO_TAPS, HPP = MASKED ? 4 : 2;   // halo: grid taps 0..HT-1, HPP pieces each
         const unsigned wdst = lds0 + B_BASE + ((gt + 3) & 3) * C::TAPB + wave * C::NBE * 1024;
         const unsigned hdst = lds0 + (acur ^ 1) * C::A_BYTES + wave * 1024;
-#define PH_DMA_B(E) lds_dma16(wb + wb_off[E], wdst + (E) * 1024)
+#define PH_DMA_B(E) lds_dma16_asis(wb + wb_off[E], wdst + (E) * 1024)
 #define PH_DMA_H(E)                                                                                         \
   do {                                                                                                      \
     if ((E) < C::NHE && wave + 4 * (E) < C::NHD)                                                            \
-      lds_dma16(((hm >> (E)) & 1) ? hb + h_off[(E) < C::NHE ? (E) : 0] : zero_src, hdst + (E) * 4096);      \
+      lds_dma16_asis(((hm >> (E)) & 1) ? hb + h_off[(E) < C::NHE ? (E) : 0] : zero_src, hdst + (E) * 4096); \
   } while (0)
         const int toff_n = ((t + 1) % NTAPS) / 3 * HPW + ((t + 1) % NTAPS) % 3;
         const int abuf_n = t + 1 == NTAPS ? (acur ^ 1) : acur;
@@ -597,24 +569,24 @@ __global__ __launch_bounds__(256) void tapconv2_kernel(PhTapConv p) {
           }
         } else if constexpr (FM == 4) {
           // ---- 32 MFMAs; the tap's DMA pieces ride between them
-          PH_KSTEP(0, 1, 1, PH_NOP_, PH_DMA_B(0), PH_NOP_, PH_NOP_, PH_DMA_B(1), PH_NOP_, PH_NOP_, PH_DMA_B(2));
-          PH_KSTEP(1, 0, 2, PH_NOP_, PH_NOP_, PH_DMA_B(3), PH_NOP_, PH_NOP_,
-                   if (t < HT) PH_DMA_H(HPP * t), PH_NOP_, if (t < HT) PH_DMA_H(HPP * t + 1));
-          PH_KSTEP(0, 1, 3, PH_NOP_, if (MASKED && t < HT) PH_DMA_H(HPP * t + 2), PH_NOP_, PH_NOP_,
-                   if (MASKED && t < HT) PH_DMA_H(HPP * t + 3), PH_NOP_, PH_NOP_, PH_NOP_);
+          PH_KSTEP(0, 1, 1, PH_NOP, PH_DMA_B(0), PH_NOP, PH_NOP, PH_DMA_B(1), PH_NOP, PH_NOP, PH_DMA_B(2));
+          PH_KSTEP(1, 0, 2, PH_NOP, PH_NOP, PH_DMA_B(3), PH_NOP, PH_NOP,
+                   if (t < HT) PH_DMA_H(HPP * t), PH_NOP, if (t < HT) PH_DMA_H(HPP * t + 1));
+          PH_KSTEP(0, 1, 3, PH_NOP, if (MASKED && t < HT) PH_DMA_H(HPP * t + 2), PH_NOP, PH_NOP,
+                   if (MASKED && t < HT) PH_DMA_H(HPP * t + 3), PH_NOP, PH_NOP, PH_NOP);
           tap_addr(toff_n, abuf_n, (gt + 1) & 3);
-          PH_KSTEP(1, 0, 0, PH_NOP_, PH_NOP_, PH_NOP_, PH_NOP_, PH_NOP_, PH_NOP_, PH_NOP_, PH_NOP_);
+          PH_KSTEP(1, 0, 0, PH_NOP, PH_NOP, PH_NOP, PH_NOP, PH_NOP, PH_NOP, PH_NOP, PH_NOP);
         } else {
           // ---- 16 MFMAs (resident weights: ring slot = tap)
-          PH_KSTEP2(0, 1, 1, PH_NOP_, PH_NOP_, PH_NOP_, if (t < C::HALO_TAPS) PH_DMA_H(2 * t));
-          PH_KSTEP2(1, 0, 2, PH_NOP_, PH_NOP_, PH_NOP_, if (t < C::HALO_TAPS) PH_DMA_H(2 * t + 1));
-          PH_KSTEP2(0, 1, 3, PH_NOP_, PH_NOP_, PH_NOP_, PH_NOP_);
+          PH_KSTEP2(0, 1, 1, PH_NOP, PH_NOP, PH_NOP, if (t < C::HALO_TAPS) PH_DMA_H(2 * t));
+          PH_KSTEP2(1, 0, 2, PH_NOP, PH_NOP, PH_NOP, if (t < C::HALO_TAPS) PH_DMA_H(2 * t + 1));
+          PH_KSTEP2(0, 1, 3, PH_NOP, PH_NOP, PH_NOP, PH_NOP);
           if (t == NTAPS - 2) {   // the next tile's halo must be visible before the last tap reads its first fragments
             PH_WAIT_VMCNT(0);
             PH_BARRIER();
           }
           tap_addr(toff_n, abuf_n, (t + 1) % NTAPS);
-          PH_KSTEP2(1, 0, 0, PH_NOP_, PH_NOP_, PH_NOP_, PH_NOP_);
+          PH_KSTEP2(1, 0, 0, PH_NOP, PH_NOP, PH_NOP, PH_NOP);
         }
         if constexpr (!RES) {
           // ---- tap end: the weight pieces of stream tap gt+2 (and a halo that is due) have landed once at most the
@@ -830,7 +802,7 @@ __global__ __launch_bounds__(512) void tapconv2_l1_kernel(PhTapConv p) {
   auto halo_piece = [&](int e) {   // e = 0 .. NHE-1 in order
     if (wm + 4 * e < C::NHD) {
       const bool ok = ((h_rowok >> (h_hr & 31)) & (h_colok >> h_hc) & 1u) != 0 && h_hr < C::HPH;
-      lds_dma16(ok ? h_hb + h_o : zero_src, a_lds + (wm + 4 * e) * 1024);
+      lds_dma16_asis(ok ? h_hb + h_o : zero_src, a_lds + (wm + 4 * e) * 1024);
     }
     h_hc += 14; h_hr += 1; h_o += hd_row;
     if (h_hc >= HPW) { h_hc -= HPW; h_hr += 1; h_o += hd_wrap; }
@@ -1014,7 +986,7 @@ __global__ __launch_bounds__(512) void tapconv2_l1_kernel(PhTapConv p) {
       const int rp = (q & 7) * 4 + (lane >> 4), u = (lane & 15) ^ (rp & PH_SWZ_MASK);
       const int slab = __builtin_amdgcn_readlane(tap_tab, tap) >> 16;
       const unsigned char* wb = reinterpret_cast<const unsigned char*>(wbase + (size_t)slab * p.Cout * p.Cin);
-      lds_dma16(wb + ((2 * rp + (u >> 3)) * p.Cin + (u & 7) * 8) * 2, lds0 + B_BASE + q * 1024);
+      lds_dma16_asis(wb + ((2 * rp + (u >> 3)) * p.Cin + (u & 7) * 8) * 2, lds0 + B_BASE + q * 1024);
     }
   }
   // tile contexts run one ahead of the store phase: each tile is decoded once
@@ -1176,9 +1148,7 @@ int launch_l1(const PhTapConv& p, hipStream_t st) {
       return PH_ELAUNCH;
     attr_done = true;
   }
-  const int total = cdiv(p.OHt, C::TH) * cdiv(p.OWt, C::TW) * p.B;
-  const int resident = ph_num_cus();
-  dim3 grid(total < resident ? total : resident);
+  dim3 grid(ph_persistent_wgs<C>(p));
   void* tok = nullptr;
   if (ph_prof_on())
     ph_prof_begin2(p.in_scale ? PH_CLS_TAPCONV2_RES_FUSEDIN : PH_CLS_TAPCONV2_RES, 2.0 * p.B * p.OHt * p.OWt * (double)p.Cout * p.ntaps * p.Cin, ph_tapconv_bytes(p, 1, 2), st, &tok);
@@ -1199,9 +1169,7 @@ int launch2(const PhTapConv& p, hipStream_t st) {
       return PH_ELAUNCH;
     attr_done = true;
   }
-  const int total = cdiv(p.OHt, C::TH) * cdiv(p.OWt, C::TW) * (p.Cout / C::BNT) * p.B;
-  const int resident = ph_num_cus();   // one workgroup per CU (LDS)
-  dim3 grid(total < resident ? total : resident);
+  dim3 grid(ph_persistent_wgs<C>(p));
   void* tok = nullptr;
   if (ph_prof_on()) {   // algorithmic FLOPs: 2 * positions * Cout * ntaps * Cin (masked: the LIVE taps of all groups)
     double taps = p.ntaps;
@@ -1269,10 +1237,7 @@ int ph_tapconv2_tile_h(const PhTapConv* p, int S, int prec) {
 
 // number of BatchNorm partial rows a launch writes = its (persistent) workgroups
 int ph_tapconv2_stat_parts(const PhTapConv* p) {
-  const int bnt = (p->Cout % 128 == 0) ? 128 : 64;
-  const int total = cdiv(p->OHt, 16) * cdiv(p->OWt, 16) * (p->Cout / bnt) * p->B;
-  const int resident = ph_num_cus();
-  return total < resident ? total : resident;
+  return p->Cout % 128 == 0 ? ph_persistent_wgs<Tap2Cfg<2, 2, 4, false>>(*p) : ph_persistent_wgs<L1Cfg>(*p);
 }
 
 // the three forms of this file; which one a descriptor takes is ph_tapconv_select's answer (conv_select.hip)

@@ -25,17 +25,9 @@
 
 namespace {
 
-__device__ const u32x4 ph3_zero16[4] = {};
-__device__ const u32x4 ph3_nan16[4] = {{0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}, {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u},
-                                       {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}, {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}};
-
-typedef __attribute__((address_space(3))) unsigned char lds_uchar;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
-__device__ __forceinline__ void lds_dma16(const void* g, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(__builtin_amdgcn_readfirstlane((int)lds_addr)), "v"(g) : "memory");
-}
-// the same with a wave-uniform base (scalar register pair) and a 32-bit per-lane byte offset: no 64-bit vector add per piece
+// tap_common.h's lds_dma16 with a wave-uniform base (scalar register pair) and a 32-bit per-lane byte offset: no 64-bit vector add per piece
 __device__ __forceinline__ void lds_dma16_s(const unsigned char* sbase, int voff, unsigned lds_addr) {
   // (both are wave-uniform by construction; readfirstlane states it for builds that do not prove it - it folds away at -O3)
   const unsigned long long sb = reinterpret_cast<unsigned long long>(sbase);
@@ -43,25 +35,6 @@ __device__ __forceinline__ void lds_dma16_s(const unsigned char* sbase, int voff
                                  (unsigned)__builtin_amdgcn_readfirstlane((int)sb);
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                : : "s"(__builtin_amdgcn_readfirstlane((int)lds_addr)), "v"(voff), "s"(sbu) : "memory");
-}
-#define PH3_WAIT_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define PH3_BARRIER() asm volatile("s_barrier" ::: "memory")
-
-// relu(x * s + h) on the 8 bf16 values of one 16-byte chunk (as conv_tap2.hip)
-__device__ __forceinline__ u32x4 bn_relu_chunk3(u32x4 v, const f32x4& sA, const f32x4& sB, const f32x4& hA, const f32x4& hB) {
-  u32x4 o;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float x0 = __builtin_bit_cast(float, v[q] << 16), x1 = __builtin_bit_cast(float, v[q] & 0xffff0000u);
-    const float s0 = q < 2 ? sA[2 * q] : sB[2 * q - 4], s1 = q < 2 ? sA[2 * q + 1] : sB[2 * q - 3];
-    const float h0 = q < 2 ? hA[2 * q] : hB[2 * q - 4], h1 = q < 2 ? hA[2 * q + 1] : hB[2 * q - 3];
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
-    bf2 r;
-    r[0] = (bf16)fmaxf(x0 * s0 + h0, 0.f);
-    r[1] = (bf16)fmaxf(x1 * s1 + h1, 0.f);
-    o[q] = __builtin_bit_cast(unsigned, r);
-  }
-  return o;
 }
 
 struct Tap3Cfg {
@@ -82,11 +55,6 @@ struct Tap3Cfg {
   static_assert(A_BYTES + (NM + 2) * ROW_BYTES < 65536, "ds_read immediate offsets");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
-
-// halo image: pixel (hr, hc), 16-byte chunk c of its 64 channels -> LDS byte offset inside an A buffer
-__device__ __forceinline__ int a3_off(int hr, int hc, int c) {
-  return (Tap3Cfg::HPW / 2 * hr + (hc >> 1)) * 256 + ((hc & 1) << 7) + ((c ^ (((hc >> 1) & 3) << 1)) << 4);
-}
 
 // HPM: the half-pair arithmetic (PH_PREC_FP16X3, ph_common.h): `in` is an fp16-pair tensor (per 64-channel slice a 128-B line
 // of hi values and one of lo values: element strides x 2), the weights hold per slice the fp16 blocks [hi 2^11 | lo | hi], the K
@@ -222,7 +190,7 @@ __global__ __launch_bounds__(256) void tapconv3_kernel(PhTapConv p) {
     }
     return m;
   };
-  const unsigned char* zero_src = reinterpret_cast<const unsigned char*>(FUSE_IN ? ph3_nan16 : ph3_zero16);
+  const unsigned char* zero_src = reinterpret_cast<const unsigned char*>(FUSE_IN ? ph_nan16 : ph_zero16);
   // BatchNorm + ReLU of the INPUT applied in LDS: every wave transforms the halo pieces it issued itself
   float* ss = reinterpret_cast<float*>(smem + C::SS_OFF);
   auto xform_halo = [&](int abuf, int k0) {
@@ -235,7 +203,7 @@ __global__ __launch_bounds__(256) void tapconv3_kernel(PhTapConv p) {
         const f32x4 sA = *reinterpret_cast<const f32x4*>(ss + k0 + cg), sB = *reinterpret_cast<const f32x4*>(ss + k0 + cg + 4);
         const f32x4 hA = *reinterpret_cast<const f32x4*>(ss + 512 + k0 + cg), hB = *reinterpret_cast<const f32x4*>(ss + 512 + k0 + cg + 4);
         u32x4* a = reinterpret_cast<u32x4*>(smem + abuf * C::A_BYTES + (wave + 4 * e) * 1024 + lane * 16);
-        *a = bn_relu_chunk3(*a, sA, sB, hA, hB);
+        *a = bn_relu_chunk(*a, sA, sB, hA, hB);
       }
   };
 
@@ -245,7 +213,7 @@ __global__ __launch_bounds__(256) void tapconv3_kernel(PhTapConv p) {
   int abase0[3], abase1[3];
 #pragma unroll
   for (int dx = 0; dx < 3; ++dx) {
-    abase0[dx] = a3_off(wm * NM, li + dx, lg);
+    abase0[dx] = halo_off<HPW>(wm * NM, li + dx, lg);
     abase1[dx] = abase0[dx] ^ 64;
   }
   int bx0[NN], bx1[NN];      // k-step 0 / k-step 1 (chunk lg + 4: address bit 6 flipped; B_BASE and the ring slots are multiples of 128)
@@ -497,9 +465,9 @@ __global__ __launch_bounds__(256) void tapconv3_kernel(PhTapConv p) {
     }
   }
   zero_acc();
-  PH3_WAIT_VMCNT(0);
+  PH_WAIT_VMCNT(0);
   if (FUSE_IN) xform_halo(0, 0);
-  PH3_BARRIER();
+  PH_BARRIER();
 
   // Fragment registers: A ring of 4 (M tile m of a k-step is read two MFMA groups ahead), B double buffered.  One k-step =
   // 8 M tiles x 4 N tiles = 32 MFMAs of 16 cycles; each M group's four MFMAs carry one A read (tile m + 2; the last two groups
@@ -512,16 +480,14 @@ __global__ __launch_bounds__(256) void tapconv3_kernel(PhTapConv p) {
     else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[M][N]) : "v"(fa[AI]), "v"(fb[BS][N]));  \
   } while (0)
 #define PH3_LD(ADDR, IMM) (*reinterpret_cast<const bf16x8*>(smem + (ADDR) + (IMM)))
-#define PH3_SB() __builtin_amdgcn_sched_barrier(0)
   // A read of M tile MT (0..7) of the k-step whose bases are (AB0, AB1)[KS] with immediate offset AOFF (buffer + tap row)
 #define PH3_LDA(AB, AOFF, MT) PH3_LD(AB, (AOFF) + (MT) * C::ROW_BYTES)
   // one group: 4 MFMAs of M tile M with A ring slot M & 3 and B set BS; RA = statement issuing this group's A read, RB = its B read
 #define PH3_GROUP(M, BS, RA, RB, F0, F1)                \
-  PH3_MM(M, 0, (M) & 3, BS); RA; PH3_SB();              \
-  PH3_MM(M, 1, (M) & 3, BS); RB; PH3_SB();              \
-  PH3_MM(M, 2, (M) & 3, BS); F0; PH3_SB();              \
-  PH3_MM(M, 3, (M) & 3, BS); F1; PH3_SB()
-#define PH3_NOP ((void)0)
+  PH3_MM(M, 0, (M) & 3, BS); RA; PH_SB();               \
+  PH3_MM(M, 1, (M) & 3, BS); RB; PH_SB();               \
+  PH3_MM(M, 2, (M) & 3, BS); F0; PH_SB();               \
+  PH3_MM(M, 3, (M) & 3, BS); F1; PH_SB()
 
   unsigned bslot_cur = 0;      // LDS byte offset of the ring slot of the tap in flight (gt & 3) * TAPB
   int gt = 0;
@@ -566,33 +532,33 @@ __global__ __launch_bounds__(256) void tapconv3_kernel(PhTapConv p) {
       lds_dma16(((hm >> (E)) & 1) ? hb + h_off[(E) < C::NHE ? (E) : 0] : zero_src, hdst + (E) * 4096);        \
   } while (0)
         // ---- k-step 0 (chunks lg): A tile m + 3 is read by group m (tiles 3..7 of this k-step, then 0..2 of k-step 1); B of k-step 1
-        PH3_GROUP(0, 0, fa[3] = PH3_LDA(abase0[dx], aoff, 3), fb[1][0] = PH3_LD(bx1[0], bslot_cur), PH3_NOP, PH3_DMA_B(0));
-        PH3_GROUP(1, 0, fa[0] = PH3_LDA(abase0[dx], aoff, 4), fb[1][1] = PH3_LD(bx1[1], bslot_cur), PH3_NOP, PH3_NOP);
-        PH3_GROUP(2, 0, fa[1] = PH3_LDA(abase0[dx], aoff, 5), fb[1][2] = PH3_LD(bx1[2], bslot_cur), PH3_NOP, PH3_DMA_B(1));
-        PH3_GROUP(3, 0, fa[2] = PH3_LDA(abase0[dx], aoff, 6), fb[1][3] = PH3_LD(bx1[3], bslot_cur), PH3_NOP, PH3_NOP);
-        PH3_GROUP(4, 0, fa[3] = PH3_LDA(abase0[dx], aoff, 7), PH3_NOP, PH3_NOP, PH3_DMA_B(2));
-        PH3_GROUP(5, 0, fa[0] = PH3_LDA(abase1[dx], aoff, 0), PH3_NOP, PH3_NOP, PH3_NOP);
-        PH3_GROUP(6, 0, fa[1] = PH3_LDA(abase1[dx], aoff, 1), PH3_NOP, PH3_NOP, PH3_DMA_B(3));
-        PH3_GROUP(7, 0, fa[2] = PH3_LDA(abase1[dx], aoff, 2), PH3_NOP, PH3_NOP, PH3_NOP);
+        PH3_GROUP(0, 0, fa[3] = PH3_LDA(abase0[dx], aoff, 3), fb[1][0] = PH3_LD(bx1[0], bslot_cur), PH_NOP, PH3_DMA_B(0));
+        PH3_GROUP(1, 0, fa[0] = PH3_LDA(abase0[dx], aoff, 4), fb[1][1] = PH3_LD(bx1[1], bslot_cur), PH_NOP, PH_NOP);
+        PH3_GROUP(2, 0, fa[1] = PH3_LDA(abase0[dx], aoff, 5), fb[1][2] = PH3_LD(bx1[2], bslot_cur), PH_NOP, PH3_DMA_B(1));
+        PH3_GROUP(3, 0, fa[2] = PH3_LDA(abase0[dx], aoff, 6), fb[1][3] = PH3_LD(bx1[3], bslot_cur), PH_NOP, PH_NOP);
+        PH3_GROUP(4, 0, fa[3] = PH3_LDA(abase0[dx], aoff, 7), PH_NOP, PH_NOP, PH3_DMA_B(2));
+        PH3_GROUP(5, 0, fa[0] = PH3_LDA(abase1[dx], aoff, 0), PH_NOP, PH_NOP, PH_NOP);
+        PH3_GROUP(6, 0, fa[1] = PH3_LDA(abase1[dx], aoff, 1), PH_NOP, PH_NOP, PH3_DMA_B(3));
+        PH3_GROUP(7, 0, fa[2] = PH3_LDA(abase1[dx], aoff, 2), PH_NOP, PH_NOP, PH_NOP);
         // ---- k-step 1 (chunks lg + 4): A tiles 3..7, then tiles 0..2 of the NEXT tap's k-step 0; B of the next tap in groups 4..7
         // (the two halo pieces are the LAST operations a tap issues: in a tap where a wave has none left - piece index past the
         // image - the end-of-tap wait below lets two more operations of the PREVIOUS tap stay in flight, and those must be its
         // halo pieces, which nobody reads before tap 6's wait, never weights that the next tap's early fragment reads need)
-        PH3_GROUP(0, 1, fa[3] = PH3_LDA(abase1[dx], aoff, 3), PH3_NOP, PH3_NOP, if (t < C::HALO_TAPS) PH3_DMA_H(2 * t));
-        PH3_GROUP(1, 1, fa[0] = PH3_LDA(abase1[dx], aoff, 4), PH3_NOP, PH3_NOP, PH3_NOP);
-        PH3_GROUP(2, 1, fa[1] = PH3_LDA(abase1[dx], aoff, 5), PH3_NOP, PH3_NOP, if (t < C::HALO_TAPS) PH3_DMA_H(2 * t + 1));
-        PH3_GROUP(3, 1, fa[2] = PH3_LDA(abase1[dx], aoff, 6), PH3_NOP, PH3_NOP, PH3_NOP);
+        PH3_GROUP(0, 1, fa[3] = PH3_LDA(abase1[dx], aoff, 3), PH_NOP, PH_NOP, if (t < C::HALO_TAPS) PH3_DMA_H(2 * t));
+        PH3_GROUP(1, 1, fa[0] = PH3_LDA(abase1[dx], aoff, 4), PH_NOP, PH_NOP, PH_NOP);
+        PH3_GROUP(2, 1, fa[1] = PH3_LDA(abase1[dx], aoff, 5), PH_NOP, PH_NOP, if (t < C::HALO_TAPS) PH3_DMA_H(2 * t + 1));
+        PH3_GROUP(3, 1, fa[2] = PH3_LDA(abase1[dx], aoff, 6), PH_NOP, PH_NOP, PH_NOP);
         // The reads below are the first of the NEXT tap: weights of ring slot (gt + 1) & 3 were published one tap ago; the next
         // slice's halo (read by tap 8) is complete at tap 6's wait and published by the barriers of taps 6 and 7.
-        PH3_GROUP(4, 1, fa[3] = PH3_LDA(abase1[dx], aoff, 7), fb[0][0] = PH3_LD(bx0[0], bslot_nxt), PH3_NOP, PH3_NOP);
-        PH3_GROUP(5, 1, fa[0] = PH3_LDA(abase0[dxn], aoffn, 0), fb[0][1] = PH3_LD(bx0[1], bslot_nxt), PH3_NOP, PH3_NOP);
-        PH3_GROUP(6, 1, fa[1] = PH3_LDA(abase0[dxn], aoffn, 1), fb[0][2] = PH3_LD(bx0[2], bslot_nxt), PH3_NOP, PH3_NOP);
-        PH3_GROUP(7, 1, fa[2] = PH3_LDA(abase0[dxn], aoffn, 2), fb[0][3] = PH3_LD(bx0[3], bslot_nxt), PH3_NOP, PH3_NOP);
+        PH3_GROUP(4, 1, fa[3] = PH3_LDA(abase1[dx], aoff, 7), fb[0][0] = PH3_LD(bx0[0], bslot_nxt), PH_NOP, PH_NOP);
+        PH3_GROUP(5, 1, fa[0] = PH3_LDA(abase0[dxn], aoffn, 0), fb[0][1] = PH3_LD(bx0[1], bslot_nxt), PH_NOP, PH_NOP);
+        PH3_GROUP(6, 1, fa[1] = PH3_LDA(abase0[dxn], aoffn, 1), fb[0][2] = PH3_LD(bx0[2], bslot_nxt), PH_NOP, PH_NOP);
+        PH3_GROUP(7, 1, fa[2] = PH3_LDA(abase0[dxn], aoffn, 2), fb[0][3] = PH3_LD(bx0[3], bslot_nxt), PH_NOP, PH_NOP);
         // ---- tap end.  The weight pieces of stream tap gt+2 (and a halo that is due) have landed once at most the pieces issued
         // during this tap are still in flight; the barrier publishes them and releases ring slot gt & 3.
-        if (t < C::HALO_TAPS) PH3_WAIT_VMCNT(6); else PH3_WAIT_VMCNT(4);
+        if (t < C::HALO_TAPS) PH_WAIT_VMCNT(6); else PH_WAIT_VMCNT(4);
         if (t == C::HALO_TAPS) { if (FUSE_IN) xform_halo(ABUF ^ 1, wk0); }
-        PH3_BARRIER();
+        PH_BARRIER();
         bslot_cur = bslot_nxt;
         ++gt;
       }
@@ -614,7 +580,7 @@ __global__ __launch_bounds__(256) void tapconv3_kernel(PhTapConv p) {
       hm_next = halo_mask(tnext.iy_base, tnext.ix_base);
     }
   }
-  PH3_WAIT_VMCNT(0);   // the refills issued past the end of the stream must not outlive the workgroup's LDS
+  PH_WAIT_VMCNT(0);   // the refills issued past the end of the stream must not outlive the workgroup's LDS
   if (p.stats) {
     for (int i = tid; i < NS * p.Cout; i += NTH) {
       const int which = i / p.Cout, ch = i - which * p.Cout;
@@ -636,9 +602,7 @@ int launch3(const PhTapConv& p, hipStream_t st) {
       return PH_ELAUNCH;
     attr_done = true;
   }
-  const int total = cdiv(p.OHt, C::TH) * cdiv(p.OWt, C::TW) * (p.Cout / C::BNT) * p.B;
-  const int resident = ph_num_cus();
-  dim3 grid(total < resident ? total : resident);
+  dim3 grid(ph_persistent_wgs<C>(p));
   void* tok = nullptr;
   if (ph_prof_on())
     ph_prof_begin2(p.in_scale ? PH_CLS_TAPCONV2_FUSEDIN : PH_CLS_TAPCONV2, 2.0 * p.B * p.OHt * p.OWt * (double)p.Cout * p.ntaps * p.Cin,

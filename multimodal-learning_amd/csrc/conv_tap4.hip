@@ -27,7 +27,6 @@
 //
 // Same GEMM view, descriptor (PhTapConv) and semantics as conv_tap2.hip / conv_tap3.hip; outputs BITWISE those of
 // tapconv2_l1_kernel (same products, same fp32 accumulation order per output: slices of 32 channels, taps in order).
-#include <mutex>
 #include "ph_common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -35,12 +34,6 @@
 #include "tap_common.h"
 
 namespace {
-
-__device__ const u32x4 ph4_zero16[4] = {};
-__device__ const u32x4 ph4_nan16[4] = {{0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}, {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u},
-                                       {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}, {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}};
-
-typedef __attribute__((address_space(3))) unsigned char lds_uchar4;
 
 #ifdef PH_TAP_TRACE      // debug build only (make trace): per-workgroup cycle accounts, read back by tests/trace_tapconv4_gpu.py
 __device__ unsigned long long ph_tap4_trace[1024 * 8];
@@ -50,29 +43,6 @@ __device__ unsigned long long ph_tap4_trace[1024 * 8];
 #define PH4_CLK() 0ull
 #define PH4_TR(k, v)
 #endif
-
-__device__ __forceinline__ void lds_dma16_4(const void* g, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(__builtin_amdgcn_readfirstlane((int)lds_addr)), "v"(g) : "memory");
-}
-#define PH4_WAIT_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define PH4_BARRIER() asm volatile("s_barrier" ::: "memory")
-
-// relu(x * s + h) on the 8 bf16 values of one 16-byte chunk (as conv_tap2.hip)
-__device__ __forceinline__ u32x4 bn_relu_chunk4(u32x4 v, const f32x4& sA, const f32x4& sB, const f32x4& hA, const f32x4& hB) {
-  u32x4 o;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float x0 = __builtin_bit_cast(float, v[q] << 16), x1 = __builtin_bit_cast(float, v[q] & 0xffff0000u);
-    const float s0 = q < 2 ? sA[2 * q] : sB[2 * q - 4], s1 = q < 2 ? sA[2 * q + 1] : sB[2 * q - 3];
-    const float h0 = q < 2 ? hA[2 * q] : hB[2 * q - 4], h1 = q < 2 ? hA[2 * q + 1] : hB[2 * q - 3];
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
-    bf2 r;
-    r[0] = (bf16)fmaxf(x0 * s0 + h0, 0.f);
-    r[1] = (bf16)fmaxf(x1 * s1 + h1, 0.f);
-    o[q] = __builtin_bit_cast(unsigned, r);
-  }
-  return o;
-}
 
 struct Tap4Cfg {
   static constexpr int NM = 4, NN = 4, NTAPS = 9;
@@ -94,11 +64,6 @@ struct Tap4Cfg {
   static_assert(A_BYTES + (NM + 2) * ROW_BYTES < 65536, "ds_read immediate offsets");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
-
-// halo image: pixel (hr, hc), 16-byte chunk c of its 64 channels -> LDS byte offset inside an A buffer (conv_tap3.hip: a3_off)
-__device__ __forceinline__ int a4_off(int hr, int hc, int c) {
-  return (Tap4Cfg::HPW / 2 * hr + (hc >> 1)) * 256 + ((hc & 1) << 7) + ((c ^ (((hc >> 1) & 3) << 1)) << 4);
-}
 
 // BST: fused BatchNorm-backward sums over the tensor this launch writes (0 = none: forward launches take sum y / sum y^2 when
 // p.stats is set).  1: dz = out * (bst_y * bst_scale + bst_shift > 0), the BatchNorm's own ReLU (bn1 of a BasicBlock, reduced
@@ -134,7 +99,7 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
   constexpr int B_BASE = C::B_BASE;
   typedef __bf16 T;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const unsigned lds0 = (unsigned)(size_t)(lds_uchar4*)smem;
+  const unsigned lds0 = (unsigned)(size_t)(lds_uchar*)smem;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // = the wave's band of four tile rows
@@ -203,7 +168,7 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
     const int hr = h_rc[e] & 0xff, hc = h_rc[e] >> 8;
     return hr < C::HPH && (unsigned)(iy_base + hr) < (unsigned)p.IH && (unsigned)(ix_base + hc) < (unsigned)p.IW;
   };
-  const unsigned char* zero_src = reinterpret_cast<const unsigned char*>(FUSE_IN ? ph4_nan16 : ph4_zero16);
+  const unsigned char* zero_src = reinterpret_cast<const unsigned char*>(FUSE_IN ? ph_nan16 : ph_zero16);
   float* ss = reinterpret_cast<float*>(smem + C::SS_OFF);
   // BatchNorm + ReLU of the INPUT applied in LDS: every wave transforms the halo pieces it issued itself
   auto xform_halo = [&](int abuf) {
@@ -216,7 +181,7 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
         const f32x4 sA = *reinterpret_cast<const f32x4*>(ss + cg), sB = *reinterpret_cast<const f32x4*>(ss + cg + 4);
         const f32x4 hA = *reinterpret_cast<const f32x4*>(ss + BNT + cg), hB = *reinterpret_cast<const f32x4*>(ss + BNT + cg + 4);
         u32x4* a = reinterpret_cast<u32x4*>(smem + abuf * C::A_BYTES + (wave + 4 * e) * 1024 + lane * 16);
-        *a = bn_relu_chunk4(*a, sA, sB, hA, hB);
+        *a = bn_relu_chunk(*a, sA, sB, hA, hB);
       }
   };
 
@@ -227,7 +192,7 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
   int abase0[3], abase1[3];
 #pragma unroll
   for (int dx = 0; dx < 3; ++dx) {
-    abase0[dx] = a4_off(wave * NM, li + dx, lg);
+    abase0[dx] = halo_off<HPW>(wave * NM, li + dx, lg);
     abase1[dx] = abase0[dx] ^ 64;
   }
   int bx0[NN], bx1[NN];
@@ -269,7 +234,7 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
       const int ch = ((R & 15) << 2) | (R >> 4);
       const int slab = p.wtap[tap];
       const unsigned char* wb = reinterpret_cast<const unsigned char*>(wbase + (size_t)slab * p.Cout * p.Cin);
-      lds_dma16_4(wb + (ch * p.Cin + (u & 7) * 8) * 2, lds0 + B_BASE + q * 1024);
+      lds_dma16(wb + (ch * p.Cin + (u & 7) * 8) * 2, lds0 + B_BASE + q * 1024);
     }
   }
   TileCtx tcur = decode(tile_id(0));
@@ -285,11 +250,11 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
 #pragma unroll
     for (int e = 0; e < C::NHE; ++e)
       if (wave + 4 * e < C::NHD)
-        lds_dma16_4(piece_ok(e, tcur.iy_base, tcur.ix_base) ? hb + h_off[e] : zero_src, lds0 + (wave + 4 * e) * 1024);
+        lds_dma16(piece_ok(e, tcur.iy_base, tcur.ix_base) ? hb + h_off[e] : zero_src, lds0 + (wave + 4 * e) * 1024);
   }
-  PH4_WAIT_VMCNT(0);
+  PH_WAIT_VMCNT(0);
   if (FUSE_IN) { xform_halo(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-  PH4_BARRIER();
+  PH_BARRIER();
 
   // two accumulator sets (OVL: the tile in the MFMAs and the tile being stored), pinned to AGPRs; acc[set][pixel row m][channel tile n]
   f32x4 acc[OVL ? 2 : 1][NM][NN];
@@ -297,15 +262,13 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
 #define PH4_MM(AS, M, N, S) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[AS][M][N]) : "v"(fa[S][M]), "v"(fb[S][N]))
 #define PH4_MM0(AS, M, N, S) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(acc[AS][M][N]) : "v"(fa[S][M]), "v"(fb[S][N]))
 #define PH4_LD(ADDR, IMM) (*reinterpret_cast<const bf16x8*>(smem + (ADDR) + (IMM)))
-#define PH4_SB() __builtin_amdgcn_sched_barrier(0)
-#define PH4_NOP ((void)0)
   // one pixel-row group of a k-step on fragment set S: four MFMAs (channel tiles 0..3); RA / RB = the reads of the NEXT k-step's
   // pixel fragment / weight fragment of the same index into set S ^ 1; F0 / F1 = filler slots
 #define PH4_GROUP(MMAC, AS, M, S, RA, RB, F0, F1)   \
-  MMAC(AS, M, 0, S); RA; PH4_SB();                  \
-  MMAC(AS, M, 1, S); RB; PH4_SB();                  \
-  MMAC(AS, M, 2, S); F0; PH4_SB();                  \
-  MMAC(AS, M, 3, S); F1; PH4_SB()
+  MMAC(AS, M, 0, S); RA; PH_SB();                   \
+  MMAC(AS, M, 1, S); RB; PH_SB();                   \
+  MMAC(AS, M, 2, S); F0; PH_SB();                   \
+  MMAC(AS, M, 3, S); F1; PH_SB()
 
   // ---- the epilogue in 8-byte pieces: piece (m, r) = pixel (row 4 wave + m, column 4 lg + r), channels 4 li .. + 3.
   // Stores and operand loads go through buffer resources of the tile's IMAGE (base + size in scalar registers): a lane outside
@@ -313,7 +276,6 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
   // branch around the instruction, and every piece issues exactly one store whatever the tile's shape, which is what lets
   // the end-of-tile wait COUNT them.
   constexpr unsigned OOB = 0x7ffffff0u;
-  constexpr int RSRC_FLAGS = 0x00020000;      // raw buffer, 32-bit offsets (gfx90a / gfx94x / gfx950 data format word)
   struct EpiCtx { __amdgpu_buffer_rsrc_t out, q0, q1; unsigned o00, rowstep, colstep; int rlim, clim; };
   const int img_bytes = p.OH * p.OW * p.Cout * 2;
   auto in_rsrc = [&](const void* base, const TileCtx& tc) {
@@ -523,7 +485,7 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
 #define PH4_DMA_H(E)                                                                                           \
   do {                                                                                                         \
     if (nvalid && (E) < C::NHE && wave + 4 * (E) < C::NHD)                                                     \
-      lds_dma16_4(piece_ok((E) < C::NHE ? (E) : 0, tnext.iy_base, tnext.ix_base) ? hb + h_off[(E) < C::NHE ? (E) : 0] : zero_src, hdst + (E) * 4096); \
+      lds_dma16(piece_ok((E) < C::NHE ? (E) : 0, tnext.iy_base, tnext.ix_base) ? hb + h_off[(E) < C::NHE ? (E) : 0] : zero_src, hdst + (E) * 4096);   \
   } while (0)
     // slot J (0..7) of k-step KS of tap t: micro-step J of the previous tile's piece 2 t + KS = (m, r) = ((2 t + KS) >> 2, .. & 3),
     // or (launches that read in their epilogue) one piece's loads
@@ -574,10 +536,10 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
         PH4_GROUP(PH4_MM, AS, 2, 1, fa[0][2] = PH4_LD(abase0[dxn], aoffn + 2 * C::ROW_BYTES), fb[0][2] = PH4_LD(bx0[2] + bextn, boffn), PH4_EPI(1, 4), PH4_EPI(1, 5));
         PH4_GROUP(PH4_MM, AS, 3, 1, fa[0][3] = PH4_LD(abase0[dxn], aoffn + 3 * C::ROW_BYTES), fb[0][3] = PH4_LD(bx0[3] + bextn, boffn), PH4_EPI(1, 6), PH4_EPI(1, 7));
       } else {
-        PH4_GROUP(PH4_MM, AS, 0, 1, PH4_NOP, PH4_NOP, PH4_NOP, PH4_NOP);
-        PH4_GROUP(PH4_MM, AS, 1, 1, PH4_NOP, PH4_NOP, PH4_NOP, PH4_NOP);
-        PH4_GROUP(PH4_MM, AS, 2, 1, PH4_NOP, PH4_NOP, PH4_NOP, PH4_NOP);
-        PH4_GROUP(PH4_MM, AS, 3, 1, PH4_NOP, PH4_NOP, PH4_NOP, PH4_NOP);
+        PH4_GROUP(PH4_MM, AS, 0, 1, PH_NOP, PH_NOP, PH_NOP, PH_NOP);
+        PH4_GROUP(PH4_MM, AS, 1, 1, PH_NOP, PH_NOP, PH_NOP, PH_NOP);
+        PH4_GROUP(PH4_MM, AS, 2, 1, PH_NOP, PH_NOP, PH_NOP, PH_NOP);
+        PH4_GROUP(PH4_MM, AS, 3, 1, PH_NOP, PH_NOP, PH_NOP, PH_NOP);
       }
     }
 #undef PH4_DMA_H
@@ -604,14 +566,14 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
       const unsigned long long q1_ = PH4_CLK();
       if constexpr (OVL) { eprev = ecur; last_as = half; }
       const unsigned long long q2_ = PH4_CLK();
-      PH4_WAIT_VMCNT(0);
+      PH_WAIT_VMCNT(0);
       if (FUSE_IN && nvalid) {
         xform_halo(half ^ 1);
         // the transform's ds_writes must have completed before the barrier lets the other waves read them (an inline-asm
         // s_barrier is invisible to the compiler's wait insertion; the first fragment reads follow the barrier at once)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
-      PH4_BARRIER();
+      PH_BARRIER();
       const unsigned long long q3_ = PH4_CLK();
       if constexpr (!OVL) epilogue_any(tcur, 0);
       cy_main += q1_ - q0_; cy_wait += q3_ - q2_; cy_epi += (q2_ - q1_) + (PH4_CLK() - q3_); ++ntile;
@@ -673,25 +635,7 @@ done:
 
 template <bool FUSE_IN, int BST, bool OVL, int ORM = 0>
 int launch4(const PhTapConv& p, hipStream_t st) {
-  using C = Tap4Cfg;
-  auto kern = tapconv4_kernel<FUSE_IN, BST, OVL, ORM>;
-  static std::once_flag attr_once;      // (one flag per template instantiation; thread-safe)
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(attr_once, [&] {
-    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-  });
-  if (attr_rc != hipSuccess) return PH_ELAUNCH;
-  const int total = cdiv(p.OHt, C::TH) * cdiv(p.OWt, C::TW) * p.B;
-  const int resident = ph_num_cus();
-  dim3 grid(total < resident ? total : resident);
-  void* tok = nullptr;
-  if (ph_prof_on())
-    ph_prof_begin2(p.in_scale ? PH_CLS_TAPCONV2_RES_FUSEDIN : PH_CLS_TAPCONV2_RES, 2.0 * p.B * p.OHt * p.OWt * (double)p.Cout * p.ntaps * p.Cin,
-                   ph_tapconv_bytes(p, 1, 2), st, &tok);
-  hipLaunchKernelGGL(kern, grid, dim3(C::NTH), C::LDS_BYTES, st, p);
-  ph_prof_end(tok, st);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
+  return ph_launch_persistent<tapconv4_kernel<FUSE_IN, BST, OVL, ORM>, Tap4Cfg>(p, st, p.in_scale ? PH_CLS_TAPCONV2_RES_FUSEDIN : PH_CLS_TAPCONV2_RES, 1, 2);
 }
 
 }  // namespace

@@ -20,7 +20,6 @@
 // Same GEMM view, descriptor (PhTapConv) and epilogue semantics as conv_tap3.hip's half-pair form: fp32 16-byte stores, fused
 // dgrad residual / mask (fp32 operands), per-workgroup BatchNorm partial sums (one row per persistent workgroup).
 #include "ph_common.h"
-#include <mutex>
 #include <type_traits>
 #include "ph_kernels.h"
 #include "tap_common.h"
@@ -30,16 +29,9 @@
 
 namespace {
 
-__device__ const u32x4 ph5_zero16[4] = {};
 #ifdef PH_TAP_TRACE
 __device__ unsigned long long ph_tap_trace[PH_TRACE_WGS * 12];
 #endif
-
-typedef __attribute__((address_space(3))) unsigned char lds_uchar;
-
-__device__ __forceinline__ void lds_dma16(const void* g, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(__builtin_amdgcn_readfirstlane((int)lds_addr)), "v"(g) : "memory");
-}
 
 struct Tap5Cfg {
   static constexpr int NW = 4, NM = 8, NN = 4, NTAPS = 9;
@@ -57,12 +49,6 @@ struct Tap5Cfg {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-// halo image: pixel (hr, hc), 16-byte chunk c of its 64 fp16 channels -> LDS byte offset inside a plane buffer (conv_tap3.hip's
-// image: swizzle by the pixel column only, a fragment's address is linear in the halo row)
-__device__ __forceinline__ int a5_off(int hr, int hc, int c) {
-  return (Tap5Cfg::HPW / 2 * hr + (hc >> 1)) * 256 + ((hc & 1) << 7) + ((c ^ (((hc >> 1) & 3) << 1)) << 4);
-}
-
 // DMA pieces a slice kind issues in tap t (k-step 1, groups 0..3) and the first piece index.  Kinds: 0 / 1 / 2 = the three slices
 // of a tile of the 3-product form (x hi . w hi 2^11 | x hi . w lo | x lo . w hi), 3 / 4 = the single slice of a tile of the hi-only
 // form on buffer 0 / 1.  Kind 1 fetches x lo of THIS tile (buffer 1, free since the previous tile's lo slice), kinds 2, 3, 4 fetch
@@ -78,15 +64,6 @@ __host__ __device__ constexpr int ph5_dma0(int kind, int t) {
 __host__ __device__ constexpr int ph5_next_kind(int kind) { return kind == 0 ? 1 : kind == 1 ? 2 : kind == 2 ? 0 : kind == 3 ? 4 : 3; }
 __host__ __device__ constexpr int ph5_abuf(int kind) { return (kind == 2 || kind == 4) ? 1 : 0; }
 __host__ __device__ constexpr int ph5_wblk(int kind) { return kind == 0 ? 0 : kind == 1 ? 1 : 2; }
-
-__device__ __forceinline__ void ph5_wait_vmcnt(int n) {
-  switch (n) {
-#define PH5_W(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    PH5_W(8) PH5_W(9) PH5_W(10) PH5_W(11) PH5_W(12) PH5_W(13) PH5_W(14) PH5_W(15) PH5_W(16) PH5_W(17) PH5_W(18) PH5_W(19) PH5_W(20)
-#undef PH5_W
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
 
 // HI1: the hi planes' product alone (PH_PREC_FP16X1 backward): one slice per tile, buffers alternate tile by tile
 template <bool HI1>
@@ -170,7 +147,7 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
     const int hc = 2 * q + (s >> 3), ch = (s & 7) ^ ((q & 3) << 1);
     h_off[e] = (int)(((long)hr * row_st + (long)hc * pix_st + ch * 8) * 2);
   }
-  const unsigned char* zero_src = reinterpret_cast<const unsigned char*>(ph5_zero16);
+  const unsigned char* zero_src = reinterpret_cast<const unsigned char*>(ph_zero16);
   // Which of its 20 pieces lie inside the image is a property of the TILE (halo origin iy_base / ix_base), the same for both
   // planes: bit e of a per-lane mask, computed once per tile - x hi of tile k + 1 (fetched during tile k's lo slice) and x lo of
   // tile k + 1 (fetched one tile later) share it.  piece_bit(e) = this lane's source pixel of piece e is inside the image.
@@ -203,7 +180,7 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
   for (int bf = 0; bf < 2; ++bf)
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
-      ab0[bf][dx] = bf * C::A_BYTES + a5_off(wave * NM, li + dx, lg);
+      ab0[bf][dx] = bf * C::A_BYTES + halo_off<HPW>(wave * NM, li + dx, lg);
       ab1[bf][dx] = ab0[bf][dx] ^ 64;
     }
 
@@ -220,7 +197,6 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
   // offset past the resource - the hardware drops its store / returns 0 for its load; 32-bit byte offsets, no 64-bit address per
   // piece, and every tile issues exactly 32 stores per wave whatever its shape.
   constexpr unsigned OOB = 0x7ffffff0u;
-  constexpr int RSRC_FLAGS = 0x00020000;      // raw buffer, 32-bit offsets (gfx90a / gfx94x / gfx950 data format word)
   const int img_bytes = p.OH * p.OW * BNT * 4;
   auto epilogue = [&](const TileCtx& tc, auto fullc, auto rmc) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(fullc)::value;
@@ -311,7 +287,6 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
     else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[M][N]) : "v"(fa[AI]), "a"(fb[SET][KS][N]));               \
   } while (0)
 #define PH5_LD(ADDR, IMM) (*reinterpret_cast<const u32x4*>(smem + (ADDR) + (IMM)))
-#define PH5_SB() __builtin_amdgcn_sched_barrier(0)
 #define PH5_LDA(AB, AOFF, MT) PH5_LD(AB, (AOFF) + (MT) * C::ROW_BYTES)
   // weight fragment (KS, N) of the tap at wave-uniform base WB -> register set SET (literal byte offset (4 KS + N) KiB - 4 KiB)
   // (WB is a per-lane 64-bit address - the lane's 16 bytes of fragment (0, 0) - made by ONE vector add per tap; the loads carry nothing
@@ -334,11 +309,10 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
   } while (0)
   // one group: 4 MFMAs of M tile M with A ring slot M & 3 on B (SET, KS); RA = this group's A read, X1 / X2 = other issue slots
 #define PH5_GROUP(M, SET, KS, RA, X1, X2)                        \
-  PH5_MM(M, 0, (M) & 3, SET, KS, first && (KS) == 0); RA; PH5_SB();  \
-  PH5_MM(M, 1, (M) & 3, SET, KS, first && (KS) == 0); X1; PH5_SB();  \
-  PH5_MM(M, 2, (M) & 3, SET, KS, first && (KS) == 0); PH5_SB();      \
-  PH5_MM(M, 3, (M) & 3, SET, KS, first && (KS) == 0); X2; PH5_SB()
-#define PH5_NOP ((void)0)
+  PH5_MM(M, 0, (M) & 3, SET, KS, first && (KS) == 0); RA; PH_SB();  \
+  PH5_MM(M, 1, (M) & 3, SET, KS, first && (KS) == 0); X1; PH_SB();  \
+  PH5_MM(M, 2, (M) & 3, SET, KS, first && (KS) == 0); PH_SB();      \
+  PH5_MM(M, 3, (M) & 3, SET, KS, first && (KS) == 0); X2; PH_SB()
 
   constexpr int KIND0 = HI1 ? 3 : 0;
   unsigned mask_cur = 0, mask_next = 0;      // piece masks of tcur / of tnext
@@ -402,20 +376,20 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
 #endif
       // ---- k-step 0 (chunks lg): A tile m + 3 is read by group m (tiles 3..7 of this k-step, then 0..2 of k-step 1); one weight
       // fragment of tap g + 2 per group
-      PH5_GROUP(0, set, 0, fa[3] = PH5_LDA(ab0[BUFC][dx], aoff, 3), PH5_BLD_I(setl, 0, wb), PH5_NOP);
-      PH5_GROUP(1, set, 0, fa[0] = PH5_LDA(ab0[BUFC][dx], aoff, 4), PH5_BLD_I(setl, 1, wb), PH5_NOP);
-      PH5_GROUP(2, set, 0, fa[1] = PH5_LDA(ab0[BUFC][dx], aoff, 5), PH5_BLD_I(setl, 2, wb), PH5_NOP);
-      PH5_GROUP(3, set, 0, fa[2] = PH5_LDA(ab0[BUFC][dx], aoff, 6), PH5_BLD_I(setl, 3, wb), PH5_NOP);
-      PH5_GROUP(4, set, 0, fa[3] = PH5_LDA(ab0[BUFC][dx], aoff, 7), PH5_BLD_I(setl, 4, wb), PH5_NOP);
-      PH5_GROUP(5, set, 0, fa[0] = PH5_LDA(ab1[BUFC][dx], aoff, 0), PH5_BLD_I(setl, 5, wb), PH5_NOP);
-      PH5_GROUP(6, set, 0, fa[1] = PH5_LDA(ab1[BUFC][dx], aoff, 1), PH5_BLD_I(setl, 6, wb), PH5_NOP);
-      PH5_GROUP(7, set, 0, fa[2] = PH5_LDA(ab1[BUFC][dx], aoff, 2), PH5_BLD_I(setl, 7, wb), PH5_NOP);
+      PH5_GROUP(0, set, 0, fa[3] = PH5_LDA(ab0[BUFC][dx], aoff, 3), PH5_BLD_I(setl, 0, wb), PH_NOP);
+      PH5_GROUP(1, set, 0, fa[0] = PH5_LDA(ab0[BUFC][dx], aoff, 4), PH5_BLD_I(setl, 1, wb), PH_NOP);
+      PH5_GROUP(2, set, 0, fa[1] = PH5_LDA(ab0[BUFC][dx], aoff, 5), PH5_BLD_I(setl, 2, wb), PH_NOP);
+      PH5_GROUP(3, set, 0, fa[2] = PH5_LDA(ab0[BUFC][dx], aoff, 6), PH5_BLD_I(setl, 3, wb), PH_NOP);
+      PH5_GROUP(4, set, 0, fa[3] = PH5_LDA(ab0[BUFC][dx], aoff, 7), PH5_BLD_I(setl, 4, wb), PH_NOP);
+      PH5_GROUP(5, set, 0, fa[0] = PH5_LDA(ab1[BUFC][dx], aoff, 0), PH5_BLD_I(setl, 5, wb), PH_NOP);
+      PH5_GROUP(6, set, 0, fa[1] = PH5_LDA(ab1[BUFC][dx], aoff, 1), PH5_BLD_I(setl, 6, wb), PH_NOP);
+      PH5_GROUP(7, set, 0, fa[2] = PH5_LDA(ab1[BUFC][dx], aoff, 2), PH5_BLD_I(setl, 7, wb), PH_NOP);
       // ---- k-step 1 (chunks lg + 4): A tiles 3..7, then tiles 0..2 of the NEXT tap's k-step 0; the halo pieces of this tap
-      PH5_GROUP(0, set, 1, fa[3] = PH5_LDA(ab1[BUFC][dx], aoff, 3), PH5_NOP, PH5_DMA(0));
-      PH5_GROUP(1, set, 1, fa[0] = PH5_LDA(ab1[BUFC][dx], aoff, 4), PH5_NOP, PH5_DMA(1));
-      PH5_GROUP(2, set, 1, fa[1] = PH5_LDA(ab1[BUFC][dx], aoff, 5), PH5_NOP, PH5_DMA(2));
-      PH5_GROUP(3, set, 1, fa[2] = PH5_LDA(ab1[BUFC][dx], aoff, 6), PH5_NOP, PH5_DMA(3));
-      PH5_GROUP(4, set, 1, fa[3] = PH5_LDA(ab1[BUFC][dx], aoff, 7), PH5_NOP, PH5_NOP);
+      PH5_GROUP(0, set, 1, fa[3] = PH5_LDA(ab1[BUFC][dx], aoff, 3), PH_NOP, PH5_DMA(0));
+      PH5_GROUP(1, set, 1, fa[0] = PH5_LDA(ab1[BUFC][dx], aoff, 4), PH_NOP, PH5_DMA(1));
+      PH5_GROUP(2, set, 1, fa[1] = PH5_LDA(ab1[BUFC][dx], aoff, 5), PH_NOP, PH5_DMA(2));
+      PH5_GROUP(3, set, 1, fa[2] = PH5_LDA(ab1[BUFC][dx], aoff, 6), PH_NOP, PH5_DMA(3));
+      PH5_GROUP(4, set, 1, fa[3] = PH5_LDA(ab1[BUFC][dx], aoff, 7), PH_NOP, PH_NOP);
       // (kind 0 has no DMA: its issue slots take the piece mask of the NEXT tile, two pieces per tap + the last two)
       if (KIND == 0) {
         if (t == 0) mask_next = 0;
@@ -429,14 +403,14 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         asm volatile("s_barrier" ::: "memory");
       }
-      PH5_GROUP(5, set, 1, fa[0] = PH5_LDA(ab0[bufn][dxn], aoffn, 0), PH5_NOP, PH5_NOP);
-      PH5_GROUP(6, set, 1, fa[1] = PH5_LDA(ab0[bufn][dxn], aoffn, 1), PH5_NOP, PH5_NOP);
-      PH5_GROUP(7, set, 1, fa[2] = PH5_LDA(ab0[bufn][dxn], aoffn, 2), PH5_NOP, PH5_NOP);
+      PH5_GROUP(5, set, 1, fa[0] = PH5_LDA(ab0[bufn][dxn], aoffn, 0), PH_NOP, PH_NOP);
+      PH5_GROUP(6, set, 1, fa[1] = PH5_LDA(ab0[bufn][dxn], aoffn, 1), PH_NOP, PH_NOP);
+      PH5_GROUP(7, set, 1, fa[2] = PH5_LDA(ab0[bufn][dxn], aoffn, 2), PH_NOP, PH_NOP);
       // ---- tap end: the weights of tap g + 1 (loaded during tap g - 1) must be in their registers.  Younger than them: the previous
       // tap's pieces, this tap's 8 weight fragments, this tap's pieces.
       // (first tap of a tile: the wait in front of the epilogue already covered the weights of tap g + 1, and nothing this tap could wait
       // for is older than the epilogue's 32 stores - a counted wait here would stall until they have drained)
-      if (!first) ph5_wait_vmcnt(ndp + 8 + nd);
+      if (!first) ph_wait_vmcnt(ndp + 8 + nd);
 #if defined(PH_TAP_TRACE) && defined(PH5_TRACE_KIND)
       if (KIND == PH5_TRACE_KIND && trace_k == 1) PH_TRACE_ACC(t + 1, wall_clock64());      // per-tap stamps of one slice of the second tile
 #endif
@@ -524,28 +498,6 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
   }
 }
 
-template <bool HI1>
-int launch5(const PhTapConv& p, hipStream_t st) {
-  using C = Tap5Cfg;
-  auto kern = tapconv5_kernel<HI1>;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [&] {
-    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-  });
-  if (attr_rc != hipSuccess) return PH_ELAUNCH;
-  const int total = cdiv(p.OHt, C::TH) * cdiv(p.OWt, C::TW) * p.B;
-  const int resident = ph_num_cus();
-  dim3 grid(total < resident ? total : resident);
-  void* tok = nullptr;
-  if (ph_prof_on())
-    ph_prof_begin2(PH_CLS_TAPCONV2_RES, 2.0 * p.B * p.OHt * p.OWt * (double)p.Cout * p.ntaps * p.Cin, ph_tapconv_bytes(p, 1, 4), st, &tok);
-  hipLaunchKernelGGL(kern, grid, dim3(C::NTH), C::LDS_BYTES, st, p);
-  ph_prof_end(tok, st);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
-}
-
 }  // namespace
 
 #ifdef PH_TAP_TRACE
@@ -567,13 +519,12 @@ bool ph_tapconv5_eligible(const PhTapConv* p) {
 }
 
 int ph_tapconv5_stat_parts(const PhTapConv* p) {
-  const int total = cdiv(p->OHt, Tap5Cfg::TH) * cdiv(p->OWt, Tap5Cfg::TW) * p->B;
-  const int resident = ph_num_cus();
-  return total < resident ? total : resident;
+  return ph_persistent_wgs<Tap5Cfg>(*p);
 }
 
 // p->hp_hi_only selects the hi-only form (PH_PREC_FP16X1)
 int ph_tapconv5_launch(const PhTapConv* p, hipStream_t st) {
   if (!ph_tapconv5_eligible(p)) return PH_EINVAL;
-  return p->hp_hi_only ? launch5<true>(*p, st) : launch5<false>(*p, st);
+  return p->hp_hi_only ? ph_launch_persistent<tapconv5_kernel<true>, Tap5Cfg>(*p, st, PH_CLS_TAPCONV2_RES, 1, 4)
+                       : ph_launch_persistent<tapconv5_kernel<false>, Tap5Cfg>(*p, st, PH_CLS_TAPCONV2_RES, 1, 4);
 }

@@ -16,7 +16,6 @@
 // Workgroup: 4 waves as 2 (pixel rows 0-7 / 8-15) x 2 (channels 0-63 / 64-127); tile 16 x 16 x 128; wave tile 8 x 4 fragments of
 // v_mfma_f32_16x16x32_bf16; 8-byte stores through a buffer resource; BatchNorm partial sums: conv_tap3.hip's row per workgroup, bitwise.
 #include "ph_common.h"
-#include <mutex>
 #include <type_traits>
 #include "ph_kernels.h"
 #include "tap_common.h"
@@ -26,13 +25,6 @@
 
 namespace {
 
-__device__ const u32x4 ph7_zero16[4] = {};
-
-typedef __attribute__((address_space(3))) unsigned char lds_uchar;
-
-__device__ __forceinline__ void lds_dma16(const void* g, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(__builtin_amdgcn_readfirstlane((int)lds_addr)), "v"(g) : "memory");
-}
 
 struct Tap7Cfg {
   static constexpr int NW = 4, WM = 2, WN = 2, NM = 8, NN = 4, NTAPS = 9, NBUF = 2;
@@ -56,19 +48,6 @@ struct Tap7Cfg {
   static constexpr int WAIT1[9] = {31, 34, 37, 39, 36, 33, 30, 28, 28};
   static constexpr int HWAIT = 40;
 };
-
-__device__ __forceinline__ int a7_off(int hr, int hc, int c) {
-  return (Tap7Cfg::HPW / 2 * hr + (hc >> 1)) * 256 + ((hc & 1) << 7) + ((c ^ (((hc >> 1) & 3) << 1)) << 4);
-}
-
-__device__ __forceinline__ void ph7_wait_vmcnt(int n) {
-  switch (n) {
-#define PH7_W(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    PH7_W(16) PH7_W(28) PH7_W(30) PH7_W(31) PH7_W(33) PH7_W(34) PH7_W(36) PH7_W(37) PH7_W(39) PH7_W(40)
-#undef PH7_W
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
 
 // BST: fused BatchNorm-backward sums over the tensor this (dgrad) launch writes (PhTapConv::bst_y, conv_tap3.hip's semantics and row
 // layout): 0 = none (rows [2][Cout]: sum y | sum y^2 of a forward launch), 1 = mask from the BatchNorm's own ReLU
@@ -150,7 +129,7 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
     const int hc = 2 * q + (s >> 3), ch = (s & 7) ^ ((q & 3) << 1);
     h_off[e] = (int)((long)hr * rowB + (long)hc * pixB + ch * 16);
   }
-  const unsigned char* zero_src = reinterpret_cast<const unsigned char*>(ph7_zero16);
+  const unsigned char* zero_src = reinterpret_cast<const unsigned char*>(ph_zero16);
   // bit e of a tile's mask: this lane's source pixel of piece e lies inside the image
   auto piece_bit = [&](const int e, const int r0, const int c0) __attribute__((always_inline)) -> unsigned {
     int ln = lane;
@@ -184,7 +163,7 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
   for (int bf = 0; bf < 2; ++bf)
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
-      ab0[bf][dx] = bf * C::A_BYTES + a7_off(wm * NM, li + dx, lg);
+      ab0[bf][dx] = bf * C::A_BYTES + halo_off<HPW>(wm * NM, li + dx, lg);
       ab1[bf][dx] = ab0[bf][dx] ^ 64;
     }
 
@@ -236,7 +215,6 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
   // n0 + 64 wn + 4 li + n: four bf16 = one 8-byte store per (m, q) through a buffer resource of the tile's image (a lane outside the
   // output gets an offset past the resource); residual / mask operands (dgrad) are loaded a tile row at a time.
   constexpr unsigned OOB = 0x7ffffff0u;
-  constexpr int RSRC_FLAGS = 0x00020000;
   const int img_bytes = p.OH * p.OW * p.Cout * 2;
   auto epilogue = [&](const TileCtx& tc, auto fullc, auto rmc) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(fullc)::value;
@@ -376,7 +354,6 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
     }                                                                                                                                               \
   } while (0)
 #define PH7_LD(ADDR, IMM) (*reinterpret_cast<const u32x4*>(smem + (ADDR) + (IMM)))
-#define PH7_SB() __builtin_amdgcn_sched_barrier(0)
 #define PH7_LDA(AB, AOFF, MT) PH7_LD(AB, (AOFF) + (MT) * C::ROW_BYTES)
   // (per-lane 64-bit address, no scalar operand: a scalar base restored by v_readlane right in front of inline assembly needs wait
   // states the hazard recognizer does not insert - conv_tap5.hip copies it with s_mov_b64 in front of every load; here ONE vector add
@@ -402,11 +379,10 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
     }                                                                \
   } while (0)
 #define PH7_GROUP(M, Q, KS, RA, X1, X2)                            \
-  PH7_MM(M, 0, (M) & 3, Q, first && (KS) == 0); RA; PH7_SB();      \
-  PH7_MM(M, 1, (M) & 3, Q, first && (KS) == 0); X1; PH7_SB();      \
-  PH7_MM(M, 2, (M) & 3, Q, first && (KS) == 0); PH7_SB();          \
-  PH7_MM(M, 3, (M) & 3, Q, first && (KS) == 0); X2; PH7_SB()
-#define PH7_NOP ((void)0)
+  PH7_MM(M, 0, (M) & 3, Q, first && (KS) == 0); RA; PH_SB();       \
+  PH7_MM(M, 1, (M) & 3, Q, first && (KS) == 0); X1; PH_SB();       \
+  PH7_MM(M, 2, (M) & 3, Q, first && (KS) == 0); PH_SB();           \
+  PH7_MM(M, 3, (M) & 3, Q, first && (KS) == 0); X2; PH_SB()
 
   {  // prologue: the image of slice 0, the weights of taps 0..3 (k-steps 0..7)
 #pragma unroll
@@ -447,21 +423,21 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
       const unsigned char* wb = (t + 4 < NTAPS) ? w_base(tcur.nb, c, t + 4) : w_base(nnb, nc, t + 4 - NTAPS);
       const int nd = C::ND[t], e0 = C::E0[t];
 #define PH7_DMA(I) do { if ((I) < nd && !(PH7_DBG & 2)) dma_piece(e0 + (I), nin, nc, (last && nvalid) ? mask_next : mask_cur, ABUF ^ 1); } while (0)
-      PH7_GROUP(0, q0, 0, fa[3] = PH7_LDA(ab0[ABUF][dx], aoff, 3), PH7_BLD_KN(ql0, 0, 0, wb), PH7_NOP);
-      PH7_GROUP(1, q0, 0, fa[0] = PH7_LDA(ab0[ABUF][dx], aoff, 4), PH7_BLD_KN(ql0, 0, 1, wb), PH7_NOP);
-      PH7_GROUP(2, q0, 0, fa[1] = PH7_LDA(ab0[ABUF][dx], aoff, 5), PH7_BLD_KN(ql0, 0, 2, wb), PH7_NOP);
-      PH7_GROUP(3, q0, 0, fa[2] = PH7_LDA(ab0[ABUF][dx], aoff, 6), PH7_BLD_KN(ql0, 0, 3, wb), PH7_NOP);
-      PH7_GROUP(4, q0, 0, fa[3] = PH7_LDA(ab0[ABUF][dx], aoff, 7), PH7_NOP, PH7_NOP);
-      PH7_GROUP(5, q0, 0, fa[0] = PH7_LDA(ab1[ABUF][dx], aoff, 0), PH7_NOP, PH7_NOP);
-      PH7_GROUP(6, q0, 0, fa[1] = PH7_LDA(ab1[ABUF][dx], aoff, 1), PH7_NOP, PH7_NOP);
-      PH7_GROUP(7, q0, 0, fa[2] = PH7_LDA(ab1[ABUF][dx], aoff, 2), PH7_NOP, PH7_NOP);
+      PH7_GROUP(0, q0, 0, fa[3] = PH7_LDA(ab0[ABUF][dx], aoff, 3), PH7_BLD_KN(ql0, 0, 0, wb), PH_NOP);
+      PH7_GROUP(1, q0, 0, fa[0] = PH7_LDA(ab0[ABUF][dx], aoff, 4), PH7_BLD_KN(ql0, 0, 1, wb), PH_NOP);
+      PH7_GROUP(2, q0, 0, fa[1] = PH7_LDA(ab0[ABUF][dx], aoff, 5), PH7_BLD_KN(ql0, 0, 2, wb), PH_NOP);
+      PH7_GROUP(3, q0, 0, fa[2] = PH7_LDA(ab0[ABUF][dx], aoff, 6), PH7_BLD_KN(ql0, 0, 3, wb), PH_NOP);
+      PH7_GROUP(4, q0, 0, fa[3] = PH7_LDA(ab0[ABUF][dx], aoff, 7), PH_NOP, PH_NOP);
+      PH7_GROUP(5, q0, 0, fa[0] = PH7_LDA(ab1[ABUF][dx], aoff, 0), PH_NOP, PH_NOP);
+      PH7_GROUP(6, q0, 0, fa[1] = PH7_LDA(ab1[ABUF][dx], aoff, 1), PH_NOP, PH_NOP);
+      PH7_GROUP(7, q0, 0, fa[2] = PH7_LDA(ab1[ABUF][dx], aoff, 2), PH_NOP, PH_NOP);
       // (a tile's k-steps 0..2 skip the wait: the one in front of the epilogue covered the fragments of its k-steps 0..3)
-      if (!(FIRSTS && t <= 1)) ph7_wait_vmcnt(C::WAIT0[t]);
+      if (!(FIRSTS && t <= 1)) ph_wait_vmcnt(C::WAIT0[t]);
       PH7_GROUP(0, q1, 1, fa[3] = PH7_LDA(ab1[ABUF][dx], aoff, 3), PH7_BLD_KN(ql1, 1, 0, wb), PH7_DMA(0));
       PH7_GROUP(1, q1, 1, fa[0] = PH7_LDA(ab1[ABUF][dx], aoff, 4), PH7_BLD_KN(ql1, 1, 1, wb), PH7_DMA(1));
       PH7_GROUP(2, q1, 1, fa[1] = PH7_LDA(ab1[ABUF][dx], aoff, 5), PH7_BLD_KN(ql1, 1, 2, wb), PH7_DMA(2));
-      PH7_GROUP(3, q1, 1, fa[2] = PH7_LDA(ab1[ABUF][dx], aoff, 6), PH7_BLD_KN(ql1, 1, 3, wb), PH7_NOP);
-      PH7_GROUP(4, q1, 1, fa[3] = PH7_LDA(ab1[ABUF][dx], aoff, 7), PH7_NOP, PH7_NOP);
+      PH7_GROUP(3, q1, 1, fa[2] = PH7_LDA(ab1[ABUF][dx], aoff, 6), PH7_BLD_KN(ql1, 1, 3, wb), PH_NOP);
+      PH7_GROUP(4, q1, 1, fa[3] = PH7_LDA(ab1[ABUF][dx], aoff, 7), PH_NOP, PH_NOP);
       // the taps without pieces take the piece mask of the NEXT tile (first slice of a tile): 3, 2, 2, 2, 2 pieces in taps 4..8
       if (FIRSTS && t >= 4) {
         if (t == 4) mask_next = piece_bit(0, tnext.r0, tnext.c0);
@@ -469,14 +445,14 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
       }
       // hand-over (last tap): this wave's pieces of the next image have landed (HWAIT), its last read of this buffer is issued
       if (t + 1 == NTAPS) {
-        ph7_wait_vmcnt(C::HWAIT);
+        ph_wait_vmcnt(C::HWAIT);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         asm volatile("s_barrier" ::: "memory");
       }
-      PH7_GROUP(5, q1, 1, fa[0] = PH7_LDA(ab0[BUFN][dxn], aoffn, 0), PH7_NOP, PH7_NOP);
-      PH7_GROUP(6, q1, 1, fa[1] = PH7_LDA(ab0[BUFN][dxn], aoffn, 1), PH7_NOP, PH7_NOP);
-      PH7_GROUP(7, q1, 1, fa[2] = PH7_LDA(ab0[BUFN][dxn], aoffn, 2), PH7_NOP, PH7_NOP);
-      if (!(FIRSTS && t == 0)) ph7_wait_vmcnt(C::WAIT1[t]);
+      PH7_GROUP(5, q1, 1, fa[0] = PH7_LDA(ab0[BUFN][dxn], aoffn, 0), PH_NOP, PH_NOP);
+      PH7_GROUP(6, q1, 1, fa[1] = PH7_LDA(ab0[BUFN][dxn], aoffn, 1), PH_NOP, PH_NOP);
+      PH7_GROUP(7, q1, 1, fa[2] = PH7_LDA(ab0[BUFN][dxn], aoffn, 2), PH_NOP, PH_NOP);
+      if (!(FIRSTS && t == 0)) ph_wait_vmcnt(C::WAIT1[t]);
 #undef PH7_DMA
     };
     tap(0); tap(1); tap(2); tap(3); tap(4); tap(5); tap(6); tap(7); tap(8);
@@ -532,23 +508,7 @@ bool ph_tapconv7_eligible(const PhTapConv* p) {
 namespace {
 template <int BST>
 int launch7(const PhTapConv* p, hipStream_t st) {
-  using C = Tap7Cfg;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [&] {
-    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(tapconv7_kernel<BST>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-  });
-  if (attr_rc != hipSuccess) return PH_ELAUNCH;
-  const int total = cdiv(p->OH, C::TH) * cdiv(p->OW, C::TW) * (p->Cout / C::BNT) * p->B;
-  const int resident = ph_num_cus();
-  dim3 grid(total < resident ? total : resident);
-  void* tok = nullptr;
-  if (ph_prof_on())
-    ph_prof_begin2(PH_CLS_TAPCONV2, 2.0 * p->B * p->OH * p->OW * (double)p->Cout * 9 * p->Cin, ph_tapconv_bytes(*p, 1, 2), st, &tok);
-  hipLaunchKernelGGL(tapconv7_kernel<BST>, grid, dim3(C::NTH), C::LDS_BYTES, st, *p);
-  ph_prof_end(tok, st);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
+  return ph_launch_persistent<tapconv7_kernel<BST>, Tap7Cfg>(*p, st, PH_CLS_TAPCONV2, 1, 2);
 }
 }  // namespace
 

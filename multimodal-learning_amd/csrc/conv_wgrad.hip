@@ -11,13 +11,9 @@
 // no float atomics).
 #include "ph_common.h"
 #include "ph_kernels.h"
+#include "tap_common.h"
 
 namespace {
-
-// one LDS-DMA wave-instruction: lane l copies 16 B from its global address g to LDS byte lds_addr + 16*l
-__device__ __forceinline__ void lds_dma16(const void* g, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(lds_addr), "v"(g) : "memory");
-}
 
 // 32-B piece swizzle of a [pixel][64 ch] bf16 image (128-B rows): makes the 4-row tr-reads conflict-free
 __device__ __forceinline__ int sw_piece(int pix, int piece) { return piece ^ (((pix >> 1) & 1) << 1); }
@@ -234,7 +230,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(PhWgrad p) {
     // front of the one barrier per tile.  The DMA is inline asm: with the builtin the compiler orders every
     // ds_read behind an outstanding LDS-DMA ("may alias") and put that vmcnt(0) in FRONT of the MFMA block, i.e.
     // the two buffers never overlapped anything.
-    typedef __attribute__((address_space(3))) unsigned char lds_uchar;
     const unsigned lds0 = (unsigned)(size_t)(lds_uchar*)smem;
     constexpr int BUF = C::D_BYTES + C::X_BYTES;
     const unsigned char* zero = reinterpret_cast<const unsigned char*>(p.zeros);

@@ -1,7 +1,15 @@
-// Pieces shared by the tap-convolution kernels (conv_tap.hip, conv_tap2.hip): the swizzled LDS image addressing,
-// the MFMA-row -> pixel permutation, and the debug-build phase tracer.
+// Pieces shared by the tap-convolution translation units.
+//   conv_tap.hip .. conv_tap7.hip, conv_tap6b.hip: the debug-build phase tracer macros.
+//   conv_tap.hip, conv_tap2.hip: the row-pair swizzled LDS image (lds_off) and the MFMA-row -> pixel permutation.
+//   conv_tap2.hip .. conv_tap7.hip, conv_tap6b.hip (the LDS-DMA kernels): lds_dma16 (conv_tap2.hip: its own form), the zero / NaN
+//     halo source tables, the counted-wait, barrier and scheduling macros, RSRC_FLAGS; conv_wgrad.hip takes lds_dma16 too.
+//   conv_tap2 / 3 / 4: bn_relu_chunk (the input's BatchNorm + ReLU applied in LDS).
+//   conv_tap3 .. conv_tap7, conv_tap6b: halo_off (the column-swizzled halo image); conv_tap5 / 6 / 6b / 7: ph_wait_vmcnt.
+//   conv_tap4 .. conv_tap7, conv_tap6b (host): ph_launch_persistent; the stat_parts functions share ph_persistent_wgs with it.
 #pragma once
+#include <mutex>
 #include "ph_common.h"
+#include "ph_kernels.h"
 
 // Debug build only (make trace): per-workgroup phase timestamps (100 MHz wall clock) of a tap-conv kernel; the
 // including file defines the buffer `__device__ unsigned long long ph_tap_trace[PH_TRACE_WGS * 12]`,
@@ -62,3 +70,97 @@ __device__ __forceinline__ void frag_row_to_pixel(int i, int& fr, int& c) {
   c = ((k >> 1) << 2) | (i & 3);
 }
 
+// ---- LDS-DMA operand streams (conv_tap2.hip's header comment says why they are inline asm with hand-counted vmcnt)
+typedef __attribute__((address_space(3))) unsigned char lds_uchar;
+
+// one LDS-DMA wave-instruction: lane l copies 16 B from its global address g to LDS byte lds_addr + 16*l.  lds_addr is
+// wave-uniform by construction; readfirstlane states it for builds that do not prove it - it folds away at -O3.  The s_nop covers
+// the hazard between the scalar write of m0 and the LDS-DMA that reads it.  (conv_tap2.hip has a form without the readfirstlane,
+// conv_tap3.hip one with a scalar base.)
+__device__ __forceinline__ void lds_dma16(const void* g, unsigned lds_addr) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(__builtin_amdgcn_readfirstlane((int)lds_addr)), "v"(g) : "memory");
+}
+
+#define PH_WAIT_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
+#define PH_BARRIER() asm volatile("s_barrier" ::: "memory")
+#define PH_SB() __builtin_amdgcn_sched_barrier(0)      // keeps the compiler from regrouping across a hand-scheduled slot
+#define PH_NOP ((void)0)                               // empty filler statement of such a slot
+// counted wait on a table entry: n is a compile-time constant after unrolling at every call site, so the switch folds to the one
+// s_waitcnt.  63 is the counter's maximum - nothing this wave issued can still be in question - and emits nothing.
+__device__ __forceinline__ void ph_wait_vmcnt(int n) {
+  switch (n) {
+#define PH_W(N) case N: PH_WAIT_VMCNT(N); break;
+#define PH_W8(A, B, C, D, E, F, G, H) PH_W(A) PH_W(B) PH_W(C) PH_W(D) PH_W(E) PH_W(F) PH_W(G) PH_W(H)
+    PH_W8(0, 1, 2, 3, 4, 5, 6, 7) PH_W8(8, 9, 10, 11, 12, 13, 14, 15) PH_W8(16, 17, 18, 19, 20, 21, 22, 23) PH_W8(24, 25, 26, 27, 28, 29, 30, 31)
+    PH_W8(32, 33, 34, 35, 36, 37, 38, 39) PH_W8(40, 41, 42, 43, 44, 45, 46, 47) PH_W8(48, 49, 50, 51, 52, 53, 54, 55)
+    PH_W(56) PH_W(57) PH_W(58) PH_W(59) PH_W(60) PH_W(61) PH_W(62)
+#undef PH_W8
+#undef PH_W
+    case 63: break;
+    default: PH_WAIT_VMCNT(0); break;
+  }
+}
+
+// buffer resource word 3 of the kernels that store through one: raw buffer, 32-bit offsets (gfx90a / gfx94x / gfx950 data format word)
+constexpr int RSRC_FLAGS = 0x00020000;
+
+namespace {
+// sources of out-of-image halo pixels (one copy per code object).  Zeros - or, when the input's BatchNorm + ReLU is applied in LDS
+// (PhTapConv::in_scale), quiet NaNs: padding must be zero AFTER that map, for any scale / shift, and fma(NaN, s, b) = NaN, the
+// ReLU's v_max_f32(NaN, 0) returns the number, 0.
+__device__ const u32x4 ph_zero16[4] = {};
+__device__ const u32x4 ph_nan16[4] = {{0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}, {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u},
+                                      {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}, {0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u}};
+}  // namespace
+
+// relu(x * s + h) on the 8 bf16 values of one 16-byte chunk (channel 2q in the low half of dword q), result rounded to
+// bf16 like the stand-alone bn_apply pass stores it
+__device__ __forceinline__ u32x4 bn_relu_chunk(u32x4 v, const f32x4& sA, const f32x4& sB, const f32x4& hA, const f32x4& hB) {
+  u32x4 o;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float x0 = __builtin_bit_cast(float, v[q] << 16), x1 = __builtin_bit_cast(float, v[q] & 0xffff0000u);
+    const float s0 = q < 2 ? sA[2 * q] : sB[2 * q - 4], s1 = q < 2 ? sA[2 * q + 1] : sB[2 * q - 3];
+    const float h0 = q < 2 ? hA[2 * q] : hB[2 * q - 4], h1 = q < 2 ? hA[2 * q + 1] : hB[2 * q - 3];
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
+    bf2 r;
+    r[0] = (bf16)fmaxf(x0 * s0 + h0, 0.f);
+    r[1] = (bf16)fmaxf(x1 * s1 + h1, 0.f);
+    o[q] = __builtin_bit_cast(unsigned, r);
+  }
+  return o;
+}
+
+// halo image of the 16x16x32 kernels (conv_tap3.hip's header comment): pixel (hr, hc) of a halo HPW pixels wide, 16-byte chunk c of
+// its 64 channels -> LDS byte offset inside an image buffer.  Swizzled by the pixel column only: linear in the halo row.
+template <int HPW>
+__device__ __forceinline__ int halo_off(int hr, int hc, int c) {
+  return (HPW / 2 * hr + (hc >> 1)) * 256 + ((hc & 1) << 7) + ((c ^ (((hc >> 1) & 3) << 1)) << 4);
+}
+
+// ---- host side of the persistent kernels: one workgroup per CU (LDS) walks a tile list of C::TH x C::TW pixels x C::BNT channels.
+// Workgroups of a launch = the BatchNorm partial rows it writes (the stat_parts functions).
+template <class C>
+int ph_persistent_wgs(const PhTapConv& p) {
+  const int total = cdiv(p.OHt, C::TH) * cdiv(p.OWt, C::TW) * (p.Cout / C::BNT) * p.B;
+  const int resident = ph_num_cus();
+  return total < resident ? total : resident;
+}
+// The launch.  KERN is a template parameter, not a run-time pointer: every kernel keeps its own once_flag and so gets its own raised
+// dynamic-LDS limit (thread-safe).  cls: profiling class; S, es: stride and element size of ph_tapconv_bytes.
+template <auto KERN, class C>
+int ph_launch_persistent(const PhTapConv& p, hipStream_t st, int cls, int S, int es) {
+  static std::once_flag once;
+  static hipError_t attr_rc = hipSuccess;
+  std::call_once(once, [] {
+    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
+  });
+  if (attr_rc != hipSuccess) return PH_ELAUNCH;
+  void* tok = nullptr;
+  if (ph_prof_on())
+    ph_prof_begin2(cls, 2.0 * p.B * p.OHt * p.OWt * (double)p.Cout * p.ntaps * p.Cin, ph_tapconv_bytes(p, S, es), st, &tok);
+  hipLaunchKernelGGL(KERN, dim3(ph_persistent_wgs<C>(p)), dim3(C::NTH), C::LDS_BYTES, st, p);
+  ph_prof_end(tok, st);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
