@@ -245,9 +245,18 @@ int ph_crd_loss_grad_pos(const float* xs, const float* xt, const int* sel, const
                          float* lossp, float* dv1, float* dv2, int B, int P, int m_neg, int feat_dim, float n_data, float inv_bnorm,
                          ph_stream_t stream);
 /* MIA-2023 v10 KNN positives (CRD_criterion_v10.py:72-79,110-116): class-masked full-bank cosine top-num_pos of each
- * query's own bank row, for both banks; labels = class of every bank row (int32 [n_data]).  The workspace size does not
- * depend on feat_dim (a pass takes up to 64 queries at every width, through the same buffers). */
+ * query's own bank row, for both banks; labels = class of every bank row (int32 [n_data]).  1 <= num_pos <= 64 (anything else
+ * is PH_EINVAL): nb / sim [B][num_pos] are the rows and similarities of a stable descending sort (lower row first among equal
+ * values, -0 = +0); a bank of fewer than num_pos rows leaves the tail at row 0x7fffffff, similarity -inf.  num_pos > 8 runs
+ * ceil(num_pos / 8) rank windows (2 + 2 ceil(num_pos / 8) launches per 64 queries, no host read, no allocation).  The workspace
+ * size does not depend on feat_dim (a pass takes up to 64 queries at every width, through the same buffers):
+ * ph_crd_bank_topk_workspace_bytes is enough for num_pos <= 8, ph_crd_bank_topk_workspace_bytes_np for the num_pos it is given
+ * (the same value for num_pos <= 8; 0 for a num_pos outside 1 .. 64).
+ * WARNING: the entry cannot see the size of `workspace`.  A call with num_pos > 8 over a buffer sized by
+ * ph_crd_bank_topk_workspace_bytes writes up to 2 x 64 x 15 x 8 bytes past its end, with no error: size every workspace by
+ * ph_crd_bank_topk_workspace_bytes_np with the num_pos of the call. */
 size_t ph_crd_bank_topk_workspace_bytes(int B, int n_data);
+size_t ph_crd_bank_topk_workspace_bytes_np(int B, int n_data, int num_pos);
 int ph_crd_bank_topk(const float* mem1, const float* mem2, const int* labels, const int64_t* idx, int PK,
                      const int64_t* batch_label, int B, int n_data, int num_pos, int feat_dim, int64_t* nb1,
                      int64_t* nb2, float* sim1, float* sim2, void* workspace, ph_stream_t stream);

@@ -91,6 +91,8 @@ class CRDLoss(nn.Module):
     """CRD_criterion_v10.py:180-239: forward(sample_weights, f_s, f_t, batch_label, idx, contrast_idx)
     -> (loss, sample_loss[B])."""
 
+    MAX_NEIGHBORS = 64      # num_pos range of ph_crd_bank_topk (include/pathomic_hip.h)
+
     def __init__(self, opt, n_data, train_class_idx):
         super().__init__()
         check_feat_dim(opt.feat_dim)
@@ -101,6 +103,13 @@ class CRDLoss(nn.Module):
         self.pos_extra = opt.pos_extra
         if self.pos_extra not in ("neighbors", "centers"):
             raise NotImplementedError("pos_extra '%s' (CRD_criterion_v10.py knows 'neighbors' and 'centers')" % self.pos_extra)
+        if self.pos_extra == "neighbors" and not 1 <= self.num_pos <= self.MAX_NEIGHBORS:
+            raise ValueError("pos_extra 'neighbors' with nce_p %d: outside 1 .. %d (ph_crd_bank_topk selects up to %d "
+                             "neighbours per query and bank)" % (self.num_pos, self.MAX_NEIGHBORS, self.MAX_NEIGHBORS))
+        if self.pos_extra == "neighbors" and self.num_pos > n_data:
+            # (a bank of fewer rows leaves empty KNN slots - row 0x7fffffff, similarity -inf - that the column lists cannot hold)
+            raise ValueError("pos_extra 'neighbors' with nce_p %d over a bank of %d rows: nce_p must not exceed n_data"
+                             % (self.num_pos, n_data))
         self.centers_kmeans = getattr(opt, "centers_kmeans", "sklearn")
         self.kmeans_iters = int(getattr(opt, "kmeans_iters", 16))
         if self.pos_extra == "centers" and self.num_pos != 2:
@@ -176,7 +185,7 @@ class CRDLoss(nn.Module):
         dev = contrast_idx.device
         nb1 = torch.empty(B, NP, device=dev, dtype=torch.int64); nb2 = torch.empty_like(nb1)
         sim1 = torch.empty(B, NP, device=dev, dtype=torch.float32); sim2 = torch.empty_like(sim1)
-        ws = torch.empty(lib().ph_crd_bank_topk_workspace_bytes(B, mem.nLem), device=dev, dtype=torch.uint8)
+        ws = torch.empty(lib().ph_crd_bank_topk_workspace_bytes_np(B, mem.nLem, NP), device=dev, dtype=torch.uint8)
         check(lib().ph_crd_bank_topk(ptr(mem.memory_v1), ptr(mem.memory_v2), ptr(mem.all_sample_labels),
                                      ptr(contrast_idx), K + 1, ptr(batch_label), B, mem.nLem, NP, D, ptr(nb1),
                                      ptr(nb2), ptr(sim1), ptr(sim2), ptr(ws), stream()), "ph_crd_bank_topk")

@@ -341,6 +341,14 @@ __device__ __forceinline__ void knn_insert(u64 (&L)[TOPK_MAX], u64 c) {
 // thr 5.1 + full 35 + merge 9.6 = 59 us.  The full pass runs at matrix time + selection time (3.9 + 2.3 us per tile and
 // SIMD): the VALU work of one wave does not hide under the other wave's fp32 MFMAs (delaying one wave of every SIMD by half a
 // matrix phase changed nothing), and the per-launch overhead of the four small launches is a third of the total.
+// num_pos > TOPK_MAX (up to 64): rank windows.  The lists stay at TOPK_MAX keys; stages 1 and 2 run once,
+// stage 2 (crd_knn_thr_kernel_win) leaving one thr per window p = 0 .. ceil(num_pos / TOPK_MAX) - 1, the TOPK_MAX (p + 1)-th largest
+// group maximum - a lower bound of the TOPK_MAX (p + 1)-th best key, by the same argument.  Window p is stages 3 and 4 over the keys
+// k with thr[p] <= k < ub[p]: ub[0] is all ones, ub[p + 1] the TOPK_MAX-th key the merge of window p wrote (0 = fewer than that
+// were left: the bank is exhausted and later windows leave empty slots).  Keys are unique (low word ~row), so window p holds
+// exactly ranks TOPK_MAX p .. TOPK_MAX p + TOPK_MAX - 1.  ub is tested only where the exact key exists, in the rare path
+// (template parameter WIN; without it the kernel is the one above, instruction for instruction); thr and ub stay in device
+// memory: 2 + 2 ceil(num_pos / TOPK_MAX) launches per 64 queries, fixed by the arguments.
 // History: one workgroup per (query, bank, slice) re-read the bank per query (1.4 GB through L2, 278 us); a thread per bank
 // row with the queries as scalar operands 120-132 us; similarity matrix [2][B][n_data] written by an MFMA kernel (59 us) and
 // re-read by a selection kernel (41 us) + merge (9 us): 136 MB of traffic for 67 MB of bank, 157-162 us per call (round 3);
@@ -403,7 +411,9 @@ __device__ __forceinline__ void knn_dma4(const void* g, unsigned lds_addr) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" : : "s"(__builtin_amdgcn_readfirstlane((int)lds_addr)), "v"(g) : "memory");
 }
 
-template <int D, int NQ, bool SAMPLE, int NWF = KNN_WAVES>      // NWF: waves of the full pass
+// NWF: waves of the full pass.  WIN: the full pass of one rank window (num_pos > TOPK_MAX) - `thr` then points at the window's
+// record [thr bank 0 | thr bank 1 | ub bank 0 | ub bank 1][B] and a key enters a list only below ub; without WIN no ub is read
+template <int D, int NQ, bool SAMPLE, int NWF = KNN_WAVES, bool WIN = false>
 __global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : NWF) * 64) void crd_bank_knn_kernel(
     const float* __restrict__ mem1, const float* __restrict__ mem2, const int* __restrict__ labels, const int64_t* __restrict__ idx,
     int PK, const int64_t* __restrict__ batch_label, int B, int n_data, int stiles, int tstride, u64* __restrict__ gmax,
@@ -477,10 +487,12 @@ __global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : NWF) * 64) void crd_ba
   const int j = lane & 31, kk = lane >> 5;
   float qn[NQ], tv[NQ];
   int ql[NQ];
-  u64 L[NQ][SAMPLE ? 1 : TOPK_MAX], tk[NQ];
+  static_assert(!(SAMPLE && WIN), "the sample pass has no window");
+  u64 L[NQ][SAMPLE ? 1 : TOPK_MAX], tk[NQ], uk[WIN ? NQ : 1];
 #pragma unroll
   for (int nq = 0; nq < NQ; ++nq) {
     const int qi = q0 + nq * 32 + j;
+    if constexpr (WIN) uk[nq] = qi < B ? thr[(2 + bank) * B + qi] : 0;
     const float* qp = qpart + (nq * 32 + j) * NPART;      // the parts in order (128: p0 + p1)
     if constexpr (NPART == 1) qn[nq] = qi < B ? sqrtf(qp[0]) : 0.f;
     else if constexpr (NPART == 2) qn[nq] = qi < B ? sqrtf(qp[0] + qp[1]) : 0.f;
@@ -578,7 +590,11 @@ __global__ __launch_bounds__((SAMPLE ? KNN_SAMPLE_WAVES : NWF) * 64) void crd_ba
             float v = den > 0.f ? acc[nq][r] / den : 0.f;
             if (masked) v = 0.f;
             const u64 key = knn_key(v, row);
-            if (key >= tk[nq] && key > L[nq][TOPK_MAX - 1]) knn_insert(L[nq], key);
+            if constexpr (WIN) {      // (keys are unique: the windows [thr, ub) of successive passes hold successive ranks)
+              if (key >= tk[nq] && key < uk[nq] && key > L[nq][TOPK_MAX - 1]) knn_insert(L[nq], key);
+            } else {
+              if (key >= tk[nq] && key > L[nq][TOPK_MAX - 1]) knn_insert(L[nq], key);
+            }
           }
         }
       }
@@ -667,6 +683,37 @@ __global__ __launch_bounds__(256) void crd_knn_thr_kernel(const u64* __restrict_
   });
 }
 
+// (crd_knn_thr_kernel_win and crd_knn_merge_kernel_win below repeat the bodies of crd_knn_thr_kernel and crd_knn_merge_kernel on
+// purpose: the two kernels of the num_pos <= TOPK_MAX call keep their text, argument lists and instruction streams.)
+// stage 2 for num_pos > TOPK_MAX, once for all npass = ceil(num_pos / TOPK_MAX) windows: win[p] = the record of pass p,
+// [thr bank 0 | thr bank 1 | ub bank 0 | ub bank 1][B].  thr of pass p = the TOPK_MAX (p + 1)-th largest group maximum (0 when
+// there are fewer), peeled TOPK_MAX at a time: pass p keeps the maxima below the last one pass p - 1 kept.  ub of pass 0 = all
+// ones; the merge of pass p writes ub of pass p + 1.
+__global__ __launch_bounds__(256) void crd_knn_thr_kernel_win(const u64* __restrict__ gmax, int ng, int npass, u64* __restrict__ win) {
+  __shared__ u64 below_s;
+  const int b = blockIdx.x, bank = blockIdx.y, B = gridDim.x;
+  const u64* g = gmax + ((size_t)bank * B + b) * ng;
+  if (threadIdx.x == 0) win[(size_t)(2 + bank) * B + b] = ~0ull;
+  u64 below = ~0ull;
+  for (int p = 0; p < npass; ++p) {
+    u64 L[TOPK_MAX];
+#pragma unroll
+    for (int k = 0; k < TOPK_MAX; ++k) L[k] = 0;
+    for (int e = threadIdx.x; e < ng; e += 256) {
+      const u64 key = g[e];
+      if (key < below && key > L[TOPK_MAX - 1]) knn_insert(L, key);
+    }
+    knn_block_best(L, TOPK_MAX, [&](int pick, u64 v) {
+      if (pick == TOPK_MAX - 1) {
+        win[((size_t)p * 4 + bank) * B + b] = v;
+        below_s = v;
+      }
+    });
+    __syncthreads();      // (also: wave 0 has read this round's wk before any wave writes the next round's)
+    below = below_s;      // (0 = fewer maxima than that: nothing is kept from here on, thr = 0)
+  }
+}
+
 // stage 4: the NP best of the keys a (query, bank) was left with, planes [k][list]
 __global__ __launch_bounds__(256) void crd_knn_merge_kernel(const u64* __restrict__ cand, int nlists, int NP, int64_t* __restrict__ nb1,
                                                             int64_t* __restrict__ nb2, float* __restrict__ sim1,
@@ -688,6 +735,31 @@ __global__ __launch_bounds__(256) void crd_knn_merge_kernel(const u64* __restric
   });
 }
 
+// stage 4 of a rank window: ranks r0 .. r0 + cnt - 1 of the NP results = the best of the window's keys; their TOPK_MAX-th is the
+// next window's upper bound (ub_next; 0 = the bank is exhausted, no key is below it; NULL behind the last window)
+__global__ __launch_bounds__(256) void crd_knn_merge_kernel_win(const u64* __restrict__ cand, int nlists, int NP, int r0, int cnt,
+                                                                u64* __restrict__ ub_next, int64_t* __restrict__ nb1,
+                                                                int64_t* __restrict__ nb2, float* __restrict__ sim1,
+                                                                float* __restrict__ sim2) {
+  const int b = blockIdx.x, bank = blockIdx.y;
+  const u64* c = cand + ((size_t)bank * gridDim.x + b) * TOPK_MAX * nlists;
+  u64 L[TOPK_MAX];
+#pragma unroll
+  for (int k = 0; k < TOPK_MAX; ++k) L[k] = 0;
+  for (int e = threadIdx.x; e < nlists; e += 256)
+    for (int k = 0; k < TOPK_MAX; ++k) {
+      const u64 key = c[(size_t)k * nlists + e];
+      if (!key) break;
+      if (key > L[TOPK_MAX - 1]) knn_insert(L, key);
+    }
+  knn_block_best(L, ub_next ? TOPK_MAX : cnt, [&](int pick, u64 v) {
+    if (pick < cnt) {
+      (bank ? nb2 : nb1)[(size_t)b * NP + r0 + pick] = v ? (int64_t)(~(unsigned)v) : (int64_t)0x7fffffff;
+      (bank ? sim2 : sim1)[(size_t)b * NP + r0 + pick] = v ? knn_value(v) : -INFINITY;
+    }
+    if (ub_next && pick == TOPK_MAX - 1) ub_next[(size_t)bank * gridDim.x + b] = v;
+  });
+}
 
 // ---- class-mean bank rows (MIA-2023 `pos_extra == "centers"`, nce_p == 2; reference
 // "MIA 2023/stage2_unimodal_student/CL_utils/CRD_criterion_v10.py":84-89,121-126: torch.mean over the bank rows of
@@ -902,7 +974,9 @@ __global__ __launch_bounds__(64) void crd_scan_neg_finish_kernel(const float* __
   } while (0)
 
 // workspace: list keys [2][B][TOPK_MAX][nlists] u64 | group maxima [2][B][2 * stiles] | thr [2][B]  (B <= 64 per pass; sized for
-// eight lists per workgroup, the four-wave form of width 256 uses half of them)
+// eight lists per workgroup, the four-wave form of width 256 uses half of them).  num_pos > TOPK_MAX: the tail is one record
+// [thr bank 0 | thr bank 1 | ub bank 0 | ub bank 1][B] per rank window instead of thr (crd_knn_thr_kernel_win)
+constexpr int KNN_MAX_POS = 64;
 static inline int knn_gx(int n_data) {
   const int g = cdiv(cdiv(n_data, 32), KNN_WAVES);
   return g < KNN_MAX_GX ? g : KNN_MAX_GX;      // one workgroup per CU over the two banks; a wave walks its tiles
@@ -916,10 +990,16 @@ size_t ph_crd_bank_topk_workspace_bytes(int B, int n_data) {
   return 2 * bc * ((size_t)knn_gx(n_data) * KNN_WAVES * TOPK_MAX + 2 * knn_stiles(n_data) + 1) * sizeof(u64) + 256;
 }
 
+size_t ph_crd_bank_topk_workspace_bytes_np(int B, int n_data, int num_pos) {
+  if (num_pos < 1 || num_pos > KNN_MAX_POS) return 0;
+  const size_t bc = B < KNN_MAX_B ? B : KNN_MAX_B, npass = cdiv(num_pos, TOPK_MAX);
+  return ph_crd_bank_topk_workspace_bytes(B, n_data) + (npass > 1 ? 2 * bc * (2 * npass - 1) * sizeof(u64) : 0);
+}
+
 int ph_crd_bank_topk(const float* mem1, const float* mem2, const int* labels, const int64_t* idx, int PK,
                      const int64_t* batch_label, int B, int n_data, int num_pos, int feat_dim, int64_t* nb1,
                      int64_t* nb2, float* sim1, float* sim2, void* workspace, hipStream_t st) {
-  if (!crd_width_ok(feat_dim) || num_pos < 1 || num_pos > TOPK_MAX || !workspace || B < 1 || n_data < 1) return PH_EINVAL;
+  if (!crd_width_ok(feat_dim) || num_pos < 1 || num_pos > KNN_MAX_POS || !workspace || B < 1 || n_data < 1) return PH_EINVAL;
   if (B > KNN_MAX_B) {
     // a lane selects for one query per 32-query block and two blocks fill its registers (accumulators + lists): larger batches
     // (the reference has no limit; a replica batch of 256 is the north-star size) run in chunks of 64 queries through the same
@@ -943,37 +1023,61 @@ int ph_crd_bank_topk(const float* mem1, const float* mem2, const int* labels, co
   void* tok = nullptr;
   if (ph_prof_on())   // algorithmic bytes: every row of both banks once + the row labels + the 2 x B x num_pos results
     ph_prof_begin(PH_CLS_CRD_TOPK, 2.0 * n_data * feat_dim * 4 + 4.0 * n_data + 2.0 * B * num_pos * 12, st, &tok);
-#define PH_KNN_LAUNCH(DW, N, SAMPLE, GX, GZ) PH_KNN_LAUNCH_W(DW, N, SAMPLE, KNN_WAVES, GX, GZ)
-#define PH_KNN_LAUNCH_W(DW, N, SAMPLE, NWF, GX, GZ)                                                                             \
+  // num_pos > TOPK_MAX runs as rank windows of TOPK_MAX: sample pass and thresholds once, then a full
+  // pass and a merge per window, 2 + 2 npass launches; `thr` of a window's full pass is its record in the workspace
+  const int npass = cdiv(num_pos, TOPK_MAX);
+  // THR: the threshold pointer the kernel reads - `thr` of the one pass, or the record of a window
+#define PH_KNN_LAUNCH(DW, N, SAMPLE, GX, GZ) PH_KNN_LAUNCH_W(DW, N, SAMPLE, KNN_WAVES, false, thr, GX, GZ)
+#define PH_KNN_LAUNCH_W(DW, N, SAMPLE, NWF, WIN, THR, GX, GZ)                                                               \
   do {                                                                                                                      \
     constexpr int NW = SAMPLE ? KNN_SAMPLE_WAVES : NWF;                                                                     \
     constexpr size_t lds = knn_lds_bytes(DW, N, NW);                                                                        \
     static_assert(lds <= 160 * 1024, "LDS of a CU");                                                                        \
     static bool done = false;                                                                                               \
     if (!done) {                                                                                                            \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(crd_bank_knn_kernel<DW, N, SAMPLE, NWF>),                       \
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(crd_bank_knn_kernel<DW, N, SAMPLE, NWF, WIN>),                  \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)                          \
         return PH_ELAUNCH;                                                                                                  \
       done = true;                                                                                                          \
     }                                                                                                                       \
-    hipLaunchKernelGGL((crd_bank_knn_kernel<DW, N, SAMPLE, NWF>), dim3(GX, 2, GZ), dim3(NW * 64), lds, st, mem1, mem2, labels, idx, \
-                       PK, batch_label, B, n_data, stiles, tstride, gmax, thr, cand);                                       \
+    hipLaunchKernelGGL((crd_bank_knn_kernel<DW, N, SAMPLE, NWF, WIN>), dim3(GX, 2, GZ), dim3(NW * 64), lds, st, mem1, mem2, \
+                       labels, idx, PK, batch_label, B, n_data, stiles, tstride, gmax, THR, cand);                          \
   } while (0)
   // one 32-query block per workgroup (grid z)
   if (feat_dim == 64) PH_KNN_LAUNCH(64, 1, true, cdiv(stiles, KNN_SAMPLE_WAVES), nq);
   else if (feat_dim == 128) PH_KNN_LAUNCH(128, 1, true, cdiv(stiles, KNN_SAMPLE_WAVES), nq);
   else PH_KNN_LAUNCH(256, 1, true, cdiv(stiles, KNN_SAMPLE_WAVES), nq);
   PH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(crd_knn_thr_kernel, dim3(B, 2), dim3(256), 0, st, gmax, 2 * stiles, thr);
-  PH_LAUNCH_CHECK();
-  if (feat_dim == 64) { if (nq == 1) PH_KNN_LAUNCH(64, 1, false, gx, 1); else PH_KNN_LAUNCH(64, 2, false, gx, 1); }
-  else if (feat_dim == 128) { if (nq == 1) PH_KNN_LAUNCH(128, 1, false, gx, 1); else PH_KNN_LAUNCH(128, 2, false, gx, 1); }
-  else if (nq == 1) PH_KNN_LAUNCH(256, 1, false, gx, 1);
-  else PH_KNN_LAUNCH_W(256, 2, false, 4, gx, 1);      // (the four-wave form: 64 queries under one image)
+  // the full pass at every width and query count; 256 x 64 queries is the four-wave form (64 queries under one image)
+#define PH_KNN_FULL(WIN, THR)                                                                                                 \
+  do {                                                                                                                        \
+    if (feat_dim == 64) { if (nq == 1) PH_KNN_LAUNCH_W(64, 1, false, KNN_WAVES, WIN, THR, gx, 1); else PH_KNN_LAUNCH_W(64, 2, false, KNN_WAVES, WIN, THR, gx, 1); } \
+    else if (feat_dim == 128) { if (nq == 1) PH_KNN_LAUNCH_W(128, 1, false, KNN_WAVES, WIN, THR, gx, 1); else PH_KNN_LAUNCH_W(128, 2, false, KNN_WAVES, WIN, THR, gx, 1); } \
+    else if (nq == 1) PH_KNN_LAUNCH_W(256, 1, false, KNN_WAVES, WIN, THR, gx, 1);                                              \
+    else PH_KNN_LAUNCH_W(256, 2, false, 4, WIN, THR, gx, 1);                                                                   \
+  } while (0)
+  if (npass == 1) {
+    hipLaunchKernelGGL(crd_knn_thr_kernel, dim3(B, 2), dim3(256), 0, st, gmax, 2 * stiles, thr);
+    PH_LAUNCH_CHECK();
+    PH_KNN_FULL(false, thr);
+    PH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(crd_knn_merge_kernel, dim3(B, 2), dim3(256), 0, st, cand, nlists, num_pos, nb1, nb2, sim1, sim2);
+  } else {
+    u64* win = thr;
+    hipLaunchKernelGGL(crd_knn_thr_kernel_win, dim3(B, 2), dim3(256), 0, st, gmax, 2 * stiles, npass, win);
+    for (int p = 0; p < npass; ++p) {
+      PH_LAUNCH_CHECK();
+      const u64* rec = win + (size_t)p * 4 * B;      // the record of window p
+      PH_KNN_FULL(true, rec);
+      PH_LAUNCH_CHECK();
+      const int r0 = p * TOPK_MAX, cnt = num_pos - r0 < TOPK_MAX ? num_pos - r0 : TOPK_MAX;
+      hipLaunchKernelGGL(crd_knn_merge_kernel_win, dim3(B, 2), dim3(256), 0, st, cand, nlists, num_pos, r0, cnt,
+                         p + 1 < npass ? win + (size_t)(p + 1) * 4 * B + 2 * B : nullptr, nb1, nb2, sim1, sim2);
+    }
+  }
+#undef PH_KNN_FULL
 #undef PH_KNN_LAUNCH
 #undef PH_KNN_LAUNCH_W
-  PH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(crd_knn_merge_kernel, dim3(B, 2), dim3(256), 0, st, cand, nlists, num_pos, nb1, nb2, sim1, sim2);
   ph_prof_end(tok, st);
   PH_LAUNCH_CHECK();
   return PH_OK;
