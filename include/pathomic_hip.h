@@ -303,6 +303,19 @@ int ph_crd_kmeans_centers(float* mem1_ext, float* mem2_ext, const int* members, 
  * GK-Refine (AEKD_loss, train_test_path_multi_distill.py:41-70) and optimiser
  * (networks_new.py:85 Adam; train_test_path_multi_distill.py:34-38 update_ema_variables)
  * ---------------------------------------------------------------------------------------------- */
+/* Argument rule of the GK-Refine entries, the masks (ph_superpixel_mask, ph_topk_threshold_mask, ph_apply_mask) and the
+ * flat-buffer updates and reductions (both Adam forms, ph_adagrad_ema_step_dev, ph_ema_update, ph_ema_update_dev, ph_l1_sum,
+ * ph_l1_sign_axpy, ph_sigmoid_range_fwd / _bwd, ph_sqdiff_sum, ph_scaled_diff, ph_maxnorm_mix); all of it is decided on the
+ * host before anything is launched:
+ *   - a NULL required pointer returns PH_EINVAL.  Optional (may be NULL) are only: ema; losses (with nl == 0) and total of
+ *     ph_gk_scale; mo_init (every call is then a first call); e_dev (= 1); mean_out; coef_dev (= 1).
+ *   - n == 0 on an elementwise update (both Adam forms, Adagrad, ph_ema_update, ph_ema_update_dev, ph_scaled_diff,
+ *     ph_l1_sign_axpy) returns PH_OK and launches nothing.  The reductions: ph_gram needs n >= 1 and ph_maxnorm_mix n >= 1
+ *     (PH_EINVAL otherwise: a cosine or a maximum of nothing); ph_sqdiff_sum and ph_l1_sum of n == 0 write 0 (* scale).
+ *   - alignment: p, g, m, v and ema of both Adam forms are read and written four floats at a time and must be 16-byte aligned
+ *     (train_step.FlatParams places every tensor so); a misaligned one returns PH_EINVAL.  n itself is free: the last 1..3
+ *     elements take a scalar path and nothing at or beyond index n is touched.  The other entries need float alignment only.
+ * ph_gram: ng in 2..5 (else PH_EINVAL).  ph_gk_scale: ng >= 1, 0 <= nl <= ng.  ph_gk_scale_momentum: ng >= 1. */
 int ph_gram(const float* G /* [ng][n] */, float* gram /* [ng*ng] */, int ng, int n, ph_stream_t stream);
 int ph_gk_scale(const float* gram, const float* const* losses /* device array of nl device scalars */, int ng, int nl,
                 float mult, float* scale, float* total, ph_stream_t stream);
@@ -337,7 +350,7 @@ int ph_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema /*
 /* HIP-graph-replayable form: hyper = device float[5] {lr, 1-beta1^t, sqrt(1-beta2^t), ema_alpha, 1-ema_alpha}.  beta1 < 0: the
  * betas are read from device memory too, hyper = float[12] with [8..11] = {beta1, 1-beta1, beta2, 1-beta2} (a schedule that
  * cycles beta1 - lr_policy onecycle, networks_new.py:124-125 - reaches a launch replayed from a captured graph) */
-int ph_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema, size_t n, double beta1,
+int ph_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema /* may be NULL */, size_t n, double beta1,
                          double beta2, double eps, double weight_decay, const float* hyper, ph_stream_t stream);
 /* torch.optim.Adagrad as define_optimizer builds it (reference MICCAI-2022/networks_new.py:86-87: lr, weight_decay,
  * initial_accumulator_value = 0.1, lr_decay 0, eps 1e-10): g' = g + wd p, sum += g'^2, p -= lr g' / (sqrt(sum) + eps), with the

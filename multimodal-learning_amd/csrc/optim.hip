@@ -322,6 +322,9 @@ __global__ void l1_sign_axpy_kernel(const float* __restrict__ w, float* __restri
   g[i] += x > 0.f ? c : (x < 0.f ? -c : 0.f);     // d|x|/dx = sgn(x), 0 at 0 (torch.abs backward)
 }
 
+// the Adam kernels read and write p, g, m, v (and ema) four floats at a time
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace
 
 int ph_gk_rows(const float* G, int ng, int B, int D, int use_thresh, float thresh, float* all_scale, hipStream_t st) {
@@ -337,6 +340,7 @@ int ph_gk_rows(const float* G, int ng, int B, int D, int use_thresh, float thres
 
 int ph_gk_scale_momentum(const float* gram, int ng, int use_thresh, float thresh, float momentum, float* mo_scale,
                          int* mo_init, hipStream_t st) {
+  if (!gram || !mo_scale || ng < 1) return PH_EINVAL;
   hipLaunchKernelGGL(gk_scale2_kernel, dim3(1), dim3(64), 0, st, gram, ng, use_thresh, thresh, momentum, mo_scale,
                      mo_init);
   PH_LAUNCH_CHECK();
@@ -344,6 +348,7 @@ int ph_gk_scale_momentum(const float* gram, int ng, int use_thresh, float thresh
 }
 
 int ph_gram(const float* G, float* gram, int ng, int n, hipStream_t st) {
+  if (!G || !gram || n < 1) return PH_EINVAL;
   switch (ng) {
     case 2: hipLaunchKernelGGL(gram_kernel<2>, dim3(1), dim3(1024), 0, st, G, gram, n); break;
     case 3: hipLaunchKernelGGL(gram_kernel<3>, dim3(1), dim3(1024), 0, st, G, gram, n); break;
@@ -357,6 +362,7 @@ int ph_gram(const float* G, float* gram, int ng, int n, hipStream_t st) {
 
 int ph_gk_scale(const float* gram, const float* const* losses, int ng, int nl, float mult, float* scale, float* total,
                 hipStream_t st) {
+  if (!gram || !scale || ng < 1 || nl < 0 || nl > ng || (nl > 0 && !losses)) return PH_EINVAL;
   hipLaunchKernelGGL(gk_scale_kernel, dim3(1), dim3(64), 0, st, gram, losses, ng, nl, mult, scale, total);
   PH_LAUNCH_CHECK();
   return PH_OK;
@@ -364,6 +370,7 @@ int ph_gk_scale(const float* gram, const float* const* losses, int ng, int nl, f
 
 int ph_gk_finish(const float* gram, const float* losses, const float* coef, const float* add, const float* logc, float mult,
                  float* scale_int, float* w, float* total, float* scaled, float* scale_ext, hipStream_t st) {
+  if (!gram || !losses || !coef || !add || !logc || !scale_int || !w || !total || !scaled || !scale_ext) return PH_EINVAL;
   hipLaunchKernelGGL(gk_finish_kernel, dim3(1), dim3(64), 0, st, gram, losses, coef, add, logc, mult, scale_int, w, total,
                      scaled, scale_ext);
   PH_LAUNCH_CHECK();
@@ -382,6 +389,9 @@ int ph_gk_finish_momentum(const float* gram, const float* losses, float alpha, f
 
 int ph_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr, double beta1,
                      double beta2, double eps, double weight_decay, int step, double ema_alpha, hipStream_t st) {
+  if (!p || !g || !m || !v) return PH_EINVAL;
+  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || !aligned16(ema)) return PH_EINVAL;
+  if (n == 0) return PH_OK;
   // bias corrections in double, exactly like torch.optim.Adam's Python-side scalars
   const float bc1 = (float)(1.0 - pow(beta1, (double)step));
   const float bc2s = (float)sqrt(1.0 - pow(beta2, (double)step));
@@ -395,6 +405,9 @@ int ph_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, s
 
 int ph_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema, size_t n, double beta1, double beta2,
                          double eps, double weight_decay, const float* hyper, hipStream_t st) {
+  if (!p || !g || !m || !v || !hyper) return PH_EINVAL;
+  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || !aligned16(ema)) return PH_EINVAL;
+  if (n == 0) return PH_OK;
   const size_t nt = (n + 3) / 4;
   void* tok = nullptr;
   if (ph_prof_on()) ph_prof_begin(PH_CLS_ADAM_EMA, (double)n * (ema ? 36.0 : 28.0), st, &tok);   // p, m, v r/w + g (+ ema r/w)
@@ -418,6 +431,8 @@ int ph_adagrad_ema_step_dev(float* p, const float* g, float* sum, float* ema, si
 }
 
 int ph_ema_update(float* ema, const float* p, size_t n, float alpha, hipStream_t st) {
+  if (!ema || !p) return PH_EINVAL;
+  if (n == 0) return PH_OK;
   hipLaunchKernelGGL(ema_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ema, p, n, alpha);
   PH_LAUNCH_CHECK();
   return PH_OK;

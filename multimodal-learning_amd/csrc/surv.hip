@@ -321,7 +321,8 @@ int ph_sigmoid_range_bwd(const float* dpred, const float* sigma, const float* ra
 }
 
 int ph_ema_update_dev(float* ema, const float* p, size_t n, const float* hyper, hipStream_t st) {
-  if (!ema || !p || !hyper || n < 1) return PH_EINVAL;
+  if (!ema || !p || !hyper) return PH_EINVAL;
+  if (n == 0) return PH_OK;
   hipLaunchKernelGGL(ema_update_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ema, p, n, hyper);
   PH_LAUNCH_CHECK();
   return PH_OK;

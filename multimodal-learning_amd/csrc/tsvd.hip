@@ -783,6 +783,7 @@ size_t ph_tsvd_workspace_bytes(int V, int B) {
 }
 
 int ph_sqdiff_sum(const float* a, const float* b, float* out, size_t n, float scale, hipStream_t st) {
+  if (!a || !b || !out) return PH_EINVAL;
   hipLaunchKernelGGL(sqdiff_sum_kernel, dim3(1), dim3(1024), 0, st, a, b, out, n, scale);
   PH_LAUNCH_CHECK();
   return PH_OK;
@@ -797,6 +798,8 @@ int ph_maxnorm_mix(const float* a, const float* b, float* out, size_t n, float w
 
 int ph_scaled_diff(const float* a, const float* b, const float* gscalar, float alpha, float* out, size_t n,
                    hipStream_t st) {
+  if (!a || !b || !gscalar || !out) return PH_EINVAL;
+  if (n == 0) return PH_OK;
   hipLaunchKernelGGL(scaled_diff_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, b, gscalar, alpha, out, n);
   PH_LAUNCH_CHECK();
   return PH_OK;
