@@ -9,6 +9,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import lib, check, ptr, stream
+from .step_graph import StepGraphs
 
 
 # ----------------------------------------------------------------------------------------- flat storage
@@ -92,6 +93,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._hyper = None        # device float[12] {lr, 1-beta1^t, sqrt(1-beta2^t), ema_alpha, 1-ema_alpha, 0, 0, 0, beta1, 1-beta1, beta2, 1-beta2}: graph-replayable
         self._hyper_host = None
         self._prepared = False
+        self._inactive = None     # ids of the parameters that take no part in the objective (set_inactive)
+
+    def _active(self, t):
+        return t.requires_grad and (self._inactive is None or id(t) not in self._inactive)
 
     def _ensure_flat(self):
         if self._flat is None:
@@ -101,8 +106,7 @@ class FusedAdam(torch.optim.Optimizer):
             self._flat = FlatParams(ps, with_grad=True)
             self._m = torch.zeros_like(self._flat.flat)
             self._v = torch.zeros_like(self._flat.flat)
-            inactive = getattr(self, "_inactive", ())
-            self._segs = self._flat.segments(lambda t: t.requires_grad and id(t) not in inactive)
+            self._segs = self._flat.segments(self._active)
             self._hyper = torch.zeros(12, device=ps[0].device, dtype=torch.float32)
             self._hyper_host = PinnedRing((12,), torch.float32)
             ops.bump_weight_epoch()
@@ -133,7 +137,7 @@ class FusedAdam(torch.optim.Optimizer):
         gradient buffer would hand the kernel a zero gradient and decay the weights.  Their segments leave the update."""
         self._inactive = {id(p) for p in params}
         if self._flat is not None:
-            self._segs = self._flat.segments(lambda t: t.requires_grad and id(t) not in self._inactive)
+            self._segs = self._flat.segments(self._active)
 
     def zero_grad(self, set_to_none=False):
         """Gradients are views of one flat buffer: zeroing is a single memset and the views persist."""
@@ -143,28 +147,31 @@ class FusedAdam(torch.optim.Optimizer):
             if t.requires_grad and (t.grad is None or t.grad.data_ptr() != f.grad.data_ptr() + 4 * o):
                 t.grad = f.grad[o:o + t.numel()].view(t.shape)
 
-    @torch.no_grad()
-    def step(self, closure=None):
+    def _begin_step(self):
+        """What every step starts with: a gradient tensor torch re-allocated (e.g. after zero_grad(set_to_none=True)) is
+        copied back into the flat buffer, and the step scalars are uploaded unless prepare_step() already did."""
         f = self._ensure_flat()
-        # a gradient tensor torch re-allocated (e.g. after zero_grad(set_to_none=True)) is copied back
         for t, o in zip(f.tensors, f.offsets):
             if t.requires_grad and t.grad is not None and t.grad.data_ptr() != f.grad.data_ptr() + 4 * o:
                 f.grad[o:o + t.numel()].copy_(t.grad.reshape(-1))
                 t.grad = f.grad[o:o + t.numel()].view(t.shape)
-        g = self.param_groups[0]
         if not self._prepared:
             self.prepare_step()
         self._prepared = False
-        segs = []
-        for (s, e) in self._segs:      # split at the EMA boundary (student params | embed params)
-            if self.ema_flat is not None and self.ema_range is not None and s < self.ema_range[1] < e:
-                segs += [(s, self.ema_range[1]), (self.ema_range[1], e)]
-            else:
-                segs.append((s, e))
-        for (s, e) in segs:
-            ema = None
-            if self.ema_flat is not None and self.ema_range is not None and s >= self.ema_range[0] and e <= self.ema_range[1]:
-                ema = self.ema_flat.flat[s:e]
+        return f, self.param_groups[0]
+
+    def _ema_segments(self):
+        """(start, end, EMA slice or None) of the updated segments, split at the EMA boundary (student params | embed params)."""
+        ema_on = self.ema_flat is not None and self.ema_range is not None
+        for (s, e) in self._segs:
+            cuts = [s, self.ema_range[1], e] if ema_on and s < self.ema_range[1] < e else [s, e]
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                yield a, b, (self.ema_flat.flat[a:b] if ema_on and a >= self.ema_range[0] and b <= self.ema_range[1] else None)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        f, g = self._begin_step()
+        for s, e, ema in self._ema_segments():
             check(lib().ph_adam_ema_step_dev(ptr(f.flat[s:e]), ptr(f.grad[s:e]), ptr(self._m[s:e]), ptr(self._v[s:e]),
                                              ptr(ema), e - s, -1.0, g["betas"][1], g["eps"],      # (beta1 < 0: betas from hyper[8..11])
                                              g["weight_decay"], ptr(self._hyper), stream()), "ph_adam_ema_step_dev")
@@ -181,7 +188,7 @@ class FusedAdam(torch.optim.Optimizer):
                                    exp_avg=self._m[o:o + t.numel()].view(t.shape).clone(),
                                    exp_avg_sq=self._v[o:o + t.numel()].view(t.shape).clone())
                            for i, (t, o) in enumerate(zip(f.tensors, f.offsets))
-                           if t.requires_grad and id(t) not in getattr(self, "_inactive", ())}
+                           if self._active(t)}
         sd["fused"] = dict(step=self._step, exp_avg=None if self._flat is None else self._m.clone(),
                            exp_avg_sq=None if self._flat is None else self._v.clone())
         return sd
@@ -193,22 +200,29 @@ class FusedAdam(torch.optim.Optimizer):
         per_param = sd.get("state") or {}
         sd["state"] = {}                   # the moments live in the flat buffers, not in torch's per-parameter state
         super().load_state_dict(sd)
-        if fused is not None and fused["exp_avg"] is not None:
+        has_fused = fused is not None and fused["exp_avg"] is not None
+        if has_fused or per_param:
             self._ensure_flat()
+            if not has_fused:
+                self._m.zero_(); self._v.zero_()
+            self._restore(fused, per_param, dict(exp_avg=self._m, exp_avg_sq=self._v))
+
+    def _restore(self, fused, per_param, bufs):
+        """The moments `bufs` (state name -> flat buffer) and the step count from the flat copies under "fused" if they are
+        there, else from torch's per-parameter state."""
+        first = next(iter(bufs))
+        if fused is not None and fused.get(first) is not None:
             self._step = fused["step"]
-            self._m.copy_(fused["exp_avg"])
-            self._v.copy_(fused["exp_avg_sq"])
+            for k, b in bufs.items():
+                b.copy_(fused[k])
         elif per_param:
-            f = self._ensure_flat()
-            steps = set()
-            self._m.zero_(); self._v.zero_()
+            f, steps = self._flat, set()
             for i, st in per_param.items():
                 t, o = f.tensors[int(i)], f.offsets[int(i)]
-                if tuple(st["exp_avg"].shape) != tuple(t.shape):
-                    raise ValueError("optimizer state %d has shape %s, parameter %s" % (int(i), tuple(st["exp_avg"].shape),
-                                                                                       tuple(t.shape)))
-                self._m[o:o + t.numel()].copy_(st["exp_avg"].reshape(-1))
-                self._v[o:o + t.numel()].copy_(st["exp_avg_sq"].reshape(-1))
+                if tuple(st[first].shape) != tuple(t.shape):
+                    raise ValueError("optimizer state %d has shape %s, parameter %s" % (int(i), tuple(st[first].shape), tuple(t.shape)))
+                for k, b in bufs.items():
+                    b[o:o + t.numel()].copy_(st[k].reshape(-1))
                 steps.add(int(float(st["step"])))
             if len(steps) != 1:
                 raise NotImplementedError("per-parameter step counts differ (%s): the fused kernel keeps one" % sorted(steps))
@@ -228,7 +242,7 @@ class FusedAdagrad(FusedAdam):
         self._flat = None
         self._step = 0
         self.ema_flat = self.ema_alpha = self.ema_range = None
-        self._hyper = self._hyper_host = None
+        self._hyper = self._hyper_host = self._inactive = None
         self._prepared = False
 
     def _ensure_flat(self):
@@ -247,26 +261,11 @@ class FusedAdagrad(FusedAdam):
 
     @torch.no_grad()
     def step(self, closure=None):
-        f = self._ensure_flat()
-        for t, o in zip(f.tensors, f.offsets):
-            if t.requires_grad and t.grad is not None and t.grad.data_ptr() != f.grad.data_ptr() + 4 * o:
-                f.grad[o:o + t.numel()].copy_(t.grad.reshape(-1))
-                t.grad = f.grad[o:o + t.numel()].view(t.shape)
-        g = self.param_groups[0]
-        if not self._prepared:
-            self.prepare_step()
-        self._prepared = False
-        for (s, e) in self._segs:
-            cuts = [s, e]
-            if self.ema_flat is not None and self.ema_range is not None and s < self.ema_range[1] < e:
-                cuts = [s, self.ema_range[1], e]
-            for a, b in zip(cuts[:-1], cuts[1:]):
-                ema = None
-                if self.ema_flat is not None and self.ema_range is not None and a >= self.ema_range[0] and b <= self.ema_range[1]:
-                    ema = self.ema_flat.flat[a:b]
-                check(lib().ph_adagrad_ema_step_dev(ptr(f.flat[a:b]), ptr(f.grad[a:b]), ptr(self._v[a:b]), ptr(ema), b - a,
-                                                    g["eps"], g["weight_decay"], ptr(self._hyper), stream()),
-                      "ph_adagrad_ema_step_dev")
+        f, g = self._begin_step()
+        for a, b, ema in self._ema_segments():
+            check(lib().ph_adagrad_ema_step_dev(ptr(f.flat[a:b]), ptr(f.grad[a:b]), ptr(self._v[a:b]), ptr(ema), b - a,
+                                                g["eps"], g["weight_decay"], ptr(self._hyper), stream()),
+                  "ph_adagrad_ema_step_dev")
         ops.bump_weight_epoch()
 
     def state_dict(self):
@@ -277,15 +276,14 @@ class FusedAdagrad(FusedAdam):
         still advance - unless the owner declares it unused (`set_inactive`, what DistillStep does for the option branches that
         leave a criterion idle)."""
         sd = torch.optim.Optimizer.state_dict(self)
-        inactive = getattr(self, "_inactive", ())
         if self._flat is not None:
             f = self._flat
             sd["state"] = {i: dict(step=torch.tensor(float(self._step)), sum=self._v[o:o + t.numel()].view(t.shape).clone())
-                           for i, (t, o) in enumerate(zip(f.tensors, f.offsets)) if t.requires_grad and id(t) not in inactive}
+                           for i, (t, o) in enumerate(zip(f.tensors, f.offsets)) if self._active(t)}
         else:
             init = float(self.param_groups[0]["initial_accumulator_value"])
             sd["state"] = {i: dict(step=torch.tensor(0.0), sum=torch.full_like(t, init, dtype=torch.float32))
-                           for i, t in enumerate(self.param_groups[0]["params"]) if t.requires_grad and id(t) not in inactive}
+                           for i, t in enumerate(self.param_groups[0]["params"]) if self._active(t)}
         sd["fused"] = dict(step=self._step, sum=None if self._flat is None else self._v.clone())
         return sd
 
@@ -296,23 +294,10 @@ class FusedAdagrad(FusedAdam):
         per_param = sd.get("state") or {}
         sd["state"] = {}
         torch.optim.Optimizer.load_state_dict(self, sd)
-        f = self._ensure_flat()
-        if fused is not None and fused.get("sum") is not None:
-            if tuple(fused["sum"].shape) != tuple(self._v.shape):
-                raise ValueError("fused accumulator has %d elements, the parameters %d" % (fused["sum"].numel(), self._v.numel()))
-            self._step = fused["step"]
-            self._v.copy_(fused["sum"])
-        elif per_param:
-            steps = set()
-            for i, st in per_param.items():
-                t, o = f.tensors[int(i)], f.offsets[int(i)]
-                if tuple(st["sum"].shape) != tuple(t.shape):
-                    raise ValueError("optimizer state %d has shape %s, parameter %s" % (int(i), tuple(st["sum"].shape), tuple(t.shape)))
-                self._v[o:o + t.numel()].copy_(st["sum"].reshape(-1))
-                steps.add(int(float(st["step"])))
-            if len(steps) != 1:
-                raise NotImplementedError("per-parameter step counts differ (%s): the fused kernel keeps one" % sorted(steps))
-            self._step = steps.pop()
+        self._ensure_flat()
+        if fused is not None and fused.get("sum") is not None and tuple(fused["sum"].shape) != tuple(self._v.shape):
+            raise ValueError("fused accumulator has %d elements, the parameters %d" % (fused["sum"].numel(), self._v.numel()))
+        self._restore(fused, per_param, dict(sum=self._v))
 
 
 def update_ema_variables(model, ema_model, alpha, global_step):
@@ -412,6 +397,15 @@ def _validate_opt(opt, who, surv_ok=False):
 
 
 # ----------------------------------------------------------------------------------------- the hot loop
+def _backward_and_update(step, loss):
+    """The end of a step (train_test_path_multi_distill.py:326-329): backward, the replicas' gradient sum, fused update + EMA."""
+    step.optimizer.zero_grad()
+    loss.backward()
+    if step.sync is not None:
+        step.sync.all_reduce_grads(step.optimizer.flat)
+    step.optimizer.step()
+
+
 class DistillStep:
     """The batch body of train() (train_test_path_multi_distill.py:242-330) over the drop-in modules:
     student fwd, EMA fwd, teacher fwd, CE + 2xKL + 2xCRD, GK-Refine, backward, fused Adam + EMA.
@@ -449,6 +443,9 @@ class DistillStep:
                              "widths [64, 128, 256]" % opt.path_dim)
         self._mo_state = None     # momentum GK-Refine weights (mia2022), updated in place on the device
         self.sampler = None       # optional ContrastIndexSampler: draws sample_idx when the batch carries None
+        self.loader = None        # optional augment.ResidentTileLoader: step(None) takes its batches from it
+        self._loader_bt = self._sample_idx_buf = self._capture_pre = None
+        self._e_dev = None        # the epoch weight (mia2022) / re-weighting switch (mia2023) as a persistent device scalar
         self._mo_init = None
         self.opt = opt
         self.device = torch.device(device)
@@ -507,8 +504,8 @@ class DistillStep:
             self.optimizer.set_inactive([p for c in unused for m_ in (c.embed_s, c.embed_t) for p in m_.parameters()])
         self.iter_num = opt.global_step
         self._want_graph = False
-        self._static = None
-        self._slots = None
+        self._static = None       # the input set of the last graph step
+        self._slots = None        # the StepGraphs of the graph path, built on first need; None drops every captured graph
         self._side_stream = torch.cuda.Stream(device=self.device) if getattr(opt, "overlap_teachers", True) else None
         # the fused teacher on a third stream (opt.teacher_streams = 1: behind the mean teacher on the second)
         self._side_stream2 = (torch.cuda.Stream(device=self.device)
@@ -681,11 +678,7 @@ class DistillStep:
             scale = None
             loss_KD = loss_div1 + loss_div2 + loss_kd1 + loss_kd2                                           # :309
         loss = self._add_reg(opt.lambda_nll * loss_cls + loss_KD)                                           # :312-313
-        self.optimizer.zero_grad()                                                                          # :326
-        loss.backward()                                                                                     # :327
-        if self.sync is not None:
-            self.sync.all_reduce_grads(self.optimizer.flat)
-        self.optimizer.step()                                                                               # :328 (+ :329 fused)
+        _backward_and_update(self, loss)                                                                    # :326-329
         return dict(loss=loss.detach(), loss_cls=loss_cls.detach(), loss_div1=loss_div1.detach(),
                     loss_div2=loss_div2.detach(), loss_kd1=loss_kd1.detach(), loss_kd2=loss_kd2.detach(),
                     scale=scale, logit_path=logit_path.detach(), pred_path=pred_path.detach(),
@@ -731,11 +724,7 @@ class DistillStep:
         else:
             loss_KD = opt.alpha * loss_div + opt.beta * loss_kd                                             # :482
         loss = self._add_reg(opt.lambda_nll * loss_cls + loss_KD)                                           # :485-486
-        self.optimizer.zero_grad()
-        loss.backward()
-        if self.sync is not None:
-            self.sync.all_reduce_grads(self.optimizer.flat)
-        self.optimizer.step()
+        _backward_and_update(self, loss)
         loss, loss_kd = loss.detach(), loss_kd.detach()
         if self.sync is not None and opt.distill in ("pkt", "similarity"):
             # every replica holds the global value: report 1 / world of it (the replicas' reports add up)
@@ -821,11 +810,7 @@ class DistillStep:
         else:
             loss_KD = opt.alpha * loss_div + opt.beta * loss_kd                                             # :309
         loss = self._add_reg(opt.lambda_nll * loss_cls + loss_KD)                                           # :312-313
-        self.optimizer.zero_grad()
-        loss.backward()
-        if self.sync is not None:
-            self.sync.all_reduce_grads(self.optimizer.flat)
-        self.optimizer.step()
+        _backward_and_update(self, loss)
         dt = lambda t: t.detach() if torch.is_tensor(t) else t      # noqa: E731
         return dict(loss=loss.detach(), loss_cls=loss_cls.detach(), loss_div1=dt(opt.alpha * loss_div1),
                     loss_div2=dt(opt.alpha * loss_div2), loss_kd1=dt(opt.beta * loss_kd1), loss_kd2=dt(opt.beta * loss_kd2),
@@ -856,7 +841,7 @@ class DistillStep:
             # the fused head WRITES fc_new2's gradients (accumulate=False) after L1RegFn.backward has added
             # lambda_reg * sgn(W) into the same flat buffer: the L1 term on fc_new2 would be lost
             return False
-        if self.variant != "miccai2022" and (self.zoo_kd is not None or not torch.is_tensor(getattr(self, "_e_dev", None))):
+        if self.variant != "miccai2022" and (self.zoo_kd is not None or not torch.is_tensor(self._e_dev)):
             return False
         if self.variant == "mia2023" and (getattr(opt, "loss_weighting", "GK_refine") != "GK_refine"
                                           or getattr(opt, "pos_extra", "neighbors") != "neighbors"):
@@ -893,11 +878,7 @@ class DistillStep:
             scale = None
             loss_KD = opt.alpha * (loss_div1 + loss_div2) + opt.beta * (loss_kd1 + loss_kd2)                # :427
         loss = self._add_reg(opt.lambda_nll * loss_cls + loss_KD)                                           # :430-431
-        self.optimizer.zero_grad()
-        loss.backward()
-        if self.sync is not None:
-            self.sync.all_reduce_grads(self.optimizer.flat)
-        self.optimizer.step()                                                                               # :446-447 fused
+        _backward_and_update(self, loss)                                                                    # :446-447 fused
         return dict(loss=loss.detach(), loss_cls=loss_cls.detach(), loss_div1=loss_div1.detach(),
                     loss_div2=loss_div2.detach(), loss_kd1=loss_kd1.detach(), loss_kd2=loss_kd2.detach(),
                     rows_div1=rows_div1.detach(), rows_kd1=rows_kd1.detach(), w1=w1.detach(), w2=w2.detach(),
@@ -961,11 +942,11 @@ class DistillStep:
             # resident tile store.  In graph mode the loader's launches are captured IN FRONT of the step's own, so a
             # replay is the whole iteration - shuffle indices, both augmented views, contrast indices, step - and the host
             # launches nothing in between (eager launches between replays cost 1-4 ms per step on this runtime).
-            loader = getattr(self, "loader", None)
+            loader = self.loader
             if loader is None:
                 raise ValueError("step(None) needs step.loader (augment.ResidentTileLoader)")
-            in_graph = getattr(self, "_want_graph", False) and self.iter_num - opt.global_step >= 2
-            if getattr(self, "_loader_bt", None) is None:
+            in_graph = self._want_graph and self.iter_num - opt.global_step >= 2
+            if self._loader_bt is None:
                 self._loader_bt = loader.next(opt.batch_size)          # allocates the resident input set
             elif not in_graph:
                 loader.next(into=self._loader_bt)
@@ -977,9 +958,9 @@ class DistillStep:
         if sample_idx is None:
             # the loader's contrast-index draw (data_loaders_MT.py:229-249) on the device: set `step.sampler` to a
             # ContrastIndexSampler built from the training labels; one launch per step, outside the captured graph
-            if getattr(self, "sampler", None) is None:
+            if self.sampler is None:
                 raise ValueError("the batch carries no sample_idx and no step.sampler (ContrastIndexSampler) is set")
-            buf = getattr(self, "_sample_idx_buf", None)
+            buf = self._sample_idx_buf
             if buf is None or buf.shape[0] != index.shape[0]:
                 buf = self._sample_idx_buf = torch.empty(index.shape[0], self.sampler.width, device=dev, dtype=torch.int64)
             sample_idx = self.sampler(index, grade, out=buf)
@@ -988,20 +969,15 @@ class DistillStep:
         self.criterion_kd.contrast.batch_norm_size = bnorm
         self.criterion_kd_path.contrast.batch_norm_size = bnorm
         e, rk = self._draw_ranks(epoch, ranks)
-        if self.variant == "mia2022":
-            # the epoch weight multiplies the CRD loss on the device: one persistent scalar so a captured graph
-            # reads the current value instead of baking the capture-time epoch in
-            if getattr(self, "_e_dev", None) is None:
+        if self.variant != "miccai2022":
+            # the epoch weight multiplies the CRD loss on the device (mia2022) / switches the re-weighting on (mia2023, :373):
+            # one persistent scalar so a captured graph reads the current value instead of baking the capture-time epoch in
+            if self._e_dev is None:
                 self._e_dev = torch.zeros(1, device=dev, dtype=torch.float32)
-            self._e_dev.fill_(float(e))
-            e = self._e_dev
-        elif self.variant == "mia2023":
-            if getattr(self, "_e_dev", None) is None:
-                self._e_dev = torch.zeros(1, device=dev, dtype=torch.float32)
-            self._e_dev.fill_(0.0 if epoch < opt.start_reweight else 1.0)         # the re-weighting switch (:373)
+            self._e_dev.fill_(float(e) if self.variant == "mia2022" else 0.0 if epoch < opt.start_reweight else 1.0)
             e = self._e_dev
         self.optimizer.ema_alpha = min(1 - 1 / (self.iter_num + 1), opt.ema_decay)                          # :36
-        use_graph = getattr(self, "_want_graph", False) and self.iter_num - opt.global_step >= 2
+        use_graph = self._want_graph and self.iter_num - opt.global_step >= 2
         if not use_graph:
             x_path = x_path.to(dev, non_blocking=True)                             # ONE H2D copy (reference: three)
             ema_x_path = ema_x_path.to(dev, non_blocking=True)
@@ -1014,22 +990,20 @@ class DistillStep:
             out = self._device_body(x_path, ema_x_path, x_omic, grade, index, sample_idx, bnorm, e, r1, r2)
             self.iter_num += 1
             return out
-        # ---- graph path: per-step scalars in device memory, inputs at fixed addresses.  A captured graph reads its
-        # inputs from the addresses it was captured with.  If the caller hands over DEVICE tensors (a loader's ring of
-        # resident batch buffers), up to two such input sets are adopted as they are - one captured graph each, sharing
-        # one memory pool - and replayed without any copy; anything else (host tensors, more than two sets) is staged
-        # into the first set's buffers by device-to-device / host-to-device copies (2 x 76 us for two 201 MB views).
+        # ---- graph path: per-step scalars in device memory, inputs at fixed addresses (step_graph.py: resident input sets
+        # are adopted and replayed without a copy, anything else is staged into one private set: 2 x 76 us for two 201 MB views)
         given = dict(zip(self._IN_NAMES, (x_path, ema_x_path, x_omic, grade, index, sample_idx)))
-        st = self._ensure_slot(given, rk, bnorm, e)
-        if st is None:                       # capture failed: eager from now on
+        if self._slots is None:
+            self._slots = StepGraphs(self.device, "distill", self._IN_NAMES, (self.model, self.ema_model, self.fix_model))
+        st = self._slots.input_set(given)
+        hit = self._graph(st, rk, bnorm, e)
+        if hit is None:                      # capture failed: eager from now on
+            self._static = None
             out = self._device_body(*[given[k].to(dev) for k in self._IN_NAMES], bnorm, e,
                                     *[None if r is None else r.to(dev) for r in rk])
             self.iter_num += 1
             return out
         self._static = st
-        for name in self._IN_NAMES:
-            if given[name].data_ptr() != st[name].data_ptr():
-                st[name].copy_(given[name], non_blocking=True)
         for j, (dst, src) in enumerate(zip(st["r"], rk)):
             if dst is not None:
                 ring = st.setdefault("r_ring", {}).get(j)
@@ -1038,79 +1012,34 @@ class DistillStep:
                 ring.upload(dst, src)
         self.optimizer.prepare_step()
         self.optimizer._prepared = False
-        st["graph"].replay()
+        hit[0].replay()
         self.iter_num += 1
-        return st["out"]
+        return hit[1]
 
     _IN_NAMES = ("x_path", "ema_x_path", "x_omic", "grade", "index", "sample_idx")
 
-    def _ensure_slot(self, given, r_like, bnorm, e):
-        """The input set (static buffers + captured graph) that serves `given`; captures its graph if needed."""
-        dev = self.device
-        names = self._IN_NAMES
-        on_dev = all(t.is_cuda and t.is_contiguous() for t in given.values())
-        ptrs = tuple(t.data_ptr() for t in given.values()) if on_dev else None
-        shapes = (tuple(given["x_path"].shape), tuple(given["x_omic"].shape), tuple(given["sample_idx"].shape))
-        slots = getattr(self, "_slots", None)
-        if slots is None or (slots and slots[0]["key"] != shapes):
-            slots = self._slots = []
-        st = next((q for q in slots if ptrs is not None and q["ptrs"] == ptrs), None)
-        if st is None and (not slots or (on_dev and len(slots) < 2)):
-            if on_dev:
-                bufs = dict(given)                    # adopted: the caller refills these tensors in place
-            else:
-                bufs = {k: torch.empty(t.shape, device=dev, dtype=t.dtype) for k, t in given.items()}
-            st = dict(key=shapes, ptrs=tuple(bufs[k].data_ptr() for k in names), graph=None, out=None,
-                      r=[None if r is None else torch.empty(tuple(r.shape), device=dev, dtype=torch.int32) for r in r_like],
-                      **bufs)
-            slots.append(st)
-        if st is None:
-            st = slots[0]
-        if st["graph"] is None:
-            lib().ph_prof_enable(0)          # event timing is an eager-mode facility
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            pool = next((q["graph"].pool() for q in slots if q["graph"] is not None), None)
-            was_prepared = self.optimizer._prepared
-            try:
-                with torch.cuda.graph(g, pool=pool, capture_error_mode=_capture_mode(self.sync)):
-                    self.optimizer._prepared = True       # the step scalars are read from device memory at replay
-                    if getattr(self, "_capture_pre", None) is not None:
-                        self._capture_pre()               # the on-device input pipeline fills this input set first
-                    st["out"] = self._device_body(st["x_path"], st["ema_x_path"], st["x_omic"], st["grade"],
-                                                  st["index"], st["sample_idx"], bnorm, e, st["r"][0], st["r"][1])
-                st["graph"] = g
-                # the graph holds raw pointers into the trunk workspaces it was captured with: keep them alive with it
-                st["ws_refs"] = [ws for net in (self.model, self.ema_model, getattr(self.fix_model, "path_net", None))
-                                 if net is not None and hasattr(net, "pinned_workspaces") for ws in net.pinned_workspaces()]
-                self.optimizer._prepared = was_prepared   # capture does not execute anything
-            except Exception as exc:     # e.g. a collective that cannot be captured on this stack: stay eager
-                import warnings
-                warnings.warn("HIP graph capture of the distill step failed (%r); continuing with eager launches" % (exc,))
-                torch.cuda.synchronize()
-                try:      # on this HIP runtime a failed capture can leave its streams in capture state for good
-                    torch.ones(1).to(self.device)
-                except Exception as exc2:
-                    raise RuntimeError("HIP graph capture of the distill step failed (%r) and the runtime did not leave capture "
-                                       "mode (%r): restart the process without enable_graph()" % (exc, exc2)) from exc
-                self._want_graph = False
-                self._static = None
-                self._slots = None
-                self.optimizer._prepared = was_prepared
-                return None
-        return st
+    def _graph(self, st, r_like, bnorm, e):
+        """(graph, outputs) of the step on the input set `st`, which owns the rank buffers `r` of the two CRD calls."""
+        if "r" not in st:
+            st["r"] = [None if r is None else torch.empty(tuple(r.shape), device=self.device, dtype=torch.int32) for r in r_like]
+        # (_capture_pre: the on-device input pipeline fills this input set first)
+        return self._slots.graph(self, st, "step", lambda: self._device_body(*[st[k] for k in self._IN_NAMES], bnorm, e, *st["r"]),
+                                 first=self._capture_pre)
 
     def precapture(self, batch, epoch=0):
         """Capture the graph for another resident input set without running a step (e.g. the second buffer of a
-        loader's two-deep ring, so that its first use does not pay the capture).  Needs one graph step done before."""
-        slots = getattr(self, "_slots", None)
-        if not slots or slots[0]["graph"] is None:
+        loader's two-deep ring, so that its first use does not pay the capture).  Needs one graph step done before.
+        False if the set cannot have a graph of its own (host tensors, or both adopted sets are other tensors)."""
+        slots = self._slots
+        if not slots or not slots[0]["graphs"]:
             raise RuntimeError("precapture: run a graph-mode step first")
         (x_path, ema_x_path), _, x_omic, _, _, grade, index, sample_idx = batch
         given = dict(zip(self._IN_NAMES, (x_path, ema_x_path, x_omic, grade, index, sample_idx)))
         bnorm = float(x_path.shape[0] * (self.sync.world_size if self.sync is not None else 1))
-        e = getattr(self, "_e_dev", None) if self.variant != "miccai2022" else epoch / self.opt.niter_decay
-        return self._ensure_slot(given, slots[0]["r"], bnorm, e) is not None
+        e = self._e_dev if self.variant != "miccai2022" else epoch / self.opt.niter_decay
+        r_like = slots[0]["r"]
+        st = slots.input_set(given, stage=False)
+        return st is not None and self._graph(st, r_like, bnorm, e) is not None
 
     # ------------------------------------------------------------------ checkpoint / resume (SURVEY row f-3)
     def state_dict(self):
@@ -1140,8 +1069,8 @@ class DistillStep:
     def _input_rng_state(self, load=None):
         """Device-side draw counters of step.sampler / step.loader (ContrastIndexSampler.step, DeviceAugment.step,
         ResidentTileLoader.batch_no) and numpy's global RNG state; `load` restores a dict this method returned."""
-        loader = getattr(self, "loader", None)
-        cells = dict(sampler=getattr(getattr(self, "sampler", None), "step", None),
+        loader = self.loader
+        cells = dict(sampler=getattr(self.sampler, "step", None),
                      loader_sampler=getattr(getattr(loader, "sampler", None), "step", None),
                      loader_aug=getattr(getattr(loader, "aug", None), "step", None),
                      loader_batch_no=getattr(loader, "batch_no", None))
@@ -1202,17 +1131,8 @@ class DistillStep:
 
     def static_inputs(self):
         """The graph path's resident input buffers (fill them in place to skip the device-to-device copy)."""
-        st = getattr(self, "_static", None)
-        return None if st is None else {k: st[k] for k in ("x_path", "ema_x_path", "x_omic", "grade", "index", "sample_idx")}
-
-
-def _capture_mode(sync):
-    """Stream-capture error mode of the step graphs.  Under data parallelism the process group's watchdog thread keeps polling
-    the completion events of earlier collectives (hipEventQuery); in the default "global" mode that call from ANOTHER thread is
-    illegal while a capture runs and takes the process down (seen intermittently with `bench.py --force-dist`): "thread_local"
-    restricts the check to the capturing thread.  Kernels enqueued on the capturing stream by other threads (autograd's
-    backward worker) are captured either way."""
-    return "thread_local" if sync is not None else "global"
+        st = self._static
+        return None if st is None else {k: st[k] for k in self._IN_NAMES}
 
 
 class _GatherRowsFn(torch.autograd.Function):
@@ -1337,6 +1257,12 @@ class TeacherStage1Step:
         n_model = len(list(self.model.parameters()))
         flat = self.optimizer.flat
         self.optimizer.ema_range = (0, flat.offsets[n_model] if n_model < len(flat.offsets) else flat.numel)
+        self._want_graph = False
+        self._g_sets = StepGraphs(self.device, "stage-1", self._IN_NAMES, (self.model, self.ema_model))
+        self._g_scal = self._g_ring = None      # the graph path's CRD weight | tau | mu of the penalty on the device
+        self._ema_side = self._tsvd_side = None      # side streams, created on first use
+        self._frozen_segs = self._surv_gather = None
+        self._f32_bufs = {}
         if sync is not None:
             crds = (self.CRD_criterion_path, self.CRD_criterion_omic, self.CRD_criterion_fuse) if self.crd_on else ()
             sync.attach_parts(crds, (flat.flat, self.ema_flat.flat), (self.model, self.ema_model))
@@ -1352,10 +1278,9 @@ class TeacherStage1Step:
             return t
         if not t.is_cuda:
             return t.float()
-        bufs = self.__dict__.setdefault("_f32_bufs", {})
-        b = bufs.get(name)
+        b = self._f32_bufs.get(name)
         if b is None or b.shape != t.shape or b.device != t.device:
-            b = bufs[name] = torch.empty(t.shape, device=t.device, dtype=torch.float32)
+            b = self._f32_bufs[name] = torch.empty(t.shape, device=t.device, dtype=torch.float32)
         b.copy_(t)
         return b
 
@@ -1365,7 +1290,7 @@ class TeacherStage1Step:
         follow here (rate from the optimiser's device record: graph-replayable).  Grading leaves them alone: its head never
         reads them."""
         opt_ = self.optimizer
-        if getattr(self, "_frozen_segs", None) is None:
+        if self._frozen_segs is None:
             f, hi = opt_.flat, opt_.ema_range[1]
             self._frozen_segs = [(s, min(e, hi)) for s, e in f.segments(lambda t: not t.requires_grad) if s < hi]
         f = opt_.flat
@@ -1429,7 +1354,7 @@ class TeacherStage1Step:
         if self.surv:
             given["survtime"] = self._as_f32("survtime", survtime)
             given["censor"] = self._as_f32("censor", censor)
-        use_graph = (getattr(self, "_want_graph", False) and not masking_on and self.iter_num - opt.global_step >= 2
+        use_graph = (self._want_graph and not masking_on and self.iter_num - opt.global_step >= 2
                      and all(torch.is_tensor(t) for t in given.values()))
         out = None
         if use_graph:
@@ -1470,73 +1395,26 @@ class TeacherStage1Step:
     _IN_NAMES = ("x_path", "ema_x_path", "x_omic", "grade", "index", "sample_idx")
 
     def _graph_step(self, given, B, do_aux, crd_w, tau, mu_pen):
-        """One step from a captured graph; None if no graph can serve it (capture failed: eager from now on).  Device-resident,
-        contiguous inputs are adopted as they are (up to two input sets, one graph each per kind of step, sharing one memory
-        pool); anything else is copied into the first set's buffers."""
-        dev = self.device
-        names = self._IN_NAMES
-        if getattr(self, "_g_scal", None) is None:
-            self._g_scal = torch.zeros(3, device=dev, dtype=torch.float32)       # CRD weight | tau | mu of the penalty
+        """One step from a captured graph; None if no graph can serve it (capture failed: eager from now on).  One graph per
+        input set (step_graph.py) and kind of step, with / without the t-SVD auxiliary update."""
+        if self._g_scal is None:
+            self._g_scal = torch.zeros(3, device=self.device, dtype=torch.float32)
             self._g_ring = PinnedRing((3,), torch.float32)
-            self._g_sets = []
-        on_dev = all(t.is_cuda and t.is_contiguous() for t in given.values())
-        ptrs = tuple(given[k].data_ptr() for k in names) if on_dev else None
-        shapes = tuple(tuple(given[k].shape) for k in names)
-        if self._g_sets and self._g_sets[0]["shapes"] != shapes:
-            self._g_sets = []
-        st = next((q for q in self._g_sets if q["adopted"] and ptrs is not None and q["ptrs"] == ptrs), None)
-        if st is None and on_dev and sum(q["adopted"] for q in self._g_sets) < 2:
-            bufs = dict(given)
-            st = dict(shapes=shapes, ptrs=ptrs, bufs=bufs, graphs={}, adopted=True)
-            self._g_sets.append(st)
-        if st is None:
-            # host tensors, or a third resident set: staged into PRIVATE buffers - never into an adopted set, whose tensors
-            # belong to the caller (a loader's ring buffer must not be overwritten behind its back, ADVICE r04)
-            st = next((q for q in self._g_sets if not q["adopted"]), None)
-            if st is None:
-                bufs = {k: torch.empty(given[k].shape, device=dev, dtype=given[k].dtype) for k in names}
-                st = dict(shapes=shapes, ptrs=tuple(bufs[k].data_ptr() for k in names), bufs=bufs, graphs={}, adopted=False)
-                self._g_sets.append(st)
-            for k in names:
-                st["bufs"][k].copy_(given[k], non_blocking=True)
+        st = self._g_sets.input_set(given)
         self._g_ring.upload(self._g_scal, [crd_w, tau, mu_pen])      # (pinned rows: no host sync per replayed step)
-        if do_aux not in st["graphs"]:
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            pool = next((gr.pool() for q in self._g_sets for gr, _, _ in q["graphs"].values()), None)
-            was_prepared = self.optimizer._prepared
-            try:
-                bf = st["bufs"]
-                if self.surv and self.sync is not None:
-                    self._surv_gather_bufs(st, bf["x_path"].shape[0])      # (allocated outside the capture)
-                with torch.cuda.graph(g, pool=pool, capture_error_mode=_capture_mode(self.sync)):
-                    self.optimizer._prepared = True       # the step scalars are read from device memory at replay
-                    out = self._device_body(bf["x_path"], bf["ema_x_path"], bf["x_omic"], bf["grade"], bf["index"],
-                                            bf["sample_idx"], B, do_aux, self._g_scal[0], self._g_scal[1], self._g_scal[2], None,
-                                            bf.get("survtime"), bf.get("censor"), st)
-                # the graph holds raw pointers into the trunk workspaces it was captured with: keep them alive with it
-                refs = [ws for net in (self.model, self.ema_model) for mod in net.modules() if hasattr(mod, "pinned_workspaces")
-                        for ws in mod.pinned_workspaces()]
-                st["graphs"][do_aux] = (g, out, refs)
-                self.optimizer._prepared = was_prepared
-            except Exception as exc:
-                import warnings
-                warnings.warn("HIP graph capture of the stage-1 step failed (%r); continuing with eager launches" % (exc,))
-                torch.cuda.synchronize()
-                try:      # on this HIP runtime a failed capture can leave its streams in capture state for good
-                    torch.ones(1).to(dev)
-                except Exception as exc2:
-                    raise RuntimeError("HIP graph capture of the stage-1 step failed (%r) and the runtime did not leave capture "
-                                       "mode (%r): restart the process without enable_graph()" % (exc, exc2)) from exc
-                self._want_graph = False
-                self._g_sets = []
-                self.optimizer._prepared = was_prepared
-                return None
-        g, out, _ = st["graphs"][do_aux]
+        hit = self._g_sets.graph(
+            self, st, do_aux,
+            lambda: self._device_body(st["x_path"], st["ema_x_path"], st["x_omic"], st["grade"], st["index"], st["sample_idx"], B,
+                                      do_aux, self._g_scal[0], self._g_scal[1], self._g_scal[2], None, st.get("survtime"),
+                                      st.get("censor"), st),
+            # (the survival gather buffers, owned by the set, are allocated outside the capture)
+            before=(lambda: self._surv_gather_bufs(st, st["x_path"].shape[0])) if self.surv and self.sync is not None else None)
+        if hit is None:
+            return None
         self.optimizer.prepare_step()
         self.optimizer._prepared = False
-        g.replay()
-        return out
+        hit[0].replay()
+        return hit[1]
 
     def _device_body(self, x_path, ema_x_path, x_omic, grade, index, sample_idx, B, do_aux, crd_w, tau, mu_pen, loss_masking,
                      survtime=None, censor=None, input_set=None):
@@ -1550,7 +1428,7 @@ class TeacherStage1Step:
         # the mean teacher's forward (no_grad, :143-145) does not depend on the student's (:137): a second stream, joined
         # before the losses, as in DistillStep._device_body
         main = torch.cuda.current_stream()
-        if getattr(self, "_ema_side", None) is None:
+        if self._ema_side is None:
             self._ema_side = torch.cuda.Stream(device=dev)
         eside = self._ema_side
         eside.wait_stream(main)
@@ -1645,7 +1523,7 @@ class TeacherStage1Step:
                 # of the tiled Jacobi): the second runs on a side stream beside the first.  The results land in the
                 # PERSISTENT auxiliary tensors (captured graphs of other input sets / of the steps without an update read them)
                 main = torch.cuda.current_stream()
-                if getattr(self, "_tsvd_side", None) is None:
+                if self._tsvd_side is None:
                     self._tsvd_side = torch.cuda.Stream(device=dev)
                 side = self._tsvd_side
                 side.wait_stream(main)
@@ -1668,11 +1546,7 @@ class TeacherStage1Step:
             if opt.tSVD_mode in ("omic", "pathomic"):
                 loss_tsvd = loss_tsvd + T.tsvd_penalty(self.adj_tensor2, self.aux_tensor2, mu_pen)
             loss = loss + loss_tsvd
-        self.optimizer.zero_grad()
-        loss.backward()
-        if self.sync is not None:
-            self.sync.all_reduce_grads(self.optimizer.flat)
-        self.optimizer.step()                                                                   # + EMA (:229) fused
+        _backward_and_update(self, loss)                                                        # + EMA (:229) fused
         if self.surv:
             self._ema_frozen()
         if self.tsvd_on:

@@ -161,3 +161,37 @@ def test_fused_adam_follows_a_cycled_beta1_inside_a_captured_graph():
     assert ref.param_groups[0]["betas"][0] != opt.beta1          # (the schedule did move beta1)
     for p, pr in zip(our_p, ref_p):
         assert (p - pr).abs().max().item() <= 2e-6 * pr.abs().max().item()
+
+
+def test_fused_adagrad_state_round_trips_in_its_own_and_in_torchs_layout():
+    """FusedAdagrad.load_state_dict on three parameters of 5, 64 and 129 elements (each padded to 16 bytes in the flat
+    buffers): its own state-dict (the flat accumulator under "fused") and a torch.optim.Adagrad one give back the accumulator
+    and the step count exactly."""
+    import multimodal_learning_amd as m
+    torch.manual_seed(6)
+    shapes = [(5,), (8, 8), (3, 43)]
+    ref_p = [torch.nn.Parameter(torch.randn(s) * 0.1) for s in shapes]
+    kw = dict(lr=2e-3, weight_decay=4e-4, initial_accumulator_value=0.1)
+    ref_opt = torch.optim.Adagrad(ref_p, **kw)
+    opt = m.FusedAdagrad([torch.nn.Parameter(p.detach().clone().cuda()) for p in ref_p], **kw)
+    for it in range(2):
+        opt.zero_grad()
+        for p, q in zip(ref_p, opt.param_groups[0]["params"]):
+            p.grad = torch.randn(p.shape) * 0.1
+            q.grad.copy_(p.grad)
+        ref_opt.step(); opt.step()
+    fresh = lambda: m.FusedAdagrad([torch.nn.Parameter(p.detach().clone().cuda()) for p in ref_p], **kw)      # noqa: E731
+    own, ck = fresh(), opt.state_dict()
+    own.load_state_dict(ck); own.load_state_dict(ck)
+    assert own._step == 2 and torch.equal(own._v, opt._v)
+    back = own.state_dict()
+    assert all(torch.equal(back["state"][i]["sum"], ck["state"][i]["sum"]) and int(back["state"][i]["step"]) == 2 for i in range(3))
+    assert torch.equal(back["fused"]["sum"], ck["fused"]["sum"]) and back["fused"]["step"] == 2
+    tor = fresh()
+    tor.load_state_dict(ref_opt.state_dict())
+    back = tor.state_dict()["state"]
+    assert tor._step == 2 and all(torch.equal(back[i]["sum"].cpu(), ref_opt.state[p]["sum"]) for i, p in enumerate(ref_p))
+    pad = tor._v.clone()
+    for t, o in zip(tor.flat.tensors, tor.flat.offsets):
+        pad[o:o + t.numel()] = 0.1
+    assert torch.equal(pad, torch.full_like(pad, 0.1)), "the padding between the parameters keeps the initial accumulator"
