@@ -926,3 +926,170 @@ int ph_stem_bwd_apply_launch(const void* dpool, const uint8_t* idx, const void* 
   PH_LAUNCH_CHECK();
   return PH_OK;
 }
+
+// ---------------------------------------------------------------- test entry points (tests/test_gpu_bn_act.py)
+// ph_debug_bn_*: C-linked doors to the launchers above for the operator-level sweep.  Not part of the public C-ABI
+// (include/pathomic_hip.h does not list them, ph_abi_version does not count them).  Each one checks its arguments and forwards
+// to the launcher; it returns PH_EINVAL, and launches nothing, for
+//   - a NULL required pointer (optional ones are named at each entry), a `prec` that is no PH_PREC_* of the tensors
+//     (PH_PREC_BF16, PH_PREC_BF16X6, PH_PREC_BF16X3, PH_PREC_FP16X3),
+//   - npix, B, H, W, HW, nparts, namax (with dzs) < 1, count <= 0,
+//   - C < 8 or C % 8 != 0; 256 % (C / 8) != 0 or C > 2048 for the reduce and apply passes (bn_apply, bn_bwd_reduce, bn_bwd_apply:
+//     a thread keeps its channel group only if C / 8 divides the block), C % 64 != 0 for the average pool and for every
+//     half-pair tensor (PH_PREC_FP16X3: out of bn_apply / bn_relu_maxpool, x of avgpool_t, dy of bn_bwd_apply), whose base must
+//     also be 256-byte aligned; C != 64 for the stem,
+//   - n < 1 or n > 20 units in the eval table, relu outside 0 .. 3, relu & 2 without y_r, y_r without scale_r / shift_r,
+//     res_as_t outside 0 .. 1, raw without idx, one of running_mean / running_var or of mscale / mshift without the other, dzs
+//     without amax / gamma / invstd, row2 outside 1 .. 2, amax with an odd H in the stem reduction, form outside 0 .. 1.
+// Everything else is the launcher's own contract (ph_kernels.h): tensors are NHWC, 16-byte aligned, of the mode's type.
+namespace {
+inline bool dbg_prec_ok(int prec) {
+  return prec == PH_PREC_BF16 || prec == PH_PREC_BF16X6 || prec == PH_PREC_BF16X3 || prec == PH_PREC_FP16X3;
+}
+inline bool dbg_c8_ok(int C) { return C >= 8 && C % 8 == 0; }
+inline bool dbg_cg_ok(int C) { return dbg_c8_ok(C) && C <= 2048 && 256 % (C / 8) == 0; }
+// a half-pair tensor of PH_PREC_FP16X3 (p may be NULL: an optional tensor that is absent)
+inline bool dbg_hp_ok(const void* p, int C, int prec) {
+  return prec != PH_PREC_FP16X3 || (C % 64 == 0 && reinterpret_cast<uintptr_t>(p) % 256 == 0);
+}
+}  // namespace
+
+extern "C" {
+
+int ph_debug_bn_pack_input(const float* x_nchw, void* x4, int B, int H, int W, int prec, hipStream_t st) {
+  if (!x_nchw || !x4 || B < 1 || H < 1 || W < 1 || !dbg_prec_ok(prec)) return PH_EINVAL;
+  return ph_pack_input_launch(x_nchw, x4, B, H, W, prec, st);
+}
+
+// running_mean / running_var (both or neither) and num_batches_tracked are optional
+int ph_debug_bn_finalize(const float* parts, int nparts, int C, double count, float eps, float momentum, const float* gamma,
+                         const float* beta, float* mean, float* invstd, float* scale, float* shift, float* running_mean,
+                         float* running_var, int64_t* num_batches_tracked, hipStream_t st) {
+  if (!parts || !gamma || !beta || !mean || !invstd || !scale || !shift) return PH_EINVAL;
+  if (nparts < 1 || C < 1 || !(count > 0.0) || (running_mean == nullptr) != (running_var == nullptr)) return PH_EINVAL;
+  return ph_bn_finalize_launch(parts, nparts, C, count, eps, momentum, gamma, beta, mean, invstd, scale, shift, running_mean,
+                               running_var, num_batches_tracked, st);
+}
+
+// host arrays of n device pointers (and n widths): the PhBnEvalTable is built here
+int ph_debug_bn_eval_params(const float* const* gamma, const float* const* beta, const float* const* running_mean,
+                            const float* const* running_var, float* const* mean, float* const* invstd, float* const* scale,
+                            float* const* shift, const int* C, int n, float eps, hipStream_t st) {
+  if (!gamma || !beta || !running_mean || !running_var || !mean || !invstd || !scale || !shift || !C) return PH_EINVAL;
+  if (n < 1 || n > 20) return PH_EINVAL;
+  PhBnEvalTable t{};
+  for (int u = 0; u < n; ++u) {
+    if (!gamma[u] || !beta[u] || !running_mean[u] || !running_var[u] || !mean[u] || !invstd[u] || !scale[u] || !shift[u] || C[u] < 1)
+      return PH_EINVAL;
+    t.gamma[u] = gamma[u]; t.beta[u] = beta[u]; t.running_mean[u] = running_mean[u]; t.running_var[u] = running_var[u];
+    t.mean[u] = mean[u]; t.invstd[u] = invstd[u]; t.scale[u] = scale[u]; t.shift[u] = shift[u];
+    t.C[u] = C[u];
+  }
+  t.n = n;
+  return ph_bn_eval_params_launch(&t, eps, st);
+}
+
+// res, y_r (with scale_r, shift_r) and out32 are optional
+int ph_debug_bn_apply(const void* y, const float* scale, const float* shift, const void* res, const void* y_r,
+                      const float* scale_r, const float* shift_r, void* out, void* out32, size_t npix, int C, int relu, int prec,
+                      int res_as_t, hipStream_t st) {
+  if (!y || !scale || !shift || !out || npix < 1 || !dbg_prec_ok(prec) || !dbg_cg_ok(C)) return PH_EINVAL;
+  if (relu < 0 || relu > 3 || ((relu & 2) && !y_r) || (y_r && (!scale_r || !shift_r))) return PH_EINVAL;
+  if (res_as_t < 0 || res_as_t > 1 || !dbg_hp_ok(out, C, prec) || (res_as_t && !dbg_hp_ok(res, C, prec))) return PH_EINVAL;
+  return ph_bn_apply_launch2(y, scale, shift, res, y_r, scale_r, shift_r, out, out32, npix, C, relu, prec, res_as_t, st);
+}
+
+// idx, raw (with idx) and out32 are optional
+int ph_debug_bn_relu_maxpool(const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, void* raw,
+                             void* out32, int B, int H, int W, int C, int prec, hipStream_t st) {
+  if (!y || !scale || !shift || !out || B < 1 || H < 1 || W < 1 || !dbg_prec_ok(prec) || !dbg_c8_ok(C)) return PH_EINVAL;
+  if ((raw && !idx) || !dbg_hp_ok(out, C, prec)) return PH_EINVAL;
+  return ph_bn_relu_maxpool_launch(y, scale, shift, out, idx, raw, out32, B, H, W, C, prec, st);
+}
+
+int ph_debug_bn_avgpool(const void* x, float* out, int B, int HW, int C, int prec, hipStream_t st) {
+  if (!x || !out || B < 1 || HW < 1 || C < 64 || C % 64 || !dbg_prec_ok(prec)) return PH_EINVAL;
+  return ph_avgpool_launch(x, out, B, HW, C, prec, st);
+}
+
+int ph_debug_bn_avgpool_t(const void* x, float* out, int B, int HW, int C, int prec, hipStream_t st) {
+  if (!x || !out || B < 1 || HW < 1 || C < 64 || C % 64 || !dbg_prec_ok(prec) || !dbg_hp_ok(x, C, prec)) return PH_EINVAL;
+  return ph_avgpool_launch_t(x, out, B, HW, C, prec, st);
+}
+
+int ph_debug_bn_avgpool_bwd(const float* g, void* dx, int B, int HW, int C, int accumulate, int prec, hipStream_t st) {
+  if (!g || !dx || B < 1 || HW < 1 || C < 64 || C % 64 || !dbg_prec_ok(prec)) return PH_EINVAL;
+  return ph_avgpool_bwd_launch(g, dx, B, HW, C, accumulate, prec, st);
+}
+
+int ph_debug_bn_bwd_parts(size_t npix, int C) {
+  if (npix < 1 || !dbg_cg_ok(C)) return PH_EINVAL;
+  return ph_bn_bwd_parts(npix, C);
+}
+
+int ph_debug_bn_stem_bwd_parts(int B, int H) {
+  if (B < 1 || H < 1) return PH_EINVAL;
+  return ph_stem_bwd_parts(B, H);
+}
+
+// a, mscale / mshift (both or neither) and amax are optional
+int ph_debug_bn_bwd_reduce(const void* g, const void* a, const void* y, const float* mean, const float* invstd, float* parts,
+                           size_t npix, int C, int prec, const float* mscale, const float* mshift, float* amax, hipStream_t st) {
+  if (!g || !y || !mean || !invstd || !parts || npix < 1 || !dbg_prec_ok(prec) || !dbg_cg_ok(C)) return PH_EINVAL;
+  if ((mscale == nullptr) != (mshift == nullptr)) return PH_EINVAL;
+  return ph_bn_bwd_reduce_launch(g, a, y, mean, invstd, parts, npix, C, prec, mscale, mshift, amax, st);
+}
+
+// dgamma, dbeta and dzs (with amax[namax], gamma, invstd) are optional
+int ph_debug_bn_bwd_finalize(const float* parts, int nparts, int C, double count, float* dgamma, float* dbeta, float* c1,
+                             float* c2, const float* amax, int namax, const float* gamma, const float* invstd, float* dzs,
+                             hipStream_t st) {
+  if (!parts || !c1 || !c2 || nparts < 1 || C < 1 || !(count > 0.0)) return PH_EINVAL;
+  if (dzs && (!amax || !gamma || !invstd || namax < 1)) return PH_EINVAL;
+  return ph_bn_bwd_finalize_launch(parts, nparts, C, count, dgamma, dbeta, c1, c2, amax, namax, gamma, invstd, dzs, st);
+}
+
+int ph_debug_bn_bwd_finalize_fused(const float* parts, int nparts, int C, double count, float* dgamma, float* dbeta, float* c1,
+                                   float* c2, const float* invstd, int row2, hipStream_t st) {
+  if (!parts || !c1 || !c2 || !invstd || nparts < 1 || C < 1 || !(count > 0.0) || (row2 != 1 && row2 != 2)) return PH_EINVAL;
+  return ph_bn_bwd_finalize_fused_launch(parts, nparts, C, count, dgamma, dbeta, c1, c2, invstd, row2, st);
+}
+
+// a, mscale / mshift (both or neither) and dzs are optional
+int ph_debug_bn_bwd_apply(const void* g, const void* a, const void* y, const float* mean, const float* invstd,
+                          const float* gamma, const float* c1, const float* c2, void* dy, size_t npix, int C, int prec,
+                          const float* mscale, const float* mshift, const float* dzs, hipStream_t st) {
+  if (!g || !y || !mean || !invstd || !gamma || !c1 || !c2 || !dy || npix < 1 || !dbg_prec_ok(prec) || !dbg_cg_ok(C)) return PH_EINVAL;
+  if ((mscale == nullptr) != (mshift == nullptr) || !dbg_hp_ok(dy, C, prec)) return PH_EINVAL;
+  return ph_bn_bwd_apply_launch(g, a, y, mean, invstd, gamma, c1, c2, dy, npix, C, prec, mscale, mshift, dzs, st);
+}
+
+// raw and amax (even H only) are optional.  form 0: the launcher's choice (raw, pooled or - odd H - per input pixel); form 1: the
+// per-input-pixel reduction at any H (the kernel the launcher starts for an odd H), without amax
+int ph_debug_bn_stem_bwd_reduce(const void* dpool, const uint8_t* idx, const void* y0, const void* raw, const float* mean,
+                                const float* invstd, const float* scale, const float* shift, float* parts, int B, int H, int W,
+                                int C, int prec, float* amax, int form, hipStream_t st) {
+  if (!dpool || !idx || !y0 || !mean || !invstd || !scale || !shift || !parts) return PH_EINVAL;
+  if (B < 1 || H < 1 || W < 1 || C != 64 || !dbg_prec_ok(prec) || form < 0 || form > 1) return PH_EINVAL;
+  if (amax && ((H & 1) || form == 1)) return PH_EINVAL;
+  if (form == 0) return ph_stem_bwd_reduce_launch(dpool, idx, y0, raw, mean, invstd, scale, shift, parts, B, H, W, C, prec, amax, st);
+  const int nb = ph_stem_bwd_parts(B, H);
+#define PH_CALL(T, TY)                                                                                                         \
+  hipLaunchKernelGGL((stem_bwd_kernel<T, TY, false>), dim3(nb), dim3(256), 0, st, (const TY*)dpool, idx, (const TY*)y0, scale, shift, \
+                     mean, invstd, nullptr, nullptr, nullptr, parts, (T*)nullptr, B, H, W, nullptr)
+  PH_DISPATCH(prec, PH_CALL);
+#undef PH_CALL
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+// dzs is optional
+int ph_debug_bn_stem_bwd_apply(const void* dpool, const uint8_t* idx, const void* y0, const float* mean, const float* invstd,
+                               const float* scale, const float* shift, const float* gamma, const float* c1, const float* c2,
+                               void* dy0, int B, int H, int W, int C, int prec, const float* dzs, hipStream_t st) {
+  if (!dpool || !idx || !y0 || !mean || !invstd || !scale || !shift || !gamma || !c1 || !c2 || !dy0) return PH_EINVAL;
+  if (B < 1 || H < 1 || W < 1 || C != 64 || !dbg_prec_ok(prec) || !dbg_hp_ok(dy0, C, prec)) return PH_EINVAL;
+  return ph_stem_bwd_apply_launch(dpool, idx, y0, mean, invstd, scale, shift, gamma, c1, c2, dy0, B, H, W, C, prec, dzs, st);
+}
+
+}  // extern "C"

@@ -40,6 +40,8 @@ def _images(B, H, seed):
 
 @pytest.mark.parametrize("mode,B", [("bf16", 64), ("bf16x6", 64), ("bf16", 256)])
 def test_every_forward_stage_at_benchmark_size(mode, B):
+    """Every forward stage at the benchmarked size against torch fed the GPU's own input of that stage.
+    (The BatchNorm, ReLU and pooling kernels one by one, bitwise and at odd sizes: tests/test_gpu_bn_act.py.)"""
     import multimodal_learning_amd as m
     from multimodal_learning_amd._lib import lib, check
     H, SUB = 512, 3                                   # reference convolutions on the first / middle / last image
@@ -239,7 +241,8 @@ def test_every_backward_stage_at_benchmark_size():
     bf16-stored tensors are held to bf16 rounding (2^-7 of the tensor's maximum), fp32 parameter gradients to 2e-3.
     ReLU masks are re-derived from bf16 data exactly as the kernels do; an element whose pre-activation is within
     rounding of zero may still fall on the other side (fused multiply-add vs two roundings), so mask-dependent tensors
-    may hold a handful (<= 1e-6 of the elements) of outliers, which are counted and printed."""
+    may hold a handful (<= 1e-6 of the elements) of outliers, which are counted and printed.
+    (The BatchNorm-backward, pooling and stem-backward kernels one by one, bitwise and without outliers: tests/test_gpu_bn_act.py.)"""
     import multimodal_learning_amd as m
     from multimodal_learning_amd import ops
     from multimodal_learning_amd._lib import lib, check, ptr, stream

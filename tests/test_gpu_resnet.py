@@ -295,7 +295,8 @@ def test_perf_mode_forward_stage_by_stage():
     input to that stage (read out of the plan workspace through ph_resnet_tensor_info), so no error is carried from stage
     to stage and each kernel family is held to bf16 rounding: stem conv (the register-prefetch / packed-store path of
     conv_stem.hip), fused BN + ReLU + max-pool, the layer-1 tap-conv (two-group kernel) with its in-kernel BatchNorm
-    statistics, BN apply, and the residual BN apply.  160 x 160 input: partial tiles everywhere."""
+    statistics, BN apply, and the residual BN apply.  160 x 160 input: partial tiles everywhere.
+    (The BatchNorm / pooling kernels one by one, bitwise and at odd sizes: tests/test_gpu_bn_act.py.)"""
     import ctypes as C
     import torch.nn.functional as F
     import multimodal_learning_amd as m
