@@ -90,6 +90,12 @@ int ph_resnet_plan_set_backward_prec(const PhResnetPlan* plan, int prec);
  * weight gradients summed from half as many partial slabs (autograd of resnets.py:58-74 has no order between a layer's
  * weight and input gradients either). */
 int ph_resnet_plan_set_backward_overlap(const PhResnetPlan* plan, int on);
+/* The stem's backward in the bf16 mode of ph_resnet_backward / _part: 1 (default; the environment variable PH_STEM_FUSE=0/1 sets
+ * the value a new plan starts with) = the stem's weight-gradient kernel forms the gradient at the stem conv's output itself,
+ * from the conv output, the pooled gradient and the arg codes - that 64-channel tensor is neither written nor read; 0 = a pass
+ * of its own writes it first.  Bitwise the same gradients.  The other arithmetics, ph_resnet_backward_input and a cut debug
+ * backward always run the separate pass. */
+int ph_resnet_plan_set_stem_fused(const PhResnetPlan* plan, int on);
 int ph_pack_input(const float* x_nchw, void* x4 /* B*H*W*4 elements of the mode's activation type */, int B, int H, int W,
                   int prec, ph_stream_t stream);
 int ph_resnet_forward(const PhResnetPlan* plan, const void* const* params, const void* packed, const float* x_nchw,

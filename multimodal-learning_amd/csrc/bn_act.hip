@@ -3,6 +3,7 @@
 // (resnets.py:150), AdaptiveAvgPool2d (resnets.py:158,234-236).  Activations are NHWC of type T
 // (bf16 in perf mode, float in parity mode); statistics are always fp32 with fp64 combination.
 #include "ph_common.h"
+#include "stem_dz.h"
 #include <cstdlib>
 #include "ph_kernels.h"
 
@@ -497,12 +498,13 @@ __global__ void bn_bwd_apply_kernel(Src src, const float* __restrict__ mean, con
 // constants live in registers (the generic kernels above spent most of their time there: 23-32 % of the HBM roofline)
 constexpr int STEM_ROWS = 16;
 
-template <typename T>
+template <typename T, typename F>
 __device__ __forceinline__ void stem_dz(const T* __restrict__ dpool, const uint8_t* __restrict__ idx, int OH, int OW,
-                                        size_t b, int h, int w, int cg, float (&dz)[8]) {
+                                        size_t b, int h, int w, int cg, F&& each) {
   // the (up to) four pooling windows that contain input pixel (h, w).  All four argmax words and gradient vectors
   // are requested unconditionally (indices clamped, contribution masked) so that the eight loads are in flight
   // together: with a branch per window the kernel paid four dependent memory round trips per pixel (535 us).
+  // each(k, g, hit): the operands of stem_dz_masked / stem_dz_value (stem_dz.h) for channel k of the group
   const int ph0 = h >> 1, ph1 = (h + 1) >> 1, pw0 = w >> 1, pw1 = (w + 1) >> 1;
   uint64_t packed[4];
   float g8[4][8];
@@ -515,22 +517,27 @@ __device__ __forceinline__ void stem_dz(const T* __restrict__ dpool, const uint8
       const int ph = a ? ph1 : ph0, pw = c ? pw1 : pw0;
       ok[a * 2 + c] = !(a && ph1 == ph0) && !(c && pw1 == pw0) && ph < OH && pw < OW;
       const int phc = ph < OH ? ph : OH - 1, pwc = pw < OW ? pw : OW - 1;
-      code[a * 2 + c] = (unsigned)((h - (2 * ph - 1)) * 3 + (w - (2 * pw - 1)));
+      code[a * 2 + c] = stem_arg_code(h, w, ph, pw);
       const size_t o8 = ((b * OH + phc) * OW + pwc) * 8 + cg;
       packed[a * 2 + c] = *reinterpret_cast<const uint64_t*>(idx + o8 * 8);
       load8(dpool + o8 * 8, g8[a * 2 + c]);
     }
+  __builtin_amdgcn_sched_barrier(0);      // (every load above is issued before the first operation on a loaded value)
 #pragma unroll
-  for (int k = 0; k < 8; ++k) dz[k] = 0.f;
+  for (int k = 0; k < 8; ++k) {
+    float g[4];
+    bool hit[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      dz[k] += (ok[q] && ((unsigned)(packed[q] >> (8 * k)) & 0xffu) == code[q]) ? g8[q][k] : 0.f;
+    for (int q = 0; q < 4; ++q) {
+      g[q] = g8[q][k];
+      hit[q] = ok[q] && ((unsigned)(packed[q] >> (8 * k)) & 0xffu) == code[q];
+    }
+    each(k, g, hit);
+  }
 }
 
 template <typename T, typename TY, bool APPLY>
-__global__ __launch_bounds__(256) void stem_bwd_kernel(const TY* __restrict__ dpool, const uint8_t* __restrict__ idx,
+__global__ __launch_bounds__(256, sizeof(TY) == 2 ? 4 : 1) void stem_bwd_kernel(const TY* __restrict__ dpool, const uint8_t* __restrict__ idx,
                                                        const TY* __restrict__ y, const float* __restrict__ scale,
                                                        const float* __restrict__ shift, const float* __restrict__ mean,
                                                        const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -555,14 +562,14 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const TY* __restrict__ dp
       const size_t i8 = ((size_t)row * W + w) * 8 + cg;
       float dz[8], yy[8];
       load8(y + i8 * 8, yy);
-      stem_dz(dpool, idx, OH, OW, b, h, w, cg, dz);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        dz[k] = (yy[k] * sc[k] + sf[k]) > 0.f ? dz[k] : 0.f;
-        const float xh = (yy[k] - mu[k]) * is[k];
-        if (APPLY) dz[k] = ga[k] * (dz[k] - k1[k] - xh * k2[k]) * dsc;
-        else { s1[k] += dz[k]; s2[k] += dz[k] * xh; }
-      }
+      stem_dz(dpool, idx, OH, OW, b, h, w, cg, [&](int k, const float (&g)[4], const bool (&hit)[4]) {
+        if (APPLY) {
+          dz[k] = stem_dz_value(g, hit, yy[k], sc[k], sf[k], mu[k], is[k], ga[k], k1[k], k2[k], dsc);
+        } else {
+          dz[k] = stem_dz_masked(g, hit, yy[k], sc[k], sf[k]);
+          s1[k] += dz[k]; s2[k] += dz[k] * stem_xhat(yy[k], mu[k], is[k]);
+        }
+      });
       if (APPLY) store8(dy + i8 * 8, dz);
     }
   }

@@ -11,6 +11,7 @@
 #include "ph_common.h"
 #include <type_traits>
 #include "ph_kernels.h"
+#include "stem_dz.h"
 
 #ifndef PH_STEM_HP_ABL      // timing ablations of the half-pair stem (make trace TRACE_TAG=_x EXTRA=-DPH_STEM_HP_ABL=n): 1 no output
 #define PH_STEM_HP_ABL 0    // stores, 2 no MFMAs
@@ -740,6 +741,12 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(PhStemPool p) {
 
 __device__ __forceinline__ int sw_piece(int pix, int piece) { return piece ^ (((pix >> 1) & 1) << 1); }
 
+// fused dz (stem_wgrad_kernel<bf16, true>): an 8 x 16 tile of conv-output pixels lies in the pooling windows of 5 x 9 pooled pixels
+constexpr int FPH = TH / 2 + 1, FPW = TW / 2 + 1, FPATCH = FPH * FPW;
+constexpr int FUSE_LDS = FPATCH * (128 + 64) + 7 * 64 * 4 + XB;
+constexpr int FGCH = (FPATCH * 8 + 255) / 256;      // 16-byte loads per thread: gradient patch (2), code patch (1)
+static_assert(FPATCH * 4 <= 256, "one 16-byte code load per thread");
+
 __device__ __forceinline__ bf16x8 tr_pair(const unsigned char* base, int off0, int off1) {
   typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
   s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off0));
@@ -749,8 +756,12 @@ __device__ __forceinline__ bf16x8 tr_pair(const unsigned char* base, int off0, i
   return u.v;
 }
 
-template <typename T>
+// FUSE (T = bf16 only): the dz tile is not loaded from p.dy but formed here, from the conv output y0, the pooled gradient and
+// the arg codes - the arithmetic of stem_bwd_kernel<.., APPLY> through the same helpers (stem_dz.h), so every dz element, and
+// with the unchanged tile / chunk / MFMA order the weight gradient, is bitwise what the separate pass gives.
+template <typename T, bool FUSE = false>
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(PhStemWgrad p) {
+  static_assert(!FUSE || std::is_same<T, bf16>::value, "the fused dz is the perf mode's");
   // T = hp16 (PH_PREC_FP16X3): two fp16 planes of dz' (a [hi 64 | lo 64] pixel record) and of the image; the leading product
   // and the two cross products accumulate separately and are combined (cross * 2^-11) when the slab is written
   constexpr bool HPM = is_hp<T>::value;
@@ -760,6 +771,13 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(PhStemWgrad p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* ldsD = smem;               // NP planes of DB
   unsigned char* ldsX = smem + DB * NP;     // NP planes of XB
+  // FUSE: the tile's 5 x 9 patch of pooled pixels - gradient [45][64] bf16, arg codes [45][64] bytes - and the per-channel
+  // constants [7][64] fp32 (scale, shift, mean, invstd, gamma * invstd, c1, c2)
+  unsigned char* ldsG = ldsX + XB * NP;
+  unsigned char* ldsI = ldsG + FPATCH * 128;
+  float* ldsC = reinterpret_cast<float*>(ldsI + FPATCH * 64);
+  unsigned char* ldsX1 = reinterpret_cast<unsigned char*>(ldsC + 7 * 64);      // FUSE: the second halo buffer
+  auto xbuf = [&](int tt) { return (FUSE && (tt & 1)) ? ldsX1 : ldsX; };
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int chunk = blockIdx.x;
   const int tiles_w = (p.OW + TW - 1) / TW, tiles_h = (p.OH + TH - 1) / TH;
@@ -786,24 +804,65 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(PhStemWgrad p) {
   constexpr int DCH = TH * TW * 8 / 256, XCH = (HP + 255) / 256;
   u32x4 dreg[PREF ? NPL : 1][PREF ? DCH : 1];
   u32x2 xreg[PREF ? NPL : 1][PREF ? XCH : 1];
-  auto prefetch = [&](int tt) {
-    if constexpr (PREF) {
+  u32x4 greg[FUSE ? FGCH : 1], creg;
+  // FUSE: thread -> (pixel, 8-channel group) so that the parities of a pixel's row and column - which of its four windows
+  // exist, and the arg code that names it in each - depend on e alone: e = 0 .. 3 = (even, even), (even, odd), (odd, even),
+  // (odd, odd); a wave still reads whole 128-byte pixel records of y0
+  const int fcg = tid & 7, fcj = (tid >> 3) & 7, frj = tid >> 6;
+  auto fpix = [&](int e) { return (2 * frj + (e >> 1)) * TW + 2 * fcj + (e & 1); };
+  auto prefetch_y = [&](int tt) {      // FUSE: the conv output of the tile, dreg[0][e] <- pixel fpix(e), channels 8 fcg ..
+    if constexpr (FUSE) {
       const int b = tt / tiles_img, ti = tt - b * tiles_img;
       const int r0 = (ti / tiles_w) * TH, c0 = (ti % tiles_w) * TW;
       const unsigned char* zero = reinterpret_cast<const unsigned char*>(stem_zero8);
 #pragma unroll
       for (int e = 0; e < DCH; ++e) {
-        const int i = tid + e * 256, pix = i >> 3, ch = i & 7;
+        const int pix = fpix(e);
         const int r = r0 + (pix >> 4), c = c0 + (pix & 15);
         const bool ok = r < p.OH && c < p.OW;
         const size_t px = ((size_t)b * p.OH + r) * p.OW + c;
-        if constexpr (HPM) {      // a [hi 64 | lo 64] fp16 pixel record
-          const unsigned char* src = ok ? reinterpret_cast<const unsigned char*>(reinterpret_cast<const f16*>(p.dy) + px * 128 + ch * 8) : zero;
-          dreg[0][e] = ld_global<u32x4>(src);
-          dreg[HPM ? 1 : 0][e] = ld_global<u32x4>(ok ? src + 128 : zero);
-        } else {
-          const unsigned char* src = ok ? reinterpret_cast<const unsigned char*>(DY + px * 64 + ch * 8) : zero;
-          dreg[0][e] = ld_global<u32x4>(src);
+        dreg[0][e] = ld_global<u32x4>(ok ? reinterpret_cast<const unsigned char*>(reinterpret_cast<const bf16*>(p.y0) + px * 64 + fcg * 8) : zero);
+      }
+    }
+  };
+  auto prefetch = [&](int tt) {
+    if constexpr (PREF) {
+      const int b = tt / tiles_img, ti = tt - b * tiles_img;
+      const int r0 = (ti / tiles_w) * TH, c0 = (ti % tiles_w) * TW;
+      const unsigned char* zero = reinterpret_cast<const unsigned char*>(stem_zero8);
+      if constexpr (FUSE) {
+        // the patch of pooled pixels (rows r0 / 2 .., columns c0 / 2 .., clamped to the pooled image: a clamped pixel belongs
+        // to no window of a pixel inside the image)
+        const int ph0 = r0 >> 1, pw0 = c0 >> 1;
+#pragma unroll
+        for (int e = 0; e < FGCH; ++e) {
+          const int i = tid + e * 256, pp = i >> 3;
+          const int ph = min(ph0 + pp / FPW, p.PH - 1), pw = min(pw0 + pp % FPW, p.PW - 1);
+          const size_t o = (((size_t)b * p.PH + ph) * p.PW + pw) * 64 + (i & 7) * 8;
+          greg[e] = ld_global<u32x4>(i < FPATCH * 8 ? reinterpret_cast<const unsigned char*>(reinterpret_cast<const bf16*>(p.dpool) + o) : zero);
+        }
+        {
+          const int pp = tid >> 2;
+          const int ph = min(ph0 + pp / FPW, p.PH - 1), pw = min(pw0 + pp % FPW, p.PW - 1);
+          const size_t o = (((size_t)b * p.PH + ph) * p.PW + pw) * 64 + (tid & 3) * 16;
+          creg = ld_global<u32x4>(tid < FPATCH * 4 ? p.idx + o : zero);
+        }
+      }
+      if constexpr (!FUSE) {      // (FUSE: prefetch_y loads y0 into dreg instead)
+#pragma unroll
+        for (int e = 0; e < DCH; ++e) {
+          const int i = tid + e * 256, pix = i >> 3, ch = i & 7;
+          const int r = r0 + (pix >> 4), c = c0 + (pix & 15);
+          const bool ok = r < p.OH && c < p.OW;
+          const size_t px = ((size_t)b * p.OH + r) * p.OW + c;
+          if constexpr (HPM) {      // a [hi 64 | lo 64] fp16 pixel record
+            const unsigned char* src = ok ? reinterpret_cast<const unsigned char*>(reinterpret_cast<const f16*>(p.dy) + px * 128 + ch * 8) : zero;
+            dreg[0][e] = ld_global<u32x4>(src);
+            dreg[HPM ? 1 : 0][e] = ld_global<u32x4>(ok ? src + 128 : zero);
+          } else {
+            const unsigned char* src = ok ? reinterpret_cast<const unsigned char*>(DY + px * 64 + ch * 8) : zero;
+            dreg[0][e] = ld_global<u32x4>(src);
+          }
         }
       }
       const int iy_base = r0 * 2 - 3, ix_base = c0 * 2 - 3;
@@ -824,33 +883,137 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(PhStemWgrad p) {
       }
     }
   };
-  auto commit = [&]() {
+  auto commit = [&](unsigned char* xdst) {      // xdst: the halo buffer to fill (FUSE: the one of the tile's parity)
     if constexpr (PREF) {
 #pragma unroll
       for (int pl = 0; pl < NPL; ++pl) {
+        if constexpr (!FUSE) {      // (FUSE: form_dz fills the dz tile)
 #pragma unroll
-        for (int e = 0; e < DCH; ++e) {
-          const int i = tid + e * 256, pix = i >> 3, ch = i & 7;
-          *reinterpret_cast<u32x4*>(ldsD + pl * DB + pix * 128 + sw_piece(pix, ch >> 1) * 32 + (ch & 1) * 16) = dreg[pl][e];
+          for (int e = 0; e < DCH; ++e) {
+            const int i = tid + e * 256, pix = i >> 3, ch = i & 7;
+            *reinterpret_cast<u32x4*>(ldsD + pl * DB + pix * 128 + sw_piece(pix, ch >> 1) * 32 + (ch & 1) * 16) = dreg[pl][e];
+          }
         }
 #pragma unroll
         for (int e = 0; e < XCH; ++e) {
           const int i = tid + e * 256;
-          if (i < HP) *reinterpret_cast<u32x2*>(ldsX + pl * XB + i * 8) = xreg[pl][e];
+          if (i < HP) *reinterpret_cast<u32x2*>(xdst + pl * XB + i * 8) = xreg[pl][e];
         }
+      }
+      if constexpr (FUSE) {
+#pragma unroll
+        for (int e = 0; e < FGCH; ++e) {
+          const int i = tid + e * 256;
+          if (i < FPATCH * 8) *reinterpret_cast<u32x4*>(ldsG + i * 16) = greg[e];
+        }
+        if (tid < FPATCH * 4) *reinterpret_cast<u32x4*>(ldsI + tid * 16) = creg;
       }
     }
   };
-  if (PREF && t_begin < t_end) prefetch(t_begin);
+  // FUSE: the thread's four dz vectors from its y0 registers and the patch in LDS, rounded to bf16, into ldsD's swizzled layout
+  auto form_dz = [&](int r0, int c0) {
+    if constexpr (FUSE) {
+      float cst[7][8];
+#pragma unroll
+      for (int v = 0; v < 7; ++v) {
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(ldsC + v * 64 + fcg * 8);
+        const f32x4 hi = *reinterpret_cast<const f32x4*>(ldsC + v * 64 + fcg * 8 + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { cst[v][k] = lo[k]; cst[v][k + 4] = hi[k]; }
+      }
+#pragma unroll
+      for (int e = 0; e < DCH; ++e) {
+        const int hpar = e >> 1, wpar = e & 1;      // (r0, c0 are even)
+        const int pix = fpix(e);
+        const int h = r0 + (pix >> 4), w = c0 + (pix & 15);
+        const bool inside = h < p.OH && w < p.OW;
+        bf16x8 gq[4];
+        u32x2 cq[4];
+        unsigned code[4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            const int q = a * 2 + c;
+            // window (a, c) is distinct from (0, .) / (., 0) only for an odd row / column: the others are never read
+            const bool exists = (!a || hpar) && (!c || wpar);
+            const int lph = frj + a * hpar, lpw = fcj + c * wpar;      // = ph - r0 / 2, pw - c0 / 2
+            const int ph = (r0 >> 1) + lph, pw = (c0 >> 1) + lpw;
+            // (a window outside the pooled image: a code no arg byte holds)
+            code[q] = (exists && ph < p.PH && pw < p.PW) ? stem_arg_code(h, w, ph, pw) : 0xffffu;
+            if (exists) {
+              gq[q] = *reinterpret_cast<const bf16x8*>(ldsG + (lph * FPW + lpw) * 128 + fcg * 16);
+              cq[q] = *reinterpret_cast<const u32x2*>(ldsI + (lph * FPW + lpw) * 64 + fcg * 8);
+            } else {
+#pragma unroll
+              for (int k = 0; k < 8; ++k) gq[q][k] = (bf16)0.f;
+              cq[q] = u32x2{0u, 0u};
+            }
+          }
+        const bf16x8 yv = __builtin_bit_cast(bf16x8, dreg[0][e]);
+        bf16x8 out;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          float g[4];
+          bool hit[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            g[q] = (float)gq[q][k];
+            hit[q] = ((cq[q][k >> 2] >> (8 * (k & 3))) & 0xffu) == code[q];
+          }
+          out[k] = (bf16)stem_dz_value(g, hit, (float)yv[k], cst[0][k], cst[1][k], cst[2][k], cst[3][k], cst[4][k], cst[5][k],
+                                       cst[6][k], 1.f);
+        }
+        u32x4 word = __builtin_bit_cast(u32x4, out);
+        if (!inside) word = u32x4{0u, 0u, 0u, 0u};      // a pixel outside OH x OW contributes no dz
+        *reinterpret_cast<u32x4*>(ldsD + pix * 128 + sw_piece(pix, fcg >> 1) * 32 + (fcg & 1) * 16) = word;
+      }
+    }
+  };
+  if constexpr (FUSE) {
+    if (tid < 64) {
+      const float is = p.invstd[tid];
+      ldsC[0 * 64 + tid] = p.scale[tid]; ldsC[1 * 64 + tid] = p.shift[tid]; ldsC[2 * 64 + tid] = p.mean[tid];
+      ldsC[3 * 64 + tid] = is; ldsC[4 * 64 + tid] = p.gamma[tid] * is; ldsC[5 * 64 + tid] = p.c1[tid];
+      ldsC[6 * 64 + tid] = p.c2[tid];
+    }
+  }
+  // FUSE, per tile: barrier | dz tile from the y0 registers and the patch -> ldsD, y0 of the next tile requested | barrier |
+  // the next tile's patch and halo (requested one tile earlier) -> LDS, the patch and halo after it requested | MFMAs.  The halo
+  // is double-buffered, so the commit needs no barrier of its own: two barriers per tile, as in the unfused kernel.
+  if constexpr (FUSE) {
+    if (t_begin < t_end) {
+      prefetch(t_begin);
+      prefetch_y(t_begin);
+      commit(xbuf(t_begin));
+      if (t_begin + 1 < t_end) prefetch(t_begin + 1);
+    }
+  } else {
+    if (PREF && t_begin < t_end) prefetch(t_begin);
+  }
   for (int tt = t_begin; tt < t_end; ++tt) {
     const int b = tt / tiles_img, ti = tt - b * tiles_img;
     const int r0 = (ti / tiles_w) * TH, c0 = (ti % tiles_w) * TW;
-    __syncthreads();
-    if constexpr (PREF) {
-      commit();
+    const unsigned char* ldsXc = xbuf(tt);
+    if constexpr (FUSE) {
+      // LDS-only barriers: __syncthreads() would drain the vector-memory counter at the barrier itself.  (The patch and halo of
+      // tile tt + 1 were requested after this tile's y0; the compiled loop waits for y0 with vmcnt(0) early in form_dz, which
+      // drains them too - in effect they are covered by one MFMA phase, as the unfused kernel's prefetch is.)
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      form_dz(r0, c0);
+      if (tt + 1 < t_end) prefetch_y(tt + 1);
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if (tt + 1 < t_end) {
+        commit(xbuf(tt + 1));
+        if (tt + 2 < t_end) prefetch(tt + 2);
+      }
+    } else if constexpr (PREF) {
+      __syncthreads();
+      commit(ldsX);
       __syncthreads();
       if (tt + 1 < t_end) prefetch(tt + 1);
     } else {
+    __syncthreads();
     for (int i = tid; i < TH * TW * 8; i += 256) {
       const int pix = i >> 3, ch = i & 7;
       const int r = r0 + (pix >> 4), c = c0 + (pix & 15);
@@ -905,7 +1068,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(PhStemWgrad p) {
           const int o0 = (hb0 + kh * HPW) * 8, o1 = (hb1 + kh * HPW) * 8;
           bf16x8 bq[NP];
 #pragma unroll
-          for (int pl = 0; pl < NP; ++pl) bq[pl] = tr_pair(ldsX + pl * XB, o0, o1);
+          for (int pl = 0; pl < NP; ++pl) bq[pl] = tr_pair(ldsXc + pl * XB, o0, o1);
           if constexpr (HPM) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -1066,12 +1229,22 @@ int ph_stem_fwd_pool_launch(const PhStemPool* p_, hipStream_t st) {
 int ph_stem_wgrad_launch(const PhStemWgrad* p, int prec, hipStream_t st) {
   dim3 grid(p->nchunks);
   void* tok = nullptr;
-  if (ph_prof_on())
-    ph_prof_begin2(PH_CLS_STEM_WGRAD, 2.0 * p->B * p->OH * p->OW * 64.0 * 147.0,
-                   ((double)p->B * p->IH * p->IW * 4 + (double)p->B * p->OH * p->OW * 64) * (prec == PH_PREC_BF16 ? 2.0 : 4.0), st, &tok);
+  if (ph_prof_on()) {
+    // bytes: the packed image + dz; fused: the packed image + y0 + the pooled gradient (2 B) and the arg codes (1 B)
+    double bytes = ((double)p->B * p->IH * p->IW * 4 + (double)p->B * p->OH * p->OW * 64) * (prec == PH_PREC_BF16 ? 2.0 : 4.0);
+    if (p->y0) bytes += (double)p->B * p->PH * p->PW * 64 * 3.0;
+    ph_prof_begin2(PH_CLS_STEM_WGRAD, 2.0 * p->B * p->OH * p->OW * 64.0 * 147.0, bytes, st, &tok);
+  }
   struct EndGuard { void* t; hipStream_t s; ~EndGuard() { ph_prof_end(t, s); } } guard{tok, st};
   const int base = TH * TW * 128 + XB;
-  if (prec == PH_PREC_BF16) {
+  if (p->y0) {      // dz formed in the kernel (perf mode only)
+    if (prec != PH_PREC_BF16 || !p->dpool || !p->idx || !p->scale || !p->shift || !p->mean || !p->invstd || !p->gamma || !p->c1 ||
+        !p->c2 || p->PH != (p->OH + 1) / 2 || p->PW != (p->OW + 1) / 2)
+      return PH_EINVAL;
+    static bool done = false;
+    if (set_lds((stem_wgrad_kernel<bf16, true>), base + FUSE_LDS, done)) return PH_ELAUNCH;
+    hipLaunchKernelGGL((stem_wgrad_kernel<bf16, true>), grid, dim3(256), base + FUSE_LDS, st, *p);
+  } else if (prec == PH_PREC_BF16) {
     static bool done = false;
     if (set_lds(stem_wgrad_kernel<bf16>, base, done)) return PH_ELAUNCH;
     hipLaunchKernelGGL(stem_wgrad_kernel<bf16>, grid, dim3(256), base, st, *p);

@@ -253,6 +253,12 @@ struct PhStemWgrad {
   int nchunks, tiles_per_chunk;
   int prod6;
   int hp_hi_only;        // half-pair mode: the hi planes' product alone (PH_PREC_FP16X1); set by the launcher
+  // y0 != null (PH_PREC_BF16 only): `dy` is not read - the kernel forms its dz tile from the conv output y0 [B][OH][OW][64], the
+  // pooled gradient dpool [B][PH][PW][64], the arg codes idx (one byte per pooled element) and the constants of
+  // ph_stem_bwd_apply_launch (64 floats each): bitwise the dz that pass writes.  PH = (OH + 1) / 2, PW = (OW + 1) / 2.
+  const void* y0; const void* dpool; const uint8_t* idx;
+  const float *mean, *invstd, *scale, *shift, *gamma, *c1, *c2;
+  int PH, PW;
 };
 int ph_stem_wgrad_launch(const PhStemWgrad* p, int prec, hipStream_t st);
 // input gradient of the 7x7/2 stem conv: dy [B][H/2][W/2][64] (type of the mode) -> dx [B][3][H][W] f32 (stem_dgrad.hip)

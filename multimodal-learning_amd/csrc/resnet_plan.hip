@@ -47,6 +47,14 @@ inline size_t up(size_t x) { return (x + ALIGN - 1) / ALIGN * ALIGN; }
 
 }  // namespace
 
+namespace {
+// A/B switch, read once: PH_STEM_FUSE=0 - new plans keep the stem's separate dz pass (ph_stem_bwd_apply_launch)
+int stem_fused_default() {
+  static const int v = [] { const char* e = getenv("PH_STEM_FUSE"); return e ? (atoi(e) != 0) : 1; }();
+  return v;
+}
+}  // namespace
+
 struct PhResnetPlan {
   int B, H, W, prec, es;
   std::vector<Unit> units;
@@ -69,6 +77,9 @@ struct PhResnetPlan {
   // dgrad chain; `dy2_off` is the second dz buffer they need.
   size_t dy2_off = 0;
   mutable int bwd_overlap = 1;
+  // perf mode: the stem's weight-gradient kernel forms dz itself (ph_resnet_plan_set_stem_fused; PH_STEM_FUSE=0/1 sets a new
+  // plan's value)
+  mutable int stem_fused = stem_fused_default();
   // PH_PREC_FP16X3: per-block max |dz| of a BatchNorm-backward reduction, and the {2^s, 2^-s} scale records of the two dz buffers
   size_t amax_off = 0, dzs_off = 0;
   // rows of a dgrad launch's fused BatchNorm-backward sums (PhTapConv::bst_y), [<= 1024][3][<= 512] floats, and the second
@@ -835,10 +846,20 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
     PH_STAGE(ph_bn_bwd_finalize_launch(parts, ph_stem_bwd_parts(P->B, u.OH), 64, (double)npix, (float*)grads[1],
                                        (float*)grads[2], c1, c2, c.amax(), ph_stem_bwd_parts(P->B, u.OH),
                                        (const float*)params[1], c.stat(u, 1), c.dzs(0), st));
-    if ((rc = claim(0))) return rc;       // the stem's dz is full resolution: only the first buffer holds it
-    PH_STAGE(ph_stem_bwd_apply_launch(gcur, ws + P->idx_off, ws + u.y_off, c.stat(u, 0), c.stat(u, 1), c.stat(u, 2),
-                                      c.stat(u, 3), (const float*)params[1], c1, c2, dzb[0], P->B, u.OH, u.OW, 64,
-                                      P->prec, c.dzs(0), st));
+    // Perf mode, whole backward: the weight-gradient kernel forms dz itself (stem_wgrad_kernel<bf16, true>) - the 64-channel dz tensor
+    // is neither written nor read.  The stage is still counted (PH_STAGE numbers are the same on every path).  A cut backward
+    // (stop > 0: the debug harness reads dz from the workspace), the image gradient (ph_resnet_backward_input) and the
+    // half-pair / split-plane arithmetics keep the separate pass.
+    const bool fuse = stop == 0 && P->prec == PH_PREC_BF16 && c.bprec() == PH_PREC_BF16 && P->stem_fused;
+    if (fuse) {
+      // (no claim(0): nothing overwrites dzb[0] on this path, so its last reader on the side stream need not be waited for)
+      PH_STAGE(PH_OK);
+    } else {
+      if ((rc = claim(0))) return rc;       // the stem's dz is full resolution: only the first buffer holds it
+      PH_STAGE(ph_stem_bwd_apply_launch(gcur, ws + P->idx_off, ws + u.y_off, c.stat(u, 0), c.stat(u, 1), c.stat(u, 2),
+                                        c.stat(u, 3), (const float*)params[1], c1, c2, dzb[0], P->B, u.OH, u.OW, 64,
+                                        P->prec, c.dzs(0), st));
+    }
     PhStemWgrad w{};
     const void* x4_ext = nullptr;
     {
@@ -852,6 +873,13 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
     w.x4 = x4_ext ? x4_ext : ws + P->x4_off; w.dy = dzb[0]; w.slab = reinterpret_cast<float*>(ws + P->slab_off);
     w.B = P->B; w.IH = P->H; w.IW = P->W; w.OH = u.OH; w.OW = u.OW;
     w.nchunks = stem_chunks(P->B, u.OH, u.OW, &w.tiles_per_chunk);
+    if (fuse) {
+      // every operand is produced on st before the event below: gcur by the last dgrad, the arg codes, y0 and the statistics by
+      // the forward, c1 / c2 by the finalize pass
+      w.dy = nullptr; w.y0 = ws + u.y_off; w.dpool = gcur; w.idx = ws + P->idx_off;
+      w.mean = c.stat(u, 0); w.invstd = c.stat(u, 1); w.scale = c.stat(u, 2); w.shift = c.stat(u, 3);
+      w.gamma = (const float*)params[1]; w.c1 = c1; w.c2 = c2; w.PH = P->PH0; w.PW = P->PW0;
+    }
     if (ov) {      // same stream as the other weight gradients: they share the slab
       hipEvent_t e = next_ev();
       if (hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(side, e, 0) != hipSuccess) return PH_ELAUNCH;
@@ -889,6 +917,14 @@ int ph_resnet_plan_set_backward_prec(const PhResnetPlan* P, int prec) {
 int ph_resnet_plan_set_backward_overlap(const PhResnetPlan* P, int on) {
   if (!P) return PH_EINVAL;
   P->bwd_overlap = on ? 1 : 0;
+  return PH_OK;
+}
+
+// A/B and test switch: 1 (default) = in perf mode the stem's weight-gradient kernel forms dz itself, 0 = the separate dz pass
+// (what every other arithmetic, a cut debug backward and the image gradient always run)
+int ph_resnet_plan_set_stem_fused(const PhResnetPlan* P, int on) {
+  if (!P) return PH_EINVAL;
+  P->stem_fused = on ? 1 : 0;
   return PH_OK;
 }
 

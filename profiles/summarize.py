@@ -50,6 +50,15 @@ def cls_of(name):
         if "16, 128, 4, 2" in n or "Li16ELi128ELi4ELi2" in n:
             return 1
         return None
+    # the stem's backward tail (traffic classes of their own, named: not classes of ph_prof_summary): the pass that writes the
+    # stem's dz (max-pool + ReLU + BatchNorm backward), and the weight-gradient kernel that forms dz itself (<bf16, true>) and
+    # so replaces that pass and the plain kernel (class 5) in the bf16 mode
+    if "stem_bwd_kernel" in n:
+        return "stem_bwd"
+    # (the profiler's demangler does not know the __bf16 code DF16b: it prints the fused instantiation's mangled
+    # name ...IDF16bLb1EE... as `stem_wgrad_kernel<bool _Accum, bool, E>` and leaves the unfused one, ...IDF16bEE..., mangled)
+    if "stem_wgrad_kernel" in n and ("Lb1E" in n or ", true>" in n or "<bool _Accum, bool, E>" in n):
+        return "stem_wgrad_fused"
     if "stem_wgrad_kernel" in n:
         return 5
     if "stem_fwd_kernel" in n:
@@ -142,7 +151,7 @@ def main():
             c = cls_of(k)
             if c is not None:
                 per[c][1] += wa[k].get("WRITE_SIZE", 0.0); per[c][3] += wc[k]
-        for c, (fe, wr, nf, nw) in sorted(per.items()):
+        for c, (fe, wr, nf, nw) in sorted(per.items(), key=lambda kv: (isinstance(kv[0], str), kv[0])):
             rd = 2.0 * fe * 1024 / max(nf, 1)        # gfx950: FETCH_SIZE counts 64 B per 128-B request
             ww = wr * 1024 / max(nw, 1)
             traffic[str(c)] = {"read_bytes_per_launch": round(rd), "write_bytes_per_launch": round(ww),
@@ -176,7 +185,7 @@ def main():
             c = cls_of(k)
             if c is not None:
                 per[c][1] += wa[k].get("WRITE_SIZE", 0.0); per[c][3] += wc[k]
-        for c, (fe, wr, nf, nw) in sorted(per.items()):
+        for c, (fe, wr, nf, nw) in sorted(per.items(), key=lambda kv: (isinstance(kv[0], str), kv[0])):
             rd = 2.0 * fe * 1024 / max(nf, 1)
             ww = wr * 1024 / max(nw, 1)
             traffic[str(c)] = {"read_bytes_per_launch": round(rd), "write_bytes_per_launch": round(ww),
@@ -197,7 +206,7 @@ def main():
             o.write("# rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum (eager bench); per launch of each kernel class\n")
             o.write("# l2_hit = HIT / (HIT + MISS) over 128-B request granules; rdreq = read requests the L2 sent to the fabric "
                     "(Infinity Cache / HBM); rdreq_dram = those addressed to device memory\n")
-            for c, d in sorted(per.items()):
+            for c, d in sorted(per.items(), key=lambda kv: (isinstance(kv[0], str), kv[0])):
                 n = max(d["n"], 1)
                 o.write(f"class {c}: l2_hit {d['TCC_HIT_sum'] / max(d['TCC_HIT_sum'] + d['TCC_MISS_sum'], 1):.3f}  "
                         f"hit {d['TCC_HIT_sum'] / n:12.0f}  miss {d['TCC_MISS_sum'] / n:12.0f}  rdreq {d['TCC_EA0_RDREQ_sum'] / n:12.0f}  "
