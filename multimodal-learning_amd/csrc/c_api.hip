@@ -54,14 +54,13 @@ bool geometry_ok(int B, int Cin, int IH, int IW, int Cout, int KS, int stride, i
   return IH + 2 * pad >= KS && IW + 2 * pad >= KS;
 }
 
-int chunks_for(int B, int OH, int OW, int S, int Cout, int Cin, int* tpc) {
-  const int th = ph_wgrad_tile_h(S);
-  const int ntiles = B * cdiv(OH, th) * cdiv(OW, 16);
-  int want = cdiv(512, (Cout / 64) * (Cin / 64));
-  if (want > ntiles) want = ntiles;
-  if (want < 1) want = 1;
-  *tpc = cdiv(ntiles, want);
-  return cdiv(ntiles, *tpc);
+struct Conv { int B, Cin, IH, IW, Cout, KS, stride, pad; };
+
+// the weight-gradient launch of convolution v: geometry and chunking of descriptor g (tensors are the caller's); returns the chunks
+int plan_wgrad(const Conv& v, PhWgrad* g) {
+  g->B = v.B;
+  ph_conv_wgrad_geometry(g, v.Cin, v.IH, v.IW, v.Cout, v.KS, v.stride, v.pad);
+  return g->nchunks = ph_wgrad_chunks(g, v.B, PH_WG_WANT_ALONE, &g->tiles_per_chunk);
 }
 }  // namespace
 
@@ -76,14 +75,17 @@ size_t ph_conv2d_workspace_bytes(int B, int Cin, int IH, int IW, int Cout, int K
   for (int prec = PH_PREC_BF16; prec <= PH_PREC_FP16X3; ++prec)
     for (int S = 1; S <= stride; ++S) nparts = std::max(nparts, ph_tapconv_stat_parts_bound(B, OH, OW, Cout, S, prec));
   const size_t parts = up((size_t)nparts * 2 * Cout * sizeof(float));
-  int tpc; const int nc = chunks_for(B, OH, OW, stride, Cout, Cin, &tpc);
+  // slab: the chunks ph_conv2d_wgrad launches with - and never fewer than a launch at the convolution's own stride would take, which
+  // is how the 1x1 / stride-2 view used to be sized (that count can be the smaller or the larger one)
+  PhWgrad g{};
+  int nc = plan_wgrad(Conv{B, Cin, IH, IW, Cout, KS, stride, pad}, &g);
+  g.S = stride;
+  nc = std::max(nc, ph_wgrad_chunks(&g, B, PH_WG_WANT_ALONE, &g.tiles_per_chunk));
   const size_t slab = up((size_t)nc * KS * KS * Cin * Cout * sizeof(float));
   return wbytes + (parts > slab ? parts : slab) + 256;
 }
 
 namespace {
-struct Conv { int B, Cin, IH, IW, Cout, KS, stride, pad; };
-
 // the forward launch of convolution v: geometry, route and weight layout of descriptor t (tensors are the caller's), *S = the stride
 // it is launched with.  PH_EINVAL before anything is written.
 int plan_fwd(const Conv& v, int prec, PhTapConv* t, int* S) {
@@ -262,22 +264,23 @@ int ph_conv2d_wgrad(const void* x, const void* dy, float* dw, int B, int Cin, in
   if (!geometry_ok(B, Cin, IH, IW, Cout, KS, stride, pad) || prec < PH_PREC_BF16 || prec > PH_PREC_FP16X1 || !x || !dy || !dw || !ws_)
     return PH_EINVAL;
   unsigned char* ws = reinterpret_cast<unsigned char*>(ws_);
-  const size_t plane = (size_t)KS * KS * Cin * Cout;
-  const int OH = (IH + 2 * pad - KS) / stride + 1, OW = (IW + 2 * pad - KS) / stride + 1;
   PhWgrad g{};
   // layout: [256 B zero page][slab]
   if (hipMemsetAsync(ws, 0, 256, st) != hipSuccess) return PH_ELAUNCH;
   g.zeros = ws;
   g.x = x; g.dy = dy; g.slab = reinterpret_cast<float*>(ws + 256);
-  g.B = B; g.IH = IH; g.IW = IW; g.Cin = Cin; g.OH = OH; g.OW = OW; g.Cout = Cout; g.S = stride; g.pad = pad; g.KS = KS;
-  if (KS == 1 && stride == 2) {
-    g.x_pix_stride = 2L * Cin; g.x_row_stride = 2L * IW * Cin; g.x_img_stride = (long)IH * IW * Cin;
-    g.IH = OH; g.IW = OW; g.S = 1;
-  }
-  g.nchunks = chunks_for(B, OH, OW, g.S, Cout, Cin, &g.tiles_per_chunk);
+  plan_wgrad(Conv{B, Cin, IH, IW, Cout, KS, stride, pad}, &g);
   int rc = ph_wgrad_launch(&g, prec, st);
   if (rc) return rc;
   return ph_wgrad_reduce_launch(g.slab, dw, g.nchunks, KS, Cout, Cin, nullptr, st);
+}
+
+// host-only test access (not part of the public C-ABI): the chunk count - slab planes of KS * KS * Cin * Cout floats behind the
+// 256-byte zero page - ph_conv2d_wgrad launches with, or PH_EINVAL.  Makes no HIP call.
+extern "C" int ph_debug_conv2d_wgrad_chunks(int B, int Cin, int IH, int IW, int Cout, int KS, int stride, int pad) {
+  if (!geometry_ok(B, Cin, IH, IW, Cout, KS, stride, pad)) return PH_EINVAL;
+  PhWgrad g{};
+  return plan_wgrad(Conv{B, Cin, IH, IW, Cout, KS, stride, pad}, &g);
 }
 
 int ph_stem_dgrad(const void* dy_nhwc, const float* w_oihw, float* dx_nchw, int B, int H, int W, int prec, hipStream_t st) {

@@ -150,3 +150,53 @@ int ph_conv_dgrad_s2_classes(const PhTapConv* t, int Cin, int IH, int IW, int Co
     }
   return PH_OK;
 }
+
+int ph_conv_dgrad_s2_merge(const PhTapConv cls[4], int ncls, int KS, PhTapConv* m, bool taken[4]) {
+  PhTapConv& mt = *m;
+  mt = cls[0];
+  mt.ncls = 0;
+  for (int i = 0; i < ncls; ++i) {
+    const PhTapConv& q = cls[i];
+    taken[i] = KS == 3 && q.ntaps <= 4 && mt.ncls < 4;
+    if (!taken[i]) continue;
+    const int k = mt.ncls++;
+    mt.c_ntaps[k] = q.ntaps; mt.c_oa_h[k] = q.oa_h; mt.c_oa_w[k] = q.oa_w; mt.c_OHt[k] = q.OHt; mt.c_OWt[k] = q.OWt;
+    for (int e = 0; e < q.ntaps; ++e) { mt.c_dy[k][e] = q.dy[e]; mt.c_dx[k][e] = q.dx[e]; mt.c_wtap[k][e] = q.wtap[e]; }
+    for (int e = q.ntaps; e < 4; ++e) { mt.c_dy[k][e] = 0; mt.c_dx[k][e] = 0; mt.c_wtap[k][e] = 0; }
+    // the descriptor's own fields: the largest class (grid extent; profiler)
+    if (k == 0 || q.OHt * q.OWt > mt.OHt * mt.OWt) { mt.OHt = q.OHt; mt.OWt = q.OWt; }
+    if (k == 0 || q.ntaps > mt.ntaps) {
+      mt.ntaps = q.ntaps;
+      for (int e = 0; e < q.ntaps; ++e) { mt.dy[e] = q.dy[e]; mt.dx[e] = q.dx[e]; mt.wtap[e] = q.wtap[e]; }
+    }
+    mt.os = 2; mt.oa_h = 0; mt.oa_w = 0; mt.iy0 = 0; mt.ix0 = 0;
+  }
+  if (mt.ncls == 1) {      // (a single class that qualified: an ordinary launch)
+    mt.ncls = 0;
+    mt.ntaps = mt.c_ntaps[0]; mt.oa_h = mt.c_oa_h[0]; mt.oa_w = mt.c_oa_w[0]; mt.OHt = mt.c_OHt[0]; mt.OWt = mt.c_OWt[0];
+    for (int e = 0; e < mt.ntaps; ++e) { mt.dy[e] = mt.c_dy[0][e]; mt.dx[e] = mt.c_dx[0][e]; mt.wtap[e] = mt.c_wtap[0][e]; }
+    return 1;
+  }
+  return mt.ncls;
+}
+
+void ph_conv_wgrad_geometry(PhWgrad* w, int Cin, int IH, int IW, int Cout, int KS, int stride, int pad) {
+  w->IH = IH; w->IW = IW; w->Cin = Cin; w->Cout = Cout;
+  w->OH = (IH + 2 * pad - KS) / stride + 1; w->OW = (IW + 2 * pad - KS) / stride + 1;
+  w->S = stride; w->pad = pad; w->KS = KS;
+  if (KS == 1 && stride == 2) {   // strided view, as in ph_conv_fwd_route
+    w->x_pix_stride = 2L * Cin; w->x_row_stride = 2L * IW * Cin; w->x_img_stride = (long)IH * IW * Cin;
+    w->IH = w->OH; w->IW = w->OW; w->S = 1;
+  }
+}
+
+int ph_wgrad_chunks(const PhWgrad* w, int B, int wg_want, int* tiles_per_chunk) {
+  const int th = ph_wgrad_tile_h(w->S);
+  const int ntiles = B * cdiv(w->OH, th) * cdiv(w->OW, 16);
+  const int blocks = (w->Cout / 64) * (w->Cin / 64);
+  int want = cdiv(wg_want, blocks);
+  if (want > ntiles) want = ntiles;
+  if (want < 1) want = 1;
+  *tiles_per_chunk = cdiv(ntiles, want);
+  return cdiv(ntiles, *tiles_per_chunk);
+}

@@ -139,6 +139,10 @@ void ph_conv_dgrad_s1_geometry(PhTapConv* t, int Cin, int IH, int IW, int Cout, 
 // *t with one class's geometry each, *tapless = some class is reached by no tap.  PH_EINVAL: a tap offset outside 0..2.
 int ph_conv_dgrad_s2_classes(const PhTapConv* t, int Cin, int IH, int IW, int Cout, int KS, int pad, PhTapConv cls[4], int* ncls,
                              bool* tapless);
+// ONE launch for the classes among cls[0 .. ncls) that can share it (PhTapConv::ncls: the 3x3 convolutions' 1 / 2 / 2 / 4 taps over
+// the same dz, disjoint output pixels).  taken[i] = class i is in *m; returns how many are.  >= 2: *m is the merged descriptor, its
+// own extent / tap fields the largest class's; 1: *m is that class as an ordinary launch (ncls = 0); 0: *m is not to be launched.
+int ph_conv_dgrad_s2_merge(const PhTapConv cls[4], int ncls, int KS, PhTapConv* m, bool taken[4]);
 
 // A/B and test switch `ph_<name>_switch(set)`: on unless ENV=0 in the environment (read once); set >= 0 sets it at run time, set < 0
 // queries.  ph_debug_set_<name>() is the run-time setter the tests use (not part of the public C-ABI).
@@ -149,6 +153,16 @@ int ph_conv_dgrad_s2_classes(const PhTapConv* t, int Cin, int IH, int IW, int Co
     return on;                                                                                            \
   }                                                                                                       \
   extern "C" int ph_debug_set_##name(int on) { return ph_##name##_switch(on ? 1 : 0); }
+// A/B switches without a run-time setter (`static const int v = ph_env_flag(..)`: read once).  Flag: NAME=1 -> 1, NAME=0 -> 0,
+// unset (or anything else) -> dflt, which may be -1 for "decide by shape".  Int: the value, dflt when unset.
+inline int ph_env_flag(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return (e && e[0] == '1') ? 1 : ((e && e[0] == '0') ? 0 : dflt);
+}
+inline int ph_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // kernel-family dispatch record for the tests (host side, not part of the public C-ABI): every launcher ORs the bit of the
 // family it runs; ph_debug_dispatch_mask() reads and ph_debug_dispatch_reset() clears it (conv_tap.hip).  Bits 0 .. 12: 1u << PH_CK_*
@@ -216,6 +230,15 @@ struct PhWgrad {
 };
 int ph_wgrad_launch(const PhWgrad* p, int prec, hipStream_t st);
 int ph_wgrad_tile_h(int S);
+// the launch geometry of a convolution's weight gradient (conv_select.hip; tensors, batch and chunking are the caller's): the dims, and
+// for 1x1 / stride 2 the stride-1 launch over the even-pixel view of x (x_*_stride, IH / IW := OH / OW, S := 1, as ph_conv_fwd_route)
+void ph_conv_wgrad_geometry(PhWgrad* w, int Cin, int IH, int IW, int Cout, int KS, int stride, int pad);
+// split-K chunks of that launch over B images (= slab planes it writes) aiming for wg_want workgroups, *tiles_per_chunk tiles each;
+// the tile height is that of the LAUNCH stride w->S, i.e. after the view.  The only sizing of a slab and the only chunking of a launch.
+int ph_wgrad_chunks(const PhWgrad* w, int B, int wg_want, int* tiles_per_chunk);
+// Workgroups a weight-gradient launch aims for when it has the chip to itself: ~2 per CU (A/B on one box: 256 -> +0.2 ms / step,
+// 384 and 768 -> +0.33)
+constexpr int PH_WG_WANT_ALONE = 512;
 // slab -> OIHW fp32 gradient; unscale (optional): the {2^s, 2^-s} record of the dz tensor, the sums are multiplied by unscale[1]
 int ph_wgrad_reduce_launch(const float* slab, float* dw_oihw, int nchunks, int KS, int Cout, int Cin, const float* unscale,
                            hipStream_t st);

@@ -50,7 +50,7 @@ inline size_t up(size_t x) { return (x + ALIGN - 1) / ALIGN * ALIGN; }
 namespace {
 // A/B switch, read once: PH_STEM_FUSE=0 - new plans keep the stem's separate dz pass (ph_stem_bwd_apply_launch)
 int stem_fused_default() {
-  static const int v = [] { const char* e = getenv("PH_STEM_FUSE"); return e ? (atoi(e) != 0) : 1; }();
+  static const int v = ph_env_flag("PH_STEM_FUSE", 1);
   return v;
 }
 }  // namespace
@@ -89,22 +89,11 @@ struct PhResnetPlan {
 
 namespace {
 
-// Workgroups a weight-gradient launch aims for.  Alone on the chip ~2 per CU is best (A/B on one box: 256 -> +0.2 ms / step,
-// 384 and 768 -> +0.33).  On the side stream of the two-stream backward (backward_impl) ONE per CU: the BatchNorm-backward
+// Workgroups a weight-gradient launch aims for (ph_wgrad_chunks).  Alone on the chip PH_WG_WANT_ALONE, ~2 per CU - the plan's slab
+// is sized for that.  On the side stream of the two-stream backward (backward_impl) ONE per CU: the BatchNorm-backward
 // passes it runs beside need the other half of every SIMD's registers and wave slots (same box, ms per step: one stream
 // 12.76 / two streams with 512: 12.63, 384: 12.47, 256: 12.31, 192: 12.2 on a box where 256 gave 11.95, 128: 13.3).
-constexpr int WG_WANT_ALONE = 512, WG_WANT_BESIDE = 256;
-int wgrad_chunks(const Unit& u, int B, int* tiles_per_chunk, int wg_want = WG_WANT_ALONE) {
-  const int th = ph_wgrad_tile_h((u.KS == 1) ? 1 : u.S);
-  const int ntiles = B * cdiv(u.OH, th) * cdiv(u.OW, 16);
-  const int blocks = (u.Cout / 64) * (u.Cin / 64);
-  int want = cdiv(wg_want, blocks);
-  if (want > ntiles) want = ntiles;
-  if (want < 1) want = 1;
-  int tpc = cdiv(ntiles, want);
-  *tiles_per_chunk = tpc;
-  return cdiv(ntiles, tpc);
-}
+constexpr int WG_WANT_BESIDE = 256;
 int stem_chunks(int B, int OH, int OW, int* tpc) {
   const int ntiles = B * cdiv(OH, 8) * cdiv(OW, 16);
   int want = ntiles < 1024 ? ntiles : 1024;   // 4 workgroups per CU: the per-tile staging latency is hidden by occupancy
@@ -130,6 +119,24 @@ unsigned long long refresh_layouts(const PhResnetPlan* P) {
   }
   return sig;
 }
+
+// The caller's pointer tables.  params: per unit 6 pointers [w (OIHW f32), gamma, beta, running_mean, running_var,
+// num_batches_tracked (i64)]; grads: per unit 3 pointers [dw (OIHW f32), dgamma, dbeta]
+struct Params {
+  const void* const* p;
+  const float* w(int ui) const { return (const float*)p[ui * 6 + 0]; }
+  const float* gamma(int ui) const { return (const float*)p[ui * 6 + 1]; }
+  const float* beta(int ui) const { return (const float*)p[ui * 6 + 2]; }
+  float* running_mean(int ui) const { return (float*)p[ui * 6 + 3]; }
+  float* running_var(int ui) const { return (float*)p[ui * 6 + 4]; }
+  int64_t* num_batches_tracked(int ui) const { return (int64_t*)p[ui * 6 + 5]; }
+};
+struct Grads {
+  void* const* p;
+  float* dw(int ui) const { return (float*)p[ui * 3 + 0]; }
+  float* dgamma(int ui) const { return (float*)p[ui * 3 + 1]; }
+  float* dbeta(int ui) const { return (float*)p[ui * 3 + 2]; }
+};
 
 }  // namespace
 
@@ -184,7 +191,9 @@ PhResnetPlan* ph_resnet_plan_create(int B, int H, int W, int prec) {
         u.st_off = take(4 * (size_t)cout * sizeof(float));
         for (int S = 1; S <= (ks == 1 ? 1 : st); ++S)      // (a 3x3 stride-2 forward may be routed to a stride-1 launch, a 1x1 always is)
           parts_max = std::max(parts_max, (size_t)ph_tapconv_stat_parts_bound(B, u.OH, u.OW, cout, S, prec) * 2 * cout * sizeof(float));
-        int tpc; int nc = wgrad_chunks(u, B, &tpc);
+        PhWgrad w{};
+        ph_conv_wgrad_geometry(&w, cin, uih, uiw, cout, ks, st, pad);
+        int tpc; int nc = ph_wgrad_chunks(&w, B, PH_WG_WANT_ALONE, &tpc);
         slab_max = std::max(slab_max, (size_t)nc * ks * ks * cin * cout * sizeof(float));
         P->units.push_back(u);
         return (int)P->units.size() - 1;
@@ -242,21 +251,21 @@ int ph_resnet_unit_shape(const PhResnetPlan* P, int u, int* out4) {
   return PH_OK;
 }
 
-// params: per unit 6 pointers [w (OIHW f32), gamma, beta, running_mean, running_var, num_batches_tracked(i64)]
-int ph_resnet_pack_weights(const PhResnetPlan* P, const void* const* params, void* packed, hipStream_t st) {
-  if (!P || !params || !packed) return PH_EINVAL;
+int ph_resnet_pack_weights(const PhResnetPlan* P, const void* const* params_, void* packed, hipStream_t st) {
+  if (!P || !params_ || !packed) return PH_EINVAL;
+  const Params params{params_};
   refresh_layouts(P);
   bf16* pk = reinterpret_cast<bf16*>(packed);
   int rc = P->prec == PH_PREC_FP16X3
-               ? ph_pack_w_stem_hp_launch(reinterpret_cast<const float*>(params[0]), pk + P->units[0].wf_off, st)
-               : ph_pack_w_stem_launch(reinterpret_cast<const float*>(params[0]), pk + P->units[0].wf_off, st);
+               ? ph_pack_w_stem_hp_launch(params.w(0), pk + P->units[0].wf_off, st)
+               : ph_pack_w_stem_launch(params.w(0), pk + P->units[0].wf_off, st);
   if (rc) return rc;
   PhPackAll t{};
   size_t acc = 0;
   for (size_t i = 1; i < P->units.size(); ++i) {
     const Unit& u = P->units[i];
     const int k = t.n++;
-    t.w[k] = reinterpret_cast<const float*>(params[i * 6 + 0]);
+    t.w[k] = params.w((int)i);
     t.dst_fwd[k] = u.wf_off; t.dst_dg[k] = u.wd_off;
     t.O[k] = u.Cout; t.I[k] = u.Cin; t.NT[k] = u.KS * u.KS;
     // the layouts the kernels of this unit's launches read (refresh_layouts above: the eligibility and switch state that picks them)
@@ -275,14 +284,14 @@ namespace {
 
 struct Ctx {
   const PhResnetPlan* P;
-  const void* const* params;
+  Params params;
   const bf16* pk;
   unsigned char* ws;
   hipStream_t st;
   int update_running;
   int eval;
   int no_masked = 0;      // A/B and test switch (forward flag bit3): first-generation kernels for the stride-2 convolutions
-  int wg_want = WG_WANT_ALONE;   // workgroups a weight-gradient launch aims for (wgrad_chunks)
+  int wg_want = PH_WG_WANT_ALONE;   // workgroups a weight-gradient launch aims for (ph_wgrad_chunks)
   float* stat(const Unit& u, int which) const {
     return reinterpret_cast<float*>(ws + u.st_off) + (size_t)which * u.Cout;
   }
@@ -291,6 +300,16 @@ struct Ctx {
   float* dzs(int k) const { return P->prec == PH_PREC_FP16X3 ? reinterpret_cast<float*>(ws + P->dzs_off) + 2 * k : nullptr; }
   float* amax() const { return P->prec == PH_PREC_FP16X3 ? reinterpret_cast<float*>(ws + P->amax_off) : nullptr; }
 };
+
+// training-mode forward BatchNorm of unit ui from its convolution's `nparts` partial rows: mean / invstd / scale / shift, and (train
+// mode) the running statistics
+int bn_finalize_fwd(const Ctx& c, int ui, const float* parts, int nparts) {
+  const Unit& u = c.P->units[ui];
+  return ph_bn_finalize_launch(parts, nparts, u.Cout, (double)c.P->B * u.OH * u.OW, 1e-5f, 0.1f, c.params.gamma(ui), c.params.beta(ui),
+                               c.stat(u, 0), c.stat(u, 1), c.stat(u, 2), c.stat(u, 3),
+                               c.update_running ? c.params.running_mean(ui) : nullptr, c.params.running_var(ui),
+                               c.params.num_batches_tracked(ui), c.st);
+}
 
 int conv_fwd(const Ctx& c, int ui, const void* in, const float* in_scale = nullptr, const float* in_shift = nullptr) {
   const PhResnetPlan* P = c.P;
@@ -305,12 +324,7 @@ int conv_fwd(const Ctx& c, int ui, const void* in, const float* in_scale = nullp
   const int S = ph_conv_fwd_route(&t, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.S, u.pad, P->prec, c.no_masked);
   int rc = ph_tapconv_launch(&t, S, P->prec, c.st);
   if (rc || c.eval) return rc;      // (eval: scale/shift were preset from the running statistics)
-  const int nparts = ph_tapconv_stat_parts(&t, S, P->prec);
-  float* rm = c.update_running ? (float*)c.params[ui * 6 + 3] : nullptr;
-  return ph_bn_finalize_launch(t.stats, nparts, u.Cout, (double)P->B * u.OH * u.OW, 1e-5f, 0.1f,
-                               (const float*)c.params[ui * 6 + 1], (const float*)c.params[ui * 6 + 2], c.stat(u, 0),
-                               c.stat(u, 1), c.stat(u, 2), c.stat(u, 3), rm, (float*)c.params[ui * 6 + 4],
-                               (int64_t*)c.params[ui * 6 + 5], c.st);
+  return bn_finalize_fwd(c, ui, t.stats, ph_tapconv_stat_parts(&t, S, P->prec));
 }
 
 // BatchNorm-backward sums a dgrad launch takes over the gradient it writes (PhTapConv::bst_y): of unit `u` (mask: its own ReLU
@@ -349,8 +363,7 @@ int conv_dgrad(const Ctx& c, int ui, const void* dy, void* dx, const void* res_g
       // (the launches get slower by more than the 30 us pass they replace, which ran beside a weight gradient anyway); B = 256: trunk
       // 23.82 -> 23.60 ms, step 36.6 -> 36.3 ms.  Default: on from B = 128 where conv_tap7.hip takes the launch (PH_BST3 / PH_BST2 = 0 / 1
       // force it off / on, 1 also on conv_tap3.hip)
-      static const int bst3 = [] { const char* e = getenv("PH_BST3"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-      static const int bst2 = [] { const char* e = getenv("PH_BST2"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
+      static const int bst3 = ph_env_flag("PH_BST3", -1), bst2 = ph_env_flag("PH_BST2", -1);
       const PhConvChoice ch = ph_tapconv_select(&f, 1, P->prec);      // the kernels that can take the sums: conv_tap3 / 4 / 7
       const bool on7 = ch.kernel == PH_CK_TAP7, dense = on7 || ch.kernel == PH_CK_TAP3, l1 = ch.kernel == PH_CK_TAP4;
       const bool big = P->B >= 128;
@@ -369,42 +382,18 @@ int conv_dgrad(const Ctx& c, int ui, const void* dy, void* dx, const void* res_g
   // 3x3 convolutions (1 / 2 / 2 / 4 taps over the same dz, disjoint output pixels) - ONE launch for all four (PhTapConv::ncls,
   // round 6: as four launches in a row layers 3.0 / 4.0 put 256 / 128 workgroups on the 256 CUs each time; PH_S2_MERGE=0
   // keeps them apart, A/B and test switch)
-  static const bool merge = [] { const char* e = getenv("PH_S2_MERGE"); return !(e && e[0] == '0'); }();
-  PhTapConv cls[4];
+  static const bool merge = ph_env_flag("PH_S2_MERGE", 1);
+  PhTapConv cls[4], mt;
   int ncls;
   bool tapless;      // (a class no tap reaches, 1x1 stride-2: the gradient is zero there; with an in-place residual (res_g == dx) the
                      // existing values already are the result, otherwise the caller pre-zeroed dx)
   int rc = ph_conv_dgrad_s2_classes(&t, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.pad, cls, &ncls, &tapless);
   if (rc) return rc;
-  PhTapConv mt = cls[0];
-  mt.ncls = 0;
-  for (int i = 0; i < ncls; ++i) {
-    const PhTapConv& q = cls[i];
-    if (merge && u.KS == 3 && q.ntaps <= 4 && mt.ncls < 4) {
-      const int k = mt.ncls++;
-      mt.c_ntaps[k] = q.ntaps; mt.c_oa_h[k] = q.oa_h; mt.c_oa_w[k] = q.oa_w; mt.c_OHt[k] = q.OHt; mt.c_OWt[k] = q.OWt;
-      for (int e = 0; e < q.ntaps; ++e) { mt.c_dy[k][e] = q.dy[e]; mt.c_dx[k][e] = q.dx[e]; mt.c_wtap[k][e] = q.wtap[e]; }
-      for (int e = q.ntaps; e < 4; ++e) { mt.c_dy[k][e] = 0; mt.c_dx[k][e] = 0; mt.c_wtap[k][e] = 0; }
-      // the descriptor's own fields: the largest class (grid extent; profiler)
-      if (k == 0 || q.OHt * q.OWt > mt.OHt * mt.OWt) { mt.OHt = q.OHt; mt.OWt = q.OWt; }
-      if (k == 0 || q.ntaps > mt.ntaps) {
-        mt.ntaps = q.ntaps;
-        for (int e = 0; e < q.ntaps; ++e) { mt.dy[e] = q.dy[e]; mt.dx[e] = q.dx[e]; mt.wtap[e] = q.wtap[e]; }
-      }
-      mt.os = 2; mt.oa_h = 0; mt.oa_w = 0; mt.iy0 = 0; mt.ix0 = 0;
-      continue;
-    }
-    if ((rc = ph_tapconv_launch(&q, 1, c.bprec(), c.st))) return rc;
-  }
-  if (mt.ncls >= 2) return ph_tapconv_launch(&mt, 1, c.bprec(), c.st);
-  if (mt.ncls == 1) {      // (a single class that qualified: an ordinary launch)
-    PhTapConv one = mt;
-    one.ncls = 0;
-    one.ntaps = mt.c_ntaps[0]; one.oa_h = mt.c_oa_h[0]; one.oa_w = mt.c_oa_w[0]; one.OHt = mt.c_OHt[0]; one.OWt = mt.c_OWt[0];
-    for (int e = 0; e < one.ntaps; ++e) { one.dy[e] = mt.c_dy[0][e]; one.dx[e] = mt.c_dx[0][e]; one.wtap[e] = mt.c_wtap[0][e]; }
-    return ph_tapconv_launch(&one, 1, c.bprec(), c.st);
-  }
-  return PH_OK;
+  bool merged[4] = {false, false, false, false};
+  const int nmerged = merge ? ph_conv_dgrad_s2_merge(cls, ncls, u.KS, &mt, merged) : 0;
+  for (int i = 0; i < ncls; ++i)      // the classes that stay apart first, in class order
+    if (!merged[i] && (rc = ph_tapconv_launch(&cls[i], 1, c.bprec(), c.st))) return rc;
+  return nmerged ? ph_tapconv_launch(&mt, 1, c.bprec(), c.st) : PH_OK;
 }
 
 int conv_wgrad(const Ctx& c, int ui, const void* x, const void* dy, float* dw, const float* dzs = nullptr) {
@@ -413,53 +402,54 @@ int conv_wgrad(const Ctx& c, int ui, const void* x, const void* dy, float* dw, c
   PhWgrad w{};
   w.x = x; w.dy = dy; w.slab = reinterpret_cast<float*>(c.ws + P->slab_off);
   w.zeros = c.ws + P->zero_off;
-  w.B = P->B; w.IH = u.IH; w.IW = u.IW; w.Cin = u.Cin; w.OH = u.OH; w.OW = u.OW; w.Cout = u.Cout;
-  w.S = u.S; w.pad = u.pad; w.KS = u.KS;
-  if (u.KS == 1 && u.S == 2) {   // strided view, as in conv_fwd
-    w.x_pix_stride = 2L * u.Cin; w.x_row_stride = 2L * u.IW * u.Cin; w.x_img_stride = (long)u.IH * u.IW * u.Cin;
-    w.IH = u.OH; w.IW = u.OW; w.S = 1;
-  }
-  w.nchunks = wgrad_chunks(u, P->B, &w.tiles_per_chunk, c.wg_want);
+  w.B = P->B;
+  ph_conv_wgrad_geometry(&w, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.S, u.pad);
+  w.nchunks = ph_wgrad_chunks(&w, P->B, c.wg_want, &w.tiles_per_chunk);
   int rc = ph_wgrad_launch(&w, c.bprec(), c.st);
   if (rc) return rc;
   return ph_wgrad_reduce_launch(w.slab, dw, w.nchunks, u.KS, u.Cout, u.Cin, dzs, c.st);
 }
 
-// BN backward of unit ui: dz = g * (a > 0) -> dgamma/dbeta, dy (into ws dy buffer).  self_mask: `a` is this unit's own
-// relu(bn(y)) (bn1 of a block) - the mask is recomputed from y and `a` is not read.
-// fused_parts > 0: the sums were taken by the dgrad launch that wrote `g` (conv_dgrad: [fused_parts][3][C] rows in the plan's
-// fparts buffer, this unit's second sum in row `row2`) - no reduction pass.  cc2: the c1 / c2 pair lives in the plan's second
-// buffer (a downsample BatchNorm finalised together with bn2, applied later).  apply = false: finalise only.
-int bn_bwd(const Ctx& c, int ui, const void* g, const void* a, void* dy, float* dgamma, float* dbeta, bool self_mask = false,
-           float* dzs = nullptr, int fused_parts = 0, int row2 = 1, bool cc2 = false, bool finalize = true, bool apply = true) {
+// BatchNorm backward of unit ui over the incoming gradient g: dz = g * (ReLU mask) -> sums -> dgamma / dbeta and the correction
+// terms c1 = mean(dz), c2 = mean(dz * xhat) -> dy.  The two steps below share this description.
+struct BnBwd {
+  int ui;
+  const void* g;
+  const void* mask;       // the activation whose sign is the ReLU mask (a > 0); null = the unit's OWN relu(bn(y)) (bn1 of a block): the
+                          // mask is recomputed from y and no activation is read
+  bool second_cc = false; // c1 / c2 live in the plan's second pair (a downsample BatchNorm finalised together with bn2, applied later)
+  float* dzs = nullptr;   // half-pair mode: the {2^s, 2^-s} scale record of the dz buffer dy goes to
+};
+struct BnBwdOps {      // the kernels' operands of a BnBwd
+  const Unit& u; size_t npix; const void* y; const float* ms; const float* mh; float* c1; float* c2;
+  BnBwdOps(const Ctx& c, const BnBwd& s)
+      : u(c.P->units[s.ui]), npix((size_t)c.P->B * u.OH * u.OW), y(c.ws + u.y_off), ms(s.mask ? nullptr : c.stat(u, 2)),
+        mh(s.mask ? nullptr : c.stat(u, 3)), c1(reinterpret_cast<float*>(c.ws + (s.second_cc ? c.P->cc2_off : c.P->cc_off))), c2(c1 + 512) {}
+};
+
+// The sums and their finalisation (dgamma, dbeta, c1, c2, the dz scale record).  fused_parts > 0: the dgrad launch that wrote `g` took
+// the sums (conv_dgrad: [fused_parts][3][C] rows in the plan's fparts buffer, this unit's second sum in row `row2`) - no reduction pass
+int bn_bwd_sums(const Ctx& c, const BnBwd& s, const Grads& gr, int fused_parts = 0, int row2 = 1) {
   const PhResnetPlan* P = c.P;
-  const Unit& u = P->units[ui];
-  const size_t npix = (size_t)P->B * u.OH * u.OW;
+  const BnBwdOps o(c, s);
+  if (fused_parts > 0)
+    return ph_bn_bwd_finalize_fused_launch(reinterpret_cast<const float*>(c.ws + P->fparts_off), fused_parts, o.u.Cout, (double)o.npix,
+                                           gr.dgamma(s.ui), gr.dbeta(s.ui), o.c1, o.c2, c.stat(o.u, 1), row2, c.st);
   float* parts = reinterpret_cast<float*>(c.ws + P->bparts_off);
-  float* c1 = reinterpret_cast<float*>(c.ws + (cc2 ? P->cc2_off : P->cc_off));
-  float* c2 = c1 + 512;
-  const void* y = c.ws + u.y_off;
-  const float* ms = self_mask ? c.stat(u, 2) : nullptr;
-  const float* mh = self_mask ? c.stat(u, 3) : nullptr;
-  if (self_mask) a = nullptr;
-  float* amax = dzs ? c.amax() : nullptr;
-  int rc = PH_OK;
-  if (finalize) {
-    if (fused_parts > 0) {
-      rc = ph_bn_bwd_finalize_fused_launch(reinterpret_cast<const float*>(c.ws + P->fparts_off), fused_parts, u.Cout, (double)npix,
-                                           dgamma, dbeta, c1, c2, c.stat(u, 1), row2, c.st);
-    } else {
-      const int nparts = ph_bn_bwd_parts(npix, u.Cout);
-      rc = ph_bn_bwd_reduce_launch(g, a, y, c.stat(u, 0), c.stat(u, 1), parts, npix, u.Cout, P->prec, ms, mh, amax, c.st);
-      if (rc) return rc;
-      rc = ph_bn_bwd_finalize_launch(parts, nparts, u.Cout, (double)npix, dgamma, dbeta, c1, c2, amax, nparts,
-                                     (const float*)c.params[ui * 6 + 1], c.stat(u, 1), dzs, c.st);
-    }
-    if (rc) return rc;
-  }
-  if (!apply) return PH_OK;
-  return ph_bn_bwd_apply_launch(g, a, y, c.stat(u, 0), c.stat(u, 1), (const float*)c.params[ui * 6 + 1], c1, c2, dy, npix,
-                                u.Cout, P->prec, ms, mh, dzs, c.st);
+  float* amax = s.dzs ? c.amax() : nullptr;
+  const int nparts = ph_bn_bwd_parts(o.npix, o.u.Cout);
+  const int rc = ph_bn_bwd_reduce_launch(s.g, s.mask, o.y, c.stat(o.u, 0), c.stat(o.u, 1), parts, o.npix, o.u.Cout, P->prec, o.ms, o.mh,
+                                         amax, c.st);
+  if (rc) return rc;
+  return ph_bn_bwd_finalize_launch(parts, nparts, o.u.Cout, (double)o.npix, gr.dgamma(s.ui), gr.dbeta(s.ui), o.c1, o.c2, amax, nparts,
+                                   c.params.gamma(s.ui), c.stat(o.u, 1), s.dzs, c.st);
+}
+
+// dy from g and the finalised c1 / c2
+int bn_bwd_apply(const Ctx& c, const BnBwd& s, void* dy) {
+  const BnBwdOps o(c, s);
+  return ph_bn_bwd_apply_launch(s.g, s.mask, o.y, c.stat(o.u, 0), c.stat(o.u, 1), c.params.gamma(s.ui), o.c1, o.c2, dy, o.npix, o.u.Cout,
+                                c.P->prec, o.ms, o.mh, s.dzs, c.st);
 }
 
 }  // namespace
@@ -486,7 +476,7 @@ int ph_resnet_forward(const PhResnetPlan* P, const void* const* params, const vo
   // half-pair mode, forward-only network (flag bit 2): nobody reads ReLU masks later, so the fp32 copies of the block outputs are
   // not written - the next block's shortcut term and the average pools read the half-pair operand images (22-23 significant
   // bits): 1.0 GB of writes per network and forward at B = 64 / 512 x 512.  PH_HP_OUT32=1 keeps the copies (A/B and test switch).
-  static const bool keep32 = [] { const char* e = getenv("PH_HP_OUT32"); return e && e[0] == '1'; }();
+  static const bool keep32 = ph_env_flag("PH_HP_OUT32", 0);
   const bool fo_hp = hp && (flags & 4) && !keep32;
   // bit6: `x_nchw` is not the image but an NHWC4 tensor of the mode's activation type that ph_pack_input produced from it
   // (the student and the teacher of the distillation step read the same x_path: packed once, train_test_path_multi_distill.py:249,256)
@@ -509,8 +499,8 @@ int ph_resnet_forward(const PhResnetPlan* P, const void* const* params, const vo
     t.n = (int)P->units.size();
     for (int i = 0; i < t.n; ++i) {
       const Unit& u = P->units[i];
-      t.gamma[i] = (const float*)params[i * 6 + 1]; t.beta[i] = (const float*)params[i * 6 + 2];
-      t.running_mean[i] = (const float*)params[i * 6 + 3]; t.running_var[i] = (const float*)params[i * 6 + 4];
+      t.gamma[i] = c.params.gamma(i); t.beta[i] = c.params.beta(i);
+      t.running_mean[i] = c.params.running_mean(i); t.running_var[i] = c.params.running_var(i);
       t.mean[i] = c.stat(u, 0); t.invstd[i] = c.stat(u, 1); t.scale[i] = c.stat(u, 2); t.shift[i] = c.stat(u, 3);
       t.C[i] = u.Cout;
     }
@@ -525,15 +515,10 @@ int ph_resnet_forward(const PhResnetPlan* P, const void* const* params, const vo
     PhStemPool s{};
     s.x4 = x4p; s.w = c.pk + u.wf_off; s.wplane = u.wplane;
     s.pooled = ws + P->p0_off; s.stats = c.eval ? nullptr : reinterpret_cast<float*>(ws + P->parts_off);
-    s.gamma = (const float*)params[1];
+    s.gamma = c.params.gamma(0);
     s.B = P->B; s.IH = P->H; s.IW = P->W; s.OH = u.OH; s.OW = u.OW; s.PH = P->PH0; s.PW = P->PW0;
     if ((rc = ph_stem_fwd_pool_launch(&s, st))) return rc;
-    float* rm = c.update_running ? (float*)params[3] : nullptr;
-    if (!c.eval && (rc = ph_bn_finalize_launch(s.stats, ph_stem_pool_stat_parts(P->B, u.OH, u.OW), 64, (double)P->B * u.OH * u.OW,
-                                    1e-5f, 0.1f, (const float*)params[1], (const float*)params[2], c.stat(u, 0),
-                                    c.stat(u, 1), c.stat(u, 2), c.stat(u, 3), rm, (float*)params[4],
-                                    (int64_t*)params[5], st)))
-      return rc;
+    if (!c.eval && (rc = bn_finalize_fwd(c, 0, s.stats, ph_stem_pool_stat_parts(P->B, u.OH, u.OW)))) return rc;
     // BatchNorm + ReLU of the pooled tensor is applied by its two consumers - layer1.0.conv1 while it stages its input
     // (PhTapConv::in_scale, like conv2 of the forward-only blocks) and layer1.0's output pass on its shortcut term - so the
     // pooled tensor stays RAW and no pass over it remains (bit 3 of the flags keeps the separate pass, as for the blocks)
@@ -549,12 +534,7 @@ int ph_resnet_forward(const PhResnetPlan* P, const void* const* params, const vo
     s.out = ws + u.y_off; s.stats = c.eval ? nullptr : reinterpret_cast<float*>(ws + P->parts_off);
     s.B = P->B; s.IH = P->H; s.IW = P->W; s.OH = u.OH; s.OW = u.OW;
     if ((rc = ph_stem_fwd_launch(&s, P->prec, st))) return rc;
-    float* rm = c.update_running ? (float*)params[3] : nullptr;
-    if (!c.eval && (rc = ph_bn_finalize_launch(s.stats, ph_stem_stat_parts(P->B, u.OH, u.OW), 64, (double)P->B * u.OH * u.OW,
-                                    1e-5f, 0.1f, (const float*)params[1], (const float*)params[2], c.stat(u, 0),
-                                    c.stat(u, 1), c.stat(u, 2), c.stat(u, 3), rm, (float*)params[4],
-                                    (int64_t*)params[5], st)))
-      return rc;
+    if (!c.eval && (rc = bn_finalize_fwd(c, 0, s.stats, ph_stem_stat_parts(P->B, u.OH, u.OW)))) return rc;
     // (forward only: nobody scatters a gradient through the pooling windows - the argmax codes are not produced)
     if ((rc = ph_bn_relu_maxpool_launch(ws + u.y_off, c.stat(u, 2), c.stat(u, 3), ws + P->p0_off,
                                         (flags & 4) ? nullptr : ws + P->idx_off, (flags & 4) ? nullptr : ws + P->p0raw_off,
@@ -573,7 +553,7 @@ int ph_resnet_forward(const PhResnetPlan* P, const void* const* params, const vo
     if ((rc = raw_in ? conv_fwd(c, b.u1, ws + b.in_off, c.stat(u0, 2), c.stat(u0, 3)) : conv_fwd(c, b.u1, ws + b.in_off))) return rc;
     // (measured per launch, B = 64, 512^2: the in-LDS pass costs the conv +10 us in layer 1 and +13 us in layers 2-4 - it
     // runs with the matrix pipe idle - against bn_apply launches of 49 / 25 / 13 / 8 us: fused where it pays)
-    static const bool fuse_all = [] { const char* e = getenv("PH_FUSE_ALL"); return e && e[0] == '1'; }();      // A/B switch
+    static const bool fuse_all = ph_env_flag("PH_FUSE_ALL", 0);      // A/B switch
     if (fuse_a1 && (b.Cout <= 128 || fuse_all)) {
       if ((rc = conv_fwd(c, b.u2, ws + u1.y_off, c.stat(u1, 2), c.stat(u1, 3)))) return rc;
     } else {
@@ -676,29 +656,19 @@ SideRes* overlap_ready(const PhResnetPlan* P, hipStream_t st) {
   return r;
 }
 
-int backward_impl(const PhResnetPlan* P, const void* const* params, const void* packed, void* ws_, const float* g_f3,
-                  const float* g_f4, void* const* grads, int part, int stop, hipStream_t st) {
-  if (!P || !params || !packed || !ws_ || !g_f4 || !grads || part < -1 || part > 1) return PH_EINVAL;
-  const int bi_hi = part == 1 ? 3 : 7, bi_lo = part == 0 ? 4 : 0;
-  Ctx c{P, params, reinterpret_cast<const bf16*>(packed), reinterpret_cast<unsigned char*>(ws_), st, 0};
-  c.no_masked = P->no_masked;
-  unsigned char* ws = c.ws;
-  unsigned char* gcur = ws + P->g0_off;
-  unsigned char* gnext = ws + P->g1_off;
-  unsigned char* dab = ws + P->da_off;
-  SideRes* const sr = stop == 0 ? overlap_ready(P, st) : nullptr;
-  const bool ov = sr != nullptr;
-  const hipStream_t side = ov ? sr->side : st;
-  Ctx cs = c;                       // the weight-gradient launches' context
-  // (PH_WG_BESIDE=n: A/B override of the side-stream weight gradients' workgroup target)
-  static const int wg_beside = [] { const char* e = getenv("PH_WG_BESIDE"); const int v = e ? atoi(e) : 0; return v > 0 ? v : WG_WANT_BESIDE; }();
-  if (ov) { cs.st = side; cs.wg_want = wg_beside; }
-  // this call's block of events (see SideRes): eager calls take one of 15 blocks (waiting for the oldest call in flight when
-  // all are held), captured calls the 16th
-  size_t ev_base = 0;
-  int ev_blk = -1;
-  bool capturing = false;
-  if (ov) {
+// One backward call's use of the side stream: its block of events, and the four orderings between the chain (the caller's stream)
+// and the weight gradients.  Off (open() not called or refused: overlap switched off, a cut debug backward, no side stream yet while
+// capturing): side() is the chain's stream and every method is a no-op.
+class SideLane {
+ public:
+  explicit SideLane(hipStream_t chain) : st(chain) {}
+  SideLane(const SideLane&) = delete;
+  SideLane& operator=(const SideLane&) = delete;
+  // takes this call's block of events (see SideRes): eager calls one of 15 blocks (waiting for the oldest call in flight when all are
+  // held, PH_EBUSY if that wait fails), captured calls the 16th
+  int open(const PhResnetPlan* P) {
+    sr = overlap_ready(P, st);
+    if (!sr) return PH_OK;
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     capturing = hipStreamIsCapturing(st, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone;
     std::lock_guard<std::mutex> lk(sr->mu);
@@ -726,49 +696,80 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
         if (hipEventSynchronize(sr->done[b]) != hipSuccess) return PH_EBUSY;
         ev_blk = (int)b;
       }
-      sr->busy[ev_blk] = true;      // (claimed; released below)
+      sr->busy[ev_blk] = true;      // (claimed; released by the destructor)
       sr->cursor = ((size_t)ev_blk + 1) % NE;
     }
-    ev_base = (size_t)ev_blk * EV_BLOCK;
-  }
-  struct BlockGuard {      // every exit path: a captured call frees the block, an eager one marks it with `done` on the stream
-    SideRes* r; int b; bool cap; hipStream_t s;
-    ~BlockGuard() {
-      if (!r || b < 0) return;
-      std::lock_guard<std::mutex> lk(r->mu);
-      if (cap) return;      // (the capture block is never marked busy)
-      if (hipEventRecord(r->done[b], s) != hipSuccess) r->busy[b] = false;
-    }
-  } guard{ov ? sr : nullptr, ev_blk, capturing, st};
-  size_t ev_used = 0;
-  unsigned char* dzb[2] = {ws + P->dy_off, ov ? ws + P->dy2_off : ws + P->dy_off};
-  hipEvent_t rd[2] = {nullptr, nullptr};    // recorded on the side stream after the last reader of dzb[k]
-  int k = 0;
-  auto next_ev = [&]() { return sr->evs[ev_base + (ev_used++ % EV_BLOCK)]; };      // (a call needs < 50)
-  // the chain is about to overwrite dzb[k]: wait for the weight gradient that read it
-  auto claim = [&](int kk) -> int {
-    if (ov && rd[kk]) { if (hipStreamWaitEvent(st, rd[kk], 0) != hipSuccess) return PH_ELAUNCH; rd[kk] = nullptr; }
     return PH_OK;
-  };
+  }
+  // every exit path: a captured call frees the block, an eager one marks it with `done` on the chain
+  ~SideLane() {
+    if (!sr || ev_blk < 0) return;
+    std::lock_guard<std::mutex> lk(sr->mu);
+    if (capturing) return;      // (the capture block is never marked busy)
+    if (hipEventRecord(sr->done[ev_blk], st) != hipSuccess) sr->busy[ev_blk] = false;
+  }
+  bool on() const { return sr != nullptr; }
+  hipStream_t side() const { return sr ? sr->side : st; }
+  // the chain has produced what the next side-stream launch reads: record on the chain, wait on the side stream
+  int fork() { return sr ? order(st, sr->side) : PH_OK; }
+  // the side stream has enqueued the last reader of dz buffer k
+  int read_done(int k) {
+    if (!sr) return PH_OK;
+    hipEvent_t d = next_ev();
+    if (hipEventRecord(d, sr->side) != hipSuccess) return PH_ELAUNCH;
+    rd[k] = d;
+    return PH_OK;
+  }
+  // the chain is about to overwrite dz buffer k: wait for the weight gradient that read it
+  int claim(int k) {
+    if (sr && rd[k]) { if (hipStreamWaitEvent(st, rd[k], 0) != hipSuccess) return PH_ELAUNCH; rd[k] = nullptr; }
+    return PH_OK;
+  }
+  // everything on the side stream happens before what the chain enqueues next
+  int join() { return sr ? order(sr->side, st) : PH_OK; }
+
+ private:
+  hipEvent_t next_ev() { return sr->evs[(size_t)ev_blk * EV_BLOCK + (ev_used++ % EV_BLOCK)]; }      // (a call needs < 50)
+  int order(hipStream_t first, hipStream_t then) {
+    hipEvent_t e = next_ev();
+    return (hipEventRecord(e, first) != hipSuccess || hipStreamWaitEvent(then, e, 0) != hipSuccess) ? PH_ELAUNCH : PH_OK;
+  }
+  hipStream_t st;
+  SideRes* sr = nullptr;
+  int ev_blk = -1;
+  bool capturing = false;
+  size_t ev_used = 0;
+  hipEvent_t rd[2] = {nullptr, nullptr};    // recorded on the side stream after the last reader of dz buffer k
+};
+
+int backward_impl(const PhResnetPlan* P, const void* const* params, const void* packed, void* ws_, const float* g_f3,
+                  const float* g_f4, void* const* grads, int part, int stop, hipStream_t st) {
+  if (!P || !params || !packed || !ws_ || !g_f4 || !grads || part < -1 || part > 1) return PH_EINVAL;
+  const int bi_hi = part == 1 ? 3 : 7, bi_lo = part == 0 ? 4 : 0;
+  Ctx c{P, {params}, reinterpret_cast<const bf16*>(packed), reinterpret_cast<unsigned char*>(ws_), st, 0};
+  c.no_masked = P->no_masked;
+  const Grads gr{grads};
+  unsigned char* ws = c.ws;
+  unsigned char* gcur = ws + P->g0_off;
+  unsigned char* gnext = ws + P->g1_off;
+  unsigned char* dab = ws + P->da_off;
+  int rc, nst = 0;
+  SideLane lane(st);
+  if (stop == 0 && (rc = lane.open(P))) return rc;
+  const bool ov = lane.on();
+  Ctx cs = c;                       // the weight-gradient launches' context
+  // (PH_WG_BESIDE=n: A/B override of the side-stream weight gradients' workgroup target, at most PH_WG_WANT_ALONE - the slab is
+  // sized for that and the chunk count grows with the target)
+  static const int wg_beside = [] { const int v = ph_env_int("PH_WG_BESIDE", 0); return v > 0 ? std::min(v, PH_WG_WANT_ALONE) : WG_WANT_BESIDE; }();
+  if (ov) { cs.st = lane.side(); cs.wg_want = wg_beside; }
+  unsigned char* dzb[2] = {ws + P->dy_off, ov ? ws + P->dy2_off : ws + P->dy_off};
+  int k = 0;
   // dz of unit ui is in dzb[kk] (produced on st): its weight gradient
   auto wgrad_of = [&](int ui, const void* x, int kk) -> int {
-    if (!ov) return conv_wgrad(c, ui, x, dzb[kk], (float*)grads[ui * 3 + 0], c.dzs(kk));
-    hipEvent_t e = next_ev();
-    if (hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(side, e, 0) != hipSuccess) return PH_ELAUNCH;
-    int r = conv_wgrad(cs, ui, x, dzb[kk], (float*)grads[ui * 3 + 0], c.dzs(kk));
-    if (r) return r;
-    hipEvent_t d = next_ev();
-    if (hipEventRecord(d, side) != hipSuccess) return PH_ELAUNCH;
-    rd[kk] = d;
-    return PH_OK;
+    int r;
+    if ((r = lane.fork()) || (r = conv_wgrad(cs, ui, x, dzb[kk], gr.dw(ui), c.dzs(kk)))) return r;
+    return lane.read_done(kk);
   };
-  auto join = [&]() -> int {
-    if (!ov) return PH_OK;
-    hipEvent_t e = next_ev();
-    if (hipEventRecord(e, side) != hipSuccess || hipStreamWaitEvent(st, e, 0) != hipSuccess) return PH_ELAUNCH;
-    return PH_OK;
-  };
-  int rc, nst = 0;
   int fused_out = 0;      // rows of fused bn2 (+ downsample) sums the last dgrad left for the block about to be processed
   if (part != 1) {
     if (hipMemsetAsync(ws + P->zero_off, 0, 256, st) != hipSuccess) return PH_ELAUNCH;
@@ -787,13 +788,12 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
     const void* xin32 = ws + b.in32_off;     // (the block input as the elementwise passes read it: the previous block's ReLU mask)
     // bn2 <- d_out * (out > 0); fused_out: the dgrad that wrote gcur (the next block's conv1 + residual) took bn2's sums - and
     // the downsample BatchNorm's, which reduces the same dz: both are finalised here, the downsample pair into the second buffer
-    if ((rc = claim(k))) return rc;
-    if (fused_out > 0 && b.uds >= 0 &&
-        (rc = bn_bwd(c, b.uds, gcur, out, nullptr, (float*)grads[b.uds * 3 + 1], (float*)grads[b.uds * 3 + 2], false, nullptr,
-                     fused_out, 2, true, true, false)))
-      return rc;
+    if ((rc = lane.claim(k))) return rc;
     const bool ds_done = fused_out > 0 && b.uds >= 0;
-    PH_STAGE(bn_bwd(c, b.u2, gcur, out, dzb[k], (float*)grads[b.u2 * 3 + 1], (float*)grads[b.u2 * 3 + 2], false, c.dzs(k), fused_out));
+    if (ds_done && (rc = bn_bwd_sums(c, BnBwd{b.uds, gcur, out, true}, gr, fused_out, 2))) return rc;
+    const BnBwd bn2{b.u2, gcur, out, false, c.dzs(k)};
+    if ((rc = bn_bwd_sums(c, bn2, gr, fused_out))) return rc;
+    PH_STAGE(bn_bwd_apply(c, bn2, dzb[k]));
     fused_out = 0;
     if (!ov) PH_STAGE(wgrad_of(b.u2, a1, k));
     int fused_a1 = 0;      // conv2's dgrad writes d_a1 and takes bn1's sums over it (mask: bn1's own ReLU, re-derived from y1)
@@ -803,9 +803,11 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
     }
     if (ov) PH_STAGE(wgrad_of(b.u2, a1, k));
     k ^= 1;
-    // bn1 <- d_a1 * (a1 > 0)
-    if ((rc = claim(k))) return rc;
-    PH_STAGE(bn_bwd(c, b.u1, dab, a1, dzb[k], (float*)grads[b.u1 * 3 + 1], (float*)grads[b.u1 * 3 + 2], true, c.dzs(k), fused_a1));
+    // bn1 <- d_a1 * (a1 > 0), the mask re-derived from y1
+    if ((rc = lane.claim(k))) return rc;
+    const BnBwd bn1{b.u1, dab, nullptr, false, c.dzs(k)};
+    if ((rc = bn_bwd_sums(c, bn1, gr, fused_a1))) return rc;
+    PH_STAGE(bn_bwd_apply(c, bn1, dzb[k]));
     if (!ov) PH_STAGE(wgrad_of(b.u1, xin, k));
     if (b.uds < 0) {
       // identity shortcut: d_xin = dgrad(conv1) + d_out * (out > 0), fused in the dgrad epilogue - which also takes the sums of
@@ -816,18 +818,20 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
         const Block& pb = P->blocks[bi - 1];
         bs.u = pb.u2; bs.u2 = pb.uds; bs.a = xin32;
       }
-        PH_STAGE(conv_dgrad(c, b.u1, dzb[k], gnext, gcur, out, c.dzs(k), &bs, &fused_out));
+      PH_STAGE(conv_dgrad(c, b.u1, dzb[k], gnext, gcur, out, c.dzs(k), &bs, &fused_out));
       if (ov) PH_STAGE(wgrad_of(b.u1, xin, k));
       k ^= 1;
     } else {
-        PH_STAGE(conv_dgrad(c, b.u1, dzb[k], gnext, nullptr, nullptr, c.dzs(k)));
+      PH_STAGE(conv_dgrad(c, b.u1, dzb[k], gnext, nullptr, nullptr, c.dzs(k)));
       if (ov) PH_STAGE(wgrad_of(b.u1, xin, k));
       k ^= 1;
-      if ((rc = claim(k))) return rc;
-      PH_STAGE(bn_bwd(c, b.uds, gcur, out, dzb[k], (float*)grads[b.uds * 3 + 1], (float*)grads[b.uds * 3 + 2], false, c.dzs(k),
-                      0, 1, ds_done, !ds_done));
+      // downsample BatchNorm <- d_out * (out > 0): its sums unless they were finalised with bn2's above (then c1 / c2 are in the second pair)
+      if ((rc = lane.claim(k))) return rc;
+      const BnBwd ds{b.uds, gcur, out, ds_done, c.dzs(k)};
+      if (!ds_done && (rc = bn_bwd_sums(c, ds, gr))) return rc;
+      PH_STAGE(bn_bwd_apply(c, ds, dzb[k]));
       if (!ov) PH_STAGE(wgrad_of(b.uds, xin, k));
-        PH_STAGE(conv_dgrad(c, b.uds, dzb[k], gnext, gnext, nullptr, c.dzs(k)));   // in-place accumulate
+      PH_STAGE(conv_dgrad(c, b.uds, dzb[k], gnext, gnext, nullptr, c.dzs(k)));   // in-place accumulate
       if (ov) PH_STAGE(wgrad_of(b.uds, xin, k));
       k ^= 1;
     }
@@ -842,10 +846,9 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
     if ((rc = ph_stem_bwd_reduce_launch(gcur, ws + P->idx_off, ws + u.y_off, ws + P->p0raw_off, c.stat(u, 0), c.stat(u, 1),
                                         c.stat(u, 2), c.stat(u, 3), parts, P->B, u.OH, u.OW, 64, P->prec, c.amax(), st)))
       return rc;
-    if (c.dzs(0) && (rc = claim(0))) return rc;      // (half-pair mode: the finalize pass rewrites buffer 0's scale record)
-    PH_STAGE(ph_bn_bwd_finalize_launch(parts, ph_stem_bwd_parts(P->B, u.OH), 64, (double)npix, (float*)grads[1],
-                                       (float*)grads[2], c1, c2, c.amax(), ph_stem_bwd_parts(P->B, u.OH),
-                                       (const float*)params[1], c.stat(u, 1), c.dzs(0), st));
+    if (c.dzs(0) && (rc = lane.claim(0))) return rc;      // (half-pair mode: the finalize pass rewrites buffer 0's scale record)
+    PH_STAGE(ph_bn_bwd_finalize_launch(parts, ph_stem_bwd_parts(P->B, u.OH), 64, (double)npix, gr.dgamma(0), gr.dbeta(0), c1, c2,
+                                       c.amax(), ph_stem_bwd_parts(P->B, u.OH), c.params.gamma(0), c.stat(u, 1), c.dzs(0), st));
     // Perf mode, whole backward: the weight-gradient kernel forms dz itself (stem_wgrad_kernel<bf16, true>) - the 64-channel dz tensor
     // is neither written nor read.  The stage is still counted (PH_STAGE numbers are the same on every path).  A cut backward
     // (stop > 0: the debug harness reads dz from the workspace), the image gradient (ph_resnet_backward_input) and the
@@ -855,9 +858,9 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
       // (no claim(0): nothing overwrites dzb[0] on this path, so its last reader on the side stream need not be waited for)
       PH_STAGE(PH_OK);
     } else {
-      if ((rc = claim(0))) return rc;       // the stem's dz is full resolution: only the first buffer holds it
+      if ((rc = lane.claim(0))) return rc;       // the stem's dz is full resolution: only the first buffer holds it
       PH_STAGE(ph_stem_bwd_apply_launch(gcur, ws + P->idx_off, ws + u.y_off, c.stat(u, 0), c.stat(u, 1), c.stat(u, 2),
-                                        c.stat(u, 3), (const float*)params[1], c1, c2, dzb[0], P->B, u.OH, u.OW, 64,
+                                        c.stat(u, 3), c.params.gamma(0), c1, c2, dzb[0], P->B, u.OH, u.OW, 64,
                                         P->prec, c.dzs(0), st));
     }
     PhStemWgrad w{};
@@ -878,16 +881,13 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
       // the forward, c1 / c2 by the finalize pass
       w.dy = nullptr; w.y0 = ws + u.y_off; w.dpool = gcur; w.idx = ws + P->idx_off;
       w.mean = c.stat(u, 0); w.invstd = c.stat(u, 1); w.scale = c.stat(u, 2); w.shift = c.stat(u, 3);
-      w.gamma = (const float*)params[1]; w.c1 = c1; w.c2 = c2; w.PH = P->PH0; w.PW = P->PW0;
+      w.gamma = c.params.gamma(0); w.c1 = c1; w.c2 = c2; w.PH = P->PH0; w.PW = P->PW0;
     }
-    if (ov) {      // same stream as the other weight gradients: they share the slab
-      hipEvent_t e = next_ev();
-      if (hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(side, e, 0) != hipSuccess) return PH_ELAUNCH;
-    }
+    if ((rc = lane.fork())) return rc;      // same stream as the other weight gradients: they share the slab
     if ((rc = ph_stem_wgrad_launch(&w, c.bprec(), cs.st))) return rc;
-    PH_STAGE(ph_stem_wgrad_reduce_launch(w.slab, (float*)grads[0], w.nchunks, c.dzs(0), cs.st));
+    PH_STAGE(ph_stem_wgrad_reduce_launch(w.slab, gr.dw(0), w.nchunks, c.dzs(0), cs.st));
   }
-  return join();
+  return lane.join();
 }
 #undef PH_STAGE
 
@@ -912,8 +912,6 @@ int ph_resnet_plan_set_backward_prec(const PhResnetPlan* P, int prec) {
 
 // A/B and test switch: 0 = the whole backward on the caller's stream (the round-2 sequence), 1 (default) = weight
 // gradients on the side stream
-// A/B and test switch (not part of the public C-ABI): 0 = every BatchNorm-backward reduction as a pass of its own
-
 int ph_resnet_plan_set_backward_overlap(const PhResnetPlan* P, int on) {
   if (!P) return PH_EINVAL;
   P->bwd_overlap = on ? 1 : 0;
@@ -981,11 +979,7 @@ int ph_resnet_backward_input(const PhResnetPlan* P, const void* const* params, c
   int rc;
   if (hipMemsetAsync(ws + P->zero_off, 0, 256, st) != hipSuccess) return PH_ELAUNCH;
   if (hipMemsetAsync(c1, 0, 1024 * sizeof(float), st) != hipSuccess) return PH_ELAUNCH;
-  auto bn_eval_bwd = [&](int ui, const void* g, const void* a, void* dy) -> int {
-    const Unit& u = P->units[ui];
-    return ph_bn_bwd_apply_launch(g, a, ws + u.y_off, c.stat(u, 0), c.stat(u, 1), (const float*)params[ui * 6 + 1], c1, c2,
-                                  dy, (size_t)P->B * u.OH * u.OW, u.Cout, P->prec, nullptr, nullptr, nullptr, st);
-  };
+  // (c1 = c2 = 0 above: bn_bwd_apply is then gamma * invstd * dz; the masks are the saved activations)
   {
     const Block& b = P->blocks[7];
     if ((rc = ph_avgpool_bwd_launch(g_f4, gcur, P->B, b.OH * b.OW, b.Cout, 0, P->prec, st))) return rc;
@@ -996,23 +990,23 @@ int ph_resnet_backward_input(const PhResnetPlan* P, const void* const* params, c
       if ((rc = ph_avgpool_bwd_launch(g_f3, gcur, P->B, b.OH * b.OW, b.Cout, 1, P->prec, st))) return rc;
     const void* out = ws + b.out_off;
     const void* a1 = ws + b.a1_off;
-    if ((rc = bn_eval_bwd(b.u2, gcur, out, dyb))) return rc;
+    if ((rc = bn_bwd_apply(c, BnBwd{b.u2, gcur, out}, dyb))) return rc;
     if ((rc = conv_dgrad(c, b.u2, dyb, dab, nullptr, nullptr))) return rc;
-    if ((rc = bn_eval_bwd(b.u1, dab, a1, dyb))) return rc;
+    if ((rc = bn_bwd_apply(c, BnBwd{b.u1, dab, a1}, dyb))) return rc;
     if (b.uds < 0) {
       if ((rc = conv_dgrad(c, b.u1, dyb, gnext, gcur, out))) return rc;
     } else {
       if ((rc = conv_dgrad(c, b.u1, dyb, gnext, nullptr, nullptr))) return rc;
-      if ((rc = bn_eval_bwd(b.uds, gcur, out, dyb))) return rc;
+      if ((rc = bn_bwd_apply(c, BnBwd{b.uds, gcur, out}, dyb))) return rc;
       if ((rc = conv_dgrad(c, b.uds, dyb, gnext, gnext, nullptr))) return rc;
     }
     unsigned char* t = gcur; gcur = gnext; gnext = t;
   }
   const Unit& u = P->units[0];
   if ((rc = ph_stem_bwd_apply_launch(gcur, ws + P->idx_off, ws + u.y_off, c.stat(u, 0), c.stat(u, 1), c.stat(u, 2),
-                                     c.stat(u, 3), (const float*)params[1], c1, c2, dyb, P->B, u.OH, u.OW, 64, P->prec, nullptr, st)))
+                                     c.stat(u, 3), c.params.gamma(0), c1, c2, dyb, P->B, u.OH, u.OW, 64, P->prec, nullptr, st)))
     return rc;
-  return ph_stem_dgrad_launch(dyb, (const float*)params[0], dx_nchw, P->B, P->H, P->W, P->prec, st);
+  return ph_stem_dgrad_launch(dyb, c.params.w(0), dx_nchw, P->B, P->H, P->W, P->prec, st);
 }
 
 // debug / test access: byte offset + dims of an intermediate activation in the workspace

@@ -47,6 +47,47 @@ def test_plan_host_logic_without_gpu():
     assert not L.ph_resnet_plan_create(4, 512, 512, 7)
 
 
+# (B, H, W, prec): workspace bytes, packed bytes, layout signature, and the ph_resnet_tensor_info offsets of (what, id) =
+# (0, 0) (0, 19) (1, 7) (2, 0) (3, 0) (4, 0) (5, 0) (6, 0) (7, 0) (8, 19) (9, 0)
+_PLAN_LAYOUT = {
+    (64, 512, 512, 0): (4299251200, 133976064, 0xa22d2738734de9e5,
+                        [134217728, 3087076352, 3120638976, 1275071488, 671089664, 3139513344, 3273731072, 3542166528, 3407948800,
+                         3103853568, 805307392]),
+    (4, 96, 160, 0): (63876608, 133976064, 0xa22d2738734de9e5,
+                      [491520, 11373568, 11504640, 4672512, 2458624, 11697152, 12188672, 13171712, 12680192, 11435008, 2950144]),
+    (6, 160, 160, 3): (155561472, 133976064, 0xd044e4369c0d8ecf,
+                       [2457600, 67345408, 67968000, 25193472, 12289024, 68779008, 71236608, 76151808, 73694208, 67652608, 17204224]),
+    (2, 64, 64, 1): (33537536, 133976064, 0xa22d2738734de9e5,
+                     [131072, 3050496, 3091456, 1215488, 656384, 3116032, 3247104, 3509248, 3378176, 3066880, 787456]),
+    (256, 128, 128, 2): (2176933376, 133976064, 0xa22d2738734de9e5,
+                         [67108864, 1526795264, 1543580672, 620760064, 335545344, 1554066432, 1621175296, 1755393024, 1688284160,
+                          1535183872, 402654208]),
+}
+_PLAN_TENSORS = ((0, 0), (0, 19), (1, 7), (2, 0), (3, 0), (4, 0), (5, 0), (6, 0), (7, 0), (8, 19), (9, 0))
+
+
+def test_plan_layout_is_pinned():
+    """The workspace layout of a plan - sizes, weight-layout signature, tensor offsets - as literals: host-code changes to the plan
+    (resnet_plan.hip) must leave them alone unless they mean to move a buffer."""
+    import ctypes
+    import multimodal_learning_amd as m
+    L = m.lib()
+    for (B, H, W, prec), (ws, packed, sig, offs) in _PLAN_LAYOUT.items():
+        p = L.ph_resnet_plan_create(B, H, W, prec)
+        assert p
+        try:
+            assert L.ph_resnet_workspace_bytes(p) == ws and L.ph_resnet_packed_bytes(p) == packed, (B, H, W, prec)
+            assert L.ph_resnet_plan_layout_sig(p) == sig, (B, H, W, prec)
+            off, dims = ctypes.c_size_t(0), (ctypes.c_int * 4)()
+            got = []
+            for what, idx in _PLAN_TENSORS:
+                assert L.ph_resnet_tensor_info(p, what, idx, ctypes.byref(off), dims) == 0
+                got.append(off.value)
+            assert got == offs, (B, H, W, prec)
+        finally:
+            L.ph_resnet_plan_destroy(p)
+
+
 def test_sgemm_splitk_rejects_nsplit_below_one_before_any_hip_call():
     """The slab depth is cdiv(K, nsplit): nsplit < 1 is PH_EINVAL on the host, never a division by zero."""
     import multimodal_learning_amd as m

@@ -7,7 +7,7 @@ import ctypes
 import pytest
 
 from tests.conv_emulation import BF16, BF16X6, BF16X3, FP16X3, FP16X1, NAMES
-from tests.conv_sweep_cases import CASES, expected_family
+from tests.conv_sweep_cases import CASES, REJECTED, expected_family
 from tests.gpu_util import DISPATCH_FAMILIES
 
 EINVAL = -22
@@ -106,3 +106,26 @@ def test_weight_layout_of_every_sweep_case():
     for case in ("s2_128_256", "s2_192_384", "s2_128_256_big"):
         assert _select(L, case, "fwd", FP16X3)[2] == WFRAG_TAP6
         assert _select(L, case, "fwd", BF16)[2] == WFRAG_ROW
+
+
+def test_workspace_covers_the_weight_gradient_slab():
+    """ph_conv2d_wgrad writes a 256-byte zero page and one fp32 [KS * KS][Cout][Cin] slab plane per chunk it launches with
+    (ph_debug_conv2d_wgrad_chunks: the same plan_wgrad call, no HIP call); ph_conv2d_workspace_bytes must cover that.  A 1x1 /
+    stride-2 convolution is launched through the stride-1 view (tile height 8, not 4) and the chunk count is not monotone in the
+    tile count: the sizing once took 170 chunks for the first named shape where the launch used 180 (5 619 968 B reported, 5 898 496
+    written), and 130 against 140 for the second."""
+    L = _lib()
+    shapes = [(B, Cin, IH, IW, Cout, KS, S, pad) for name, (Cin, Cout, IH, IW, KS, S, pad, B) in CASES.items() if name not in REJECTED]
+    named = [(4, 64, 130, 130, 128, 1, 2, 0), (5, 64, 98, 98, 128, 1, 2, 0)]
+    sweep = [(B, Cin, 2 * OH, 2 * OH, Cout, 1, 2, 0) for (Cin, Cout) in ((64, 128), (128, 256), (256, 512))
+             for B in range(1, 9) for OH in range(1, 70)]
+    for a in shapes + named + sweep:
+        B, Cin, IH, IW, Cout, KS, S, pad = a
+        chunks = L.ph_debug_conv2d_wgrad_chunks(*a)
+        assert chunks >= 1, a
+        assert L.ph_conv2d_workspace_bytes(*a) >= 256 + chunks * KS * KS * Cin * Cout * 4, (a, chunks)
+    for a in named:      # (what the two named shapes launch with)
+        assert L.ph_debug_conv2d_wgrad_chunks(*a) == {130: 180, 98: 140}[a[2]]
+    for name in REJECTED:
+        Cin, Cout, IH, IW, KS, S, pad, B = CASES[name]
+        assert L.ph_debug_conv2d_wgrad_chunks(B, Cin, IH, IW, Cout, KS, S, pad) == EINVAL

@@ -67,6 +67,29 @@ def test_conv_fwd_dgrad_wgrad(case, prec):
     assert_close(wr.grad, dw.cpu(), 1e-6, 2e-5 if prec == 1 else 2e-3, "conv wgrad")
 
 
+def test_wgrad_1x1_stride2_stays_inside_the_reported_workspace():
+    """1x1 / stride 2 through the stride-1 view at a size where the view's chunk count (180) exceeds the stride-2 count (170) the
+    workspace was once sized with: the workspace is allocated at exactly ph_conv2d_workspace_bytes, the guard band behind it is
+    intact after the call, and the gradient meets the bf16 weight-gradient tolerance of test_conv_fwd_dgrad_wgrad."""
+    from tests.gpu_util import nhwc, assert_close
+    m, L, ptr, stream, check = _setup()
+    B, Cin, Cout, H = 4, 64, 128, 130
+    OH = (H - 1) // 2 + 1
+    g = torch.Generator().manual_seed(130)
+    x = torch.randn(B, Cin, H, H, generator=g).bfloat16().float()
+    dy = torch.randn(B, Cout, OH, OH, generator=g).bfloat16().float()
+    ref = torch.einsum("bohw,bihw->oi", dy.double(), x[:, :, ::2, ::2].double()).reshape(Cout, Cin, 1, 1)
+    nbytes, band = L.ph_conv2d_workspace_bytes(B, Cin, H, H, Cout, 1, 2, 0), 1 << 20
+    ws = torch.empty(nbytes + band, device="cuda", dtype=torch.uint8)
+    ws[nbytes:] = 0xA5
+    xd = nhwc(x, torch.bfloat16); dyd = nhwc(dy, torch.bfloat16)
+    dw = torch.empty(Cout, Cin, 1, 1, device="cuda")
+    check(L.ph_conv2d_wgrad(ptr(xd), ptr(dyd), ptr(dw), B, Cin, H, H, Cout, 1, 2, 0, 0, ptr(ws), stream()), "wgrad")
+    torch.cuda.synchronize()
+    assert bool((ws[nbytes:] == 0xA5).all()), "ph_conv2d_wgrad wrote past ph_conv2d_workspace_bytes"
+    assert_close(ref, dw.cpu(), 1e-6, 2e-3, "conv wgrad")
+
+
 def test_half_pair_storage_round_trip():
     """ph_hp_pack / ph_hp_unpack (PH_PREC_FP16X3 storage): x ~= hi + lo * 2^-11 keeps 22 significant bits over the fp16
     exponent range, and a power-of-two scale applied before the split is exact."""
