@@ -432,7 +432,10 @@ int ph_conv2d_wgrad(const void* x, const void* dy, float* dw_oihw, int B, int Ci
  * to the student rows f_s [B, D] (the teacher rows f_t are constants), fixed summation order.
  * ph_pkt_loss_grad: "MIA 2022/distiller_zoo/PKT.py":17-46 (cosine-similarity probabilities, KL, eps 1e-7).
  * ph_rkd_loss_grad: "MIA 2022/distiller_zoo/RKD.py":15-58 (w_d * smooth-L1 of mean-normalised pairwise distances +
- * w_a * smooth-L1 of the B^3 angles); B <= 128, D <= 512.
+ * w_a * smooth-L1 of the B^3 angles); one workgroup per anchor with its unit vectors and angles in LDS: 2 <= B <= 128,
+ * 1 <= D <= 512 AND (B (D + 1) + B (B + 1) + B) * 4 <= 150 KiB (every B <= 128 at D = 128, B <= 105 at D = 256, B <= 81 at
+ * D = 384, B <= 66 at D = 512), else PH_EINVAL before any HIP call.  ph_rkd_one_workgroup_fits is that rule for (B, D) (host only,
+ * 1 / 0); a shape it refuses belongs to ph_rkd_loss_grad_part over the full anchor range.
  * ph_rkd_loss_grad_part (csrc/zoo_rkd.hip): the same loss, RKD.py:15-58, on Bg gathered rows (2 <= Bg <= 1024,
  * 1 <= D <= 512), restricted to the anchors [anchor_lo, anchor_lo + n_anchors) of the angle term (RKD.py:33-43) and to the
  * same rows of the distance matrix (RKD.py:21-31).  loss_part [1] and dx_part [Bg][D] (the gradient with respect to EVERY
@@ -494,6 +497,7 @@ size_t ph_pkt_workspace_bytes(int B, int D);
 int ph_pkt_loss_grad(const float* f_s, const float* f_t, float* loss, float* dx, int B, int D, void* workspace,
                      ph_stream_t stream);
 size_t ph_rkd_workspace_bytes(int B, int D);
+int ph_rkd_one_workgroup_fits(int B, int D);
 int ph_rkd_loss_grad(const float* f_s, const float* f_t, float* loss, float* dx, int B, int D, float w_d, float w_a,
                      void* workspace, ph_stream_t stream);
 size_t ph_rkd_part_workspace_bytes(int Bg, int D, int n_anchors);

@@ -77,6 +77,7 @@ SIGNATURES = {
     "ph_pkt_workspace_bytes": (sz, [i32, i32]),
     "ph_pkt_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
     "ph_rkd_workspace_bytes": (sz, [i32, i32]),
+    "ph_rkd_one_workgroup_fits": (i32, [i32, i32]),
     "ph_rkd_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp]),
     "ph_rkd_part_workspace_bytes": (sz, [i32, i32, i32]),
     "ph_rkd_loss_grad_part": (i32, [vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp]),

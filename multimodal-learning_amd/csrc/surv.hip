@@ -70,7 +70,8 @@ struct SurvGatheredRows {
 //   S_ki = sum_j [t_j >= t_i] exp(p_kj);  cox_k = -mean_i c_i (p_ki - log S_ki)           (utils.py:361-376)
 //   d cox_k / d p_kl = -(c_l - exp(p_kl) sum_i c_i [t_l >= t_i] / S_ki) / B
 // The three risk sums share one pass over t (LDS).  The per-prediction summation order is cox_kernel's, so each Cox
-// term is bitwise the one ph_cox_loss_grad computes.  KD terms: mse(a, b) = mean_i (a_i - b_i)^2 over the EMA
+// term is bitwise the one ph_cox_loss_grad computes, and with nt = 0 each gradient row is lambda_cox times its dtheta
+// (bitwise at lambda_cox = 1; tests/test_gpu_zoo_sweep.py).  KD terms: mse(a, b) = mean_i (a_i - b_i)^2 over the EMA
 // teacher's predictions q (constants), combined as train_test_MT.py:180-201 for nt = 1 / 2 / 3 (nt = 0: off).
 // The body is shared by both addressing forms: every sum runs over the B global rows in the same order whatever the
 // addressing, so the gathered form is bitwise the form on the concatenated vectors.  dgrad [3][nout] receives the rows

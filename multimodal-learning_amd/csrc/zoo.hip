@@ -2,7 +2,8 @@
 // PKT.py":17-46) and RKD ("MIA 2022/distiller_zoo/RKD.py":15-58), selected by `--distill pkt|rkd` in
 // train_test_path_multi_distill_v2.py:339-342.  Both are functions of the pairwise geometry of one batch of feature rows;
 // each entry computes the loss AND its gradient with respect to the student rows in closed form (the teacher rows are
-// constants), in a fixed summation order (no atomics).  Small problems (B <= 128 rows of D <= 512): latency-bound.
+// constants), in a fixed summation order (no atomics).  Small problems (PKT: any B; RKD: B <= 128 rows of D <= 512 within
+// ph_rkd_one_workgroup_fits' LDS rule): latency-bound.
 #include "ph_common.h"
 #include "ph_kernels.h"
 
@@ -268,13 +269,20 @@ __global__ __launch_bounds__(1024) void cox_kernel(const float* __restrict__ the
   l = block_sum(l, red);
   if (tid == 0) loss[0] = -l / (float)B;
   if (dtheta) {
+    // times 1 / B, not over B: the form of surv_stage1_body (csrc/surv.hip), whose gradient rows at lambda_cox = 1 are these bit for bit
+    // (test_fused_stage1_cox_terms_are_ph_cox_loss_grad_bitwise caught the division at B = 1023 and 1025: 4 .. 7 rows one ulp apart)
+    const float inv_b = 1.f / (float)B;
     for (int k = tid; k < B; k += 1024) {
       float a = 0.f;
       for (int i = 0; i < B; ++i) a += tt[k] >= tt[i] ? w[i] : 0.f;
-      dtheta[k] = -(c[k] - e[k] * a) / (float)B;
+      dtheta[k] = -(c[k] - e[k] * a) * inv_b;
     }
   }
 }
+
+// dynamic LDS of rkd_angle_kernel: E [B][D + 1], A [B][B + 1], nv [B]
+constexpr size_t RKD_ANGLE_LDS_MAX = 150 * 1024;
+size_t rkd_angle_lds_bytes(int B, int D) { return ((size_t)B * (D + 1) + (size_t)B * (B + 1) + B) * sizeof(float); }
 
 }  // namespace
 
@@ -314,11 +322,16 @@ size_t ph_rkd_workspace_bytes(int B, int D) {
   return ((size_t)B * B * D + (size_t)3 * B * B + B + 16) * sizeof(float);
 }
 
+// Host only: whether rkd_angle_kernel's E [B][D + 1], A [B][B + 1] and nv [B] fit the LDS it may ask for - the shapes
+// ph_rkd_loss_grad takes (at D = 128 every B <= 128; at D = 256 up to 105 rows, at D = 384 up to 81, at D = 512 up to 66).
+int ph_rkd_one_workgroup_fits(int B, int D) {
+  return B >= 2 && B <= 128 && D >= 1 && D <= 512 && rkd_angle_lds_bytes(B, D) <= RKD_ANGLE_LDS_MAX;
+}
+
 int ph_rkd_loss_grad(const float* f_s, const float* f_t, float* loss, float* dx, int B, int D, float w_d, float w_a,
                      void* ws_, hipStream_t st) {
-  if (!f_s || !f_t || !loss || !dx || !ws_ || B < 2 || B > 128 || D < 1 || D > 512) return PH_EINVAL;
-  const size_t lds = ((size_t)B * (D + 1) + (size_t)B * (B + 1) + B) * sizeof(float);
-  if (lds > 150 * 1024) return PH_EINVAL;
+  if (!f_s || !f_t || !loss || !dx || !ws_ || !ph_rkd_one_workgroup_fits(B, D)) return PH_EINVAL;
+  const size_t lds = rkd_angle_lds_bytes(B, D);
   float* ws = reinterpret_cast<float*>(ws_);
   float* dv = ws; float* gs = dv + (size_t)B * B * D; float* gt = gs + (size_t)B * B; float* W = gt + (size_t)B * B;
   float* part = W + (size_t)B * B;
@@ -330,7 +343,7 @@ int ph_rkd_loss_grad(const float* f_s, const float* f_t, float* loss, float* dx,
   static bool attr_done = false;
   if (!attr_done) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(rkd_angle_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            150 * 1024) != hipSuccess)
+                            (int)RKD_ANGLE_LDS_MAX) != hipSuccess)
       return PH_ELAUNCH;
     attr_done = true;
   }

@@ -1,6 +1,6 @@
 // RKD ("MIA 2022/distiller_zoo/RKD.py":15-58) over a batch of up to 1024 rows, split by anchor ranges so that the
-// replicas of a data-parallel run each take a slice of the B^3 * D angle term (csrc/zoo.hip holds the B <= 128 form,
-// whose anchor kernel keeps E [B][D] and A [B][B] in LDS).  ph_rkd_loss_grad_part computes, for the anchors
+// replicas of a data-parallel run each take a slice of the B^3 * D angle term (csrc/zoo.hip holds the one-workgroup form
+// for B <= 128 rows whose E [B][D] and A [B][B] fit its anchor kernel's LDS: ph_rkd_one_workgroup_fits).  ph_rkd_loss_grad_part computes, for the anchors
 // [anchor_lo, anchor_lo + n_anchors) of the gathered rows, the part of the loss and of its gradient with respect to
 // EVERY student row that those anchors (angle term) and those rows of the distance matrix (distance term) produce; the
 // parts of any partition of [0, Bg) add up to the loss / gradient of the whole batch.  Global quantities (the two mean

@@ -5,8 +5,9 @@
 kernels of the hot path (fp32 GEMM, row L2 normalisation, squared-difference reduction, the KL kernels); the teacher
 side is treated as a constant (the trainers pass it detached).  `RKDLoss` ("MIA 2022/distiller_zoo/RKD.py") and `PKT`
 ("MIA 2022/distiller_zoo/PKT.py"), the `--distill rkd|pkt` choices of train_test_path_multi_distill_v2.py:339-342, are
-closed-form loss + gradient kernels of their own (csrc/zoo.hip; above 128 rows and under data parallelism RKD runs the
-anchor-partitioned kernels of csrc/zoo_rkd.hip).  The other zoo members are not built.
+closed-form loss + gradient kernels of their own (csrc/zoo.hip; where a batch does not fit the one-workgroup form's LDS -
+above 128 rows, or fewer at feature widths above 128 - and under data parallelism RKD runs the anchor-partitioned kernels
+of csrc/zoo_rkd.hip).  The other zoo members are not built.
 
 `Similarity`, `PKT` and `RKDLoss` relate every row of a batch to every other row.  Given a `sync` object (dist.ReplicaSync:
 one process per GPU, each holding `n` rows) they evaluate the loss of the GLOBAL batch of `world_size * n` rows, as the
@@ -27,7 +28,6 @@ from .tsvd import _SqDiffFn
 
 
 RKD_MAX_ROWS = 1024       # ph_rkd_loss_grad_part: rows of the (global) batch
-_RKD_ONE_WG_ROWS = 128    # ph_rkd_loss_grad: the anchor kernel keeps E [B][D] and A [B][B] in LDS
 
 
 def _gather_pair(f_s, f_t, sync):
@@ -76,7 +76,7 @@ class _LossGradFn(torch.autograd.Function):
         if kind == "pkt":
             ws = torch.empty(lib().ph_pkt_workspace_bytes(B, D), device=f_s.device, dtype=torch.uint8)
             check(lib().ph_pkt_loss_grad(ptr(f_s), ptr(f_t), ptr(loss), ptr(dx), B, D, ptr(ws), stream()), "ph_pkt_loss_grad")
-        elif B <= _RKD_ONE_WG_ROWS:
+        elif lib().ph_rkd_one_workgroup_fits(B, D):     # the anchor kernel keeps E [B][D] and A [B][B] in LDS
             ws = torch.empty(lib().ph_rkd_workspace_bytes(B, D), device=f_s.device, dtype=torch.uint8)
             check(lib().ph_rkd_loss_grad(ptr(f_s), ptr(f_t), ptr(loss), ptr(dx), B, D, float(w_d), float(w_a), ptr(ws),
                                          stream()), "ph_rkd_loss_grad")
@@ -149,8 +149,10 @@ class PKT(nn.Module):
 
 
 class RKDLoss(nn.Module):
-    """RKD.py:8-45: w_d * distance-wise + w_a * angle-wise relational losses (0-d).  Up to 128 rows: the one-workgroup-per-
-    anchor kernels of csrc/zoo.hip; up to 1024 rows: the tiled kernels of csrc/zoo_rkd.hip over the full anchor range.
+    """RKD.py:8-45: w_d * distance-wise + w_a * angle-wise relational losses (0-d).  Where ph_rkd_one_workgroup_fits(B, D)
+    (at most 128 rows, and B (D + 1) + B (B + 1) + B floats within 150 KiB of LDS: 105 rows at D = 256, 66 at D = 512): the
+    one-workgroup-per-anchor kernels of csrc/zoo.hip; otherwise, up to 1024 rows of up to 512 features: the tiled kernels of
+    csrc/zoo_rkd.hip over the full anchor range.
     `sync`: this replica's anchor range of the global batch (world_size * B <= 1024); the value is this replica's PART of
     the global loss, see the module docstring."""
 

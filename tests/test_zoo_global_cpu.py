@@ -1,8 +1,8 @@
 """CPU side of the relational distillation losses over the global batch: the argument checks of
 ph_rkd_loss_grad_part (they return before any HIP call, so they run without a GPU), its workspace size, and - under gloo
 with two processes - the two autograd forms the data-parallel criteria use: the row all-gather with the local backward
-(pkt, similarity) and the anchor-partitioned RKD wrapper, whose kernel call is replaced here by `rkd_part_torch`, a
-torch restatement of the kernel's contract."""
+(pkt, similarity) and the anchor-partitioned RKD wrapper, whose kernel call is replaced here by `rkd_part_torch`, the
+torch statement of the kernel's contract (tests/zoo_emulation.py)."""
 import ctypes as C
 import os
 import socket
@@ -13,40 +13,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.zoo_emulation import rkd_part_torch      # the contract of a part, stated once
+
 EINVAL = -22
-
-
-def rkd_part_torch(g_s, g_t, anchor_lo, n_anchors, w_d, w_a):
-    """The contract of ph_rkd_loss_grad_part in torch (RKD.py:15-58 restricted to an anchor range): the rows
-    [lo, lo + n) of the distance matrix and the anchors [lo, lo + n) of the angle tensor, with the mean distances and the
-    normalisers Bg^2 / Bg^3 of ALL rows.  Returns (loss_part [1], dx_part [Bg, D])."""
-    def pdist(e):
-        sq = (e[:, None, :] - e[None, :, :]).pow(2).sum(2)
-        d = sq.clamp(min=1e-12).sqrt()
-        return d * (1.0 - torch.eye(e.shape[0], dtype=e.dtype))
-
-    def angles(e, sl):
-        v = e[None, :, :] - e[sl, None, :]                       # [n, Bg, D]: v[a, j] = x_j - x_(lo + a)
-        u = v / v.norm(dim=2, keepdim=True).clamp(min=1e-12)
-        return torch.bmm(u, u.transpose(1, 2))
-
-    huber = torch.nn.functional.smooth_l1_loss
-    x = g_s.detach().clone().requires_grad_(True)
-    t = g_t.detach()
-    Bg = x.shape[0]
-    sl = slice(anchor_lo, anchor_lo + n_anchors)
-    with torch.no_grad():
-        t_d = pdist(t)
-        t_d = t_d / t_d[t_d > 0].mean()
-        t_a = angles(t, sl)
-    with torch.enable_grad():                 # (grad mode is off inside an autograd Function's forward)
-        d = pdist(x)
-        d = d / d[d > 0].mean()
-        loss_d = huber(d[sl], t_d[sl], reduction="sum") / float(Bg * Bg)
-        loss_a = huber(angles(x, sl), t_a, reduction="sum") / float(Bg) ** 3
-        loss = w_d * loss_d + w_a * loss_a
-        dx, = torch.autograd.grad(loss, x)
-    return loss.detach().reshape(1), dx
 
 
 def _lib():
