@@ -7,7 +7,7 @@ import torch.optim.lr_scheduler as lr_scheduler
 from torch.nn import Parameter
 
 from . import ops
-from .fusion import BilinearFusion
+from .fusion import BilinearFusion, PolynomialFusion
 from .resnets import ResNet18
 from .utils import init_net, init_max_weights
 
@@ -107,10 +107,13 @@ def define_act_layer(act_type="Tanh"):
 
 def define_bifusion(fusion_type, skip=1, use_bilinear=1, gate1=1, gate2=1, dim1=32, dim2=32, scale_dim1=1,
                     scale_dim2=1, mmhid=32, dropout_rate=0.25):
-    """networks_new.py:148-154"""
+    """networks_new.py:148-154; 'polynomial_fusion' as in "MIA 2023/stage2_unimodal_student/networks_new.py":148-155"""
     if fusion_type == "pofusion":
         return BilinearFusion(skip=skip, use_bilinear=use_bilinear, gate1=gate1, gate2=gate2, dim1=dim1, dim2=dim2,
                               scale_dim1=scale_dim1, scale_dim2=scale_dim2, mmhid=mmhid, dropout_rate=dropout_rate)
+    if fusion_type == "polynomial_fusion":
+        return PolynomialFusion(skip=skip, use_bilinear=use_bilinear, gate1=gate1, gate2=gate2, dim1=dim1, dim2=dim2,
+                                scale_dim1=scale_dim1, scale_dim2=scale_dim2, mmhid=mmhid, dropout_rate=dropout_rate)
     raise NotImplementedError("fusion type [%s] is not found" % fusion_type)
 
 

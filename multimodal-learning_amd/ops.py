@@ -86,8 +86,8 @@ def _ones(n, device):
     return _ones_cache[key]
 
 
-def sgemm(A, Bm, bias, out, M, N, K, sam, sak, sbk, sbn, act=ACT_NONE, accumulate=False):
-    check(lib().ph_sgemm(ptr(A), ptr(Bm), ptr(bias), ptr(out), M, N, K, sam, sak, sbk, sbn, N, act,
+def sgemm(A, Bm, bias, out, M, N, K, sam, sak, sbk, sbn, act=ACT_NONE, accumulate=False, ldc=None):
+    check(lib().ph_sgemm(ptr(A), ptr(Bm), ptr(bias), ptr(out), M, N, K, sam, sak, sbk, sbn, N if ldc is None else ldc, act,
                          int(accumulate), stream()), "ph_sgemm")
     return out
 
@@ -131,6 +131,83 @@ class LinearFn(torch.autograd.Function):
             db = torch.empty(N, device=g.device, dtype=torch.float32)
             sgemm(_ones(Bn, g.device), g, None, db, 1, N, Bn, 0, 1, N, 1)   # db = 1^T dY
         return dx, dw, db
+
+
+# ---- a linear map over a row-wise concatenation (x_0 | x_1 | ...), some blocks followed by a column of ones, without forming
+# the concatenation: a sum of GEMMs over column blocks of the weight (the fusion head's skip connection and linear gate,
+# fusion.py:43,61).  `blocks` is a list of (x_i [B, k_i] contiguous, one_follows).
+def _cat_layout(blocks):
+    """[(column offset of block i, k_i)], [columns that multiply an appended 1], total width"""
+    offs, ones, off = [], [], 0
+    for x, one in blocks:
+        offs.append((off, x.shape[1]))
+        off += x.shape[1]
+        if one:
+            ones.append(off)
+            off += 1
+    return offs, ones, off
+
+
+def cat_linear_fwd(blocks, w, b):
+    """y[B,N] = (x_0 | [1] | x_1 | [1] | ...) @ w[N,Kt]^T + b"""
+    w = _f32(w)
+    blocks = [(_f32(x), one) for x, one in blocks]
+    offs, ones, Kt = _cat_layout(blocks)
+    N = w.shape[0]
+    if Kt != w.shape[1]:
+        raise RuntimeError("cat_linear: blocks span %d columns, the weight has %d" % (Kt, w.shape[1]))
+    Bn = blocks[0][0].shape[0]
+    y = torch.empty(Bn, N, device=w.device, dtype=torch.float32)
+    for i, ((x, _), (off, k)) in enumerate(zip(blocks, offs)):
+        sgemm(x, w[:, off:], b if i == 0 else None, y, Bn, N, k, k, 1, 1, Kt, accumulate=i > 0)
+    if len(ones) == 2:      # both appended-1 columns in one K = 2 product: A is a broadcast 1, B steps from column to column
+        sgemm(_ones(1, w.device), w[:, ones[0]:], None, y, Bn, N, 2, 0, 0, ones[1] - ones[0], Kt, accumulate=True)
+    else:
+        for c in ones:
+            sgemm(_ones(1, w.device), w[:, c:], None, y, Bn, N, 1, 0, 0, 1, Kt, accumulate=True)
+    return y
+
+
+class CatLinearFn(torch.autograd.Function):
+    """cat_linear_fwd taped: every block's input gradient from its column block of the weight, the weight gradient
+    written block by block into column slices of one [N, Kt] tensor (ldc = Kt), the appended-1 columns get 1^T dY."""
+
+    @staticmethod
+    def forward(ctx, w, b, ones_after, *xs):
+        blocks = list(zip(xs, ones_after))
+        ctx.save_for_backward(w, *xs)
+        ctx.ones_after, ctx.has_bias = tuple(ones_after), b is not None
+        return cat_linear_fwd(blocks, w, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        w, *xs = ctx.saved_tensors
+        g = _f32(g)
+        offs, ones, Kt = _cat_layout(list(zip(xs, ctx.ones_after)))
+        Bn, N = g.shape
+        one = _ones(1, g.device)
+        dxs = []
+        for i, (x, (off, k)) in enumerate(zip(xs, offs)):
+            dx = None
+            if ctx.needs_input_grad[3 + i]:
+                dx = torch.empty_like(x)
+                sgemm(g, w[:, off:], None, dx, Bn, k, N, N, 1, Kt, 1)              # dX_i = dY @ W[:, block i]
+            dxs.append(dx)
+        dw = db = None
+        if ctx.needs_input_grad[0]:
+            dw = torch.empty_like(w)
+            for x, (off, k) in zip(xs, offs):
+                sgemm(g, x, None, dw[:, off:], N, k, Bn, 1, N, k, 1, ldc=Kt)       # dW[:, block i] = dY^T @ X_i
+            for c in ones:
+                sgemm(g, one, None, dw[:, c:], N, 1, Bn, 1, N, 0, 0, ldc=Kt)       # dW[:, c] = dY^T 1
+        if ctx.has_bias and ctx.needs_input_grad[1]:
+            db = torch.empty(N, device=g.device, dtype=torch.float32)
+            sgemm(_ones(Bn, g.device), g, None, db, 1, N, Bn, 0, 1, N, 1)
+        return (dw, db, None) + tuple(dxs)
+
+
+def cat_linear(blocks, w, b):
+    return CatLinearFn.apply(w, b, tuple(one for _, one in blocks), *[_f32(x) for x, _ in blocks])
 
 
 # ---- autograd forms of the SNN / fusion operators (stage-1 teacher training, SURVEY row f-1).  The frozen teacher of the

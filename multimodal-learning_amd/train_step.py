@@ -388,8 +388,8 @@ def _validate_opt(opt, who, surv_ok=False):
     if getattr(opt, "optimizer_type", "adam") not in ("adam", "adagrad"):
         raise NotImplementedError("%s: optimizer_type %r (adam and adagrad are built; adabound needs the absent `adabound` "
                                   "package, networks_new.py:82-83)" % (who, opt.optimizer_type))
-    if getattr(opt, "fusion_type", "pofusion") != "pofusion":
-        raise NotImplementedError("%s: fusion_type %r (pofusion is built)" % (who, opt.fusion_type))
+    if getattr(opt, "fusion_type", "pofusion") not in ("pofusion", "polynomial_fusion"):
+        raise NotImplementedError("%s: fusion_type %r (pofusion and polynomial_fusion are built)" % (who, opt.fusion_type))
     if getattr(opt, "return_grad", "False") != "False":
         raise NotImplementedError("%s: return_grad needs the reference's absent my_utils.compute_gradients" % who)
     if getattr(opt, "use_vgg_features", 0):
@@ -1247,6 +1247,15 @@ class TeacherStage1Step:
             self._batch_idx = 0
         self.optimizer = define_optimizer(opt, module_list if self.crd_on else self.model)      # :86-94
         self.scheduler = define_scheduler(opt, self.optimizer)
+        # a fusion gate that is off leaves linear_h_k / linear_z_k unread (fusion.py:45-46,52-53): they stay in the optimiser's
+        # list as in the reference, where their .grad stays None and the update skips them - unless the regulariser reaches
+        # them (`--reg_type all` sums |W| over every parameter and gives them a gradient)
+        fusion = getattr(self.model, "fusion", None)
+        unused = fusion.unused_parameters() if hasattr(fusion, "unused_parameters") else []
+        self._unused_ids = set()
+        if unused and opt.reg_type != "all" and hasattr(self.optimizer, "set_inactive"):
+            self.optimizer.set_inactive(unused)
+            self._unused_ids = {id(p) for p in unused}
         self.iter_num = opt.global_step
         self.model.train(); self.ema_model.train()
         self.ema_flat = FlatParams(list(self.ema_model.parameters()))
@@ -1288,11 +1297,13 @@ class TeacherStage1Step:
         """update_ema_variables (:34-38, :229) covers EVERY parameter, output_range / output_shift included; the fused Adam step
         updates the EMA copy of the trained ones only.  Under surv the sigmoid head reads those two, so their EMA copies
         follow here (rate from the optimiser's device record: graph-replayable).  Grading leaves them alone: its head never
-        reads them."""
+        reads them.  The student tensors that an option leaves unused (`_unused_ids`: no gradient, no Adam update) follow under
+        both tasks: update_ema_variables still moves their EMA copies towards the unchanged student values."""
         opt_ = self.optimizer
         if self._frozen_segs is None:
             f, hi = opt_.flat, opt_.ema_range[1]
-            self._frozen_segs = [(s, min(e, hi)) for s, e in f.segments(lambda t: not t.requires_grad) if s < hi]
+            left_out = lambda t: (self.surv and not t.requires_grad) or id(t) in self._unused_ids      # noqa: E731
+            self._frozen_segs = [(s, min(e, hi)) for s, e in f.segments(left_out) if s < hi]
         f = opt_.flat
         for s, e in self._frozen_segs:
             check(lib().ph_ema_update_dev(ptr(self.ema_flat.flat[s:e]), ptr(f.flat[s:e]), e - s, ptr(opt_._hyper), stream()),
@@ -1547,7 +1558,7 @@ class TeacherStage1Step:
                 loss_tsvd = loss_tsvd + T.tsvd_penalty(self.adj_tensor2, self.aux_tensor2, mu_pen)
             loss = loss + loss_tsvd
         _backward_and_update(self, loss)                                                        # + EMA (:229) fused
-        if self.surv:
+        if self.surv or self._unused_ids:
             self._ema_frozen()
         if self.tsvd_on:
             # the adjacency tensors are kept as VALUES: with their grad_fn they would keep this step's autograd graph - and the
