@@ -48,17 +48,28 @@ typedef struct ihipStream_t* ph_stream_t; /* a hipStream_t */
 int ph_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
- * ResNet-18 trunk: conv7x7/2-BN-ReLU-maxpool, 8 BasicBlocks, global avg-pool of layer3 and layer4.
+ * BasicBlock ResNet trunk: conv7x7/2-BN-ReLU-maxpool, four layers of layers4[0..3] BasicBlocks at 64 / 128 / 256 / 512
+ * channels (ResNet-18: {2, 2, 2, 2}, ResNet-34: {3, 4, 6, 3}), global avg-pool of layer3 and layer4.
  * Replaces ResNet._forward_impl up to the pooled features (resnets.py:217-236, BasicBlock :58-74) and
  * its autograd backward.  Train-mode BatchNorm everywhere (train_test_path_multi_distill.py:231-232).
  *
- * params: 20 units x 6 pointers [conv weight OIHW f32, bn weight, bn bias, running_mean, running_var,
- *         num_batches_tracked (int64)] in state_dict order: conv1/bn1, then per block conv1/bn1,
- *         conv2/bn2, downsample.0/downsample.1 (layer2-4 block 0 only).
- * grads : 20 units x 3 pointers [d conv weight (OIHW f32), d bn weight, d bn bias] (overwritten).
+ * A "unit" is one convolution with its BatchNorm.  Units follow state_dict order: conv1/bn1, then per block conv1/bn1,
+ * conv2/bn2, downsample.0/downsample.1 (block 0 of layers 2-4 only).  A plan has
+ * N (ph_resnet_num_units) = 1 + 2 * (layers4[0] + .. + layers4[3]) + 3 of them: 20 for ResNet-18, 36 for ResNet-34.
+ * Blocks are numbered 0 .. sum(layers4) - 1 in the same order.
+ *
+ * params: N units x 6 pointers [conv weight OIHW f32, bn weight, bn bias, running_mean, running_var,
+ *         num_batches_tracked (int64)].
+ * grads : N units x 3 pointers [d conv weight (OIHW f32), d bn weight, d bn bias] (overwritten).
+ *
+ * ph_resnet_plan_create_layers returns NULL, before any allocation or HIP call, for layers4 == NULL, an entry below 1 or
+ * above PH_RESNET_MAX_BLOCKS, B < 1, H or W < 32, an unknown prec, or PH_PREC_FP16X3 with H or W no multiple of 4.
+ * ph_resnet_plan_create is ph_resnet_plan_create_layers with layers4 = {2, 2, 2, 2}.
  * ---------------------------------------------------------------------------------------------- */
+#define PH_RESNET_MAX_BLOCKS 64  /* BasicBlocks per layer (torchvision's deepest stage, ResNet-152 layer3, has 36) */
 typedef struct PhResnetPlan PhResnetPlan;
 PhResnetPlan* ph_resnet_plan_create(int B, int H, int W, int prec);
+PhResnetPlan* ph_resnet_plan_create_layers(int B, int H, int W, int prec, const int* layers4);
 void ph_resnet_plan_destroy(PhResnetPlan* plan);
 size_t ph_resnet_workspace_bytes(const PhResnetPlan* plan);
 size_t ph_resnet_packed_bytes(const PhResnetPlan* plan);
@@ -103,9 +114,9 @@ int ph_resnet_forward(const PhResnetPlan* plan, const void* const* params, const
 int ph_resnet_backward(const PhResnetPlan* plan, const void* const* params, const void* packed, void* workspace,
                        const float* g_f3 /* may be NULL */, const float* g_f4, void* const* grads,
                        ph_stream_t stream);
-/* The same backward in two calls for a data-parallel caller: part 0 = layers 4 and 3 (afterwards the gradients of
- * layers 3-4, 93 % of the trunk's parameter bytes, are final and their all-reduce can start), part 1 = layers 2, 1 and
- * the stem; part -1 = everything (== ph_resnet_backward).  The reference's DataParallel reduces after the whole
+/* The same backward in two calls for a data-parallel caller: part 0 = every block of layers 4 and 3 (afterwards the
+ * gradients of layers 3-4, 93 % of the trunk's parameter bytes, are final and their all-reduce can start), part 1 = layers
+ * 2, 1 and the stem; part -1 = everything (== ph_resnet_backward).  The reference's DataParallel reduces after the whole
  * backward (utils.py:257-260). */
 int ph_resnet_backward_part(const PhResnetPlan* plan, const void* const* params, const void* packed, void* workspace,
                             const float* g_f3, const float* g_f4, void* const* grads, int part, ph_stream_t stream);

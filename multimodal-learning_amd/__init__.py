@@ -10,7 +10,7 @@ from . import _lib
 from ._lib import build, lib, LIB_PATH
 from .ops import set_precision, get_precision
 from .utils import init_net, init_max_weights, count_parameters
-from .resnets import ResNet, ResNet18, BasicBlock
+from .resnets import ResNet, ResNet18, ResNet34, BasicBlock
 from .fusion import BilinearFusion, PolynomialFusion
 from .networks_new import (define_net, define_optimizer, define_reg, define_scheduler, define_act_layer,
                            define_bifusion, MaxNet, PathomicNet, get_resnet)
@@ -30,7 +30,7 @@ from . import augment
 from .options import stage2_opt
 
 __all__ = ["build", "lib", "set_precision", "get_precision", "init_net", "init_max_weights", "count_parameters",
-           "ResNet", "ResNet18", "BasicBlock", "BilinearFusion", "PolynomialFusion", "define_net", "define_optimizer", "define_reg",
+           "ResNet", "ResNet18", "ResNet34", "BasicBlock", "BilinearFusion", "PolynomialFusion", "define_net", "define_optimizer", "define_reg",
            "define_scheduler", "define_act_layer", "define_bifusion", "MaxNet", "PathomicNet", "get_resnet",
            "DistillKL", "CRDLoss", "ContrastLoss_v2", "Embed", "Normalize", "ContrastMemory_v3", "AEKD_loss", "momentum_AEKD_loss",
            "update_ema_variables", "DistillStep", "FusedAdam", "FusedAdagrad", "FlatParams", "TeacherStage1Step", "dist", "stage2_opt"]

@@ -18,6 +18,7 @@ vp, i32, i64, f32, f64, sz, u64, lng = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SIGNATURES = {
     "ph_abi_version": (i32, []),
     "ph_resnet_plan_create": (vp, [i32, i32, i32, i32]),
+    "ph_resnet_plan_create_layers": (vp, [i32, i32, i32, i32, vp]),
     "ph_resnet_plan_destroy": (None, [vp]),
     "ph_resnet_workspace_bytes": (sz, [vp]),
     "ph_resnet_packed_bytes": (sz, [vp]),

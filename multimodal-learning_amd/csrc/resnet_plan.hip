@@ -1,4 +1,5 @@
-// Host-side runtime for the ResNet-18 trunk (reference resnets.py:126-236, BasicBlock :37-74):
+// Host-side runtime for the BasicBlock ResNet trunk of any depth - ResNet-18 {2,2,2,2}, ResNet-34 {3,4,6,3}, .. - (reference
+// resnets.py:126-236, BasicBlock :37-74):
 // a static plan (layer table + workspace layout in one HBM arena, no allocation at run time) and the
 // forward / backward launch sequences over the kernels in conv_*.hip and bn_act.hip.
 //
@@ -59,6 +60,10 @@ struct PhResnetPlan {
   int B, H, W, prec, es;
   std::vector<Unit> units;
   std::vector<Block> blocks;
+  // depth: BasicBlocks per layer, the last block of layers 3 / 4 (the pooled features f3 / f4 and where their gradients enter) and the
+  // first block of layer 3 (where the two-part backward is cut)
+  int nblk[4] = {2, 2, 2, 2};
+  int f3_block = 5, f4_block = 7, split_block = 4;
   size_t x4_off, p0_off, p0raw_off, idx_off, parts_off, parts_bytes;
   size_t g0_off, g1_off, dy_off, da_off, slab_off, slab_bytes, bparts_off, cc_off, zero_off;
   size_t ws_bytes, packed_bytes;
@@ -142,12 +147,19 @@ struct Grads {
 
 extern "C" {
 
-PhResnetPlan* ph_resnet_plan_create(int B, int H, int W, int prec) {
+PhResnetPlan* ph_resnet_plan_create_layers(int B, int H, int W, int prec, const int* layers4) {
+  if (!layers4) return nullptr;
+  for (int li = 0; li < 4; ++li)
+    if (layers4[li] < 1 || layers4[li] > PH_RESNET_MAX_BLOCKS) return nullptr;
   if (B < 1 || H < 32 || W < 32 || (prec != PH_PREC_BF16 && !PH_IS_SPLIT_PREC(prec) && prec != PH_PREC_FP16X3)) return nullptr;
   if (prec == PH_PREC_FP16X3 && ((H | W) & 3)) return nullptr;   // (even stem output: the pooled form of the stem's BatchNorm-backward sums)
   PhResnetPlan* P = new (std::nothrow) PhResnetPlan();
   if (!P) return nullptr;
   P->B = B; P->H = H; P->W = W; P->prec = prec; P->es = prec == PH_PREC_BF16 ? 2 : 4;
+  for (int li = 0; li < 4; ++li) P->nblk[li] = layers4[li];
+  P->split_block = P->nblk[0] + P->nblk[1];
+  P->f3_block = P->split_block + P->nblk[2] - 1;
+  P->f4_block = P->f3_block + P->nblk[3];
   const size_t es = P->es;
   size_t off = 0, woff = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = up(off + bytes); return o; };
@@ -174,7 +186,7 @@ PhResnetPlan* ph_resnet_plan_create(int B, int H, int W, int prec) {
   size_t in_off = P->p0_off, in32_off = p032_off;
   const int planes[4] = {64, 128, 256, 512};
   for (int li = 0; li < 4; ++li)
-    for (int bi = 0; bi < 2; ++bi) {
+    for (int bi = 0; bi < P->nblk[li]; ++bi) {
       const int stride = (li > 0 && bi == 0) ? 2 : 1;
       const int pl = planes[li];
       Block b{};
@@ -240,6 +252,11 @@ PhResnetPlan* ph_resnet_plan_create(int B, int H, int W, int prec) {
   return P;
 }
 
+PhResnetPlan* ph_resnet_plan_create(int B, int H, int W, int prec) {
+  const int resnet18[4] = {2, 2, 2, 2};
+  return ph_resnet_plan_create_layers(B, H, W, prec, resnet18);
+}
+
 void ph_resnet_plan_destroy(PhResnetPlan* P) { delete P; }
 size_t ph_resnet_workspace_bytes(const PhResnetPlan* P) { return P ? P->ws_bytes : 0; }
 size_t ph_resnet_packed_bytes(const PhResnetPlan* P) { return P ? P->packed_bytes : 0; }
@@ -260,22 +277,27 @@ int ph_resnet_pack_weights(const PhResnetPlan* P, const void* const* params_, vo
                ? ph_pack_w_stem_hp_launch(params.w(0), pk + P->units[0].wf_off, st)
                : ph_pack_w_stem_launch(params.w(0), pk + P->units[0].wf_off, st);
   if (rc) return rc;
-  PhPackAll t{};
-  size_t acc = 0;
-  for (size_t i = 1; i < P->units.size(); ++i) {
-    const Unit& u = P->units[i];
-    const int k = t.n++;
-    t.w[k] = params.w((int)i);
-    t.dst_fwd[k] = u.wf_off; t.dst_dg[k] = u.wd_off;
-    t.O[k] = u.Cout; t.I[k] = u.Cin; t.NT[k] = u.KS * u.KS;
-    // the layouts the kernels of this unit's launches read (refresh_layouts above: the eligibility and switch state that picks them)
-    t.frag[k] = u.wfrag_f | (u.wfrag_d << 2);
-    t.start[k] = acc;
-    acc += u.wplane;
+  // one launch per std::size(PhPackAll::w) units (the table is a kernel argument): ResNet-18's 19 units in one
+  constexpr size_t PER = std::size(PhPackAll{}.w);
+  for (size_t i0 = 1; i0 < P->units.size(); i0 += PER) {
+    PhPackAll t{};
+    size_t acc = 0;
+    for (size_t i = i0; i < P->units.size() && i < i0 + PER; ++i) {
+      const Unit& u = P->units[i];
+      const int k = t.n++;
+      t.w[k] = params.w((int)i);
+      t.dst_fwd[k] = u.wf_off; t.dst_dg[k] = u.wd_off;
+      t.O[k] = u.Cout; t.I[k] = u.Cin; t.NT[k] = u.KS * u.KS;
+      // the layouts the kernels of this unit's launches read (refresh_layouts above: the eligibility and switch state that picks them)
+      t.frag[k] = u.wfrag_f | (u.wfrag_d << 2);
+      t.start[k] = acc;
+      acc += u.wplane;
+    }
+    t.start[t.n] = acc;
+    t.total = acc;
+    if ((rc = ph_pack_all_launch(&t, pk, P->prec == PH_PREC_BF16 ? 1 : (P->prec == PH_PREC_FP16X3 ? -3 : 3), st))) return rc;
   }
-  t.start[t.n] = acc;
-  t.total = acc;
-  return ph_pack_all_launch(&t, pk, P->prec == PH_PREC_BF16 ? 1 : (P->prec == PH_PREC_FP16X3 ? -3 : 3), st);
+  return PH_OK;
 }
 
 }  // extern "C"
@@ -495,16 +517,22 @@ int ph_resnet_forward(const PhResnetPlan* P, const void* const* params, const vo
   const unsigned char* x4p = (flags & 64) ? reinterpret_cast<const unsigned char*>(x_nchw) : ws + P->x4_off;
   if (!(flags & 64) && (rc = ph_pack_input_launch(x_nchw, ws + P->x4_off, P->B, P->H, P->W, P->prec, st))) return rc;
   if (c.eval) {
-    PhBnEvalTable t{};
-    t.n = (int)P->units.size();
-    for (int i = 0; i < t.n; ++i) {
-      const Unit& u = P->units[i];
-      t.gamma[i] = c.params.gamma(i); t.beta[i] = c.params.beta(i);
-      t.running_mean[i] = c.params.running_mean(i); t.running_var[i] = c.params.running_var(i);
-      t.mean[i] = c.stat(u, 0); t.invstd[i] = c.stat(u, 1); t.scale[i] = c.stat(u, 2); t.shift[i] = c.stat(u, 3);
-      t.C[i] = u.Cout;
+    // one launch per std::size(PhBnEvalTable::C) units (the table is a kernel argument): ResNet-18's 20 in one
+    constexpr int PER = (int)std::size(PhBnEvalTable{}.C);
+    const int nu = (int)P->units.size();
+    for (int i0 = 0; i0 < nu; i0 += PER) {
+      PhBnEvalTable t{};
+      t.n = std::min(PER, nu - i0);
+      for (int k = 0; k < t.n; ++k) {
+        const int i = i0 + k;
+        const Unit& u = P->units[i];
+        t.gamma[k] = c.params.gamma(i); t.beta[k] = c.params.beta(i);
+        t.running_mean[k] = c.params.running_mean(i); t.running_var[k] = c.params.running_var(i);
+        t.mean[k] = c.stat(u, 0); t.invstd[k] = c.stat(u, 1); t.scale[k] = c.stat(u, 2); t.shift[k] = c.stat(u, 3);
+        t.C[k] = u.Cout;
+      }
+      if ((rc = ph_bn_eval_params_launch(&t, 1e-5f, st))) return rc;
     }
-    if ((rc = ph_bn_eval_params_launch(&t, 1e-5f, st))) return rc;
   }
   bool p0_raw = false;
   if ((flags & 4) && !(flags & 32) && P->prec == PH_PREC_BF16) {
@@ -575,8 +603,9 @@ int ph_resnet_forward(const PhResnetPlan* P, const void* const* params, const vo
                                         P->prec, fo_hp ? 1 : 0, st);
     }
     if (rc) return rc;
-    if ((bi == 5 && f3) || (bi == 7 && f4)) {
-      float* dst = bi == 5 ? f3 : f4;
+    const bool is_f3 = (int)bi == P->f3_block;
+    if ((is_f3 && f3) || ((int)bi == P->f4_block && f4)) {
+      float* dst = is_f3 ? f3 : f4;
       if ((rc = fo_hp ? ph_avgpool_launch_t(ws + b.out_off, dst, P->B, b.OH * b.OW, b.Cout, P->prec, st)
                       : ph_avgpool_launch(ws + b.out32_off, dst, P->B, b.OH * b.OW, b.Cout, P->prec, st)))
         return rc;
@@ -614,11 +643,12 @@ namespace {
 // captured and never destroyed: a stream that has taken part in a capture as a forked branch must outlive every later capture
 // on the same origin stream (destroying the plan-owned stream of an earlier round-3 build produced rare segfaults inside
 // hipStreamEndCapture of LATER captures), and streams of the torch pool are not destroyed either.  Every call reserves its own
-// block of 64 events, so two backward passes in flight never share one.
+// block of events, so two backward passes in flight never share one.  A block starts with EV_BLOCK events and grows to what the
+// deepest plan seen so far needs (events_needed: two per unit) - outside stream captures only.
 struct SideRes {
   hipStream_t side = nullptr;
-  std::vector<hipEvent_t> evs;
-  // A backward call holds one block of EV_BLOCK events until the work it enqueued has run: `done[b]` is recorded on the
+  std::vector<hipEvent_t> evs[16];      // per block
+  // A backward call holds one block of events until the work it enqueued has run: `done[b]` is recorded on the
   // caller's stream when the call returns and the block is handed out again only once that event has completed.  A call made
   // inside a stream capture frees its block at once (the capture turns its event waits into graph edges and keeps no
   // reference to the events).
@@ -629,6 +659,20 @@ struct SideRes {
 };
 constexpr size_t EV_BLOCK = 64, EV_BLOCKS = 16;
 #define PH_EBUSY (-16)
+
+// events one backward call takes from its block: per convolution unit one fork + one read_done (wgrad_of), the stem's fork, the join
+size_t events_needed(const PhResnetPlan* P) { return 2 * P->units.size() + 2; }
+
+// block b of r holds at least n events (r->mu held, not inside a stream capture)
+bool grow_events(SideRes* r, size_t b, size_t n) {
+  std::vector<hipEvent_t>& v = r->evs[b];
+  while (v.size() < n) {
+    hipEvent_t e;
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return false;
+    v.push_back(e);
+  }
+  return true;
+}
 
 SideRes* overlap_ready(const PhResnetPlan* P, hipStream_t st) {
   static SideRes* res[16] = {nullptr};
@@ -643,22 +687,28 @@ SideRes* overlap_ready(const PhResnetPlan* P, hipStream_t st) {
   SideRes* r = new (std::nothrow) SideRes();
   if (!r) return nullptr;
   if (hipStreamCreateWithFlags(&r->side, hipStreamNonBlocking) != hipSuccess) { delete r; return nullptr; }
-  r->evs.resize(EV_BLOCK * EV_BLOCKS + EV_BLOCKS);
-  for (size_t i = 0; i < r->evs.size(); ++i)
-    if (hipEventCreateWithFlags(&r->evs[i], hipEventDisableTiming) != hipSuccess) {
-      for (size_t j = 0; j < i; ++j) (void)hipEventDestroy(r->evs[j]);
-      (void)hipStreamDestroy(r->side);      // (never used: safe to destroy)
-      delete r;
-      return nullptr;
+  bool ok = true;
+  for (size_t b = 0; b < EV_BLOCKS && ok; ++b) {
+    r->done[b] = nullptr; r->busy[b] = false;
+    ok = grow_events(r, b, EV_BLOCK) && hipEventCreateWithFlags(&r->done[b], hipEventDisableTiming) == hipSuccess;
+  }
+  if (!ok) {
+    for (size_t b = 0; b < EV_BLOCKS; ++b) {
+      for (hipEvent_t e : r->evs[b]) (void)hipEventDestroy(e);
+      if (r->done[b]) (void)hipEventDestroy(r->done[b]);
     }
-  for (size_t b = 0; b < EV_BLOCKS; ++b) { r->done[b] = r->evs[EV_BLOCK * EV_BLOCKS + b]; r->busy[b] = false; }
+    (void)hipStreamDestroy(r->side);      // (never used: safe to destroy)
+    delete r;
+    return nullptr;
+  }
   res[dev] = r;
   return r;
 }
 
 // One backward call's use of the side stream: its block of events, and the four orderings between the chain (the caller's stream)
 // and the weight gradients.  Off (open() not called or refused: overlap switched off, a cut debug backward, no side stream yet while
-// capturing): side() is the chain's stream and every method is a no-op.
+// capturing, or a captured call of a plan deeper than every plan an eager call has run yet - the capture block cannot grow inside a
+// capture, and a training loop runs its first steps eagerly): side() is the chain's stream and every method is a no-op.
 class SideLane {
  public:
   explicit SideLane(hipStream_t chain) : st(chain) {}
@@ -672,7 +722,9 @@ class SideLane {
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     capturing = hipStreamIsCapturing(st, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone;
     std::lock_guard<std::mutex> lk(sr->mu);
+    const size_t need = events_needed(P);
     if (capturing) {
+      if (sr->evs[EV_BLOCKS - 1].size() < need) { sr = nullptr; return PH_OK; }
       // A captured call uses the block RESERVED for captures: the capture turns its event waits into graph edges and keeps no
       // reference to the events, so the block is free again when the call returns, and no hipEventQuery ever runs inside a
       // capture (in the default "global" capture mode a query from the capturing thread would invalidate it - ADVICE r04).
@@ -698,7 +750,11 @@ class SideLane {
       }
       sr->busy[ev_blk] = true;      // (claimed; released by the destructor)
       sr->cursor = ((size_t)ev_blk + 1) % NE;
+      // this call's block and the captures' block hold what this plan needs (a capture of the same plan follows eager steps)
+      if (!grow_events(sr, (size_t)ev_blk, need) || !grow_events(sr, EV_BLOCKS - 1, need)) return PH_ELAUNCH;
     }
+    // (a copy: an eager call on another thread may grow the captures' block while a captured call uses it)
+    ev.assign(sr->evs[ev_blk].begin(), sr->evs[ev_blk].begin() + need);
     return PH_OK;
   }
   // every exit path: a captured call frees the block, an eager one marks it with `done` on the chain
@@ -729,7 +785,7 @@ class SideLane {
   int join() { return sr ? order(sr->side, st) : PH_OK; }
 
  private:
-  hipEvent_t next_ev() { return sr->evs[(size_t)ev_blk * EV_BLOCK + (ev_used++ % EV_BLOCK)]; }      // (a call needs < 50)
+  hipEvent_t next_ev() { return ev[ev_used++ % ev.size()]; }      // (events_needed() of them: each is used once)
   int order(hipStream_t first, hipStream_t then) {
     hipEvent_t e = next_ev();
     return (hipEventRecord(e, first) != hipSuccess || hipStreamWaitEvent(then, e, 0) != hipSuccess) ? PH_ELAUNCH : PH_OK;
@@ -739,19 +795,24 @@ class SideLane {
   int ev_blk = -1;
   bool capturing = false;
   size_t ev_used = 0;
+  std::vector<hipEvent_t> ev;      // this call's events
   hipEvent_t rd[2] = {nullptr, nullptr};    // recorded on the side stream after the last reader of dz buffer k
 };
 
 int backward_impl(const PhResnetPlan* P, const void* const* params, const void* packed, void* ws_, const float* g_f3,
                   const float* g_f4, void* const* grads, int part, int stop, hipStream_t st) {
   if (!P || !params || !packed || !ws_ || !g_f4 || !grads || part < -1 || part > 1) return PH_EINVAL;
-  const int bi_hi = part == 1 ? 3 : 7, bi_lo = part == 0 ? 4 : 0;
+  // part 0 = every block of layers 4 and 3, part 1 = the rest.  The cut is the first block of layer 3, a downsample block: no dgrad
+  // takes BatchNorm-backward sums across it (Bst below is for identity blocks), so the two parts launch what the whole does
+  const int bi_hi = part == 1 ? P->split_block - 1 : P->f4_block, bi_lo = part == 0 ? P->split_block : 0;
   Ctx c{P, {params}, reinterpret_cast<const bf16*>(packed), reinterpret_cast<unsigned char*>(ws_), st, 0};
   c.no_masked = P->no_masked;
   const Grads gr{grads};
   unsigned char* ws = c.ws;
   unsigned char* gcur = ws + P->g0_off;
   unsigned char* gnext = ws + P->g1_off;
+  // the block gradient ping-pongs once per block: part 1 starts in the buffer where part 0's blocks left it
+  if (part == 1 && ((P->f4_block - P->split_block + 1) & 1)) std::swap(gcur, gnext);
   unsigned char* dab = ws + P->da_off;
   int rc, nst = 0;
   SideLane lane(st);
@@ -773,12 +834,12 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
   int fused_out = 0;      // rows of fused bn2 (+ downsample) sums the last dgrad left for the block about to be processed
   if (part != 1) {
     if (hipMemsetAsync(ws + P->zero_off, 0, 256, st) != hipSuccess) return PH_ELAUNCH;
-    const Block& b = P->blocks[7];
+    const Block& b = P->blocks[P->f4_block];
     PH_STAGE(ph_avgpool_bwd_launch(g_f4, gcur, P->B, b.OH * b.OW, b.Cout, 0, P->prec, st));
   }
   for (int bi = bi_hi; bi >= bi_lo; --bi) {
     const Block& b = P->blocks[bi];
-    if (bi == 5 && g_f3) {
+    if (bi == P->f3_block && g_f3) {
       PH_STAGE(ph_avgpool_bwd_launch(g_f3, gcur, P->B, b.OH * b.OW, b.Cout, 1, P->prec, st));
       fused_out = 0;      // (sums taken before this addition would be stale: the separate reduction runs)
     }
@@ -812,7 +873,7 @@ int backward_impl(const PhResnetPlan* P, const void* const* params, const void* 
     if (b.uds < 0) {
       // identity shortcut: d_xin = dgrad(conv1) + d_out * (out > 0), fused in the dgrad epilogue - which also takes the sums of
       // the PREVIOUS block's bn2 (and downsample BatchNorm) over d_xin * (xin > 0).  Not where f3's gradient is added to
-      // d_xin afterwards (block 5 with g_f3: its producer is a downsample block anyway).
+      // d_xin afterwards (the last block of layer 3 with g_f3: its producer is a downsample block anyway).
       Bst bs;
       if (bi > bi_lo) {
         const Block& pb = P->blocks[bi - 1];
@@ -941,10 +1002,10 @@ int ph_resnet_backward(const PhResnetPlan* P, const void* const* params, const v
   return backward_impl(P, params, packed, ws_, g_f3, g_f4, grads, -1, 0, st);
 }
 
-// part -1: everything; part 0: layers 4 and 3 (blocks 7..4); part 1: layers 2 and 1 (blocks 3..0) and the stem.  After
-// part 0 every gradient of layers 3-4 (93 % of the trunk's parameter bytes) is final: a data-parallel caller starts
-// their all-reduce there and overlaps it with part 1.  An even number of blocks per part keeps the ping-pong buffers
-// of the block gradient where the next part expects them.
+// part -1: everything; part 0: every block of layers 4 and 3; part 1: layers 2 and 1 and the stem.  After
+// part 0 every gradient of layers 3-4 (93 % of the trunk's parameter bytes, ResNet-18 and ResNet-34 alike) is final: a
+// data-parallel caller starts their all-reduce there and overlaps it with part 1.  Part 1 picks the block gradient up from
+// the ping-pong buffer part 0's block count left it in (backward_impl).
 int ph_resnet_backward_part(const PhResnetPlan* P, const void* const* params, const void* packed, void* ws_,
                             const float* g_f3, const float* g_f4, void* const* grads, int part, hipStream_t st) {
   return backward_impl(P, params, packed, ws_, g_f3, g_f4, grads, part, 0, st);
@@ -981,12 +1042,12 @@ int ph_resnet_backward_input(const PhResnetPlan* P, const void* const* params, c
   if (hipMemsetAsync(c1, 0, 1024 * sizeof(float), st) != hipSuccess) return PH_ELAUNCH;
   // (c1 = c2 = 0 above: bn_bwd_apply is then gamma * invstd * dz; the masks are the saved activations)
   {
-    const Block& b = P->blocks[7];
+    const Block& b = P->blocks[P->f4_block];
     if ((rc = ph_avgpool_bwd_launch(g_f4, gcur, P->B, b.OH * b.OW, b.Cout, 0, P->prec, st))) return rc;
   }
-  for (int bi = 7; bi >= 0; --bi) {
+  for (int bi = P->f4_block; bi >= 0; --bi) {
     const Block& b = P->blocks[bi];
-    if (bi == 5 && g_f3)
+    if (bi == P->f3_block && g_f3)
       if ((rc = ph_avgpool_bwd_launch(g_f3, gcur, P->B, b.OH * b.OW, b.Cout, 1, P->prec, st))) return rc;
     const void* out = ws + b.out_off;
     const void* a1 = ws + b.a1_off;

@@ -8,7 +8,7 @@ from torch.nn import Parameter
 
 from . import ops
 from .fusion import BilinearFusion, PolynomialFusion
-from .resnets import ResNet18
+from .resnets import ResNet18, ResNet34
 from .utils import init_net, init_max_weights
 
 
@@ -18,7 +18,7 @@ def define_net(opt, k, path_only=False, omic_only=False):
     act = define_act_layer(act_type=opt.act_type)
     init_max = True if opt.init_type == "max" else False
     if opt.mode == "path":
-        net = get_resnet(path_dim=opt.path_dim, act=act, label_dim=opt.label_dim)
+        net = get_resnet(path_dim=opt.path_dim, act=act, label_dim=opt.label_dim, path_arch=path_arch_of(opt))
     elif opt.mode == "omic":
         net = MaxNet(input_dim=opt.input_size_omic, omic_dim=opt.omic_dim, dropout_rate=opt.dropout_rate, act=act,
                      label_dim=opt.label_dim, init_max=init_max)
@@ -29,7 +29,7 @@ def define_net(opt, k, path_only=False, omic_only=False):
                                           "(networks_new.py:372-402): out of scope")
             net = PathomicNet(opt=opt, act=act, k=k)
         if path_only:
-            net = get_resnet(path_dim=opt.path_dim, act=act, label_dim=opt.label_dim)
+            net = get_resnet(path_dim=opt.path_dim, act=act, label_dim=opt.label_dim, path_arch=path_arch_of(opt))
         if omic_only:
             net = MaxNet(input_dim=opt.input_size_omic, omic_dim=opt.omic_dim, dropout_rate=opt.dropout_rate,
                          act=act, label_dim=opt.label_dim, init_max=init_max)
@@ -189,9 +189,20 @@ def _maxnet_forward_autograd(self, x):
 MaxNet._forward_autograd = _maxnet_forward_autograd
 
 
-def get_resnet(path_dim=32, act=None, label_dim=1, **kwargs):
-    """networks_new.py:258-259"""
-    return ResNet18(path_dim=path_dim, act=act, num_classes=label_dim, **kwargs)
+PATH_ARCHS = {"resnet18": ResNet18, "resnet34": ResNet34}
+
+
+def path_arch_of(opt):
+    """`opt.path_arch`: the path encoder's trunk, "resnet18" (the reference's only one, and the default where the option is
+    absent) or "resnet34"; get_resnet raises for anything else."""
+    return getattr(opt, "path_arch", "resnet18")
+
+
+def get_resnet(path_dim=32, act=None, label_dim=1, path_arch="resnet18", **kwargs):
+    """networks_new.py:258-259; `path_arch` (not in the reference) picks the BasicBlock depth"""
+    if path_arch not in PATH_ARCHS:
+        raise NotImplementedError("path_arch %r is not implemented (built: resnet18, resnet34)" % (path_arch,))
+    return PATH_ARCHS[path_arch](path_dim=path_dim, act=act, num_classes=label_dim, **kwargs)
 
 
 class PathomicNet(nn.Module):
@@ -201,7 +212,8 @@ class PathomicNet(nn.Module):
     def __init__(self, opt, act, k):
         super().__init__()
         init_max = True if opt.init_type == "max" else False
-        self.path_net = get_resnet(path_dim=opt.path_dim, act=act, label_dim=opt.label_dim, return_grad=opt.return_grad)
+        self.path_net = get_resnet(path_dim=opt.path_dim, act=act, label_dim=opt.label_dim, return_grad=opt.return_grad,
+                                   path_arch=path_arch_of(opt))
         self.omic_net = MaxNet(input_dim=opt.input_size_omic, omic_dim=opt.omic_dim, return_grad=opt.return_grad,
                                dropout_rate=opt.dropout_rate, act=act, label_dim=opt.label_dim, init_max=init_max)
         self.bilinear_dim = 20

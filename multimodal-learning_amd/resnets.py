@@ -1,4 +1,4 @@
-"""Drop-in for the reference's MICCAI-2022/resnets.py (ResNet / BasicBlock / ResNet18): same module tree,
+"""Drop-in for the reference's MICCAI-2022/resnets.py (ResNet / BasicBlock / ResNet18 / ResNet34): same module tree,
 same ``state_dict`` keys (OIHW fp32 at the boundary), same ``forward(**kwargs)`` 5-tuple
 (resnets.py:267-272) - but the trunk forward AND backward run as hand-written HIP kernels through
 ``ph_resnet_forward`` / ``ph_resnet_backward`` (include/pathomic_hip.h).
@@ -15,7 +15,7 @@ from torch.nn import Parameter
 from . import ops
 from ._lib import lib, check, ptr, stream, require_cuda
 
-__all__ = ["ResNet", "ResNet18", "BasicBlock"]
+__all__ = ["ResNet", "ResNet18", "ResNet34", "BasicBlock"]
 
 
 def conv3x3(in_planes, out_planes, stride=1):
@@ -47,13 +47,15 @@ class BasicBlock(nn.Module):
 class _Plan:
     """RAII wrapper of a PhResnetPlan."""
 
-    def __init__(self, B, H, W, prec):
-        self.h = lib().ph_resnet_plan_create(B, H, W, prec)
+    def __init__(self, B, H, W, prec, layers=(2, 2, 2, 2)):
+        layers = tuple(int(n) for n in layers)
+        self.h = lib().ph_resnet_plan_create_layers(B, H, W, prec, (C.c_int * 4)(*layers))
         if not self.h:
-            raise RuntimeError(f"ph_resnet_plan_create({B},{H},{W},{prec}) failed")
+            raise RuntimeError(f"ph_resnet_plan_create_layers({B},{H},{W},{prec},{list(layers)}) failed")
         self.ws_bytes = lib().ph_resnet_workspace_bytes(self.h)
         self.packed_bytes = lib().ph_resnet_packed_bytes(self.h)
-        self.key = (B, H, W, prec)
+        self.key = (B, H, W, prec)      # (the depths are the network's: every plan of one network has the same)
+        self.layers = layers
 
     def __del__(self):
         try:
@@ -61,6 +63,20 @@ class _Plan:
                 lib().ph_resnet_plan_destroy(self.h)
         except Exception:
             pass
+
+
+class _PlanCache(dict):
+    """A network's plans by (B, H, W, precision) + its four depths.  A lookup by the workspace key (B, H, W, precision) alone - what
+    `_ws_cache` and `_Plan.key` carry, and what tools index this cache with - finds the plan of this network's depths."""
+
+    def __init__(self, layers):
+        super().__init__()
+        self.layers = tuple(layers)
+
+    def __missing__(self, key):
+        if len(key) == 4 and key + self.layers in self:
+            return self[key + self.layers]
+        raise KeyError(key)
 
 
 class _TrunkFn(torch.autograd.Function):
@@ -200,6 +216,13 @@ class ResNet(nn.Module):
     def __init__(self, block, layers, path_dim=32, act=None, num_classes=7, return_grad="False",
                  zero_init_residual=False):
         super().__init__()
+        if block is not BasicBlock:
+            raise NotImplementedError("only BasicBlock trunks (ResNet-18, ResNet-34, any four depths) are on the hot path; "
+                                      "Bottleneck trunks (ResNet-50 and deeper) are not built, and the reference's own "
+                                      "ResNet34/50 factories are dead code (SURVEY.md section 2.1 row 3)")
+        layers = [int(n) for n in layers]
+        if len(layers) != 4 or min(layers) < 1 or max(layers) > MAX_BLOCKS:
+            raise ValueError("layers must be four block counts in 1 .. %d, got %r" % (MAX_BLOCKS, layers))
         self.inplanes = 64
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -227,10 +250,8 @@ class ResNet(nn.Module):
             for m in self.modules():
                 if isinstance(m, BasicBlock):
                     nn.init.constant_(m.bn2.weight, 0)
-        if list(layers) != [2, 2, 2, 2] or block is not BasicBlock:
-            raise NotImplementedError("only ResNet-18 (BasicBlock, [2,2,2,2]) is on the hot path; the reference's "
-                                      "ResNet34/50 factories are dead code (SURVEY.md section 2.1 row 3)")
-        self._plans = {}
+        self._layers = tuple(layers)
+        self._plans = _PlanCache(self._layers)
         self._packed = None
         self._packed_versions = None
         self._packed_key = None
@@ -279,9 +300,9 @@ class ResNet(nn.Module):
         return self._table
 
     def _get_plan(self, B, H, W, prec=None):
-        key = (B, H, W, ops.get_precision() if prec is None else prec)
+        key = (B, H, W, ops.get_precision() if prec is None else prec) + self._layers
         if key not in self._plans:
-            self._plans[key] = _Plan(*key)
+            self._plans[key] = _Plan(*key[:4], layers=self._layers)
         return self._plans[key]
 
     def _get_packed(self, plan):
@@ -405,6 +426,9 @@ class ResNet(nn.Module):
         return self._forward_impl(kwargs["x_path"])
 
 
+MAX_BLOCKS = 64      # PH_RESNET_MAX_BLOCKS of include/pathomic_hip.h
+
+
 def ResNet18(pretrained=True, progress=True, path_dim=32, act=None, num_classes=1, **kwargs):
     """resnets.py:287-295.  The reference loads ImageNet weights from a hard-coded relative path
     (resnets.py:278-282, strict=False); here `pretrained` loads the same file only if it exists."""
@@ -412,6 +436,19 @@ def ResNet18(pretrained=True, progress=True, path_dim=32, act=None, num_classes=
     if pretrained:
         import os
         path = "../pathomic_fusion_20211126/pretrained_resnet/resnet18-5c106cde.pth"
+        if os.path.exists(path):
+            model.load_state_dict(torch.load(path), strict=False)
+    return model
+
+
+def ResNet34(pretrained=True, progress=True, path_dim=32, act=None, num_classes=1, **kwargs):
+    """The deeper BasicBlock trunk, [3, 4, 6, 3], with ResNet18's signature (the reference's own factory, resnets.py:298-306,
+    hands `_resnet` too few arguments and cannot be called).  `pretrained` loads torchvision's ImageNet file from
+    beside ResNet18's if it exists (strict=False, as there)."""
+    model = ResNet(BasicBlock, [3, 4, 6, 3], path_dim, act, num_classes, **kwargs)
+    if pretrained:
+        import os
+        path = "../pathomic_fusion_20211126/pretrained_resnet/resnet34-333f7ec4.pth"
         if os.path.exists(path):
             model.load_state_dict(torch.load(path), strict=False)
     return model

@@ -394,6 +394,8 @@ def _validate_opt(opt, who, surv_ok=False):
         raise NotImplementedError("%s: return_grad needs the reference's absent my_utils.compute_gradients" % who)
     if getattr(opt, "use_vgg_features", 0):
         raise NotImplementedError("%s: use_vgg_features (pre-extracted features bypass the ResNet trunk)" % who)
+    if getattr(opt, "path_arch", "resnet18") not in ("resnet18", "resnet34"):
+        raise NotImplementedError("%s: path_arch %r (the BasicBlock trunks resnet18 and resnet34 are built)" % (who, opt.path_arch))
 
 
 # ----------------------------------------------------------------------------------------- the hot loop
