@@ -574,6 +574,21 @@ size_t ph_slic_workspace_bytes(int n, int H, int W, int K);
 int ph_slic_lab(const uint8_t* rgb, uint32_t* lab, size_t npix, void* workspace, ph_stream_t stream);
 int ph_slic(const uint8_t* tiles, int16_t* labels, int n, int H, int W, int K, int compactness, int iters, void* workspace,
             ph_stream_t stream);
+/* Connectivity pass over int16 label maps [n][H][W] with labels in [0, N) (a rule of this project's
+ * own, integers only, independent of the order of evaluation, equal to tests/slic_connect_emulation.py on every pixel).
+ * A component is a maximal 4-connected set of pixels of one label; its first pixel is its lowest raster index y W + x.
+ * The principal component of a label is its largest (tie: the lowest first pixel) and is never relabelled.  A component
+ * that is not principal, has fewer than min_size pixels and does not start at pixel (0, 0) takes the final label of the
+ * component that holds the pixel above its first pixel (in row 0: the pixel to its left); every other component keeps
+ * its label.  The rule is applied once; min_size = 1 is the identity.  A pixel whose label lies outside [0, N) indexes
+ * no table: its component keeps its label.
+ * Bounds: 1 <= n <= 65535, 1 <= H, W <= 8192, 1 <= N <= 2048, min_size >= 1, non-NULL pointers; anything else is
+ * PH_EINVAL (the workspace size: 0) before any launch.  labels_in == labels_out is allowed.  Seven kernels on `stream`,
+ * a fixed sequence without a host read (capturable).  Workspace: two 32-bit words per pixel and one 64-bit word per
+ * label and tile, as ph_slic_connect_workspace_bytes says (host only). */
+size_t ph_slic_connect_workspace_bytes(int n, int H, int W, int N);
+int ph_slic_connect(const int16_t* labels_in, int16_t* labels_out, int n, int H, int W, int N, int min_size, void* workspace,
+                    ph_stream_t stream);
 
 /* On-device contrast-index sampler (reference MICCAI-2022/data_loaders_MT.py:229-249 and the neg_mode
  * variants of "MIA 2023/stage2_unimodal_student/data_loaders_MT.py":205-238).  out[b] = [positives | K negatives]:

@@ -93,6 +93,8 @@ SIGNATURES = {
     "ph_slic_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ph_slic_lab": (i32, [vp, vp, sz, vp, vp]),
     "ph_slic": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "ph_slic_connect_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "ph_slic_connect": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "ph_apply_mask": (i32, [vp, vp, vp, i32, i32, sz, vp]),
     "ph_topk_threshold_mask": (i32, [vp, vp, i32, i32, i32, vp]),
     "ph_maxnorm_mix": (i32, [vp, vp, vp, sz, f32, f32, vp]),

@@ -189,15 +189,18 @@ class ResidentSuperpixelLoader(ResidentTileLoader):
     """The batch tuple of the MIA-2023 stage-1 masking trainer (data_loaders_MT_SP.py:453) produced on the device:
     ((x_path, sp_mask, ema_x_path, ema_sp_mask, x_path_m_v1, x_path_m_v2), 0, x_omic, 0, 0, grade, index, sample_idx).
     At construction the tile store is segmented once (`superpixel.slic_segment`, opt.num_superpixels components,
-    compactness 10, as :303-304) and the int16 maps stay next to the tiles; a batch is four augmented views with the
+    compactness 10, as :303-304; `enforce_connectivity` / `min_size_factor`: its connectivity pass, off by default)
+    and the int16 maps stay next to the tiles; a batch is four augmented views with the
     label maps of views 0 and 1 (`DeviceAugmentSP`).  `num_labels` is the number of labels N of a map; where the options
     carry no `num_superpixels_max` it is set to N, so that the step's superpixel_attention_mask call reads nothing back."""
 
-    def __init__(self, opt, tiles_u8, x_omic, grade, device="cuda", seed=0, compactness=10, iters=10, chunk=None):
+    def __init__(self, opt, tiles_u8, x_omic, grade, device="cuda", seed=0, compactness=10, iters=10, chunk=None,
+                 enforce_connectivity=False, min_size_factor=0.25):
         from .superpixel import slic_segment
         super().__init__(opt, tiles_u8, x_omic, grade, device, seed)
         self.aug = DeviceAugmentSP(opt, self.device, seed)
-        self.sp_maps, self.num_labels = slic_segment(self.tiles, int(opt.num_superpixels), compactness, iters, chunk=chunk)
+        self.sp_maps, self.num_labels = slic_segment(self.tiles, int(opt.num_superpixels), compactness, iters, chunk=chunk,
+                                                     enforce_connectivity=enforce_connectivity, min_size_factor=min_size_factor)
         if getattr(opt, "num_superpixels_max", None) is None:
             opt.num_superpixels_max = self.num_labels
 

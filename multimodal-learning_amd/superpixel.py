@@ -22,12 +22,47 @@ def slic_num_labels(H, W, num_components):
     return N
 
 
-def slic_segment(tiles_u8, num_components, compactness=10, iters=10, out=None, chunk=None):
+def slic_connect(labels_i16, num_labels, min_size, out=None, chunk=None):
+    """The connectivity pass of `slic_segment` on its own (csrc/slic.hip): labels_i16 int16
+    [n, H, W] (device) with labels in [0, num_labels) -> int16 [n, H, W] in which every 4-connected component that is not
+    the largest of its label, has fewer than `min_size` pixels and does not start at pixel (0, 0) carries the final label
+    of the component above (in row 0: left of) its first pixel.  `out` may be `labels_i16` itself.  The store is walked
+    in chunks of `chunk` tiles (default: a workspace of about 256 MB); tiles are independent."""
+    t = require_cuda(labels_i16, "labels_i16")
+    if t.dtype != torch.int16 or t.dim() != 3 or t.shape[0] < 1 or not t.is_contiguous():
+        raise RuntimeError("labels_i16 must be a contiguous int16 [n, H, W] tensor")
+    n, H, W = t.shape
+    if not (1 <= H <= 8192 and 1 <= W <= 8192) or not (1 <= int(num_labels) <= 2048) or int(min_size) < 1:
+        raise ValueError("needs tiles of 1..8192 pixels a side, 1 <= num_labels <= 2048 and min_size >= 1")
+    if out is None:
+        out = torch.empty_like(t)
+    elif tuple(out.shape) != (n, H, W) or out.dtype != torch.int16 or not out.is_contiguous() or out.device != t.device:
+        raise RuntimeError("out must be a contiguous int16 [n, H, W] tensor on the labels' device")
+    if chunk is None:
+        chunk = max(1, (256 << 20) // (8 * H * W))
+    chunk = max(1, min(int(chunk), n, 65535))
+    ws = torch.empty(lib().ph_slic_connect_workspace_bytes(chunk, H, W, int(num_labels)), device=t.device, dtype=torch.uint8)
+    for lo in range(0, n, chunk):
+        m = min(chunk, n - lo)
+        check(lib().ph_slic_connect(ptr(t[lo:]), ptr(out[lo:]), m, H, W, int(num_labels), int(min_size), ptr(ws), stream()),
+              "ph_slic_connect")
+    return out
+
+
+def slic_min_size(H, W, num_labels, min_size_factor=0.25):
+    """min_size of the connectivity pass: floor(min_size_factor * ((H W) // N)), at least 1."""
+    return max(1, int(float(min_size_factor) * ((int(H) * int(W)) // int(num_labels))))
+
+
+def slic_segment(tiles_u8, num_components, compactness=10, iters=10, out=None, chunk=None, enforce_connectivity=False,
+                 min_size_factor=0.25):
     """SLIC superpixels on the device (csrc/slic.hip): tiles_u8 [n, H, W, 3] uint8 (device) ->
     (labels int16 [n, H, W] in [0, N), N).  The role of `fast_slic.Slic(num_components, compactness).iterate` in the
     reference's loader (data_loaders_MT_SP.py:303-304) - the same interface, an all-integer definition of its own, not
     bit parity.  The store is walked in chunks of `chunk` tiles (default: a workspace of about 256 MB); tiles are
-    segmented independently, so the result does not depend on the chunking.  `out`: int16 [n, H, W] to fill."""
+    segmented independently, so the result does not depend on the chunking.  `out`: int16 [n, H, W] to fill.
+    `enforce_connectivity`: run `slic_connect` over the maps in place with min_size = floor(min_size_factor * ((H W) // N)),
+    at least 1 (0.25: fast_slic's default factor); off by default, and then the maps are those of the segmentation alone."""
     t = require_cuda(tiles_u8, "tiles_u8")
     if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
         raise RuntimeError("tiles_u8 must be uint8 [n, H, W, 3]")
@@ -36,6 +71,8 @@ def slic_segment(tiles_u8, num_components, compactness=10, iters=10, out=None, c
     N = slic_num_labels(H, W, num_components)
     if not (0 <= int(compactness) <= 1024) or int(iters) < 1:
         raise ValueError("compactness must lie in 0..1024 and iters be at least 1")
+    if enforce_connectivity and not float(min_size_factor) >= 0.0:
+        raise ValueError("min_size_factor must not be negative")
     if out is None:
         out = torch.empty(n, H, W, device=t.device, dtype=torch.int16)
     elif tuple(out.shape) != (n, H, W) or out.dtype != torch.int16 or not out.is_contiguous() or out.device != t.device:
@@ -48,6 +85,8 @@ def slic_segment(tiles_u8, num_components, compactness=10, iters=10, out=None, c
         m = min(chunk, n - lo)
         check(lib().ph_slic(ptr(t[lo:]), ptr(out[lo:]), m, H, W, int(num_components), int(compactness), int(iters), ptr(ws),
                             stream()), "ph_slic")
+    if enforce_connectivity:
+        slic_connect(out, N, slic_min_size(H, W, N, min_size_factor), out=out, chunk=chunk)
     return out, N
 
 
