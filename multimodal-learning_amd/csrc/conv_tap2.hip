@@ -110,26 +110,16 @@ __global__ __launch_bounds__(256) void tapconv2_kernel(PhTapConv p) {
   PH_TRACE(0);
 
   // ---- tile list of this (persistent) workgroup.  Linear tile id -> (spatial tile fastest, Cout block, image).
-  // The workgroups of one XCD (blockIdx.x % 8: hardware round-robin) walk one contiguous eighth of the list, so
-  // neighbouring halos and the weight block of a Cout block are shared inside one L2.
+  // The walk (XCD-contiguous) and the division are tap_common.h's (PH_TILE_LIST, ph_fdiv).
   struct TileCtx { int tile, r0, c0, n0, b, iy_base, ix_base; const T* in; };
-  // q = a / d for 0 <= a < 2^22 with a precomputed float reciprocal and one correction step (the decode below runs
-  // once per tile on the critical path; hardware integer division costs ~40 instructions per quotient)
   const float rcp_sp = 1.0f / (float)tiles_sp, rcp_nb = 1.0f / (float)nblk, rcp_tw = 1.0f / (float)tiles_w;
-  auto fdiv = [](int a, int d, float rcp) {
-    int q = (int)((float)a * rcp);
-    int r = a - q * d;
-    if (r >= d) ++q;
-    if (r < 0) --q;
-    return q;
-  };
   auto decode = [&](int t) -> TileCtx {
     TileCtx c;
-    const int rest = fdiv(t, tiles_sp, rcp_sp);
+    const int rest = ph_fdiv(t, tiles_sp, rcp_sp);
     c.tile = t - rest * tiles_sp;
-    c.b = fdiv(rest, nblk, rcp_nb);
+    c.b = ph_fdiv(rest, nblk, rcp_nb);
     c.n0 = (rest - c.b * nblk) * BNT;
-    const int trow = fdiv(c.tile, tiles_w, rcp_tw);
+    const int trow = ph_fdiv(c.tile, tiles_w, rcp_tw);
     c.r0 = trow * TH;
     c.c0 = (c.tile - trow * tiles_w) * TW;
     c.iy_base = c.r0 + p.iy0;
@@ -137,18 +127,7 @@ __global__ __launch_bounds__(256) void tapconv2_kernel(PhTapConv p) {
     c.in = reinterpret_cast<const T*>(p.in) + (size_t)c.b * img_st;
     return c;
   };
-  const int G = gridDim.x;
-  const bool xcd_map = (G & 7) == 0 && G < total;
-  const int per_xcd = (total + 7) >> 3;
-  auto tile_id = [&](int k) -> int {   // k-th tile of this workgroup, -1 when the list is exhausted
-    if (!xcd_map) {
-      const int t = (int)blockIdx.x + k * G;
-      return t < total ? t : -1;
-    }
-    const int local = ((int)blockIdx.x >> 3) + k * (G >> 3);
-    const int t = ((int)blockIdx.x & 7) * per_xcd + local;
-    return (local < per_xcd && t < total) ? t : -1;
-  };
+  PH_TILE_LIST(tile_id, total);
 
   const int nsl_c = p.Cin >> 6;      // 64-channel slices of the real channel count
   const int nsl_sh = nsl_c == 1 ? 0 : (nsl_c == 2 ? 1 : (nsl_c == 4 ? 2 : 3));
@@ -716,18 +695,11 @@ __global__ __launch_bounds__(512) void tapconv2_l1_kernel(PhTapConv p) {
 
   struct TileCtx { int r0, c0, b, iy_base, ix_base; const T* in; };
   const float rcp_sp = 1.0f / (float)tiles_sp, rcp_tw = 1.0f / (float)tiles_w;
-  auto fdiv = [](int a, int d, float rcp) {
-    int q = (int)((float)a * rcp);
-    int r = a - q * d;
-    if (r >= d) ++q;
-    if (r < 0) --q;
-    return q;
-  };
   auto decode = [&](int t) -> TileCtx {
     TileCtx c;
-    c.b = fdiv(t, tiles_sp, rcp_sp);
+    c.b = ph_fdiv(t, tiles_sp, rcp_sp);
     const int tile = t - c.b * tiles_sp;
-    const int trow = fdiv(tile, tiles_w, rcp_tw);
+    const int trow = ph_fdiv(tile, tiles_w, rcp_tw);
     c.r0 = trow * TH;
     c.c0 = (tile - trow * tiles_w) * TW;
     c.iy_base = c.r0 + p.iy0;
@@ -736,18 +708,7 @@ __global__ __launch_bounds__(512) void tapconv2_l1_kernel(PhTapConv p) {
     return c;
   };
   // the workgroup's tile list (same XCD-contiguous order as above); group g takes entries g, g + 2, g + 4, ...
-  const int G = gridDim.x;
-  const bool xcd_map = (G & 7) == 0 && G < total;
-  const int per_xcd = (total + 7) >> 3;
-  auto tile_id = [&](int k) -> int {
-    if (!xcd_map) {
-      const int t = (int)blockIdx.x + k * G;
-      return t < total ? t : -1;
-    }
-    const int local = ((int)blockIdx.x >> 3) + k * (G >> 3);
-    const int t = ((int)blockIdx.x & 7) * per_xcd + local;
-    return (local < per_xcd && t < total) ? t : -1;
-  };
+  PH_TILE_LIST(tile_id, total);
   int K = 0;
   while (tile_id(K) >= 0) ++K;
   const int n_mine = (K - grp + 1) >> 1;       // tiles of this group

@@ -99,20 +99,13 @@ __global__ __launch_bounds__(256) void tapconv3_kernel(PhTapConv p) {
   // ---- tile list (as tapconv2_kernel): linear tile id -> (spatial tile fastest, Cout block, image), XCD-contiguous
   struct TileCtx { int r0, c0, n0, b, iy_base, ix_base; const T* in; };
   const float rcp_sp = 1.0f / (float)tiles_sp, rcp_nb = 1.0f / (float)nblk, rcp_tw = 1.0f / (float)tiles_w;
-  auto fdiv = [](int a, int d, float rcp) {
-    int q = (int)((float)a * rcp);
-    int r = a - q * d;
-    if (r >= d) ++q;
-    if (r < 0) --q;
-    return q;
-  };
   auto decode = [&](int t) -> TileCtx {
     TileCtx c;
-    const int rest = fdiv(t, tiles_sp, rcp_sp);
+    const int rest = ph_fdiv(t, tiles_sp, rcp_sp);
     const int tile = t - rest * tiles_sp;
-    c.b = fdiv(rest, nblk, rcp_nb);
+    c.b = ph_fdiv(rest, nblk, rcp_nb);
     c.n0 = (rest - c.b * nblk) * BNT;
-    const int trow = fdiv(tile, tiles_w, rcp_tw);
+    const int trow = ph_fdiv(tile, tiles_w, rcp_tw);
     c.r0 = trow * TH;
     c.c0 = (tile - trow * tiles_w) * TW;
     // (wave-uniform values computed through float arithmetic: pin them to scalar registers - as vector registers they were
@@ -126,18 +119,7 @@ __global__ __launch_bounds__(256) void tapconv3_kernel(PhTapConv p) {
     c.in = reinterpret_cast<const T*>(p.in) + (size_t)c.b * img_st;
     return c;
   };
-  const int G = gridDim.x;
-  const bool xcd_map = (G & 7) == 0 && G < total;
-  const int per_xcd = (total + 7) >> 3;
-  auto tile_id = [&](int k) -> int {
-    if (!xcd_map) {
-      const int t = (int)blockIdx.x + k * G;
-      return t < total ? t : -1;
-    }
-    const int local = ((int)blockIdx.x >> 3) + k * (G >> 3);
-    const int t = ((int)blockIdx.x & 7) * per_xcd + local;
-    return (local < per_xcd && t < total) ? t : -1;
-  };
+  PH_TILE_LIST(tile_id, total);
   const int nslices = (p.Cin >> 6) * ((HPM && !p.hp_hi_only) ? 3 : 1);      // even (the launcher checks): the A buffer index is compile-time inside a slice pair
 
   // weight slab of tap t = wtap[0] + t * (wtap[1] - wtap[0]) (the launcher checks: forward 0, 1, .., 8; dgrad 8, 7, .., 0)

@@ -133,18 +133,7 @@ __global__ __launch_bounds__(256) void tapconv4_kernel(PhTapConv p) {
     c.in = reinterpret_cast<const T*>(p.in) + (size_t)c.b * img_st;
     return c;
   };
-  const int G = gridDim.x;
-  const bool xcd_map = (G & 7) == 0 && G < total;
-  const int per_xcd = (total + 7) >> 3;
-  auto tile_id = [&](int k) -> int {
-    if (!xcd_map) {
-      const int t = (int)blockIdx.x + k * G;
-      return t < total ? t : -1;
-    }
-    const int local = ((int)blockIdx.x >> 3) + k * (G >> 3);
-    const int t = ((int)blockIdx.x & 7) * per_xcd + local;
-    return (local < per_xcd && t < total) ? t : -1;
-  };
+  PH_TILE_LIST(tile_id, total);
 
   // ---- per-lane DMA sources.  Halo piece h = wave + 4 e covers row pairs 4 h .. 4 h + 3 of the image; lane l fills slot l & 15 of
   // row pair rp = 4 h + (l >> 4): halo row rp / 9, column 2 (rp % 9) + (slot >> 3), chunk (slot & 7) ^ T(column)

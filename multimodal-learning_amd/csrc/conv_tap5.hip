@@ -87,18 +87,11 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
   // ---- tile list: linear tile id -> (spatial tile fastest, image), XCD-contiguous (as conv_tap3.hip)
   struct TileCtx { int r0, c0, b, iy_base, ix_base; const unsigned char* in; };
   const float rcp_sp = 1.0f / (float)tiles_sp, rcp_tw = 1.0f / (float)tiles_w;
-  auto fdiv = [](int a, int d, float rcp) {
-    int q = (int)((float)a * rcp);
-    int r = a - q * d;
-    if (r >= d) ++q;
-    if (r < 0) --q;
-    return q;
-  };
   auto decode = [&](int t) __attribute__((always_inline)) -> TileCtx {
     TileCtx c;
-    c.b = fdiv(t, tiles_sp, rcp_sp);
+    c.b = ph_fdiv(t, tiles_sp, rcp_sp);
     const int tile = t - c.b * tiles_sp;
-    const int trow = fdiv(tile, tiles_w, rcp_tw);
+    const int trow = ph_fdiv(tile, tiles_w, rcp_tw);
     c.r0 = trow * TH;
     c.c0 = (tile - trow * tiles_w) * TW;
     c.b = __builtin_amdgcn_readfirstlane(c.b);
@@ -110,18 +103,7 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
     c.in = reinterpret_cast<const unsigned char*>(p.in) + ((long)c.b * img_st + (long)c.iy_base * row_st + (long)c.ix_base * pix_st) * 2;
     return c;
   };
-  const int G = gridDim.x;
-  const bool xcd_map = (G & 7) == 0 && G < total;
-  const int per_xcd = (total + 7) >> 3;
-  auto tile_id = [&](int k) -> int {
-    if (!xcd_map) {
-      const int t = (int)blockIdx.x + k * G;
-      return t < total ? t : -1;
-    }
-    const int local = ((int)blockIdx.x >> 3) + k * (G >> 3);
-    const int t = ((int)blockIdx.x & 7) * per_xcd + local;
-    return (local < per_xcd && t < total) ? t : -1;
-  };
+  PH_TILE_LIST(tile_id, total);
 
   // ---- weights: tap slab t = wtap[0] + t * (wtap[1] - wtap[0]) (forward 0..8, dgrad 8..0).  The 64 -> 64 slabs are packed
   // FRAGMENT-MAJOR for this kernel (conv_wgrad.hip: pack_all_tiled_hp_kernel, ph5_frag_index below): per tap

@@ -8,7 +8,7 @@
 // This kernel is the same GEMM (same tile, same wave grid, same fragment mapping, same summation order: its outputs are bitwise
 // conv_tap3.hip's) on conv_tap6.hip's machinery:
 //   * weight fragments from global memory straight into registers, FOUR taps ahead, in a window of nine k-step sets (six in
-//     accumulation registers, three in vector registers), from a fragment-major copy of the packed weights ([tap][Cout / 64][Cin / 64]
+//     accumulation registers, three in vector registers: tap_window.h), from a fragment-major copy of the packed weights ([tap][Cout / 64][Cin / 64]
 //     x 8 KiB, every load instruction one contiguous KiB: plane 1 of the unit's packed region, which perf mode does not otherwise use);
 //   * the halo image of the NEXT 64-channel slice by LDS-DMA in the first four taps of the current one; a piece may stay in flight for
 //     4.5 taps, the hand-over barrier in the slice's last tap is the only workgroup barrier: one per 9 taps instead of nine;
@@ -18,10 +18,12 @@
 #include "ph_common.h"
 #include <type_traits>
 #include "ph_kernels.h"
-#include "tap_common.h"
 #ifndef PH7_DBG
 #define PH7_DBG 0      // ablation builds (timing only): 2 = no image pieces inside the slices, 4 = no weight loads inside the slices, 8 = no stores
 #endif
+#define PHW_DBG PH7_DBG
+#define PHW_MFMA v_mfma_f32_16x16x32_bf16
+#include "tap_window.h"
 
 namespace {
 
@@ -74,20 +76,13 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
   // ---- tile list (conv_tap3.hip's): linear tile id -> (spatial tile fastest, Cout block, image), XCD-contiguous
   struct TileCtx { int r0, c0, b, nb; const unsigned char* in; };      // in: pixel (r0 - 1, c0 - 1), slice 0
   const float rcp_sp = 1.0f / (float)tiles_sp, rcp_nb = 1.0f / (float)nblk, rcp_tw = 1.0f / (float)tiles_w;
-  auto fdiv = [](int a, int d, float rcp) {
-    int q = (int)((float)a * rcp);
-    int r = a - q * d;
-    if (r >= d) ++q;
-    if (r < 0) --q;
-    return q;
-  };
   auto decode = [&](int t) __attribute__((always_inline)) -> TileCtx {
     TileCtx c;
-    const int rest = fdiv(t, tiles_sp, rcp_sp);
+    const int rest = ph_fdiv(t, tiles_sp, rcp_sp);
     const int tile = t - rest * tiles_sp;
-    c.b = fdiv(rest, nblk, rcp_nb);
+    c.b = ph_fdiv(rest, nblk, rcp_nb);
     c.nb = rest - c.b * nblk;
-    const int trow = fdiv(tile, tiles_w, rcp_tw);
+    const int trow = ph_fdiv(tile, tiles_w, rcp_tw);
     c.r0 = trow * TH;
     c.c0 = (tile - trow * tiles_w) * TW;
     c.b = __builtin_amdgcn_readfirstlane(c.b);
@@ -97,18 +92,7 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
     c.in = reinterpret_cast<const unsigned char*>(p.in) + (long)c.b * imgB + (long)(c.r0 - 1) * rowB + (long)(c.c0 - 1) * pixB;
     return c;
   };
-  const int GR = gridDim.x;
-  const bool xcd_map = (GR & 7) == 0 && GR < total;
-  const int per_xcd = (total + 7) >> 3;
-  auto tile_id = [&](int k) -> int {
-    if (!xcd_map) {
-      const int t = (int)blockIdx.x + k * GR;
-      return t < total ? t : -1;
-    }
-    const int local = ((int)blockIdx.x >> 3) + k * (GR >> 3);
-    const int t = ((int)blockIdx.x & 7) * per_xcd + local;
-    return (local < per_xcd && t < total) ? t : -1;
-  };
+  PH_TILE_LIST(tile_id, total);
 
   // ---- weights: the fragment-major copy (plane 1 of the unit's packed region): [slab wtap[t]][Cout / 64][Cin / 64] x 8 KiB; a wave
   // reads row block 2 nb + wn.  Base + 4 KiB: the 8 fragments of a (tap, slice) are the immediates -4096 .. 3072.
@@ -339,50 +323,7 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
   if (nvalid) tnext = decode(tn);
   unsigned mask_cur = 0, mask_next = 0;
 
-  // Fragment registers: A ring of 4; B nine k-step sets (4 N tiles each): k-step j of the stream (18 per slice) multiplies set
-  // j % 9 while the fragments of k-step j + 8 are loaded into set (j + 8) % 9 (conv_tap6.hip).  Sets 0..5 in accumulation registers,
-  // 6..8 in vector registers.
-  u32x4 fa[4], fba[6][NN], fbv[3][NN];
-#define PH7_MM(M, N, AI, Q, FIRST)                                                                                                                  \
-  do {                                                                                                                                              \
-    if ((Q) < 6) {                                                                                                                                  \
-      if (FIRST) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(acc[M][N]) : "v"(fa[AI]), "a"(fba[(Q) < 6 ? (Q) : 0][N]));          \
-      else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[M][N]) : "v"(fa[AI]), "a"(fba[(Q) < 6 ? (Q) : 0][N]));                \
-    } else {                                                                                                                                        \
-      if (FIRST) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(acc[M][N]) : "v"(fa[AI]), "v"(fbv[(Q) >= 6 ? (Q) - 6 : 0][N]));     \
-      else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[M][N]) : "v"(fa[AI]), "v"(fbv[(Q) >= 6 ? (Q) - 6 : 0][N]));           \
-    }                                                                                                                                               \
-  } while (0)
-#define PH7_LD(ADDR, IMM) (*reinterpret_cast<const u32x4*>(smem + (ADDR) + (IMM)))
-#define PH7_LDA(AB, AOFF, MT) PH7_LD(AB, (AOFF) + (MT) * C::ROW_BYTES)
-  // (per-lane 64-bit address, no scalar operand: a scalar base restored by v_readlane right in front of inline assembly needs wait
-  // states the hazard recognizer does not insert - conv_tap5.hip copies it with s_mov_b64 in front of every load; here ONE vector add
-  // per tap makes the address and the eight loads carry nothing but an immediate)
-#define PH7_BLD(Q, N, WB, OFF)                                                                                             \
-  do {                                                                                                                     \
-    if ((Q) < 6) asm volatile("global_load_dwordx4 %0, %1, off offset:" #OFF : "=a"(fba[(Q) < 6 ? (Q) : 0][N]) : "v"(WB) : "memory");     \
-    else asm volatile("global_load_dwordx4 %0, %1, off offset:" #OFF : "=v"(fbv[(Q) >= 6 ? (Q) - 6 : 0][N]) : "v"(WB) : "memory");       \
-  } while (0)
-#define PH7_BLD_KN(Q, KS, N, WB)                                     \
-  do {                                                               \
-    if (PH7_DBG & 4) break;                                          \
-    if ((KS) == 0) {                                                 \
-      if ((N) == 0) PH7_BLD(Q, 0, WB, -4096);                        \
-      else if ((N) == 1) PH7_BLD(Q, 1, WB, -3072);                   \
-      else if ((N) == 2) PH7_BLD(Q, 2, WB, -2048);                   \
-      else PH7_BLD(Q, 3, WB, -1024);                                 \
-    } else {                                                         \
-      if ((N) == 0) PH7_BLD(Q, 0, WB, 0);                            \
-      else if ((N) == 1) PH7_BLD(Q, 1, WB, 1024);                    \
-      else if ((N) == 2) PH7_BLD(Q, 2, WB, 2048);                    \
-      else PH7_BLD(Q, 3, WB, 3072);                                  \
-    }                                                                \
-  } while (0)
-#define PH7_GROUP(M, Q, KS, RA, X1, X2)                            \
-  PH7_MM(M, 0, (M) & 3, Q, first && (KS) == 0); RA; PH_SB();       \
-  PH7_MM(M, 1, (M) & 3, Q, first && (KS) == 0); X1; PH_SB();       \
-  PH7_MM(M, 2, (M) & 3, Q, first && (KS) == 0); PH_SB();           \
-  PH7_MM(M, 3, (M) & 3, Q, first && (KS) == 0); X2; PH_SB()
+  PHW_FRAGMENTS;      // A ring of 4, B nine k-step sets (tap_window.h)
 
   {  // prologue: the image of slice 0, the weights of taps 0..3 (k-steps 0..7)
 #pragma unroll
@@ -390,20 +331,13 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
 #pragma unroll
     for (int e = 0; e < C::NHE; ++e) dma_piece(e, tcur.in, 0, mask_cur, 0);
     const unsigned char *wb0 = w_base(tcur.nb, 0, 0), *wb1 = w_base(tcur.nb, 0, 1), *wb2 = w_base(tcur.nb, 0, 2), *wb3 = w_base(tcur.nb, 0, 3);
-    PH7_BLD(0, 0, wb0, -4096); PH7_BLD(0, 1, wb0, -3072); PH7_BLD(0, 2, wb0, -2048); PH7_BLD(0, 3, wb0, -1024);
-    PH7_BLD(1, 0, wb0, 0); PH7_BLD(1, 1, wb0, 1024); PH7_BLD(1, 2, wb0, 2048); PH7_BLD(1, 3, wb0, 3072);
-    PH7_BLD(2, 0, wb1, -4096); PH7_BLD(2, 1, wb1, -3072); PH7_BLD(2, 2, wb1, -2048); PH7_BLD(2, 3, wb1, -1024);
-    PH7_BLD(3, 0, wb1, 0); PH7_BLD(3, 1, wb1, 1024); PH7_BLD(3, 2, wb1, 2048); PH7_BLD(3, 3, wb1, 3072);
-    PH7_BLD(4, 0, wb2, -4096); PH7_BLD(4, 1, wb2, -3072); PH7_BLD(4, 2, wb2, -2048); PH7_BLD(4, 3, wb2, -1024);
-    PH7_BLD(5, 0, wb2, 0); PH7_BLD(5, 1, wb2, 1024); PH7_BLD(5, 2, wb2, 2048); PH7_BLD(5, 3, wb2, 3072);
-    PH7_BLD(6, 0, wb3, -4096); PH7_BLD(6, 1, wb3, -3072); PH7_BLD(6, 2, wb3, -2048); PH7_BLD(6, 3, wb3, -1024);
-    PH7_BLD(7, 0, wb3, 0); PH7_BLD(7, 1, wb3, 1024); PH7_BLD(7, 2, wb3, 2048); PH7_BLD(7, 3, wb3, 3072);
+    PHW_PROLOGUE_LOADS(wb0, wb1, wb2, wb3);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  fa[0] = PH7_LDA(ab0[0][0], 0, 0);
-  fa[1] = PH7_LDA(ab0[0][0], 0, 1);
-  fa[2] = PH7_LDA(ab0[0][0], 0, 2);
+  fa[0] = PHW_LDA(ab0[0][0], 0, 0);
+  fa[1] = PHW_LDA(ab0[0][0], 0, 1);
+  fa[2] = PHW_LDA(ab0[0][0], 0, 2);
 
   // One slice = 9 taps x 2 k-steps x 8 MFMA groups.  ABUF (literal): the buffer of its image; FIRSTS (literal): it opens a tile
   // (first k-step writes the accumulators, first k-steps skip the waits: the one in front of the epilogue covered their fragments).
@@ -418,26 +352,15 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
       const int tnx = (t + 1) % NTAPS, dyn = tnx / 3, dxn = tnx % 3;
       const int aoff = dy * C::ROW_BYTES, aoffn = dyn * C::ROW_BYTES;
       const int BUFN = (t + 1 == NTAPS) ? (ABUF ^ 1) : ABUF;
-      const int q0 = (2 * t) % 9, q1 = (2 * t + 1) % 9, ql0 = (2 * t + 8) % 9, ql1 = (2 * t + 9) % 9;
       const bool first = FIRSTS && t == 0;
       const unsigned char* wb = (t + 4 < NTAPS) ? w_base(tcur.nb, c, t + 4) : w_base(nnb, nc, t + 4 - NTAPS);
       const int nd = C::ND[t], e0 = C::E0[t];
 #define PH7_DMA(I) do { if ((I) < nd && !(PH7_DBG & 2)) dma_piece(e0 + (I), nin, nc, (last && nvalid) ? mask_next : mask_cur, ABUF ^ 1); } while (0)
-      PH7_GROUP(0, q0, 0, fa[3] = PH7_LDA(ab0[ABUF][dx], aoff, 3), PH7_BLD_KN(ql0, 0, 0, wb), PH_NOP);
-      PH7_GROUP(1, q0, 0, fa[0] = PH7_LDA(ab0[ABUF][dx], aoff, 4), PH7_BLD_KN(ql0, 0, 1, wb), PH_NOP);
-      PH7_GROUP(2, q0, 0, fa[1] = PH7_LDA(ab0[ABUF][dx], aoff, 5), PH7_BLD_KN(ql0, 0, 2, wb), PH_NOP);
-      PH7_GROUP(3, q0, 0, fa[2] = PH7_LDA(ab0[ABUF][dx], aoff, 6), PH7_BLD_KN(ql0, 0, 3, wb), PH_NOP);
-      PH7_GROUP(4, q0, 0, fa[3] = PH7_LDA(ab0[ABUF][dx], aoff, 7), PH_NOP, PH_NOP);
-      PH7_GROUP(5, q0, 0, fa[0] = PH7_LDA(ab1[ABUF][dx], aoff, 0), PH_NOP, PH_NOP);
-      PH7_GROUP(6, q0, 0, fa[1] = PH7_LDA(ab1[ABUF][dx], aoff, 1), PH_NOP, PH_NOP);
-      PH7_GROUP(7, q0, 0, fa[2] = PH7_LDA(ab1[ABUF][dx], aoff, 2), PH_NOP, PH_NOP);
+      // k-step 0, and in its first groups the weight loads of tap t + 4 (tap_window.h)
+      PHW_TAP_K0(t, ABUF, dx, aoff, wb);
       // (a tile's k-steps 0..2 skip the wait: the one in front of the epilogue covered the fragments of its k-steps 0..3)
       if (!(FIRSTS && t <= 1)) ph_wait_vmcnt(C::WAIT0[t]);
-      PH7_GROUP(0, q1, 1, fa[3] = PH7_LDA(ab1[ABUF][dx], aoff, 3), PH7_BLD_KN(ql1, 1, 0, wb), PH7_DMA(0));
-      PH7_GROUP(1, q1, 1, fa[0] = PH7_LDA(ab1[ABUF][dx], aoff, 4), PH7_BLD_KN(ql1, 1, 1, wb), PH7_DMA(1));
-      PH7_GROUP(2, q1, 1, fa[1] = PH7_LDA(ab1[ABUF][dx], aoff, 5), PH7_BLD_KN(ql1, 1, 2, wb), PH7_DMA(2));
-      PH7_GROUP(3, q1, 1, fa[2] = PH7_LDA(ab1[ABUF][dx], aoff, 6), PH7_BLD_KN(ql1, 1, 3, wb), PH_NOP);
-      PH7_GROUP(4, q1, 1, fa[3] = PH7_LDA(ab1[ABUF][dx], aoff, 7), PH_NOP, PH_NOP);
+      PHW_TAP_K1(t, ABUF, dx, aoff, wb, PH7_DMA(0), PH7_DMA(1), PH7_DMA(2), PH_NOP, PH_NOP);
       // the taps without pieces take the piece mask of the NEXT tile (first slice of a tile): 3, 2, 2, 2, 2 pieces in taps 4..8
       if (FIRSTS && t >= 4) {
         if (t == 4) mask_next = piece_bit(0, tnext.r0, tnext.c0);
@@ -449,9 +372,8 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         asm volatile("s_barrier" ::: "memory");
       }
-      PH7_GROUP(5, q1, 1, fa[0] = PH7_LDA(ab0[BUFN][dxn], aoffn, 0), PH_NOP, PH_NOP);
-      PH7_GROUP(6, q1, 1, fa[1] = PH7_LDA(ab0[BUFN][dxn], aoffn, 1), PH_NOP, PH_NOP);
-      PH7_GROUP(7, q1, 1, fa[2] = PH7_LDA(ab0[BUFN][dxn], aoffn, 2), PH_NOP, PH_NOP);
+      // the last three groups read the first A fragments of the next tap
+      PHW_TAP_K1_NEXT(t, BUFN, dxn, aoffn);
       if (!(FIRSTS && t == 0)) ph_wait_vmcnt(C::WAIT1[t]);
 #undef PH7_DMA
     };

@@ -5,6 +5,8 @@
 //     halo source tables, the counted-wait, barrier and scheduling macros, RSRC_FLAGS; conv_wgrad.hip takes lds_dma16 too.
 //   conv_tap2 / 3 / 4: bn_relu_chunk (the input's BatchNorm + ReLU applied in LDS).
 //   conv_tap3 .. conv_tap7, conv_tap6b: halo_off (the column-swizzled halo image); conv_tap5 / 6 / 6b / 7: ph_wait_vmcnt.
+//   conv_tap2 .. conv_tap7, conv_tap6b (the persistent kernels): ph_fdiv (conv_tap4: its own integer form) and PH_TILE_LIST.
+//   conv_tap6 / 6b / 7 take the nine-set weight window from tap_window.h, which includes this file.
 //   conv_tap4 .. conv_tap7, conv_tap6b (host): ph_launch_persistent; the stat_parts functions share ph_persistent_wgs with it.
 #pragma once
 #include <mutex>
@@ -137,6 +139,35 @@ template <int HPW>
 __device__ __forceinline__ int halo_off(int hr, int hc, int c) {
   return (HPW / 2 * hr + (hc >> 1)) * 256 + ((hc & 1) << 7) + ((c ^ (((hc >> 1) & 3) << 1)) << 4);
 }
+
+// ---- tile list of a persistent workgroup (conv_tap2 .. conv_tap7, conv_tap6b).  What a linear tile id MEANS - image-major or
+// Cout-block-major, the input pointer - is each kernel's `decode`; the division it needs and the walk over the ids are here.
+// q = a / d for 0 <= a < 2^22 with a precomputed float reciprocal and one correction step (a decode runs once per tile on the
+// critical path; hardware integer division costs ~40 instructions per quotient)
+__device__ __forceinline__ int ph_fdiv(int a, int d, float rcp) {
+  int q = (int)((float)a * rcp);
+  int r = a - q * d;
+  if (r >= d) ++q;
+  if (r < 0) --q;
+  return q;
+}
+// The workgroups of one XCD (blockIdx.x % 8: hardware round-robin) walk one contiguous eighth of the list, so neighbouring halos
+// and the weight block of a Cout block are shared inside one L2.  PH_TILE_LIST(tile_id, total) declares tile_id(k): the k-th tile of
+// this workgroup, -1 when its list is exhausted.  (A macro that declares a lambda, not a struct or a function: those are simplified
+// on their own before they are inlined, and the kernels that walk the list then compile to another schedule - profiles/EXPERIMENTS.md.)
+#define PH_TILE_LIST(TILE_ID, TOTAL)                                     \
+  const int tl_wgs = gridDim.x;                                          \
+  const bool tl_xcd_map = (tl_wgs & 7) == 0 && tl_wgs < (TOTAL);         \
+  const int tl_per_xcd = ((TOTAL) + 7) >> 3;                             \
+  auto TILE_ID = [&](int k) -> int {                                     \
+    if (!tl_xcd_map) {                                                   \
+      const int t = (int)blockIdx.x + k * tl_wgs;                        \
+      return t < (TOTAL) ? t : -1;                                       \
+    }                                                                    \
+    const int local = ((int)blockIdx.x >> 3) + k * (tl_wgs >> 3);        \
+    const int t = ((int)blockIdx.x & 7) * tl_per_xcd + local;            \
+    return (local < tl_per_xcd && t < (TOTAL)) ? t : -1;                 \
+  }
 
 // ---- host side of the persistent kernels: one workgroup per CU (LDS) walks a tile list of C::TH x C::TW pixels x C::BNT channels.
 // Workgroups of a launch = the BatchNorm partial rows it writes (the stat_parts functions).
