@@ -624,6 +624,41 @@ int ph_tsvd_update_aux_dev(const float* adj, float* aux, float* tnn /* may be NU
                            void* workspace, ph_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The tail of the patch-level test pass: nine overlapping patches per test ROI
+ * (data_loaders_MT.py:67-77, train_test_path_multi_distill.py:360-366, "MIA 2023/stage2_unimodal_student/train_test_path_multi_distill.py":489-492), scored per
+ * patch and per patient.  The reference copies every prediction row to the host and calls sklearn / pandas there.
+ *
+ * ph_rank_counts: micro-averaged roc_auc_score and average_precision_score (core/utils_analysis.py:160-161,
+ * train_test_path_multi_distill.py:516-526) as exact counts.  pred f32 [N][C], grade int64 [N]; the M = N * C pairs
+ * (score pred[n][c], label grade[n] == c) are compared all against all (j side staged in LDS in tiles of 256).
+ * counts int64 [4] = {P, concordant, tied, bad}: P positives; concordant / tied = the (positive i, negative j) pairs with
+ * s_i > s_j / s_i == s_j; bad = non-finite scores + labels outside [0, C).  ap_sum float64 [1] = the sum over the positives
+ * of ge_pos_i / ge_all_i (ge_all_i = #{j: s_j >= s_i}, ge_pos_i the positives among them), added in a fixed order (a tree
+ * over each block of 256 pairs, then block t, t + 256, .. per thread and the same tree): two runs agree bitwise.
+ * With Q = M - P:  AUC = (concordant + tied / 2) / (P Q),  AP = ap_sum / P - sklearn's values, ties included.  Integer totals
+ * by 64-bit atomics: exact, independent of the order.  N >= 1, C >= 1, M <= 1048576; workspace: the bytes
+ * ph_rank_counts_workspace_bytes gives (0 for a refused shape; host only).
+ * ph_confusion_counts: conf int64 [C][C], row = grade[n], column = arg-max of pred[n] (the FIRST maximum, as np.argmax) -
+ * the integers behind f1_score(average="micro" | None) (utils_analysis.py:162-163) and the accuracy.  A row whose label lies
+ * outside [0, C) is left out.  N >= 1, 1 <= C <= 16.
+ * ph_group_agg: the per-patient groupby('TCGA ID').agg(fun) of utils_analysis.py:123.  x f32 [N][C]; the groups as a CSR
+ * built by the caller: offsets int32 [G + 1], order int32 [N] (the rows of group g are order[offsets[g]] ..
+ * order[offsets[g + 1] - 1], ascending; groups need not be contiguous in x); out f32 [G][C].  PH_AGG_MEAN: float64 sum in
+ * that order, divided by the count, rounded to float32 once.  PH_AGG_MAX: exact, starting from -inf.  offsets_host is the
+ * HOST copy of offsets: it is checked before the launch (offsets[0] = 0, offsets[G] = N, no empty group - else PH_EINVAL).
+ * 1 <= G <= N <= 16777216, 1 <= C <= 4096.
+ * All three return PH_EINVAL for a NULL pointer or a size outside the stated range before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define PH_AGG_MEAN 0
+#define PH_AGG_MAX 1
+size_t ph_rank_counts_workspace_bytes(int N, int C);
+int ph_rank_counts(const float* pred, const int64_t* grade, int N, int C, int64_t* counts, double* ap_sum, void* workspace,
+                   ph_stream_t stream);
+int ph_confusion_counts(const float* pred, const int64_t* grade, int N, int C, int64_t* conf, ph_stream_t stream);
+int ph_group_agg(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C, int G,
+                 int fun, float* out, ph_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * In-library kernel timer for bench.py's `roofline` object: HIP events around every MFMA kernel launch on the
  * launch stream.  Classes: 0 first-generation tap-conv Cout=64 (dgrad parity classes), 1 first-generation tap-conv
  * Cout>=128 stride 1 (1x1, dgrad parity classes), 2 tap-conv stride 2, 3 wgrad, 4 stem forward, 5 stem wgrad,

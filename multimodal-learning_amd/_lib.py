@@ -75,6 +75,10 @@ SIGNATURES = {
     "ph_surv_pack_rows": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "ph_surv_stage1_loss_grad_gathered": (i32, [vp, i32, i32, i32, i32, f32, f32, vp, vp, vp]),
     "ph_cindex_counts": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ph_rank_counts_workspace_bytes": (sz, [i32, i32]),
+    "ph_rank_counts": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
+    "ph_confusion_counts": (i32, [vp, vp, i32, i32, vp, vp]),
+    "ph_group_agg": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "ph_pkt_workspace_bytes": (sz, [i32, i32]),
     "ph_pkt_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
     "ph_rkd_workspace_bytes": (sz, [i32, i32]),

@@ -220,3 +220,123 @@ class ResidentSuperpixelLoader(ResidentTileLoader):
             idx_buf.copy_(index)
         self.sampler(idx_buf, grade, out=sample_idx)
         return into
+
+
+def patch_offsets(extent, S, grid):
+    """Top (or left) offsets of the `grid` overlapping crops of size S along a side of `extent` pixels: k * (extent - S) /
+    (grid - 1), which must be an integer; grid = 1 is the centre crop."""
+    extent, S, grid = int(extent), int(S), int(grid)
+    if grid < 1:
+        raise ValueError("grid must be at least 1")
+    if S < 1 or S > extent:
+        raise ValueError("patch size %d does not fit a side of %d pixels" % (S, extent))
+    if grid == 1:
+        return [(extent - S) // 2]
+    if (extent - S) % (grid - 1):
+        raise ValueError("a grid of %d patches of %d over %d pixels has the non-integer stride %d / %d"
+                         % (grid, S, extent, extent - S, grid - 1))
+    return [k * ((extent - S) // (grid - 1)) for k in range(grid)]
+
+
+class _Rows:
+    def __init__(self, n):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+
+class ResidentPatchLoader:
+    """The reference's `test_loader_patches` (MICCAI-2022/data_loaders_MT.py:67-77: nine overlapping 512 x 512 patches of
+    every 1024 x 1024 test ROI) produced on the device from a resident uint8 store tiles_u8 [n, SH, SW, 3].
+
+    Row r is ROI r // grid^2, grid cell (gy, gx) = divmod(r % grid^2, grid); its crop of size S = opt.input_size_path sits
+    at top = gy * (SH - S) / (grid - 1), left = gx * (SW - S) / (grid - 1) (grid = 1: the centre crop).  Iteration yields the
+    test loader's 6-tuple (x_path, 0, x_omic, 0, 0, grade) in row order in batches of opt.batch_size, the last one partial
+    (shuffle=False, no drop_last), so evaluate.test / test_model / test_teacher consume it unchanged.
+
+    x_path = (u8 / 255 - 0.5) / 0.5 in float32, cut straight out of the store by ph_augment_apply_v with one view, no flip
+    and every colour step disabled.  The reference runs its TRAINING transform - random flips and colour jitter - on the
+    test patches too, an artefact of reusing PathomicDatasetLoader; that is deliberately not reproduced: a test pass here
+    is deterministic.
+
+    `patient`: one hashable id per ROI (None: every ROI its own patient), mapped at construction to dense ids 0..G-1 in
+    order of first appearance; a patient whose ROIs carry different grades raises ValueError.  row_patient (int64 [rows],
+    device), patients (the ids, host), patient_grade (int64 [G], device), num_patients; group_offsets / group_order: the
+    CSR of the rows per patient that evaluate.aggregate_by_patient hands to ph_group_agg."""
+
+    def __init__(self, opt, tiles_u8, x_omic, grade, patient=None, grid=3, device="cuda"):
+        import numpy as np
+        from .ops import group_csr
+        self.device = torch.device(device)
+        self.tiles = require_cuda(tiles_u8, "tiles_u8")
+        if self.tiles.dtype != torch.uint8 or self.tiles.dim() != 4 or self.tiles.shape[3] != 3:
+            raise RuntimeError("tiles_u8 must be uint8 [n, SH, SW, 3]")
+        self.tiles = self.tiles.contiguous()
+        n, SH, SW, _ = self.tiles.shape
+        self.S, self.grid, self.batch_size = int(opt.input_size_path), int(grid), int(opt.batch_size)
+        tops, lefts = patch_offsets(SH, self.S, self.grid), patch_offsets(SW, self.S, self.grid)
+        if self.batch_size < 1:
+            raise ValueError("opt.batch_size must be positive")
+        grade_h = np.asarray(grade.cpu() if torch.is_tensor(grade) else grade).reshape(-1).astype(np.int64)
+        if grade_h.shape[0] != n or x_omic.shape[0] != n:
+            raise ValueError("one omic row and one grade per ROI")
+        ids = list(range(n)) if patient is None else list(patient)
+        if len(ids) != n:
+            raise ValueError("one patient id per ROI")
+        dense, self.patients, pgrade = {}, [], []
+        roi_patient = np.empty(n, dtype=np.int64)
+        for i, pid in enumerate(ids):
+            if pid not in dense:
+                dense[pid] = len(self.patients)
+                self.patients.append(pid)
+                pgrade.append(int(grade_h[i]))
+            elif pgrade[dense[pid]] != int(grade_h[i]):
+                raise ValueError("patient %r has ROIs of different grades (%d and %d)" % (pid, pgrade[dense[pid]], int(grade_h[i])))
+            roi_patient[i] = dense[pid]
+        self.num_patients = len(self.patients)
+        cells = self.grid * self.grid
+        self.n_rows = n * cells
+        self.dataset = _Rows(self.n_rows)
+        row_roi = np.repeat(np.arange(n, dtype=np.int64), cells)
+        row_patient = roi_patient[row_roi]
+        # one parameter row per patch (the layout of DeviceAugment): flips 0, top, left, factors of the disabled colour
+        # steps, order 0 1 2 3, column 13 = 15 (all four steps off)
+        prm = np.zeros((self.n_rows, 1, NPARAM), dtype=np.float32)
+        cell = np.arange(self.n_rows) % cells
+        prm[:, 0, 2] = np.asarray(tops, dtype=np.float32)[cell // self.grid]
+        prm[:, 0, 3] = np.asarray(lefts, dtype=np.float32)[cell % self.grid]
+        prm[:, 0, 4:7] = 1.0
+        prm[:, 0, 8:12] = (0, 1, 2, 3)
+        prm[:, 0, 13] = 15
+        self.params = torch.from_numpy(prm).to(self.device)
+        self.row_roi = torch.from_numpy(row_roi).to(self.device)
+        self.row_patient = torch.from_numpy(row_patient).to(self.device)
+        self.patient_grade_host = np.asarray(pgrade, dtype=np.int64)
+        self.patient_grade = torch.from_numpy(self.patient_grade_host).to(self.device)
+        self.x_omic = x_omic.to(self.device).float().contiguous()
+        self.grade = torch.from_numpy(grade_h).to(self.device)
+        self.group_offsets_host, order = group_csr(row_patient, self.num_patients)
+        self.group_offsets = torch.from_numpy(self.group_offsets_host).to(self.device)
+        self.group_order = torch.from_numpy(order).to(self.device)
+
+    def __len__(self):
+        return (self.n_rows + self.batch_size - 1) // self.batch_size
+
+    def rows(self, lo, hi):
+        """The batch of rows lo .. hi - 1."""
+        import ctypes as C
+        B, S = hi - lo, self.S
+        _, SH, SW, _ = self.tiles.shape
+        roi = self.row_roi[lo:hi]
+        params = self.params[lo:hi].clone()       # the kernel keeps its grey-sum scratch in the row: a fresh copy per call
+        x_path = torch.empty(B, 3, S, S, device=self.device, dtype=torch.float32)
+        outs = (C.c_void_p * 1)(ptr(x_path))
+        check(lib().ph_augment_apply_v(ptr(self.tiles), None, ptr(roi), ptr(params), outs, None, B, 1, SH, SW, S, stream()),
+              "ph_augment_apply_v")
+        z = torch.zeros(B, device=self.device)
+        return (x_path, z, self.x_omic[roi], z, z, self.grade[roi])
+
+    def __iter__(self):
+        for lo in range(0, self.n_rows, self.batch_size):
+            yield self.rows(lo, min(lo + self.batch_size, self.n_rows))

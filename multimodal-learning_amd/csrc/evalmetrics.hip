@@ -1,0 +1,216 @@
+// The tail of the patch-level test pass: what the reference computes on the host, with sklearn and pandas,
+// after copying every prediction row off the device -
+//   ph_rank_counts       roc_auc_score / average_precision_score(average="micro")   (core/utils_analysis.py:160-161,
+//                        train_test_path_multi_distill.py:516-526) as exact pair counts,
+//   ph_confusion_counts  f1_score of the arg-max grades (utils_analysis.py:162-163) as the C x C confusion matrix,
+//   ph_group_agg         groupby('TCGA ID').agg(max | mean) of the patch rows per patient (utils_analysis.py:123).
+// The scores are log-probabilities (negative): nothing here relies on their sign.
+#include "ph_common.h"
+#include "ph_kernels.h"
+
+namespace {
+
+constexpr int RANK_TILE = 256;            // pairs per workgroup and j-tile length of the all-pairs count
+constexpr int RANK_MAX_M = 1 << 20;
+constexpr int CONF_THREADS = 256;
+constexpr int CONF_MAX_C = 16;
+constexpr int AGG_MAX_N = 1 << 24;
+constexpr int AGG_MAX_C = 4096;
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// fixed-tree sum of RANK_TILE doubles (red[t] += red[t + o], o = 128 .. 1): the order tests/eval_emulation.py restates
+__device__ __forceinline__ double tile_tree_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int o = RANK_TILE >> 1; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// Pair i = n * C + c has score pred[i] and label (grade[n] == c).  Thread = pair i; the j pairs stream through LDS in tiles.
+// For a positive i:  ge_all = #{j: s_j >= s_i}, ge_pos = the positives among them, below = #{j negative: s_j < s_i},
+// equal = #{j negative: s_j == s_i}.  counts[0..3] += P, concordant, tied, bad (64-bit integer atomics: exact, independent of the
+// order); part[block] = the tile-tree sum of ge_pos / ge_all over the block's positives (0.0 for every other thread).
+// A NaN score compares false everywhere and is counted in `bad`, as is a label outside [0, C) (which makes no pair positive).
+__global__ __launch_bounds__(RANK_TILE) void rank_counts_kernel(const float* __restrict__ pred, const int64_t* __restrict__ grade,
+                                                                int M, int C, unsigned long long* __restrict__ counts,
+                                                                double* __restrict__ part) {
+  __shared__ float2 sj[RANK_TILE];       // .x = the score of a positive pair j, .y = of a negative one; the other half NaN
+  __shared__ double red[RANK_TILE];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * RANK_TILE + tid;
+  const bool live = i < M;
+  const float qnan = __builtin_nanf("");
+  float si = 0.f;
+  bool pos = false;
+  unsigned int bad = 0;
+  if (live) {
+    si = pred[i];
+    const int n = i / C, c = i - n * C;
+    const int64_t g = grade[n];
+    pos = g == (int64_t)c;
+    bad = (isfinite(si) ? 0u : 1u) + ((c == 0 && (g < 0 || g >= (int64_t)C)) ? 1u : 0u);
+  }
+  // A NaN compares false with everything: the half of sj[j] that does not apply, the padding of the last tile and a NaN
+  // score all drop out of every count, so the inner loop has a fixed length and no label test.
+  unsigned int ge_pos = 0, ge_neg = 0, below = 0, equal = 0;
+  for (int j0 = 0; j0 < M; j0 += RANK_TILE) {
+    const int j = j0 + tid;
+    float2 v = make_float2(qnan, qnan);
+    if (j < M) {
+      const int n = j / C;
+      const float s = pred[j];
+      if (grade[n] == (int64_t)(j - n * C)) v.x = s; else v.y = s;
+    }
+    __syncthreads();
+    sj[tid] = v;
+    __syncthreads();
+    if (!pos) continue;        // (no early exit: every thread takes part in the barriers)
+#pragma unroll 8
+    for (int jj = 0; jj < RANK_TILE; ++jj) {
+      const float2 w = sj[jj];
+      ge_pos += w.x >= si ? 1u : 0u;
+      ge_neg += w.y >= si ? 1u : 0u;
+      below += w.y < si ? 1u : 0u;
+      equal += w.y == si ? 1u : 0u;
+    }
+  }
+  const unsigned int ge_all = ge_pos + ge_neg;
+  // ge_all >= 1 for a finite positive (j = i); a NaN positive has ge_all = 0: its term is left out (the flag reports it)
+  const double term = (pos && ge_all > 0) ? (double)ge_pos / (double)ge_all : 0.0;
+  const double tsum = tile_tree_sum(term, red);
+  if (tid == 0) part[blockIdx.x] = tsum;
+  const int lane = tid & 63;
+  const unsigned long long a = wave_sum_u64(pos ? 1ull : 0ull), b = wave_sum_u64(below), c = wave_sum_u64(equal),
+                           d = wave_sum_u64(bad);
+  if (lane == 0) {
+    if (a) atomicAdd(&counts[0], a);
+    if (b) atomicAdd(&counts[1], b);
+    if (c) atomicAdd(&counts[2], c);
+    if (d) atomicAdd(&counts[3], d);
+  }
+}
+
+// One workgroup: thread t adds part[t], part[t + 256], ... in that order, then the tile tree.  Fixed order: two runs agree bitwise.
+__global__ __launch_bounds__(RANK_TILE) void rank_finish_kernel(const double* __restrict__ part, int nblocks,
+                                                                double* __restrict__ ap_sum) {
+  __shared__ double red[RANK_TILE];
+  double v = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += RANK_TILE) v += part[b];
+  const double s = tile_tree_sum(v, red);
+  if (threadIdx.x == 0) ap_sum[0] = s;
+}
+
+// conf[t * C + p] += 1 for every row whose label t lies in [0, C), p = the first maximum of the row (np.argmax: a later equal
+// value does not replace it).  A row whose label is out of range is left out - it has no cell.  Per-block histogram in LDS.
+__global__ __launch_bounds__(CONF_THREADS) void confusion_counts_kernel(const float* __restrict__ pred, const int64_t* __restrict__ grade,
+                                                                        int N, int C, unsigned long long* __restrict__ conf) {
+  __shared__ unsigned int hist[CONF_MAX_C * CONF_MAX_C];
+  const int tid = threadIdx.x;
+  for (int k = tid; k < C * C; k += CONF_THREADS) hist[k] = 0;
+  __syncthreads();
+  const int n = blockIdx.x * CONF_THREADS + tid;
+  if (n < N) {
+    const float* row = pred + (size_t)n * C;
+    float best = row[0];
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+      const float v = row[c];
+      if (v > best) { best = v; arg = c; }
+    }
+    const int64_t g = grade[n];
+    if (g >= 0 && g < (int64_t)C) atomicAdd(&hist[(int)g * C + arg], 1u);
+  }
+  __syncthreads();
+  for (int k = tid; k < C * C; k += CONF_THREADS)
+    if (hist[k]) atomicAdd(&conf[k], (unsigned long long)hist[k]);
+}
+
+// Thread = (group g, column c).  Rows order[offsets[g]] .. order[offsets[g + 1] - 1], in that (ascending) order.
+// mean: float64 running sum, one division, one rounding to float32.  max: starts at -inf (the inputs are negative).
+// A row index outside [0, N) is skipped and the offsets are clamped to [0, N]: device data cannot make the kernel read
+// outside x (the entry validates the host copy of the offsets).
+__global__ void group_agg_kernel(const float* __restrict__ x, const int32_t* __restrict__ offsets, const int32_t* __restrict__ order,
+                                 int N, int C, int G, int fun, float* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)G * C) return;
+  const int g = (int)(t / C), c = (int)(t - (size_t)g * C);
+  const int lo = min(max(offsets[g], 0), N), hi = min(max(offsets[g + 1], lo), N);
+  if (fun == 0) {
+    double acc = 0.0;
+    for (int k = lo; k < hi; ++k) {
+      const int r = order[k];
+      if (r < 0 || r >= N) continue;
+      acc += (double)x[(size_t)r * C + c];
+    }
+    out[t] = (float)(acc / (double)(hi - lo));
+  } else {
+    float m = -INFINITY;
+    for (int k = lo; k < hi; ++k) {
+      const int r = order[k];
+      if (r < 0 || r >= N) continue;
+      m = fmaxf(m, x[(size_t)r * C + c]);
+    }
+    out[t] = m;
+  }
+}
+
+bool rank_shape_ok(int N, int C) { return N >= 1 && C >= 1 && (int64_t)N * C <= RANK_MAX_M; }
+
+}  // namespace
+
+#include "pathomic_hip.h"
+
+extern "C" {
+
+size_t ph_rank_counts_workspace_bytes(int N, int C) {
+  if (!rank_shape_ok(N, C)) return 0;
+  return sizeof(double) * (size_t)cdiv(N * C, RANK_TILE);
+}
+
+int ph_rank_counts(const float* pred, const int64_t* grade, int N, int C, int64_t* counts, double* ap_sum, void* workspace,
+                   hipStream_t st) {
+  if (!pred || !grade || !counts || !ap_sum || !workspace || !rank_shape_ok(N, C)) return PH_EINVAL;
+  const int M = N * C, nblocks = cdiv(M, RANK_TILE);
+  if (hipMemsetAsync(counts, 0, sizeof(int64_t) * 4, st) != hipSuccess) return PH_ELAUNCH;
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(rank_counts_kernel, dim3(nblocks), dim3(RANK_TILE), 0, st, pred, grade, M, C,
+                     reinterpret_cast<unsigned long long*>(counts), part);
+  PH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rank_finish_kernel, dim3(1), dim3(RANK_TILE), 0, st, part, nblocks, ap_sum);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_confusion_counts(const float* pred, const int64_t* grade, int N, int C, int64_t* conf, hipStream_t st) {
+  if (!pred || !grade || !conf || N < 1 || C < 1 || C > CONF_MAX_C) return PH_EINVAL;
+  if (hipMemsetAsync(conf, 0, sizeof(int64_t) * C * C, st) != hipSuccess) return PH_ELAUNCH;
+  hipLaunchKernelGGL(confusion_counts_kernel, dim3(cdiv(N, CONF_THREADS)), dim3(CONF_THREADS), 0, st, pred, grade, N, C,
+                     reinterpret_cast<unsigned long long*>(conf));
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_group_agg(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C, int G,
+                 int fun, float* out, hipStream_t st) {
+  if (!x || !offsets || !order || !offsets_host || !out) return PH_EINVAL;
+  if (N < 1 || N > AGG_MAX_N || C < 1 || C > AGG_MAX_C || G < 1 || G > N) return PH_EINVAL;
+  if (fun != PH_AGG_MEAN && fun != PH_AGG_MAX) return PH_EINVAL;
+  if (offsets_host[0] != 0 || offsets_host[G] != N) return PH_EINVAL;
+  for (int g = 0; g < G; ++g)
+    if (offsets_host[g + 1] <= offsets_host[g]) return PH_EINVAL;        // an empty (or negative) group
+  const size_t n = (size_t)G * C;
+  hipLaunchKernelGGL(group_agg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, offsets, order, N, C, G, fun, out);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+}  // extern "C"

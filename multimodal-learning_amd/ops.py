@@ -592,6 +592,79 @@ def cindex_counts(survtime, event, hazards):
     return out
 
 
+AGG_FUN = {"mean": 0, "max": 1}          # PH_AGG_MEAN, PH_AGG_MAX
+
+
+def _pred_grade(pred, grade, what):
+    pred = _f32(pred)
+    if pred.dim() != 2 or grade.numel() != pred.shape[0]:
+        raise ValueError("%s: pred [N, C] float32 and one grade per row" % what)
+    return pred, require_cuda(grade, "grade").reshape(-1).long().contiguous()
+
+
+def rank_counts(pred, grade, out=None):
+    """The counts behind the micro-averaged ROC-AUC and average precision (ph_rank_counts) of scores pred [N, C] against
+    the labels grade [N]: an int64 [5] device tensor {P, concordant, tied, bad, ap_sum}, the last word holding the BITS of
+    the float64 sum (`out[4:5].view(torch.float64)`).  `out`: five int64 words of a caller's buffer to fill instead."""
+    pred, grade = _pred_grade(pred, grade, "rank_counts")
+    N, C = pred.shape
+    nbytes = lib().ph_rank_counts_workspace_bytes(N, C)
+    if nbytes == 0:
+        raise ValueError("rank_counts: N >= 1, C >= 1 and N * C <= 1048576 (got %d x %d)" % (N, C))
+    if out is None:
+        out = torch.empty(5, device=pred.device, dtype=torch.int64)
+    ws = torch.empty(nbytes // 8, device=pred.device, dtype=torch.float64)
+    check(lib().ph_rank_counts(ptr(pred), ptr(grade), N, C, ptr(out), out.data_ptr() + 32, ptr(ws), stream()), "ph_rank_counts")
+    return out
+
+
+def confusion_counts(pred, grade, out=None):
+    """int64 [C, C] device tensor: row = true grade, column = arg-max of the row of pred (first maximum), ph_confusion_counts."""
+    pred, grade = _pred_grade(pred, grade, "confusion_counts")
+    N, C = pred.shape
+    if not 1 <= C <= 16 or N < 1:
+        raise ValueError("confusion_counts: N >= 1 and 1 <= C <= 16 (got %d x %d)" % (N, C))
+    if out is None:
+        out = torch.empty(C, C, device=pred.device, dtype=torch.int64)
+    check(lib().ph_confusion_counts(ptr(pred), ptr(grade), N, C, ptr(out), stream()), "ph_confusion_counts")
+    return out
+
+
+def group_csr(group_of_row, num_groups):
+    """The CSR ph_group_agg reads, from a HOST sequence of one dense group id per row: (offsets int32 [G + 1] numpy,
+    order int32 [N] numpy), the rows of a group ascending."""
+    import numpy as np
+    g = np.asarray(group_of_row, dtype=np.int64).reshape(-1)
+    if g.size and (g.min() < 0 or g.max() >= num_groups):
+        raise ValueError("group ids must lie in [0, %d)" % num_groups)
+    order = np.argsort(g, kind="stable").astype(np.int32)
+    offsets = np.zeros(num_groups + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum(np.bincount(g, minlength=num_groups))
+    return offsets, order
+
+
+def group_agg(x, offsets_dev, order_dev, offsets_host, fun):
+    """out [G, C] = mean or max of the rows of x [N, C] per group (ph_group_agg); offsets_host: the numpy int32 copy of
+    offsets_dev (the entry checks it on the host: an empty group raises)."""
+    import numpy as np
+    if fun not in AGG_FUN:
+        raise ValueError('agg must be "mean" or "max", got %r' % (fun,))
+    x = _f32(x)
+    oh = np.ascontiguousarray(offsets_host, dtype=np.int32)
+    G = oh.shape[0] - 1
+    if x.dim() != 2 or order_dev.numel() != x.shape[0] or offsets_dev.numel() != G + 1:
+        raise ValueError("group_agg: x [N, C], order [N], offsets [G + 1]")
+    if offsets_dev.dtype != torch.int32 or order_dev.dtype != torch.int32:
+        raise ValueError("group_agg: offsets and order are int32")
+    out = torch.empty(G, x.shape[1], device=x.device, dtype=torch.float32)
+    rc = lib().ph_group_agg(ptr(x), ptr(require_cuda(offsets_dev).contiguous()), ptr(require_cuda(order_dev).contiguous()),
+                            oh.ctypes.data, x.shape[0], x.shape[1], G, AGG_FUN[fun], ptr(out), stream())
+    if rc == -22:
+        raise ValueError("ph_group_agg refused the groups: offsets must start at 0, end at N and leave no group empty")
+    check(rc, "ph_group_agg")
+    return out
+
+
 class L2NormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
