@@ -1,6 +1,7 @@
 """Drop-in for the hot-loop functions of the reference's MICCAI-2022/train_test_path_multi_distill.py:
 ``update_ema_variables`` (:34-38), ``AEKD_loss`` (:41-70) and the batch body of ``train()`` (:242-330,
 here ``DistillStep``), plus the fused optimiser behind ``define_optimizer`` (networks_new.py:80-90)."""
+import collections
 import math
 
 import numpy as np
@@ -313,11 +314,11 @@ def update_ema_variables(model, ema_model, alpha, global_step):
     ops.bump_weight_epoch()
 
 
-def AEKD_loss(opt, optimizer, main_loss, feat_s, loss_t_list, sync=None):
-    """GK-Refine (train_test_path_multi_distill.py:41-70): weights = row sums of the (x len(loss_t_list))
-    cosine Gram matrix of d loss_i / d feat_s.  The reference obtains each gradient by a FULL backward pass
-    (5 ResNet-18 backward passes thrown away except the hook value, :49-56); the identical values are the
-    VJPs stopped at feat_s, so this costs a few [B,128]-sized kernels.  Returns (scale[5], total_KD_loss)."""
+def _gk_gram(opt, main_loss, feat_s, loss_t_list, sync=None):
+    """The front end of every scalar GK-Refine form: d loss_i / d feat_s per loss (the CE gradient last when opt.CE_grads),
+    stacked, their Gram matrix (ph_gram), summed over the replicas.  The reference obtains each gradient by a FULL backward
+    pass (5 ResNet-18 backward passes thrown away except the hook value, train_test_path_multi_distill.py:49-56); the identical
+    values are the VJPs stopped at feat_s, so this costs a few [B,128]-sized kernels.  Returns (gram[ng * ng], ng)."""
     losses = list(loss_t_list) + ([main_loss] if opt.CE_grads else [])
     grads = [torch.autograd.grad(l, feat_s, retain_graph=True)[0] for l in losses]
     ng = len(grads)
@@ -326,34 +327,42 @@ def AEKD_loss(opt, optimizer, main_loss, feat_s, loss_t_list, sync=None):
     check(lib().ph_gram(ptr(G), ptr(gram), ng, G.shape[1], stream()), "ph_gram")
     if sync is not None:
         sync.all_reduce_sum(gram)        # global-batch cosine under data parallelism
-    scale = torch.empty(ng, device=G.device, dtype=torch.float32)
+    return gram, ng
+
+
+def AEKD_loss(opt, optimizer, main_loss, feat_s, loss_t_list, sync=None):
+    """GK-Refine (train_test_path_multi_distill.py:41-70): weights = row sums of the (x len(loss_t_list))
+    cosine Gram matrix of d loss_i / d feat_s (_gk_gram).  Returns (scale[5], total_KD_loss)."""
+    gram, ng = _gk_gram(opt, main_loss, feat_s, loss_t_list, sync)
+    scale = torch.empty(ng, device=gram.device, dtype=torch.float32)
     check(lib().ph_gk_scale(ptr(gram), None, ng, 0, float(len(loss_t_list)), ptr(scale), None, stream()), "ph_gk_scale")
     losses_div_tensor = torch.stack(list(loss_t_list))
     total_KD_loss = torch.dot(scale[:-1], losses_div_tensor)      # :68 (mirrors the slicing as written)
     return scale, total_KD_loss
 
 
-def momentum_AEKD_loss(opt, optimizer, main_loss, feat_s, loss_t_list, mo_scale, sync=None):
-    """GK-Refine of the MIA-2022 trainer ("MIA 2022/train_test_path_multi_distill_v2.py":89-132): like AEKD_loss but
-    the cosine Gram is NOT multiplied by len(loss_t_list) (:113), may be binarised with `opt.thresh` when
-    opt.grads_thresh == "True" (:114-115) and the weights are an EMA over iterations with opt.grads_m (:121-124).
-    `mo_scale` is None on the first call; returns (mo_scale, total_KD_loss)."""
-    losses = list(loss_t_list) + ([main_loss] if opt.CE_grads else [])
-    grads = [torch.autograd.grad(l, feat_s, retain_graph=True)[0] for l in losses]
-    ng = len(grads)
-    G = torch.stack([g.reshape(-1) for g in grads]).contiguous()
-    gram = torch.empty(ng * ng, device=G.device, dtype=torch.float32)
-    check(lib().ph_gram(ptr(G), ptr(gram), ng, G.shape[1], stream()), "ph_gram")
-    if sync is not None:
-        sync.all_reduce_sum(gram)
-    if mo_scale is None:
-        state = torch.zeros(ng, device=G.device, dtype=torch.float32)
-        init = torch.zeros(1, device=G.device, dtype=torch.int32)
-    else:
-        state = mo_scale.detach().clone()
-        init = torch.ones(1, device=G.device, dtype=torch.int32)
+def _gk_momentum_scale(opt, main_loss, feat_s, loss_t_list, state, init, sync=None):
+    """The weights of the MIA-2022 trainer's GK-Refine ("MIA 2022/train_test_path_multi_distill_v2.py":89-132): the cosine
+    Gram is NOT multiplied by len(loss_t_list) (:113), may be binarised with `opt.thresh` when opt.grads_thresh == "True"
+    (:114-115), and the weights are an EMA over iterations with opt.grads_m (:121-124), updated in place in the caller's
+    `state` (`init`: device int32 [1], 0 = no earlier iteration; both None: fresh ones).  Returns (state, init)."""
+    gram, ng = _gk_gram(opt, main_loss, feat_s, loss_t_list, sync)
+    if state is None:
+        state = torch.zeros(ng, device=gram.device, dtype=torch.float32)
+        init = torch.zeros(1, device=gram.device, dtype=torch.int32)
     check(lib().ph_gk_scale_momentum(ptr(gram), ng, 1 if opt.grads_thresh == "True" else 0, float(opt.thresh),
                                      float(opt.grads_m), ptr(state), ptr(init), stream()), "ph_gk_scale_momentum")
+    return state, init
+
+
+def momentum_AEKD_loss(opt, optimizer, main_loss, feat_s, loss_t_list, mo_scale, sync=None):
+    """GK-Refine of the MIA-2022 trainer (_gk_momentum_scale) with the trainer's calling convention: `mo_scale` is None on
+    the first call; returns (mo_scale, total_KD_loss)."""
+    state = init = None
+    if mo_scale is not None:
+        state = mo_scale.detach().clone()
+        init = torch.ones(1, device=state.device, dtype=torch.int32)
+    state, _ = _gk_momentum_scale(opt, main_loss, feat_s, loss_t_list, state, init, sync)
     total_KD_loss = torch.dot(state[:-1], torch.stack(list(loss_t_list)))
     return state, total_KD_loss
 
@@ -396,6 +405,78 @@ def _validate_opt(opt, who, surv_ok=False):
         raise NotImplementedError("%s: use_vgg_features (pre-extracted features bypass the ResNet trunk)" % who)
     if getattr(opt, "path_arch", "resnet18") not in ("resnet18", "resnet34"):
         raise NotImplementedError("%s: path_arch %r (the BasicBlock trunks resnet18 and resnet34 are built)" % (who, opt.path_arch))
+
+
+# What DistillStep's generic loss path does for one option combination (distill_loss_plan):
+#   kl          teachers that feed a KL term, in the trainers' order: a subset of ("fuse", "ema")
+#   feat        the feature-level term: "crd2" (criterion_kd on the fused teacher + criterion_kd_path on the mean teacher),
+#               "crd1" (one call, through criterion_kd whichever teacher is chosen), "zoo" (a distiller_zoo criterion on the
+#               fused teacher's feature) or "none"
+#   weighting   "gk" (the variant's GK-Refine) or "sum" (fixed weights alpha / beta)
+#   rank_draws  host RNG rank draws per step (memory_new.py:311): one per CRD call of the MICCAI-2022 bank, else 0
+#   unused      names of the CRD criteria whose embedding heads sit in the optimiser without ever receiving a gradient
+#   crd_heads   whether the CRD embedding heads are in the optimiser's parameter list at all
+#   report      what the returned loss terms are: "scaled" (alpha * div, beta * kd), "unscaled_rows" (div, kd as computed, plus
+#               the MIA-2023 per-sample extras rows_div1, rows_kd1, w1, w2) or "baseline" (div as computed, beta * kd)
+#   kd_global   the zoo criterion returns the GLOBAL batch's loss on every replica: reported as 1 / world_size of it
+LossPlan = collections.namedtuple("LossPlan", "kl feat weighting rank_draws unused crd_heads report kd_global")
+
+ZOO_DISTILL = ("kd", "feats_KL", "rkd", "pkt", "similarity")      # `--distill` baselines of the MIA-2022 trainer (kd: no criterion)
+
+
+def distill_loss_plan(opt, variant, sync=None):
+    """The ONE place that reads num_teachers / which_teacher / distill / assign_weights: which terms the generic loss path of
+    DistillStep computes, how it weights and reports them (LossPlan) - or, for a combination the reference's batch body cannot
+    run or this package does not build, the exception (the reference's own type where it fails itself).  Pure: no device, no
+    networks, no library."""
+    nt, which, distill = opt.num_teachers, opt.which_teacher, opt.distill
+    gk = opt.assign_weights == "True"
+    kl = ("fuse", "ema") if nt == 2 else {"fuse": ("fuse",), "self_EMA": ("ema",)}.get(which, ()) if nt == 1 else ()
+    if variant == "mia2022" and distill != "crd":
+        # train_test_path_multi_distill_v2.py:316-342, 419-483: KL to one or two teachers plus one feature-level criterion
+        # between the student feature and the fused teacher's, no embedding heads in the optimiser
+        from .distiller_zoo import RKD_MAX_ROWS
+        if distill not in ZOO_DISTILL:
+            raise NotImplementedError("--distill %s (built: crd, kd, feats_KL, rkd, pkt, similarity)" % distill)
+        spans_batch = sync is not None and distill in ("rkd", "pkt", "similarity")
+        if spans_batch:
+            # these relate every row of the batch to every other row: under data parallelism the criterion sees the
+            # GLOBAL batch (the reference's nn.DataParallel gathers the outputs, :286, :307-308)
+            need = ("all_gather_cat", "all_reduce_sum") if distill == "rkd" else ("all_gather_cat",)
+            lack = [c for c in need if not callable(getattr(sync, c, None))]
+            if lack:
+                raise NotImplementedError("--distill %s with data parallelism spans the global batch: the sync object "
+                                          "must provide %s" % (distill, ", ".join(lack)))
+            if distill == "rkd" and opt.batch_size * sync.world_size > RKD_MAX_ROWS:
+                raise ValueError("--distill rkd: global batch %d x %d exceeds the %d rows of the partitioned RKD kernel"
+                                 % (opt.batch_size, sync.world_size, RKD_MAX_ROWS))
+        if not kl:                                                                                          # :419-422
+            raise NotImplementedError("num_teachers %r / which_teacher %r" % (nt, which))
+        if gk and not (distill == "kd" and nt == 2):
+            raise NotImplementedError("assign_weights with --distill %s: the trainer builds KD_loss_list only for crd and "
+                                      "kd with two teachers (:463-468)" % distill)
+        return LossPlan(kl, "none" if distill == "kd" else "zoo", "gk" if gk else "sum", 0, (), False, "baseline",
+                        spans_batch and distill != "rkd")       # (rkd returns this replica's PART of the global loss)
+    if not kl:
+        # :263-271 define loss_div in three branches only; anything else reaches `loss_KD = opt.alpha * loss_div` unbound
+        raise UnboundLocalError("local variable 'loss_div' referenced before assignment (num_teachers %r / which_teacher "
+                                "%r: train_test_path_multi_distill.py:263-271)" % (nt, which))
+    if distill not in ("crd", "kd"):
+        raise NotImplementedError(distill)                                                                  # :289-290
+    if gk and nt != 2:
+        # :293-301 build KD_loss_list under `if opt.num_teachers == 2` only; :304 then reads it
+        raise UnboundLocalError("local variable 'KD_loss_list' referenced before assignment (--assign_weights True needs "
+                                "--num_teachers 2: train_test_path_multi_distill.py:293-304)")
+    if gk and variant == "mia2023" and getattr(opt, "loss_weighting", "GK_refine") != "GK_refine":
+        raise NotImplementedError("loss_weighting '%s' (the shipped command uses GK_refine)" % opt.loss_weighting)
+    # `--distill kd`: no CRD call, both criteria idle; `--num_teachers 1`: ONE call through criterion_kd whichever teacher is
+    # chosen (:282-285), criterion_kd_path idle
+    feat, unused = (("none", ("criterion_kd", "criterion_kd_path")) if distill == "kd" else
+                    ("crd2", ()) if nt == 2 else ("crd1", ("criterion_kd_path",)))
+    calls = {"crd2": 2, "crd1": 1, "none": 0}[feat]
+    # only the MIA-2023 body with both CRD calls reports its terms unscaled, with the per-sample values
+    report = "unscaled_rows" if variant == "mia2023" and feat == "crd2" else "scaled"
+    return LossPlan(kl, feat, "gk" if gk else "sum", calls if variant == "miccai2022" else 0, unused, True, report, False)
 
 
 # ----------------------------------------------------------------------------------------- the hot loop
@@ -467,41 +548,21 @@ class DistillStep:
         self.criterion_kd_path = CRDLoss(opt, n_data).to(self.device)              # :206
         self.module_list = nn.ModuleList([self.model, self.criterion_kd.embed_s, self.criterion_kd.embed_t,
                                           self.criterion_kd_path.embed_s, self.criterion_kd_path.embed_t])
-        # the other `--distill` choices of the MIA-2022 trainer (train_test_path_multi_distill_v2.py:316-342): one
-        # feature-level baseline criterion, no embedding heads in the optimiser
-        self.zoo_kd = None
-        if variant == "mia2022" and opt.distill != "crd":
+        # the option combination decides the loss path ONCE (or raises where the reference's body, or this package, cannot run it)
+        self.plan = plan = distill_loss_plan(opt, variant, sync)
+        self.zoo_kd = None        # the feature-level baseline criterion of the MIA-2022 trainer's other `--distill` choices
+        if plan.feat == "zoo":
             from . import distiller_zoo as Z
-            zoo = {"kd": None, "feats_KL": Z.feats_KL, "rkd": Z.RKDLoss, "pkt": Z.PKT, "similarity": Z.Similarity}
-            if opt.distill not in zoo:
-                raise NotImplementedError("--distill %s (built: crd, kd, feats_KL, rkd, pkt, similarity)" % opt.distill)
-            if sync is not None and opt.distill in ("rkd", "pkt", "similarity"):
-                # these relate every row of the batch to every other row: under data parallelism the criterion sees the
-                # GLOBAL batch (the reference's nn.DataParallel gathers the outputs, :286, :307-308)
-                need = ("all_gather_cat", "all_reduce_sum") if opt.distill == "rkd" else ("all_gather_cat",)
-                lack = [c for c in need if not callable(getattr(sync, c, None))]
-                if lack:
-                    raise NotImplementedError("--distill %s with data parallelism spans the global batch: the sync object "
-                                              "must provide %s" % (opt.distill, ", ".join(lack)))
-                if opt.distill == "rkd" and opt.batch_size * sync.world_size > Z.RKD_MAX_ROWS:
-                    raise ValueError("--distill rkd: global batch %d x %d exceeds the %d rows of the partitioned RKD kernel"
-                                     % (opt.batch_size, sync.world_size, Z.RKD_MAX_ROWS))
-                self.zoo_kd = zoo[opt.distill](sync=sync)
-            else:
-                self.zoo_kd = zoo[opt.distill]() if zoo[opt.distill] is not None else False
-            self.module_list = nn.ModuleList([self.model])
+            # (rkd / pkt / similarity relate the rows of the batch: with a sync object, those of the GLOBAL batch)
+            self.zoo_kd = (Z.feats_KL() if opt.distill == "feats_KL" else
+                           {"rkd": Z.RKDLoss, "pkt": Z.PKT, "similarity": Z.Similarity}[opt.distill](sync=sync))
+        if not plan.crd_heads:
+            self.module_list = nn.ModuleList([self.model])                         # v2 :316-342: no embedding heads in the optimiser
         self.optimizer = define_optimizer(opt, self.module_list)                   # :211
         self.scheduler = define_scheduler(opt, self.optimizer)                     # :212
-        # option branches that leave a CRD criterion unused (`--distill kd`: both; `--num_teachers 1`: criterion_kd_path, the
-        # one call goes through criterion_kd whichever teacher is chosen, :282-285): its embedding heads stay in the
-        # optimiser's parameter list as in the reference, where their .grad stays None and the update skips them
-        self._branch_check()
-        unused = []
-        if self.zoo_kd is None:
-            if opt.distill == "kd":
-                unused = [self.criterion_kd, self.criterion_kd_path]
-            elif opt.num_teachers == 1:
-                unused = [self.criterion_kd_path]
+        # a CRD criterion the option branch leaves unused: its embedding heads stay in the optimiser's parameter list as in
+        # the reference, where their .grad stays None and the update skips them
+        unused = [getattr(self, c) for c in plan.unused]
         if unused and hasattr(self.optimizer, "set_inactive"):
             self.optimizer.set_inactive([p for c in unused for m_ in (c.embed_s, c.embed_t) for p in m_.parameters()])
         self.iter_num = opt.global_step
@@ -580,7 +641,6 @@ class DistillStep:
     # ------------------------------------------------------------------ one step
     def _device_body(self, x_path, ema_x_path, x_omic, grade, index, sample_idx, bnorm, e, r1, r2):
         """Everything of the step that runs on the device (capturable in one HIP graph)."""
-        opt = self.opt
         # The two teachers' forwards do not depend on the student's: they run on a second stream (a parallel branch
         # of the captured graph) so their small-kernel tails overlap the student's convolutions.
         main = torch.cuda.current_stream()
@@ -616,6 +676,7 @@ class DistillStep:
                 _, ema_path_feat, ema_logit_path, _, _ = self.ema_model(x_path=ema_x_path)                  # :254
                 fuse_feat, _, _, _, logits, pred, _, _, _, _, _ = self.fix_model(x_path=x_path, x_omic=x_omic)  # :256
         self._stamp(2)
+        teachers = (ema_logit_path, logits[-1], fuse_feat, ema_path_feat)
         if self._fused_head_ok():
             # :262-313 as one function of the student feature (loss_head.py): same values, ~50 launches instead of ~125
             from .loss_head import FusedDistillLossFn, FusedMia2023LossFn, LossHeadCtx
@@ -640,184 +701,122 @@ class DistillStep:
             self._stamp(6)
             o = Hc.out
             extra = {k: o[k] for k in ("rows_div1", "rows_kd1", "w1", "w2") if k in o}       # (the MIA-2023 body's per-sample values)
-            return dict(loss=loss.detach(), loss_cls=o["loss_cls"], loss_div1=o["loss_div1"], loss_div2=o["loss_div2"],
-                        loss_kd1=o["loss_kd1"], loss_kd2=o["loss_kd2"], scale=o["scale"], logit_path=o["logit_path"],
-                        pred_path=o["pred_path"], path_feat=path_feat.detach(), ema_logit=ema_logit_path,
-                        fuse_logit=logits[-1], fuse_feat=fuse_feat, ema_feat=ema_path_feat, **extra)
+            return self._result(loss, o["loss_cls"], [o["loss_div1"], o["loss_div2"], o["loss_kd1"], o["loss_kd2"]], o["scale"],
+                                (o["logit_path"], o["pred_path"], path_feat), teachers, extra)
+        return self._generic_loss(e, r1, r2, grade, index, sample_idx, bnorm, path_feat, logit_path, pred_path, teachers)
+
+    @staticmethod
+    def _result(loss, loss_cls, terms, scale, student, teachers, extra=None):
+        """What a step returns: the loss, its terms [div1, div2, kd1, kd2] (by the plan's reporting convention), the GK-Refine
+        weights (None with fixed weights), the student's and the teachers' outputs - all detached device tensors."""
+        d = [t.detach() for t in [loss, loss_cls, *terms, *student]]
+        ema_logit, fuse_logit, fuse_feat, ema_feat = teachers
+        return dict(loss=d[0], loss_cls=d[1], loss_div1=d[2], loss_div2=d[3], loss_kd1=d[4], loss_kd2=d[5], scale=scale,
+                    logit_path=d[6], pred_path=d[7], path_feat=d[8], ema_logit=ema_logit, fuse_logit=fuse_logit,
+                    fuse_feat=fuse_feat, ema_feat=ema_feat, **(extra or {}))
+
+    def _generic_loss(self, e, r1, r2, grade, index, sample_idx, bnorm, path_feat, logit_path, pred_path, teachers):
+        """Losses, backward and update of the three batch bodies on the generic autograd path, every option branch
+        (MICCAI-2022 train_test_path_multi_distill.py:262-329, "MIA 2022/train_test_path_multi_distill_v2.py":419-486,
+        "MIA 2023/stage2_unimodal_student/train_test_path_multi_distill.py":348-448), as `self.plan` lays it out: KL terms,
+        feature terms, weighting, total, update, report.  Every value stays on the device.  `e`: the epoch fraction (MICCAI),
+        the epoch weight of the CRD loss (MIA-2022) or the re-weighting switch (MIA-2023: 0 while epoch < opt.start_reweight -
+        query weights all ones, :373-375 -, then 1) as a device scalar."""
+        opt, v, plan = self.opt, self.variant, self.plan
+        a, b = opt.alpha, opt.beta
+        ema_logit_path, fuse_logit, fuse_feat, ema_path_feat = teachers
+        rows = v == "mia2023"                   # (its DistillKL / CRDLoss also return the per-sample rows)
+        z = torch.zeros((), device=self.device)                   # a term the branch does not have
         loss_cls = ops.NLLFn.apply(pred_path, grade, bnorm)                                                 # :262
-        if self.zoo_kd is None and not (opt.num_teachers == 2 and opt.distill == "crd"):
-            return self._branch_tail(e, r1, grade, index, sample_idx, loss_cls, path_feat, logit_path, pred_path, ema_path_feat,
-                                     ema_logit_path, fuse_feat, logits)
-        if self.variant == "mia2023":
-            return self._mia2023_tail(e, loss_cls, grade, index, sample_idx, path_feat, logit_path, pred_path,
-                                      ema_path_feat, ema_logit_path, fuse_feat, logits)
-        if self.zoo_kd is not None:
-            return self._mia2022_baseline_tail(loss_cls, path_feat, logit_path, pred_path, ema_path_feat, ema_logit_path,
-                                               fuse_feat, logits)
-        loss_div1 = self.criterion_div(logit_path, logits[-1].detach())                                     # :264
-        loss_div2 = self.criterion_div(logit_path, ema_logit_path.detach())                                 # :265
-        if self.variant == "mia2022":
-            # v2 trainer :436-437: the first argument is the epoch weight of the per-sample CRD loss; result shape [1]
-            loss_kd1, loss_kd2 = self._two_chains(
-                lambda: self.criterion_kd(e, path_feat, fuse_feat.detach(), index, sample_idx).reshape(()),
-                lambda: self.criterion_kd_path(e, path_feat, ema_path_feat.detach(), index, sample_idx).reshape(()))
+
+        # ---- 1. KL terms (:263-271; v2 :419-422; MIA-2023 :349-350)
+        div1 = div2 = kd1 = kd2 = z
+        rows_div1 = rows_div2 = rows_kd1 = rows_kd2 = w1 = w2 = None
+        if "fuse" in plan.kl:
+            r = self.criterion_div(logit_path, fuse_logit.detach())                                         # :264
+            div1, rows_div1 = r if rows else (r, None)
+        if "ema" in plan.kl:
+            r = self.criterion_div(logit_path, ema_logit_path.detach())                                     # :265
+            div2, rows_div2 = r if rows else (r, None)
+
+        # ---- 2. feature terms
+        if rows and plan.feat in ("crd2", "crd1"):
+            from .mia2023 import assign_sample_weights
+            # :361-364 - log-probability margins: the softmax normaliser cancels, so the kernel reads the logits
+            w1 = assign_sample_weights(logit_path, fuse_logit, grade, opt.discrep_scale, opt.max_discrep, from_logits=True)
+            w2 = assign_sample_weights(logit_path, ema_logit_path, grade, opt.discrep_scale, opt.max_discrep, from_logits=True)
+            w1 = (1.0 + e * w1).view(-1, 1); w2 = (1.0 + e * w2).view(-1, 1)                                # :373-382
+
+        def crd(criterion, t_feat, w, ranks):
+            """One CRD call -> (loss, per-sample rows or None)."""
+            if v == "miccai2022":
+                return criterion(e, path_feat, t_feat.detach(), index, sample_idx, ranks=ranks), None       # :278-279
+            if v == "mia2022":
+                # v2 trainer :436-437: the first argument is the epoch weight of the per-sample CRD loss; result shape [1]
+                return criterion(e, path_feat, t_feat.detach(), index, sample_idx).reshape(()), None
+            return criterion(w, path_feat, t_feat.detach(), grade, index, sample_idx)                       # :386, :388
+        if plan.feat == "crd2":
+            # (the only place with two independent chains: the second runs on the head's side stream, one stream under sync)
+            (kd1, rows_kd1), (kd2, rows_kd2) = self._two_chains(lambda: crd(self.criterion_kd, fuse_feat, w1, r1),
+                                                                lambda: crd(self.criterion_kd_path, ema_path_feat, w2, r2))
+        elif plan.feat == "crd1":
+            # one teacher: the call goes through criterion_kd with that teacher's feature (MICCAI :282-285)
+            kd1, rows_kd1 = crd(self.criterion_kd, *((fuse_feat, w1) if "fuse" in plan.kl else (ema_path_feat, w2)), r1)
+        elif plan.feat == "zoo":
+            kd1 = self.zoo_kd(path_feat, fuse_feat.detach()).reshape(())                                    # v2 :430-457
+
+        # ---- 3. weighting
+        scaled = [a * div1, a * div2, b * kd1, b * kd2]                                                     # :293-297
+        scale = None
+        if plan.weighting == "sum" and plan.feat == "crd2" and not rows:
+            loss_KD = scaled[0] + scaled[1] + scaled[2] + scaled[3]                                         # :309 (two teachers)
+        elif plan.weighting == "sum":
+            # :309 as the one-teacher / kd branches reach it, v2 :482, MIA-2023 :427 (a missing term is an exact zero)
+            loss_KD = a * (div1 + div2) + b * (kd1 + kd2)
+        elif rows:
+            from .mia2023 import GK_refine_thresh
+            # MIA-2023 :407-414: per-sample rows; the CRD body's list is scaled, the `--distill kd` list is NOT (:414)
+            gk_list = [a * rows_div1, a * rows_div2, b * rows_kd1, b * rows_kd2] if plan.feat == "crd2" else [rows_div1, rows_div2]
+            scale, loss_KD = GK_refine_thresh(opt, self.optimizer, loss_cls, path_feat, gk_list,             # :422
+                                              batch_norm_size=self.criterion_div.batch_norm_size, sync=self.sync)
         else:
-            loss_kd1, loss_kd2 = self._two_chains(
-                lambda: self.criterion_kd(e, path_feat, fuse_feat.detach(), index, sample_idx, ranks=r1),         # :278
-                lambda: self.criterion_kd_path(e, path_feat, ema_path_feat.detach(), index, sample_idx, ranks=r2))  # :279
-        loss_div1 = opt.alpha * loss_div1; loss_div2 = opt.alpha * loss_div2                                # :293-294
-        loss_kd1 = opt.beta * loss_kd1; loss_kd2 = opt.beta * loss_kd2                                      # :296-297
-        KD_loss_list = [loss_div1, loss_div2, loss_kd1, loss_kd2]
-        if opt.assign_weights == "True" and self.variant == "mia2022":
-            # v2 trainer :474-477: momentum GK-Refine; the weight vector lives in ONE device buffer updated in place
-            # (so that a captured HIP graph keeps reading / writing the same storage), x len(list) unless thresholded
-            scale, loss_KD = self._momentum_gk(loss_cls, path_feat, KD_loss_list)
-            if opt.grads_thresh == "False":
-                loss_KD = loss_KD * len(KD_loss_list)
-        elif opt.assign_weights == "True":
-            scale, loss_KD = AEKD_loss(opt, self.optimizer, loss_cls, path_feat, KD_loss_list, self.sync)   # :304
-        else:
-            scale = None
-            loss_KD = loss_div1 + loss_div2 + loss_kd1 + loss_kd2                                           # :309
+            gk_list = scaled if plan.feat == "crd2" else scaled[:2]                                         # :293-300 (kd: the KL terms)
+            if v == "miccai2022":
+                scale, loss_KD = AEKD_loss(opt, self.optimizer, loss_cls, path_feat, gk_list, self.sync)    # :304
+            else:
+                # v2 trainer :474-477: momentum GK-Refine; the weight vector lives in ONE device buffer updated in place
+                # (so that a captured HIP graph keeps reading / writing the same storage), x len(list) unless thresholded
+                self._mo_state, self._mo_init = _gk_momentum_scale(opt, loss_cls, path_feat, gk_list, self._mo_state,
+                                                                   self._mo_init, self.sync)
+                self._mo_init.fill_(1)
+                scale = self._mo_state.clone()       # a value snapshot for the caller; no graph through the weights
+                loss_KD = torch.dot(scale[:-1], torch.stack([l.reshape(()) for l in gk_list]))
+                if opt.grads_thresh == "False":
+                    loss_KD = loss_KD * len(gk_list)
+
+        # ---- 4. total, 5. update
         loss = self._add_reg(opt.lambda_nll * loss_cls + loss_KD)                                           # :312-313
         _backward_and_update(self, loss)                                                                    # :326-329
-        return dict(loss=loss.detach(), loss_cls=loss_cls.detach(), loss_div1=loss_div1.detach(),
-                    loss_div2=loss_div2.detach(), loss_kd1=loss_kd1.detach(), loss_kd2=loss_kd2.detach(),
-                    scale=scale, logit_path=logit_path.detach(), pred_path=pred_path.detach(),
-                    path_feat=path_feat.detach(), ema_logit=ema_logit_path, fuse_logit=logits[-1],
-                    fuse_feat=fuse_feat, ema_feat=ema_path_feat)
 
-    def _mia2022_baseline_tail(self, loss_cls, path_feat, logit_path, pred_path, ema_path_feat, ema_logit_path, fuse_feat,
-                               logits):
-        """The `--distill kd | feats_KL | rkd | pkt | similarity` baselines of the MIA-2022 trainer
-        ("MIA 2022/train_test_path_multi_distill_v2.py":419-483): KL to one or two teachers plus one feature-level
-        criterion between the student feature and the fused teacher feature, summed with fixed weights alpha / beta
-        (GK-Refine needs the per-loss list, which the trainer only builds for crd and kd with two teachers).
-
-        Under data parallelism `rkd | pkt | similarity` are losses of the GLOBAL batch (distiller_zoo).  The value that enters
-        backward() is what the criterion returns - this replica's part of the global loss with the summed gradient behind it
-        (rkd), or the global loss itself (pkt, similarity: every replica evaluates it, the backward keeps its own rows) - so
-        that the replicas' parameter gradients add up to the single-process gradient.  The REPORTED `loss_kd1` and `loss`
-        follow the step's convention that the replicas' values add up to the single-process ones: this replica's part
-        (rkd), the global value / world_size (pkt, similarity)."""
-        opt = self.opt
-        z = torch.zeros((), device=self.device)
-        loss_div1 = loss_div2 = z
-        if opt.num_teachers == 2:                                                                           # :419-422
-            loss_div1 = self.criterion_div(logit_path, logits[-1].detach())
-            loss_div2 = self.criterion_div(logit_path, ema_logit_path.detach())
-        elif opt.num_teachers == 1 and opt.which_teacher == "fuse":
-            loss_div1 = self.criterion_div(logit_path, logits[-1].detach())
-        elif opt.num_teachers == 1 and opt.which_teacher == "self_EMA":
-            loss_div2 = self.criterion_div(logit_path, ema_logit_path.detach())
-        else:
-            raise NotImplementedError("num_teachers %r / which_teacher %r" % (opt.num_teachers, opt.which_teacher))
-        loss_div = loss_div1 + loss_div2
-        loss_kd = z if self.zoo_kd is False else self.zoo_kd(path_feat, fuse_feat.detach()).reshape(())     # :430-457
-        scale = None
-        if opt.assign_weights == "True":
-            if not (opt.distill == "kd" and opt.num_teachers == 2):
-                raise NotImplementedError("assign_weights with --distill %s: the trainer builds KD_loss_list only for crd and "
-                                          "kd with two teachers (:463-468)" % opt.distill)
-            KD_loss_list = [opt.alpha * loss_div1, opt.alpha * loss_div2]
-            scale, loss_KD = self._momentum_gk(loss_cls, path_feat, KD_loss_list)                           # :474
-            if opt.grads_thresh == "False":
-                loss_KD = loss_KD * len(KD_loss_list)
-        else:
-            loss_KD = opt.alpha * loss_div + opt.beta * loss_kd                                             # :482
-        loss = self._add_reg(opt.lambda_nll * loss_cls + loss_KD)                                           # :485-486
-        _backward_and_update(self, loss)
-        loss, loss_kd = loss.detach(), loss_kd.detach()
-        if self.sync is not None and opt.distill in ("pkt", "similarity"):
-            # every replica holds the global value: report 1 / world of it (the replicas' reports add up)
+        # ---- 6. report (the plan's convention; DESIGN.md section 1)
+        student = (logit_path, pred_path, path_feat)
+        if plan.report == "scaled":
+            return self._result(loss, loss_cls, scaled, scale, student, teachers)
+        if plan.report == "unscaled_rows":
+            return self._result(loss, loss_cls, [div1, div2, kd1, kd2], scale, student, teachers,
+                                dict(rows_div1=rows_div1.detach(), rows_kd1=rows_kd1.detach(), w1=w1.detach(), w2=w2.detach()))
+        # "baseline": the KL terms as computed, beta * criterion.  Under data parallelism rkd / pkt / similarity are losses of the
+        # GLOBAL batch (distiller_zoo).  The value that entered backward() is what the criterion returns - this replica's part of
+        # the global loss with the summed gradient behind it (rkd), or the global loss itself (pkt, similarity: every replica
+        # evaluates it, the backward keeps its own rows) - so that the replicas' parameter gradients add up to the single-process
+        # gradient.  The REPORTED `loss_kd1` and `loss` follow the step's convention that the replicas' values add up to the
+        # single-process ones: this replica's part (rkd), the global value / world_size (pkt, similarity: plan.kd_global).
+        loss, kd = loss.detach(), kd1.detach()
+        if plan.kd_global:
             w = float(self.sync.world_size)
-            loss = loss - opt.beta * (loss_kd - loss_kd / w)
-            loss_kd = loss_kd / w
-        return dict(loss=loss, loss_cls=loss_cls.detach(), loss_div1=loss_div1.detach(), loss_div2=loss_div2.detach(),
-                    loss_kd1=(opt.beta * loss_kd).detach(), loss_kd2=z, scale=scale, logit_path=logit_path.detach(),
-                    pred_path=pred_path.detach(), path_feat=path_feat.detach(), ema_logit=ema_logit_path,
-                    fuse_logit=logits[-1], fuse_feat=fuse_feat, ema_feat=ema_path_feat)
-
-    def _branch_check(self):
-        """Option combinations the reference's batch body itself cannot run fail here, with its own exception type."""
-        opt = self.opt
-        if self.zoo_kd is not None:
-            return
-        if not (opt.num_teachers == 2 or (opt.num_teachers == 1 and opt.which_teacher in ("fuse", "self_EMA"))):
-            # :263-271 define loss_div in three branches only; anything else reaches `loss_KD = opt.alpha * loss_div` unbound
-            raise UnboundLocalError("local variable 'loss_div' referenced before assignment (num_teachers %r / which_teacher "
-                                    "%r: train_test_path_multi_distill.py:263-271)" % (opt.num_teachers, opt.which_teacher))
-        if opt.distill not in ("crd", "kd"):
-            raise NotImplementedError(opt.distill)                                                          # :289-290
-        if opt.assign_weights == "True" and opt.num_teachers != 2:
-            # :293-301 build KD_loss_list under `if opt.num_teachers == 2` only; :304 then reads it
-            raise UnboundLocalError("local variable 'KD_loss_list' referenced before assignment (--assign_weights True needs "
-                                    "--num_teachers 2: train_test_path_multi_distill.py:293-304)")
-
-    def _branch_tail(self, e, r1, grade, index, sample_idx, loss_cls, path_feat, logit_path, pred_path, ema_path_feat,
-                     ema_logit_path, fuse_feat, logits):
-        """The batch body's non-default option branches, all three trainers (MICCAI-2022 train_test_path_multi_distill.py:263-309,
-        "MIA 2022/train_test_path_multi_distill_v2.py":419-482, "MIA 2023/stage2_unimodal_student/
-        train_test_path_multi_distill.py":348-427): `--num_teachers 1` with `--which_teacher fuse | self_EMA` (ONE KL term and ONE
-        CRD call - through criterion_kd whichever teacher is chosen - summed with the fixed weights alpha / beta) and
-        `--distill kd` (no CRD term; with two teachers and `--assign_weights True` GK-Refine over the two KL terms).  Generic
-        autograd path; every value stays on the device."""
-        opt, v = self.opt, self.variant
-        z = torch.zeros((), device=self.device)
-        two = opt.num_teachers == 2
-        fuse_on = two or opt.which_teacher == "fuse"
-        ema_on = two or opt.which_teacher == "self_EMA"
-        rows = v == "mia2023"                   # (its DistillKL / CRDLoss also return the per-sample rows)
-        loss_div1 = loss_div2 = loss_kd1 = loss_kd2 = z
-        rows_div1 = rows_div2 = rows_kd1 = rows_kd2 = None
-        if fuse_on:
-            r = self.criterion_div(logit_path, logits[-1].detach())
-            loss_div1, rows_div1 = r if rows else (r, None)
-        if ema_on:
-            r = self.criterion_div(logit_path, ema_logit_path.detach())
-            loss_div2, rows_div2 = r if rows else (r, None)
-        loss_div = loss_div1 + loss_div2
-        if opt.distill == "crd":
-            if rows:
-                from .mia2023 import assign_sample_weights
-                w1 = assign_sample_weights(logit_path, logits[-1], grade, opt.discrep_scale, opt.max_discrep, from_logits=True)
-                w2 = assign_sample_weights(logit_path, ema_logit_path, grade, opt.discrep_scale, opt.max_discrep, from_logits=True)
-                w1 = (1.0 + e * w1).view(-1, 1); w2 = (1.0 + e * w2).view(-1, 1)
-            # one teacher: the call goes through criterion_kd with that teacher's feature (MICCAI :282-285)
-            t_feat, w = (fuse_feat, w1 if rows else None) if fuse_on else (ema_path_feat, w2 if rows else None)
-            if v == "miccai2022":
-                loss_kd1 = self.criterion_kd(e, path_feat, t_feat.detach(), index, sample_idx, ranks=r1)
-            elif v == "mia2022":
-                loss_kd1 = self.criterion_kd(e, path_feat, t_feat.detach(), index, sample_idx).reshape(())
-            else:
-                loss_kd1, rows_kd1 = self.criterion_kd(w, path_feat, t_feat.detach(), grade, index, sample_idx)
-        loss_kd = loss_kd1 + loss_kd2
-        scale = None
-        if opt.assign_weights == "True":       # (two teachers, --distill kd: _branch_check)
-            if v == "miccai2022":
-                KD_loss_list = [opt.alpha * loss_div1, opt.alpha * loss_div2]                               # :293-300
-                scale, loss_KD = AEKD_loss(opt, self.optimizer, loss_cls, path_feat, KD_loss_list, self.sync)
-            elif v == "mia2022":
-                KD_loss_list = [opt.alpha * loss_div1, opt.alpha * loss_div2]
-                scale, loss_KD = self._momentum_gk(loss_cls, path_feat, KD_loss_list)
-                if opt.grads_thresh == "False":
-                    loss_KD = loss_KD * len(KD_loss_list)
-            else:
-                from .mia2023 import GK_refine_thresh
-                if getattr(opt, "loss_weighting", "GK_refine") != "GK_refine":
-                    raise NotImplementedError("loss_weighting '%s' (the shipped command uses GK_refine)" % opt.loss_weighting)
-                KD_loss_list = [rows_div1, rows_div2]                                                       # (:414: unscaled rows)
-                scale, loss_KD = GK_refine_thresh(opt, self.optimizer, loss_cls, path_feat, KD_loss_list,
-                                                  batch_norm_size=self.criterion_div.batch_norm_size, sync=self.sync)
-        else:
-            loss_KD = opt.alpha * loss_div + opt.beta * loss_kd                                             # :309
-        loss = self._add_reg(opt.lambda_nll * loss_cls + loss_KD)                                           # :312-313
-        _backward_and_update(self, loss)
-        dt = lambda t: t.detach() if torch.is_tensor(t) else t      # noqa: E731
-        return dict(loss=loss.detach(), loss_cls=loss_cls.detach(), loss_div1=dt(opt.alpha * loss_div1),
-                    loss_div2=dt(opt.alpha * loss_div2), loss_kd1=dt(opt.beta * loss_kd1), loss_kd2=dt(opt.beta * loss_kd2),
-                    scale=scale, logit_path=logit_path.detach(), pred_path=pred_path.detach(), path_feat=path_feat.detach(),
-                    ema_logit=ema_logit_path, fuse_logit=logits[-1], fuse_feat=fuse_feat, ema_feat=ema_path_feat)
+            loss = loss - b * (kd - kd / w)
+            kd = kd / w
+        return self._result(loss, loss_cls, [div1, div2, b * kd, z], scale, student, teachers)
 
     def _add_reg(self, loss):
         """+ opt.lambda_reg * define_reg(opt, model) (train_test_path_multi_distill.py:312-313)."""
@@ -833,7 +832,7 @@ class DistillStep:
         """The closed-form loss head covers the shipped MICCAI and MIA-2022 stage-2 commands: two teachers, CRD, GK-Refine
         (plain / momentum) with the CE gradient, a log-softmax grading head.  `opt.fused_loss_head = False` selects the
         generic autograd path."""
-        opt = self.opt
+        opt, plan = self.opt, self.plan
         if getattr(opt, "sample_KD", "False") != "False":
             # per-sample CRD rows ([B]-shaped loss_kd): the reference's body then fails inside AEKD_loss's `loss_t.backward()`
             # ("grad can be implicitly created only for scalar outputs") - the generic path fails the same way, the closed
@@ -843,84 +842,24 @@ class DistillStep:
             # the fused head WRITES fc_new2's gradients (accumulate=False) after L1RegFn.backward has added
             # lambda_reg * sgn(W) into the same flat buffer: the L1 term on fc_new2 would be lost
             return False
-        if self.variant != "miccai2022" and (self.zoo_kd is not None or not torch.is_tensor(self._e_dev)):
+        if self.variant != "miccai2022" and not torch.is_tensor(self._e_dev):
             return False
-        if self.variant == "mia2023" and (getattr(opt, "loss_weighting", "GK_refine") != "GK_refine"
-                                          or getattr(opt, "pos_extra", "neighbors") != "neighbors"):
+        if self.variant == "mia2023" and getattr(opt, "pos_extra", "neighbors") != "neighbors":
             return False
-        return (self.variant in ("miccai2022", "mia2022", "mia2023") and getattr(opt, "fused_loss_head", True)
-                and opt.assign_weights == "True"
-                and bool(opt.CE_grads) and opt.num_teachers == 2 and opt.distill == "crd"
+        return (getattr(opt, "fused_loss_head", True) and plan.feat == "crd2" and plan.weighting == "gk"
+                and bool(opt.CE_grads)
                 and isinstance(getattr(self.model, "fc_new2", None), nn.Linear)
                 and isinstance(getattr(self.model, "act", None), nn.LogSoftmax))
-
-    def _mia2023_tail(self, rw, loss_cls, grade, index, sample_idx, path_feat, logit_path, pred_path, ema_path_feat,
-                      ema_logit_path, fuse_feat, logits):
-        """Losses, backward and update of the MIA-2023 batch body
-        ("MIA 2023/stage2_unimodal_student/train_test_path_multi_distill.py":348-448).  `rw` is a device scalar:
-        0 while epoch < opt.start_reweight (query weights are all ones, :373-375), 1 afterwards (1 + discrepancy)."""
-        from .mia2023 import assign_sample_weights, GK_refine_thresh
-        opt = self.opt
-        loss_div1, rows_div1 = self.criterion_div(logit_path, logits[-1].detach())                          # :349
-        loss_div2, rows_div2 = self.criterion_div(logit_path, ema_logit_path.detach())                      # :350
-        # :361-364 - log-probability margins: the softmax normaliser cancels, so the kernel reads the logits
-        w1 = assign_sample_weights(logit_path, logits[-1], grade, opt.discrep_scale, opt.max_discrep, from_logits=True)
-        w2 = assign_sample_weights(logit_path, ema_logit_path, grade, opt.discrep_scale, opt.max_discrep, from_logits=True)
-        w1 = (1.0 + rw * w1).view(-1, 1); w2 = (1.0 + rw * w2).view(-1, 1)                                  # :373-382
-        (loss_kd1, rows_kd1), (loss_kd2, rows_kd2) = self._two_chains(
-            lambda: self.criterion_kd(w1, path_feat, fuse_feat.detach(), grade, index, sample_idx),            # :386
-            lambda: self.criterion_kd_path(w2, path_feat, ema_path_feat.detach(), grade, index, sample_idx))    # :388
-        KD_loss_list = [opt.alpha * rows_div1, opt.alpha * rows_div2, opt.beta * rows_kd1, opt.beta * rows_kd2]  # :407-414
-        if opt.assign_weights == "True":
-            if getattr(opt, "loss_weighting", "GK_refine") != "GK_refine":
-                raise NotImplementedError("loss_weighting '%s' (the shipped command uses GK_refine)" % opt.loss_weighting)
-            scale, loss_KD = GK_refine_thresh(opt, self.optimizer, loss_cls, path_feat, KD_loss_list,        # :422
-                                              batch_norm_size=self.criterion_div.batch_norm_size, sync=self.sync)
-        else:
-            scale = None
-            loss_KD = opt.alpha * (loss_div1 + loss_div2) + opt.beta * (loss_kd1 + loss_kd2)                # :427
-        loss = self._add_reg(opt.lambda_nll * loss_cls + loss_KD)                                           # :430-431
-        _backward_and_update(self, loss)                                                                    # :446-447 fused
-        return dict(loss=loss.detach(), loss_cls=loss_cls.detach(), loss_div1=loss_div1.detach(),
-                    loss_div2=loss_div2.detach(), loss_kd1=loss_kd1.detach(), loss_kd2=loss_kd2.detach(),
-                    rows_div1=rows_div1.detach(), rows_kd1=rows_kd1.detach(), w1=w1.detach(), w2=w2.detach(),
-                    scale=scale, logit_path=logit_path.detach(), pred_path=pred_path.detach(),
-                    path_feat=path_feat.detach(), ema_logit=ema_logit_path, fuse_logit=logits[-1],
-                    fuse_feat=fuse_feat, ema_feat=ema_path_feat)
-
-    def _momentum_gk(self, main_loss, feat_s, loss_t_list):
-        """momentum_AEKD_loss ("MIA 2022/train_test_path_multi_distill_v2.py":89-132) with persistent device state."""
-        opt = self.opt
-        losses = list(loss_t_list) + ([main_loss] if opt.CE_grads else [])
-        grads = [torch.autograd.grad(l, feat_s, retain_graph=True)[0] for l in losses]
-        ng = len(grads)
-        G = torch.stack([g.reshape(-1) for g in grads]).contiguous()
-        gram = torch.empty(ng * ng, device=G.device, dtype=torch.float32)
-        check(lib().ph_gram(ptr(G), ptr(gram), ng, G.shape[1], stream()), "ph_gram")
-        if self.sync is not None:
-            self.sync.all_reduce_sum(gram)
-        if self._mo_state is None:
-            self._mo_state = torch.zeros(ng, device=G.device, dtype=torch.float32)
-            self._mo_init = torch.zeros(1, device=G.device, dtype=torch.int32)
-        check(lib().ph_gk_scale_momentum(ptr(gram), ng, 1 if opt.grads_thresh == "True" else 0, float(opt.thresh),
-                                         float(opt.grads_m), ptr(self._mo_state), ptr(self._mo_init), stream()),
-              "ph_gk_scale_momentum")
-        self._mo_init.fill_(1)
-        scale = self._mo_state.clone()       # a value snapshot for the caller; no graph through the weights
-        total_KD_loss = torch.dot(scale[:-1], torch.stack([l.reshape(()) for l in loss_t_list]))
-        return scale, total_KD_loss
 
     def _draw_ranks(self, epoch, ranks):
         """Host-RNG rank draws of memory_new.py:311 for the two CRD calls (kd1 then kd2), as device int32."""
         e = epoch / self.opt.niter_decay
-        if self.variant != "miccai2022":
-            return e, [None, None]         # the vanilla / KNN banks have no rank-drawn pair selection
         out = []
-        # the host RNG advances once per CRD CALL (memory_new.py:311): two calls in the shipped command, one with
-        # --num_teachers 1 (through criterion_kd), none with --distill kd
-        ncalls = 0 if self.opt.distill != "crd" else (2 if self.opt.num_teachers == 2 else 1)
+        # the host RNG advances once per CRD CALL of the MICCAI-2022 bank (memory_new.py:311): two calls in the shipped command,
+        # one with --num_teachers 1 (through criterion_kd), none with --distill kd; the vanilla / KNN banks of the other
+        # variants have no rank-drawn pair selection
         for i, crd in enumerate((self.criterion_kd, self.criterion_kd_path)):
-            if i >= ncalls:
+            if i >= self.plan.rank_draws:
                 out.append(None)
                 continue
             r = ranks[i] if ranks is not None else crd.contrast.draw_ranks(e, crd.select_pos_mode)

@@ -707,7 +707,7 @@ def test_fused_loss_head_equals_generic_autograd_path():
 @pytest.mark.parametrize("grads_thresh", ["False", "True"])
 def test_fused_loss_head_equals_generic_autograd_path_mia2022(grads_thresh):
     """The same for the MIA-2022 body (loss_head.py, variant mia2022: v3 bank with the epoch weight on the device, momentum
-    GK-Refine through ph_gk_finish_momentum) against its generic autograd path (DistillStep._momentum_gk), two consecutive
+    GK-Refine through ph_gk_finish_momentum) against its generic autograd path (DistillStep._generic_loss over train_step._gk_momentum_scale), two consecutive
     steps so that the moving average of the weights is exercised, plain and binarised (`grads_thresh`) cosine sums."""
     import multimodal_learning_amd as m
     from oracle import weights as W
@@ -765,7 +765,7 @@ def test_fused_loss_head_equals_generic_autograd_path_mia2022(grads_thresh):
 def test_fused_loss_head_equals_generic_autograd_path_mia2023(use_thresh):
     """The same for the MIA-2023 body (loss_head.FusedMia2023LossFn: per-sample KL / CRD rows under the discrepancy weights,
     per-sample GK-Refine weights from the closed-form gradient rows) against its generic autograd path
-    (DistillStep._mia2023_tail), with the re-weighting switched on, binarised and ReLU-ed cosine sums."""
+    (DistillStep._generic_loss), with the re-weighting switched on, binarised and ReLU-ed cosine sums."""
     import multimodal_learning_amd as m
     from oracle import weights as W
     from oracle.step import default_opt, synthetic_batch
@@ -1364,5 +1364,81 @@ def test_mia_option_branches_vs_reference_golden(golden_dir, variant, name):
             skipped = set(str(s) for s in g[pre + f"no_grad{it}"])
             assert "crd1.embed_t.linear.weight" in skipped and torch.equal(step.criterion_kd_path.embed_t.linear.weight, e_t1)
         R.finish()
+    finally:
+        m.set_precision("bf16")
+
+
+BASE_KEYS = {"loss", "loss_cls", "loss_div1", "loss_div2", "loss_kd1", "loss_kd2", "scale", "logit_path", "pred_path", "path_feat",
+             "ema_logit", "fuse_logit", "fuse_feat", "ema_feat"}
+MIA2023_KEYS = {"rows_div1", "rows_kd1", "w1", "w2"}
+# (variant, option overrides, how the reported terms combine into the loss, the extra keys)
+REPORT_CASES = {
+    "miccai2022-t2_crd_sum": ("miccai2022", dict(num_teachers=2, distill="crd"), "scaled", set()),
+    "mia2023-t2_crd_sum": ("mia2023", dict(num_teachers=2, distill="crd"), "unscaled", MIA2023_KEYS),
+    "miccai2022-t1_fuse_crd": ("miccai2022", dict(num_teachers=1, which_teacher="fuse", distill="crd"), "scaled", set()),
+    "mia2022-t2_feats_KL": ("mia2022", dict(num_teachers=2, distill="feats_KL"), "unscaled_div", set()),
+}
+
+
+@pytest.mark.parametrize("case", list(REPORT_CASES))
+def test_fixed_weight_branches_report_their_terms_by_convention(case):
+    """What the returned dict MEANS at alpha, beta != 1 (generic autograd path, fixed weights, one step), one configuration per
+    reporting convention of DistillStep (`distill_loss_plan(...).report`):
+      * the MICCAI-2022 / MIA-2022 CRD bodies and every one-teacher / `--distill kd` branch report alpha- / beta-SCALED terms:
+        loss = loss_cls + loss_div1 + loss_div2 + loss_kd1 + loss_kd2;
+      * the MIA-2023 default body reports UNSCALED terms and its four per-sample extras:
+        loss = loss_cls + alpha (loss_div1 + loss_div2) + beta (loss_kd1 + loss_kd2);
+      * the MIA-2022 baseline criteria report unscaled KL terms and the beta-scaled criterion:
+        loss = loss_cls + alpha (loss_div1 + loss_div2) + loss_kd1.
+    1e-5 relative (fp32 sums of five terms; the bound of the neighbouring tests for the same identity), and the exact key set."""
+    import multimodal_learning_amd as m
+    from oracle import weights as W
+    from oracle.losses import CRDState
+    from oracle.step import default_opt, synthetic_batch
+    from oracle.variants import CRDv3State, CRDv10State
+    variant, kw, convention, extras = REPORT_CASES[case]
+    B, H, n_data, K = 8, 64, 256, 64
+    labels = torch.arange(n_data) % 3
+    vkw = {"miccai2022": dict(nce_p=120, nce_k=K, nce_p2=20, nce_k2=48),
+           "mia2022": dict(nce_k=K, grads_m=0.9, grads_thresh="False", thresh=0.1, niter_decay=10),
+           "mia2023": dict(nce_k=K, nce_p=4, pos_extra="neighbors", neg_mode="all_others", start_reweight=0, discrep_scale=1,
+                           max_discrep=2.0, use_grads_thresh="True", grads_thresh=0.1, loss_weighting="GK_refine")}[variant]
+    opt = default_opt(batch_size=B, alpha=0.7, beta=0.3, assign_weights="False", **vkw, **kw)
+    opt.fused_loss_head = False
+    extra = dict(train_class_idx=[np.nonzero((labels == c).numpy())[0] for c in range(3)]) if variant == "mia2023" else {}
+    m.set_precision("bf16x6")
+    try:
+        step = m.DistillStep(opt, n_data, device="cuda", variant=variant, **extra)
+        step.model.load_state_dict(W.make_state_dict(W.student_shapes(), 1))
+        step.ema_model.load_state_dict(W.make_state_dict(W.student_shapes(), 2))
+        step.fix_model.load_state_dict(W.make_state_dict(W.teacher_shapes(320), 3))
+        for i, crd in enumerate((step.criterion_kd, step.criterion_kd_path)):
+            crd.embed_s.load_state_dict(W.make_state_dict(W.embed_shapes(), 10 + 2 * i))
+            crd.embed_t.load_state_dict(W.make_state_dict(W.embed_shapes(), 11 + 2 * i))
+            st = (CRDState(n_data, opt.feat_dim, opt.nce_p, opt.nce_k, seed=20 + i) if variant == "miccai2022" else
+                  CRDv3State(n_data, K=K, seed=20 + i) if variant == "mia2022" else CRDv10State(n_data, labels, K=K, seed=20 + i))
+            crd.contrast.memory_v1.copy_(st.memory_v1); crd.contrast.memory_v2.copy_(st.memory_v2)
+            crd.contrast.verbose = False
+        bt = synthetic_batch(B, H, n_data=n_data, P=opt.nce_p if variant == "miccai2022" else 1, K=K, seed=800)
+        if variant == "mia2023":
+            bt["grade"] = labels[bt["index"]].long()
+        ranks = [np.random.RandomState(i).choice(np.arange(30, 100), 20, replace=False) for i in range(2)]
+        out = step.step(_tuple(bt), epoch=2, ranks=ranks if variant == "miccai2022" else None)
+        assert not step._fused_head_ok()
+        t = {k: float(out[k]) for k in ("loss", "loss_cls", "loss_div1", "loss_div2", "loss_kd1", "loss_kd2")}
+        if convention == "scaled":
+            expect = t["loss_cls"] + t["loss_div1"] + t["loss_div2"] + t["loss_kd1"] + t["loss_kd2"]
+        elif convention == "unscaled":
+            expect = t["loss_cls"] + opt.alpha * (t["loss_div1"] + t["loss_div2"]) + opt.beta * (t["loss_kd1"] + t["loss_kd2"])
+        else:
+            expect = t["loss_cls"] + opt.alpha * (t["loss_div1"] + t["loss_div2"]) + t["loss_kd1"]
+        print(f"\n{case}: {t} expect {expect!r} rel {abs(t['loss'] - expect) / abs(expect):.2e}")
+        assert abs(t["loss"] - expect) <= 1e-5 * abs(expect), (case, t, expect)
+        assert t["loss_div1"] > 0 and t["loss_kd1"] > 0
+        if kw["num_teachers"] == 1 or convention == "unscaled_div":
+            assert t["loss_kd2"] == 0.0
+        assert (t["loss_div2"] == 0.0) == (kw["num_teachers"] == 1)
+        assert out["scale"] is None
+        assert set(out) == BASE_KEYS | extras, sorted(set(out) ^ (BASE_KEYS | extras))
     finally:
         m.set_precision("bf16")
