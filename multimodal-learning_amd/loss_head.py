@@ -18,14 +18,18 @@ The MIA-2022 stage-2 body ("MIA 2022/train_test_path_multi_distill_v2.py":419-48
 same function of the student feature with two differences: its CRD criterion is the plain v3 bank (one positive, no
 discrepancy selection) whose loss carries the epoch weight e (a device scalar), and GK-Refine keeps an exponential moving
 average of the weights across iterations (`step._mo_state`, the trainer's order [div1, div2, kd1, kd2, CE]) with an optional
-binarisation - ph_gk_finish_momentum."""
+binarisation - ph_gk_finish_momentum.
+
+Two autograd functions - FusedDistillLossFn (MICCAI-2022, MIA-2022: five scalar weights from the Gram matrix) and
+FusedMia2023LossFn (a [5, B] table of per-sample weights, ph_gk_rows) - over three shared pieces: `_logit_losses` (logits,
+KL / CE means and their logit gradients), `_crd_chain` (one CRD term: Embed, normalise, the variant's CRD core as a callable,
+the gradient row of G; the two chains of a step go through DistillStep._two_chains, the second on the head's side stream)
+and `_head_grads` (backward: the gradients of fc_new2 and of the four Embed heads, on that side stream)."""
 import torch
 
 from . import ops
 from ._lib import lib, check, ptr, stream
 from .CL_utils.memory_new import crd_core
-
-_ORDER_INT = (0, 1, 4, 2, 3)      # external [div1, div2, kd1, kd2, CE] -> internal [div1, div2, CE, kd1, kd2] position
 
 
 class LossHeadCtx:
@@ -41,7 +45,7 @@ class LossHeadCtx:
 
 
 def _const(step, name, values, dtype=torch.float32):
-    cache = step.__dict__.setdefault("_lh_const", {})
+    cache = step._lh_const
     key = (name, tuple(values))
     if key not in cache:
         cache[key] = torch.tensor(list(values), device=step.device, dtype=dtype)
@@ -54,6 +58,86 @@ def _grad_dst(p):
     return p.grad
 
 
+def _logit_losses(H, feat, n_loss):
+    """What both heads start with: the student's logits / pred through fc_new2, and ph_logit_losses - the batch means of
+    KL to the fused teacher, KL to the EMA teacher and CE into Lb[0:3] (Lb has `n_loss` entries), their gradients with respect
+    to the logits into dl [3, B, Cc].  -> (feat as fp32, logits, pred, Lb, dl, the two teachers' logits, grade)."""
+    opt, fc = H.step.opt, H.step.model.fc_new2
+    feat = ops._f32(feat).contiguous()
+    B, dev = feat.shape[0], feat.device
+    logits = ops.linear_fwd(feat, fc.weight, fc.bias)
+    pred = torch.empty_like(logits)
+    Lb = torch.empty(n_loss, device=dev, dtype=torch.float32)
+    dl = torch.empty(3, B, logits.shape[1], device=dev, dtype=torch.float32)
+    yts = (ops._f32(H.t_logit).contiguous(), ops._f32(H.ema_logit).contiguous())
+    grade = H.grade.contiguous()
+    check(lib().ph_logit_losses(ptr(logits), ptr(yts[0]), ptr(yts[1]), ptr(grade), ptr(pred), ptr(Lb), ptr(dl), B, logits.shape[1],
+                                float(opt.kd_T), 1.0 / H.bnorm, stream()), "ph_logit_losses")
+    return feat, logits, pred, Lb, dl, yts, grade
+
+
+def _crd_chain(crd, feat, tf, g_row, core):
+    """One CRD term as a function of the student feature: Embed + l2-normalise student and teacher, `core(v1, v2)` ->
+    (loss, d loss / d v1, d loss / d v2, *whatever else it allocated) - the only variant-specific part -, then
+    d loss / d feat = l2norm_bwd(dv1) @ W_embed_s into `g_row`, a row of G.  ~10 short launches on the current stream.
+    -> (what `_head_grads` needs, the core's loss, every other tensor made here: the caller keeps them alive past the join)."""
+    L, st = lib(), stream()
+    B, D = feat.shape
+    dev = feat.device
+    tf = ops._f32(tf).contiguous()
+    es, et = crd.embed_s.linear, crd.embed_t.linear
+    Do = es.weight.shape[0]
+    v1 = torch.empty(B, Do, device=dev, dtype=torch.float32); n1 = torch.empty(B, device=dev)
+    v2 = torch.empty_like(v1); n2 = torch.empty_like(n1)
+    pre_s = ops.linear_fwd(feat, es.weight, es.bias)
+    check(L.ph_l2norm_fwd(ptr(pre_s), ptr(v1), ptr(n1), B, Do, st), "ph_l2norm_fwd")
+    pre_t = ops.linear_fwd(tf, et.weight, et.bias)
+    check(L.ph_l2norm_fwd(ptr(pre_t), ptr(v2), ptr(n2), B, Do, st), "ph_l2norm_fwd")
+    loss, dv1, dv2, *made = core(v1, v2)
+    dps = torch.empty_like(v1)
+    check(L.ph_l2norm_bwd(ptr(dv1), ptr(v1), ptr(n1), ptr(dps), B, Do, st), "ph_l2norm_bwd")
+    ops.sgemm(dps, es.weight, None, g_row, B, D, Do, Do, 1, D, 1)
+    return (dps, dv2, v2, n2, tf), loss, (v1, n1, pre_s, pre_t, dv1, *made)
+
+
+def _head_grads(step, feat, dlt, crd_saved, weights):
+    """The backward's tail: fc_new2's gradients from `dlt` = d loss / d logits, and per CRD criterion k the gradients of its
+    student head from dps * weights[k] and of its teacher head from l2norm_bwd(dv2) * weights[k], written straight into the
+    .grad buffers.  `weights[k]` broadcasts against [B, Do]: one element (scalar GK-Refine weights) or [B, 1] (per sample).
+    Only d loss / d feat feeds the trunk backward, so these 14 short launches go to the head's side stream, beside the trunk
+    backward; DistillStep joins it before the optimiser step (not under data parallelism: the all-reduce of the late
+    gradient slice starts inside the trunk backward and reads them)."""
+    model = step.model
+    L = lib()
+    B, D = feat.shape
+    Cc = dlt.shape[1]
+    hs = step._head_side if step.sync is None else None
+    if hs is not None:
+        hs.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(hs):              # (None: stay on the current stream)
+        stb = stream()
+        ones = ops._ones(B, feat.device)
+        ops.sgemm(dlt, feat, None, _grad_dst(model.fc_new2.weight), Cc, D, B, 1, Cc, D, 1)      # dW2 = dlogit^T feat
+        ops.sgemm(ones, dlt, None, _grad_dst(model.fc_new2.bias), 1, Cc, B, 0, 1, Cc, 1)
+        for crd, (dps, dv2, v2, n2, tf), wk in zip((step.criterion_kd, step.criterion_kd_path), crd_saved, weights):
+            es, et = crd.embed_s.linear, crd.embed_t.linear
+            Do = es.weight.shape[0]
+            gs = dps * wk
+            ops.sgemm(gs, feat, None, _grad_dst(es.weight), Do, D, B, 1, Do, D, 1)
+            ops.sgemm(ones, gs, None, _grad_dst(es.bias), 1, Do, B, 0, 1, Do, 1)
+            dpt = torch.empty_like(v2)
+            check(L.ph_l2norm_bwd(ptr(dv2), ptr(v2), ptr(n2), ptr(dpt), B, Do, stb), "ph_l2norm_bwd")
+            gt = dpt * wk
+            Dt = tf.shape[1]
+            ops.sgemm(gt, tf, None, _grad_dst(et.weight), Do, Dt, B, 1, Do, Dt, 1)
+            ops.sgemm(ones, gt, None, _grad_dst(et.bias), 1, Do, B, 0, 1, Do, 1)
+        if hs is not None:
+            # what was allocated on the main stream and is read here must not be reused before this stream is done with it;
+            # gs / dpt / gt were allocated under this stream and belong to its pool (as do the second chain's saved tensors)
+            for t in (feat, dlt, *weights, *(t for saved in crd_saved for t in saved)):
+                t.record_stream(hs)
+
+
 class FusedDistillLossFn(torch.autograd.Function):
     """loss = lambda_nll * CE + sum_i scale_i * KD_i as a function of the student feature; TERMINAL: backward ignores the
     incoming gradient value (it is the 1.0 of loss.backward()) and writes the gradients of fc_new2 and of the four CRD
@@ -62,61 +146,23 @@ class FusedDistillLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, H):
         step = H.step
-        opt, model = step.opt, step.model
+        opt = step.opt
         L = lib()
         st = stream()
-        feat = ops._f32(feat).contiguous()
+        feat, logits, pred, Lb, dl, _, _ = _logit_losses(H, feat, 5)   # unscaled losses, internal order [div1, div2, CE, kd1, kd2]
         B, D = feat.shape
         dev = feat.device
-        W2, b2 = model.fc_new2.weight, model.fc_new2.bias
+        W2 = step.model.fc_new2.weight
         Cc = W2.shape[0]
-        inv = 1.0 / H.bnorm
-        T = float(opt.kd_T)
-        logits = ops.linear_fwd(feat, W2, b2)
-        pred = torch.empty_like(logits)
-        Lb = torch.empty(5, device=dev, dtype=torch.float32)      # unscaled losses, internal order [div1, div2, CE, kd1, kd2]
-        dl = torch.empty(3, B, Cc, device=dev, dtype=torch.float32)   # d loss / d logits for div1, div2, CE
-        yt1, yt2, grade = ops._f32(H.t_logit).contiguous(), ops._f32(H.ema_logit).contiguous(), H.grade.contiguous()
-        check(L.ph_logit_losses(ptr(logits), ptr(yt1), ptr(yt2), ptr(grade), ptr(pred), ptr(Lb), ptr(dl), B, Cc, T, inv, st),
-              "ph_logit_losses")
         G = torch.empty(5, B, D, device=dev, dtype=torch.float32)
         ops.sgemm(dl, W2, None, G, 3 * B, D, Cc, Cc, 1, D, 1)          # rows 0..2: d{div1, div2, CE}/d feat = dlogit @ W2
-        crd_saved = [None, None]
-
-        def crd_chain(k, crd, tf, rk):
-            stc = stream()
-            tf = ops._f32(tf).contiguous()
-            es, et = crd.embed_s.linear, crd.embed_t.linear
-            v1 = torch.empty(B, es.weight.shape[0], device=dev, dtype=torch.float32); n1 = torch.empty(B, device=dev)
-            v2 = torch.empty_like(v1); n2 = torch.empty_like(n1)
-            pre_s = ops.linear_fwd(feat, es.weight, es.bias)
-            check(L.ph_l2norm_fwd(ptr(pre_s), ptr(v1), ptr(n1), B, v1.shape[1], stc), "ph_l2norm_fwd")
-            pre_t = ops.linear_fwd(tf, et.weight, et.bias)
-            check(L.ph_l2norm_fwd(ptr(pre_t), ptr(v2), ptr(n2), B, v2.shape[1], stc), "ph_l2norm_fwd")
-            _, dv1, dv2 = crd_core(v1, v2, crd.contrast, H.index, H.sample_idx, rk, False, loss_out=Lb[3 + k])
-            dps = torch.empty_like(v1)
-            check(L.ph_l2norm_bwd(ptr(dv1), ptr(v1), ptr(n1), ptr(dps), B, v1.shape[1], stc), "ph_l2norm_bwd")
-            Do = es.weight.shape[0]
-            ops.sgemm(dps, es.weight, None, G[3 + k], B, D, Do, Do, 1, D, 1)      # d CRD_k / d feat
-            crd_saved[k] = (dps, dv2, v2, n2, tf)
-            return (tf, v1, n1, v2, n2, pre_s, pre_t, dv1, dv2, dps)
-
         chains = ((step.criterion_kd, H.fuse_feat, H.r1), (step.criterion_kd_path, H.ema_feat, H.r2))
-        # the two CRD terms are independent chains of ~10 short launches (two banks, two pairs of heads): the second runs on a
-        # side stream beside the first (not under data parallelism: its all-gathers must keep one issue order on every rank)
-        hs = step._head_stream() if step.sync is None and hasattr(step, "_head_stream") else None
-        if hs is not None:
-            main_s = torch.cuda.current_stream()
-            hs.wait_stream(main_s)
-            with torch.cuda.stream(hs):
-                made = crd_chain(1, *chains[1])
-                for t in made:
-                    t.record_stream(main_s)
-            crd_chain(0, *chains[0])
-            main_s.wait_stream(hs)
-        else:
-            for k, (crd, tf, rk) in enumerate(chains):
-                crd_chain(k, crd, tf, rk)
+
+        def chain(k):                                                  # row 3 + k: d CRD_k / d feat
+            crd, tf, rk = chains[k]
+            return _crd_chain(crd, feat, tf, G[3 + k], lambda v1, v2: crd_core(v1, v2, crd.contrast, H.index, H.sample_idx, rk,
+                                                                               False, loss_out=Lb[3 + k]))
+        done = step._two_chains(lambda: chain(0), lambda: chain(1))
         gram = torch.empty(25, device=dev, dtype=torch.float32)
         check(L.ph_gram(ptr(G), ptr(gram), 5, B * D, st), "ph_gram")
         if step.sync is not None:
@@ -140,16 +186,12 @@ class FusedDistillLossFn(torch.autograd.Function):
         w, total, scaled = fin[5:10], fin[10], fin[11:16]
         H.out = dict(loss_cls=scaled[2], loss_div1=scaled[0], loss_div2=scaled[1], loss_kd1=scaled[3], loss_kd2=scaled[4],
                      scale=fin[16:21], logit_path=logits, pred_path=pred)
-        ctx.H, ctx.feat, ctx.dl, ctx.G, ctx.w, ctx.crd_saved = H, feat, dl, G, w, crd_saved
+        ctx.H, ctx.feat, ctx.dl, ctx.G, ctx.w, ctx.crd_saved = H, feat, dl, G, w, [c[0] for c in done]
         return total
 
     @staticmethod
     def backward(ctx, g):
         H, feat, dl, G, w = ctx.H, ctx.feat, ctx.dl, ctx.G, ctx.w
-        step = H.step
-        model = step.model
-        L = lib()
-        st = stream()
         B, D = feat.shape
         dev = feat.device
         Cc = dl.shape[2]
@@ -157,37 +199,7 @@ class FusedDistillLossFn(torch.autograd.Function):
         ops.sgemm(w, G, None, dfeat, 1, B * D, 5, 5, 1, B * D, 1)                       # sum_i w_i G_i
         dlt = torch.empty(B, Cc, device=dev, dtype=torch.float32)
         ops.sgemm(w, dl, None, dlt, 1, B * Cc, 3, 3, 1, B * Cc, 1)                      # w[0:3] . {dl_div1, dl_div2, dl_CE}
-        # Only dfeat feeds the trunk backward: the gradients of fc_new2 and of the four CRD heads (14 short launches) go to the
-        # side stream, beside the trunk backward; DistillStep joins it before the optimiser step
-        # (not under data parallelism: the all-reduce of the late gradient slice starts inside the trunk backward and reads them)
-        hs = step._head_stream() if step.sync is None and hasattr(step, "_head_stream") else None
-        main_s = torch.cuda.current_stream()
-        if hs is not None:
-            hs.wait_stream(main_s)
-        with torch.cuda.stream(hs if hs is not None else main_s):
-            stb = stream()
-            ones = ops._ones(B, dev)
-            ops.sgemm(dlt, feat, None, _grad_dst(model.fc_new2.weight), Cc, D, B, 1, Cc, D, 1)      # dW2 = dlogit^T feat
-            ops.sgemm(ones, dlt, None, _grad_dst(model.fc_new2.bias), 1, Cc, B, 0, 1, Cc, 1)
-            for k, (crd, (dps, dv2, v2, n2, tf)) in enumerate(zip((step.criterion_kd, step.criterion_kd_path), ctx.crd_saved)):
-                wk = w[3 + k:4 + k]
-                es, et = crd.embed_s.linear, crd.embed_t.linear
-                Do = es.weight.shape[0]
-                gs = dps * wk
-                ops.sgemm(gs, feat, None, _grad_dst(es.weight), Do, D, B, 1, Do, D, 1)
-                ops.sgemm(ones, gs, None, _grad_dst(es.bias), 1, Do, B, 0, 1, Do, 1)
-                dpt = torch.empty_like(v2)
-                check(L.ph_l2norm_bwd(ptr(dv2), ptr(v2), ptr(n2), ptr(dpt), B, v2.shape[1], stb), "ph_l2norm_bwd")
-                gt = dpt * wk
-                Dt = tf.shape[1]
-                ops.sgemm(gt, tf, None, _grad_dst(et.weight), Do, Dt, B, 1, Do, Dt, 1)
-                ops.sgemm(ones, gt, None, _grad_dst(et.bias), 1, Do, B, 0, 1, Do, 1)
-            if hs is not None:
-                for t in (dlt, feat, w, dl):
-                    t.record_stream(hs)
-                for dps, dv2, v2, n2, tf in ctx.crd_saved:
-                    for t in (dps, dv2, v2, n2, tf):
-                        t.record_stream(hs)
+        _head_grads(H.step, feat, dlt, ctx.crd_saved, (w[3:4], w[4:5]))
         ctx.crd_saved = None
         return dfeat, None
 
@@ -205,27 +217,21 @@ class FusedMia2023LossFn(torch.autograd.Function):
     def forward(ctx, feat, H):
         from .mia2023 import assign_sample_weights
         step = H.step
-        opt, model = step.opt, step.model
+        opt = step.opt
         L = lib()
         st = stream()
-        feat = ops._f32(feat).contiguous()
+        if feat.shape[1] not in (64, 128, 256):      # before anything runs: the CRD chains below update the banks
+            raise ValueError("MIA-2023 loss head: feature rows of width %d; ph_gk_rows is built for the widths [64, 128, 256]"
+                             % feat.shape[1])
+        # Lb: batch means of KL to the fused teacher, to the EMA teacher, CE; dl: d (those means) / d logits
+        feat, logits, pred, Lb, dl, yts, grade = _logit_losses(H, feat, 3)
         B, D = feat.shape
-        if D not in (64, 128, 256):      # before anything runs: the CRD chains below update the banks
-            raise ValueError("MIA-2023 loss head: feature rows of width %d; ph_gk_rows is built for the widths [64, 128, 256]" % D)
         dev = feat.device
-        W2, b2 = model.fc_new2.weight, model.fc_new2.bias
+        W2 = step.model.fc_new2.weight
         Cc = W2.shape[0]
         inv = 1.0 / H.bnorm
         T = float(opt.kd_T)
         a, b, lam = float(opt.alpha), float(opt.beta), float(opt.lambda_nll)
-        logits = ops.linear_fwd(feat, W2, b2)
-        pred = torch.empty_like(logits)
-        Lb = torch.empty(3, device=dev, dtype=torch.float32)           # batch means: KL to the fused teacher, to the EMA teacher, CE
-        dl = torch.empty(3, B, Cc, device=dev, dtype=torch.float32)    # d (those means) / d logits
-        yts = (ops._f32(H.t_logit).contiguous(), ops._f32(H.ema_logit).contiguous())
-        grade = H.grade.contiguous()
-        check(L.ph_logit_losses(ptr(logits), ptr(yts[0]), ptr(yts[1]), ptr(grade), ptr(pred), ptr(Lb), ptr(dl), B, Cc, T, inv, st),
-              "ph_logit_losses")
         rows_div = torch.empty(2, B, device=dev, dtype=torch.float32)   # per-sample KL (:349-350)
         for k in range(2):
             check(L.ph_kl_rows_fwd(ptr(logits), ptr(yts[k]), ptr(rows_div[k]), B, Cc, T, st), "ph_kl_rows_fwd")
@@ -235,45 +241,19 @@ class FusedMia2023LossFn(torch.autograd.Function):
         G = torch.empty(5, B, D, device=dev, dtype=torch.float32)       # the trainer's order [div1, div2, kd1, kd2, CE]
         ops.sgemm(dl[0:2], W2, None, G[0:2], 2 * B, D, Cc, Cc, 1, D, 1)
         ops.sgemm(dl[2], W2, None, G[4], B, D, Cc, Cc, 1, D, 1)
-        lossp = [None, None]
-        crd_saved = [None, None]
-
-        def crd_chain(k, crd, tf):
-            stc = stream()
-            tf = ops._f32(tf).contiguous()
-            es, et = crd.embed_s.linear, crd.embed_t.linear
-            v1 = torch.empty(B, es.weight.shape[0], device=dev, dtype=torch.float32); n1 = torch.empty(B, device=dev)
-            v2 = torch.empty_like(v1); n2 = torch.empty_like(n1)
-            pre_s = ops.linear_fwd(feat, es.weight, es.bias)
-            check(L.ph_l2norm_fwd(ptr(pre_s), ptr(v1), ptr(n1), B, v1.shape[1], stc), "ph_l2norm_fwd")
-            pre_t = ops.linear_fwd(tf, et.weight, et.bias)
-            check(L.ph_l2norm_fwd(ptr(pre_t), ptr(v2), ptr(n2), B, v2.shape[1], stc), "ph_l2norm_fwd")
-            idx1, knn = crd.neighbor_columns(B, v1.shape[1], grade, H.sample_idx)
-            rows, dv1, dv2 = crd_core(v1, v2, crd.contrast, H.index, idx1, None, True)     # rows: (s + t) losses / bsz per sample
-            crd.contrast.last.update(knn)
-            dps = torch.empty_like(v1)
-            check(L.ph_l2norm_bwd(ptr(dv1), ptr(v1), ptr(n1), ptr(dps), B, v1.shape[1], stc), "ph_l2norm_bwd")
-            Do = es.weight.shape[0]
-            ops.sgemm(dps, es.weight, None, G[2 + k], B, D, Do, Do, 1, D, 1)              # d rows[b] / d feat[b]
-            lossp[k] = rows
-            crd_saved[k] = (dps, dv2, v2, n2, tf)
-            return (tf, v1, n1, v2, n2, pre_s, pre_t, dv1, dv2, dps, rows, idx1) + tuple(knn.values())
-
         chains = ((step.criterion_kd, H.fuse_feat), (step.criterion_kd_path, H.ema_feat))
-        hs = step._head_stream() if step.sync is None and hasattr(step, "_head_stream") else None
-        if hs is not None:
-            main_s = torch.cuda.current_stream()
-            hs.wait_stream(main_s)
-            with torch.cuda.stream(hs):
-                made = crd_chain(1, *chains[1])
-                for t in made:
-                    if torch.is_tensor(t):
-                        t.record_stream(main_s)
-            crd_chain(0, *chains[0])
-            main_s.wait_stream(hs)
-        else:
-            for k, (crd, tf) in enumerate(chains):
-                crd_chain(k, crd, tf)
+
+        def chain(k):                                                   # row 2 + k: d rows[b] / d feat[b]
+            crd, tf = chains[k]
+
+            def core(v1, v2):
+                idx1, knn = crd.neighbor_columns(B, v1.shape[1], grade, H.sample_idx)
+                rows, dv1, dv2 = crd_core(v1, v2, crd.contrast, H.index, idx1, None, True)     # rows: (s + t) losses / bsz per sample
+                crd.contrast.last.update(knn)
+                return (rows, dv1, dv2, idx1, *knn.values())
+            return _crd_chain(crd, feat, tf, G[2 + k], core)
+        done = step._two_chains(lambda: chain(0), lambda: chain(1))
+        lossp = [c[1] for c in done]
         s = torch.empty(B, 5, device=dev, dtype=torch.float32)
         check(L.ph_gk_rows(ptr(G), 5, B, D, 1 if opt.use_grads_thresh == "True" else 0, float(opt.grads_thresh), ptr(s), st),
               "ph_gk_rows")
@@ -291,49 +271,14 @@ class FusedMia2023LossFn(torch.autograd.Function):
                      loss_kd1=(ws[0] * lossp[0]).sum(), loss_kd2=(ws[1] * lossp[1]).sum(),
                      rows_div1=rows_div[0], rows_kd1=ws[0] * lossp[0] * H.bnorm, w1=ws[0].view(-1, 1), w2=ws[1].view(-1, 1),
                      scale=mean_scale, logit_path=logits, pred_path=pred)
-        ctx.H, ctx.feat, ctx.dl, ctx.G, ctx.Cf, ctx.crd_saved = H, feat, dl, G, Cf, crd_saved
+        ctx.H, ctx.feat, ctx.dl, ctx.G, ctx.Cf, ctx.crd_saved = H, feat, dl, G, Cf, [c[0] for c in done]
         return total
 
     @staticmethod
     def backward(ctx, g):
         H, feat, dl, G, Cf = ctx.H, ctx.feat, ctx.dl, ctx.G, ctx.Cf
-        step = H.step
-        model = step.model
-        L = lib()
-        B, D = feat.shape
-        dev = feat.device
-        Cc = dl.shape[2]
         dfeat = (Cf.unsqueeze(-1) * G).sum(0)
         dlt = Cf[0].unsqueeze(-1) * dl[0] + Cf[1].unsqueeze(-1) * dl[1] + Cf[4].unsqueeze(-1) * dl[2]
-        hs = step._head_stream() if step.sync is None and hasattr(step, "_head_stream") else None
-        main_s = torch.cuda.current_stream()
-        if hs is not None:
-            hs.wait_stream(main_s)
-        with torch.cuda.stream(hs if hs is not None else main_s):
-            stb = stream()
-            ones = ops._ones(B, dev)
-            ops.sgemm(dlt, feat, None, _grad_dst(model.fc_new2.weight), Cc, D, B, 1, Cc, D, 1)      # dW2 = dlogit^T feat
-            ops.sgemm(ones, dlt, None, _grad_dst(model.fc_new2.bias), 1, Cc, B, 0, 1, Cc, 1)
-            made = [dlt]
-            for k, (crd, (dps, dv2, v2, n2, tf)) in enumerate(zip((step.criterion_kd, step.criterion_kd_path), ctx.crd_saved)):
-                wk = Cf[2 + k].unsqueeze(-1)
-                es, et = crd.embed_s.linear, crd.embed_t.linear
-                Do = es.weight.shape[0]
-                gs = dps * wk
-                ops.sgemm(gs, feat, None, _grad_dst(es.weight), Do, D, B, 1, Do, D, 1)
-                ops.sgemm(ones, gs, None, _grad_dst(es.bias), 1, Do, B, 0, 1, Do, 1)
-                dpt = torch.empty_like(v2)
-                check(L.ph_l2norm_bwd(ptr(dv2), ptr(v2), ptr(n2), ptr(dpt), B, v2.shape[1], stb), "ph_l2norm_bwd")
-                gt = dpt * wk
-                Dt = tf.shape[1]
-                ops.sgemm(gt, tf, None, _grad_dst(et.weight), Do, Dt, B, 1, Do, Dt, 1)
-                ops.sgemm(ones, gt, None, _grad_dst(et.bias), 1, Do, B, 0, 1, Do, 1)
-                made += [gs, dpt, gt]
-            if hs is not None:
-                for t in [feat, Cf, dl] + made:
-                    t.record_stream(hs)
-                for dps, dv2, v2, n2, tf in ctx.crd_saved:
-                    for t in (dps, dv2, v2, n2, tf):
-                        t.record_stream(hs)
+        _head_grads(H.step, feat, dlt, ctx.crd_saved, (Cf[2].unsqueeze(-1), Cf[3].unsqueeze(-1)))
         ctx.crd_saved = None
         return dfeat, None

@@ -530,6 +530,7 @@ class DistillStep:
         self._loader_bt = self._sample_idx_buf = self._capture_pre = None
         self._e_dev = None        # the epoch weight (mia2022) / re-weighting switch (mia2023) as a persistent device scalar
         self._mo_init = None
+        self._lh_const = {}       # loss_head._const: small constant device vectors by value (not part of state_dict)
         self.opt = opt
         self.device = torch.device(device)
         self.sync = sync
@@ -612,13 +613,14 @@ class DistillStep:
                 # (stamp 11: the moment the first phase starts - bench.py's `comm` reports the window it has to hide in)
                 self.model._grad_ready_hook = lambda: (self._stamp(11), self.sync.begin_grad_slice(self.optimizer.flat, lo))[1]
 
-    def _head_stream(self):
-        return self._head_side
-
     def _two_chains(self, f1, f2):
-        """Two independent launch chains (the two CRD criteria: separate banks, separate heads): the second on the head's side
-        stream, joined before anything reads its result; autograd replays each backward on the stream its forward used.  One
-        stream under data parallelism (the criteria's all-gathers must keep one issue order on every rank)."""
+        """Two independent launch chains of ~10 short launches (the two CRD criteria: separate banks, separate heads), of the
+        generic path and of the fused loss head alike: the second is issued first, on the head's side stream, the first on the
+        current stream, then the join - before anything reads the second's result; autograd replays each backward on the
+        stream its forward used.  One stream, f1 then f2, under data parallelism (the criteria's all-gathers must keep one
+        issue order on every rank).  Every tensor f2 hands back (nested tuples included) was allocated in the side stream's
+        pool and is used on this one from here on: each is recorded on it - after the join; recording before it is
+        equivalent, the record only has to precede the tensor's release."""
         hs = self._head_side if self.sync is None else None
         if hs is None:
             return f1(), f2()
@@ -628,9 +630,13 @@ class DistillStep:
             r2 = f2()
         r1 = f1()
         main.wait_stream(hs)
-        for t in (r2 if isinstance(r2, (tuple, list)) else (r2,)):
+        todo = [r2]
+        while todo:
+            t = todo.pop()
             if torch.is_tensor(t):
                 t.record_stream(main)
+            elif isinstance(t, (tuple, list)):
+                todo.extend(t)
         return r1, r2
 
     def _stamp(self, k):
@@ -688,9 +694,9 @@ class DistillStep:
             self.optimizer.zero_grad()                                                                      # :326
             self._stamp(3)
             loss.backward()                                                                                 # :327
-            # the heads' weight gradients (loss_head.py) - joined only where loss_head forks that stream (`hs = ... if
-            # step.sync is None`): under data parallelism it never joins the capture, and waiting on a stream outside a
-            # capture invalidates the capture (hipErrorStreamCaptureIsolation)
+            # the heads' weight gradients (loss_head._head_grads) - joined only where it forks that stream (`sync is None`):
+            # under data parallelism it never joins the capture, and waiting on a stream outside a capture invalidates the
+            # capture (hipErrorStreamCaptureIsolation)
             if self._head_side is not None and self.sync is None:
                 torch.cuda.current_stream().wait_stream(self._head_side)
             self._stamp(5)

@@ -44,6 +44,33 @@ def grad_row(R, ref, truth, got, atol, rtol, what):
     R.rows.append((what + " [golden %.2e | truth %.2e | golden-truth %.2e]" % (e_ref, e_tru, d_ref), 0.0 if ok else e_ref, mx, tol))
 
 
+def _mk_variant_step(variant, opt):
+    """A MIA-2022 / MIA-2023 step at n_data 256 / 512 (three classes, bank row i of class i % 3) with seeded weights and banks
+    -> (step, n_data, labels or None)."""
+    import multimodal_learning_amd as m
+    from oracle import weights as W
+    from oracle.variants import CRDv3State, CRDv10State
+    if variant == "mia2022":
+        n_data, labels = 256, None
+        step = m.DistillStep(opt, n_data, device="cuda", variant="mia2022")
+    else:
+        n_data = 512
+        labels = torch.arange(n_data) % 3
+        class_idx = [np.nonzero((labels == c).numpy())[0] for c in range(3)]
+        step = m.DistillStep(opt, n_data, device="cuda", variant="mia2023", train_class_idx=class_idx)
+    step.model.load_state_dict(W.make_state_dict(W.student_shapes(), 1))
+    step.ema_model.load_state_dict(W.make_state_dict(W.student_shapes(), 2))
+    step.fix_model.load_state_dict(W.make_state_dict(W.teacher_shapes(320), 3))
+    for i, crd in enumerate((step.criterion_kd, step.criterion_kd_path)):
+        crd.embed_s.load_state_dict(W.make_state_dict(W.embed_shapes(), 10 + 2 * i))
+        crd.embed_t.load_state_dict(W.make_state_dict(W.embed_shapes(), 11 + 2 * i))
+        st = (CRDv3State(n_data, K=opt.nce_k, seed=20 + i) if variant == "mia2022" else
+              CRDv10State(n_data, labels, K=opt.nce_k, seed=20 + i))
+        crd.contrast.memory_v1.copy_(st.memory_v1); crd.contrast.memory_v2.copy_(st.memory_v2)
+        crd.contrast.verbose = False
+    return step, n_data, labels
+
+
 def _tuple(bt):
     B = bt["x_path"].shape[0]
     return ((bt["x_path"], bt["ema_x_path"]), torch.zeros(B), bt["x_omic"], torch.zeros(B), torch.zeros(B),
@@ -710,26 +737,15 @@ def test_fused_loss_head_equals_generic_autograd_path_mia2022(grads_thresh):
     GK-Refine through ph_gk_finish_momentum) against its generic autograd path (DistillStep._generic_loss over train_step._gk_momentum_scale), two consecutive
     steps so that the moving average of the weights is exercised, plain and binarised (`grads_thresh`) cosine sums."""
     import multimodal_learning_amd as m
-    from oracle import weights as W
     from oracle.step import default_opt, synthetic_batch
-    from oracle.variants import CRDv3State
-    n_data, K = 256, 64
+    K = 64
     m.set_precision("bf16x6")
     try:
         res = {}
         for fused in (True, False):
             opt = default_opt(nce_k=K, grads_m=0.9, grads_thresh=grads_thresh, thresh=0.1, niter_decay=10)
             opt.fused_loss_head = fused
-            step = m.DistillStep(opt, n_data, device="cuda", variant="mia2022")
-            step.model.load_state_dict(W.make_state_dict(W.student_shapes(), 1))
-            step.ema_model.load_state_dict(W.make_state_dict(W.student_shapes(), 2))
-            step.fix_model.load_state_dict(W.make_state_dict(W.teacher_shapes(320), 3))
-            for i, crd in enumerate((step.criterion_kd, step.criterion_kd_path)):
-                crd.embed_s.load_state_dict(W.make_state_dict(W.embed_shapes(), 10 + 2 * i))
-                crd.embed_t.load_state_dict(W.make_state_dict(W.embed_shapes(), 11 + 2 * i))
-                st = CRDv3State(n_data, K=K, seed=20 + i)
-                crd.contrast.memory_v1.copy_(st.memory_v1); crd.contrast.memory_v2.copy_(st.memory_v2)
-                crd.contrast.verbose = False
+            step, n_data, _ = _mk_variant_step("mia2022", opt)
             rec = []
             for it in range(2):
                 bt = synthetic_batch(8, 64, n_data=n_data, P=1, K=K, seed=400 + it)
@@ -767,12 +783,8 @@ def test_fused_loss_head_equals_generic_autograd_path_mia2023(use_thresh):
     per-sample GK-Refine weights from the closed-form gradient rows) against its generic autograd path
     (DistillStep._generic_loss), with the re-weighting switched on, binarised and ReLU-ed cosine sums."""
     import multimodal_learning_amd as m
-    from oracle import weights as W
     from oracle.step import default_opt, synthetic_batch
-    from oracle.variants import CRDv10State
-    n_data, K, B = 512, 64, 8
-    labels = torch.arange(n_data) % 3
-    class_idx = [np.nonzero((labels == c).numpy())[0] for c in range(3)]
+    K, B = 64, 8
     m.set_precision("bf16x6")
     try:
         res = {}
@@ -781,16 +793,7 @@ def test_fused_loss_head_equals_generic_autograd_path_mia2023(use_thresh):
                               max_discrep=2.0, use_grads_thresh=use_thresh, grads_thresh=0.1, loss_weighting="GK_refine",
                               batch_size=B)
             opt.fused_loss_head = fused
-            step = m.DistillStep(opt, n_data, device="cuda", variant="mia2023", train_class_idx=class_idx)
-            step.model.load_state_dict(W.make_state_dict(W.student_shapes(), 1))
-            step.ema_model.load_state_dict(W.make_state_dict(W.student_shapes(), 2))
-            step.fix_model.load_state_dict(W.make_state_dict(W.teacher_shapes(320), 3))
-            for i, crd in enumerate((step.criterion_kd, step.criterion_kd_path)):
-                crd.embed_s.load_state_dict(W.make_state_dict(W.embed_shapes(), 10 + 2 * i))
-                crd.embed_t.load_state_dict(W.make_state_dict(W.embed_shapes(), 11 + 2 * i))
-                st = CRDv10State(n_data, labels, K=K, seed=20 + i)
-                crd.contrast.memory_v1.copy_(st.memory_v1); crd.contrast.memory_v2.copy_(st.memory_v2)
-                crd.contrast.verbose = False
+            step, n_data, labels = _mk_variant_step("mia2023", opt)
             bt = synthetic_batch(B, 64, n_data=n_data, P=1, K=K, seed=500)
             bt["grade"] = labels[bt["index"]].long()
             out = step.step(_tuple(bt), epoch=2)
@@ -1154,6 +1157,69 @@ def test_multi_stream_step_equals_one_stream_step_and_phase_markers_are_ordered(
     assert (t[[0, 1, 2, 3, 4, 5, 6, 8, 9]] > 0).all()
     assert t[0] <= t[1] <= t[2] <= t[3] <= t[4] <= t[5] <= t[6]      # pack, student fwd, join, head fwd, head bwd, bwd, Adam
     assert t[0] <= t[8] <= t[2] and t[0] <= t[9] <= t[2]              # both teachers finish before the join
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["mia2022", "mia2023"])
+def test_multi_stream_fused_head_equals_one_stream_head_mia_variants(variant):
+    """The counterpart of the test above for the other two fused loss heads (loss_head.py: MIA-2022 momentum GK-Refine,
+    MIA-2023 per-sample head): the second CRD chain and the heads' weight gradients run on the head's side stream.  Steps
+    built as in test_fused_loss_head_equals_generic_autograd_path_mia2022 / _mia2023, perf mode; enable_graph() replays from
+    the third step on, so each arm runs its two eager steps and then two steps from the captured graph.  Two multi-stream
+    runs agree bitwise in everything (a missing dependency would show as run-to-run noise); the one-stream run
+    (`overlap_teachers` / `overlap_head` off, `_no_bwd_overlap`) agrees bitwise in the FIRST step's head outputs - same
+    forward, same head; later steps see weight gradients summed from other chunks."""
+    import multimodal_learning_amd as m
+    from oracle.step import default_opt, synthetic_batch
+    m.set_precision("bf16")
+    K, B, n_steps = 64, 8, 4
+    head_keys = ("loss", "loss_kd1", "loss_kd2", "scale", "logit_path")
+
+    def run(streams):
+        if variant == "mia2022":
+            opt = default_opt(nce_k=K, grads_m=0.9, grads_thresh="False", thresh=0.1, niter_decay=10)
+        else:
+            opt = default_opt(nce_k=K, nce_p=4, pos_extra="neighbors", neg_mode="all_others", start_reweight=0, discrep_scale=1,
+                              max_discrep=2.0, use_grads_thresh="True", grads_thresh=0.1, loss_weighting="GK_refine",
+                              batch_size=B)
+        opt.fused_loss_head = True
+        opt.overlap_teachers, opt.overlap_head = streams, streams
+        step, n_data, labels = _mk_variant_step(variant, opt)
+        step.model._no_bwd_overlap = not streams
+        step.enable_graph()
+        losses, first = [], None
+        for it in range(n_steps):
+            bt = synthetic_batch(B, 64, n_data=n_data, P=1, K=K, seed=(400 if variant == "mia2022" else 500) + it)
+            if labels is not None:
+                bt["grade"] = labels[bt["index"]].long()
+            out = step.step(_tuple(bt), epoch=3 + it if variant == "mia2022" else 2)
+            if it == 0:
+                assert step._fused_head_ok()
+                first = {k: out[k].detach().clone() for k in head_keys}
+            losses.append(out["loss"].item())
+        torch.cuda.synchronize()
+        state = {"model." + k: v.clone() for k, v in step.model.state_dict().items()}
+        for name, crd in (("kd", step.criterion_kd), ("kd_path", step.criterion_kd_path)):
+            state[name + ".memory_v1"] = crd.contrast.memory_v1.clone()
+        if variant == "mia2022":
+            state["_mo_state"] = step._mo_state.clone()
+        return losses, first, state, step
+
+    la, fa, _, _ = run(False)
+    lb, fb, sb, step = run(True)
+    lc, fc, sc, _ = run(True)
+    assert step._slots and step._slots[0]["graph"] is not None, "the multi-stream step was not captured"
+    print(f"\n{variant}: losses one stream {la}, multi-stream {lb} / {lc}")
+    # no race: the multi-stream trajectory is bitwise reproducible
+    assert lb == lc, (lb, lc)
+    for k in sb:
+        assert torch.equal(sb[k], sc[k]), k
+    for k in head_keys:
+        assert torch.equal(fb[k], fc[k]), k
+    # against one stream: the first step's head outputs bitwise
+    for k in head_keys:
+        assert torch.equal(fa[k], fb[k]), (k, fa[k], fb[k])
+    assert all(np.isfinite(la)) and all(np.isfinite(lb))
 
 
 BRANCH_NAMES = ["t1_fuse_crd", "t1_ema_crd", "t1_fuse_kd", "t1_ema_kd", "t2_kd_gk", "t2_kd_sum", "t2_crd_sum"]
