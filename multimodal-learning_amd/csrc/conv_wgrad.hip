@@ -13,6 +13,10 @@
 #include "ph_kernels.h"
 #include "tap_common.h"
 
+// PH_WG_LEAN=0 (ph_debug_set_wg_lean(0)): the perf-mode weight gradients run the loop of wgrad_kernel<.., LEAN = false> - bitwise the
+// same gradients
+PH_SWITCH(wg_lean, "PH_WG_LEAN")
+
 namespace {
 
 // 32-B piece swizzle of a [pixel][64 ch] bf16 image (128-B rows): makes the 4-row tr-reads conflict-free
@@ -30,6 +34,8 @@ struct WgCfg {
   // perf mode: two LDS buffers (tile t+1 lands by LDS-DMA while tile t feeds the MFMAs)
   static constexpr int LDS_BYTES = SPLIT ? (D_BYTES + X_BYTES) * NP : 2 * (D_BYTES + X_BYTES);
   static constexpr int NT = KS * KS;
+  // LDS-DMA pieces (1 KiB = 8 pixel rows, one wave-instruction) per wave and tile: dz, halo (the last one may be a partial round)
+  static constexpr int NDP = BM * 8 / 256, NHP = (HPP * 8 + 255) / 256, NPIECES = NDP + NHP;
 };
 
 // stage 8 channels of one pixel into plane 0 (bf16) or into the 3 split planes (fp32 source)
@@ -62,11 +68,15 @@ __device__ __forceinline__ bf16x8 tr_pair(const unsigned char* base, int off0, i
   return u.v;
 }
 
-template <typename T, int S, int TH, int KS>
+// LEAN (perf mode only; PH_WG_LEAN, default on): the halo-row-major MFMA stream and the precomputed LDS-DMA issue below.  LEAN =
+// false is the loop as it was - the A/B arm and the reference of tests/test_gpu_wgrad_lean.py; both arms write bitwise the same slab.
+// (A template parameter, i.e. two kernels: a run-time flag inside one kernel would make each arm pay for the other's registers.)
+template <typename T, int S, int TH, int KS, bool LEAN>
 __global__ __launch_bounds__(256) void wgrad_kernel(PhWgrad p) {
   using C = WgCfg<T, S, TH, KS>;
   constexpr bool SPLIT = C::SPLIT, HPM = C::HPM;
-  constexpr int TW = C::TW, BM = C::BM, HPW = C::HPW, HP = C::HP, NT = C::NT, NP = C::NP;
+  constexpr int TW = C::TW, BM = C::BM, HPH = C::HPH, HPW = C::HPW, HP = C::HP, NT = C::NT, NP = C::NP;
+  static_assert(!(LEAN && SPLIT), "the lean loop is a perf-mode (LDS-DMA) loop");
   typedef typename std::conditional<HPM, f16, T>::type TI;       // element type as the staging code addresses it
   constexpr int EW = HPM ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -196,6 +206,56 @@ __global__ __launch_bounds__(256) void wgrad_kernel(PhWgrad p) {
       }
     }
   };
+  // ---- LEAN: the same 72 MFMAs walked by HALO ROW.  The x fragment of (k-step kk, tap kh, kw) is halo pixel (kk + kh) HPW + kw + u:
+  // it depends on h = kk + kh and kw only, so compute_p reads each of the (TH + 2) * 3 = 30 distinct fragments up to three times (72
+  // read pairs + 8 for dz = 160 ds_read_b64_tr_b16 per tile; the LDS allowed 320 cycles per k-step against 288 of MFMA).  Here fragment
+  // j = 3 h + kw is read ONCE (30 + 8 pairs = 76 reads) and feeds acc[3 kh + kw] += A(h - kh) * B(h, kw) for every kh with 0 <= h - kh <
+  // TH: 3 / 6 / 9 ... 9 / 6 / 3 MFMAs per halo row.  Every accumulator still receives its TH products in increasing kk from the same
+  // operand bytes, so the slab is bitwise compute_p's.  What that loop learned is kept: an address is one of the five base registers
+  // + an immediate (swizzle bit = bit 1 of the halo pixel = bit1(hoff) ^ bit1(u) ^ (bit0(hoff) & bit0(u)), hoff = h HPW + kw), the x
+  // reads run three fragments (>= 3 MFMAs, 9 in the full rows) ahead in a ring of four, A(h + 1) is read in the middle of row h into
+  // a ring of four (A(h - 3) was last used in row h - 1), MFMAs are asm volatile behind sched_barriers, one body for both buffers.
+  // dma(k): piece k of the NEXT item's operands, one behind each of the first ten MFMAs (below: why no read of this buffer can see
+  // one).  The slots are early on purpose: a piece issued late in the stream has not landed at the vmcnt(0) that ends the tile.  One
+  // piece every 7th MFMA (the last one 5 MFMAs before the wait) cost 0.1 - 0.2 ms of the 22.4 ms B = 256 trunk against these slots,
+  // one every 3rd measured the same as these; the B = 64 step did not tell the three apart (profiles/EXPERIMENTS.md).
+  auto compute_l = [&](const int boff, auto dma) __attribute__((always_inline)) {
+    if constexpr (PIPE && LEAN) {
+      const unsigned char* dD = smem + boff;
+      const unsigned char* dX = dD + C::D_BYTES;
+      constexpr int NF = (TH + 2) * 3, LF = 3, DMA_FIRST = 0, DMA_STEP = 1;
+      bf16x8 af[4], bfr[4];
+      auto ldA = [&](const int kk) { return tr_pair(dD, baseA + kk * 2048, baseA + 512 + kk * 2048); };
+      auto ldB = [&](const int j) {
+        const int hoff = (j / 3) * HPW + (j % 3);
+        const int flip = (hoff >> 1) & 1;
+        const int base = (hoff & 1) ? (flip ? bO1 : bO0) : (flip ? bE1 : bE0);
+        return tr_pair(dX, base + hoff * 128, base + hoff * 128 + 512);
+      };
+      af[0] = ldA(0);
+#pragma unroll
+      for (int j = 0; j < LF; ++j) bfr[j] = ldB(j);
+      int m = 0;      // (MFMA index: a constant after unrolling)
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        const int h = j / 3, kw = j % 3;
+        if (j + LF < NF) bfr[(j + LF) & 3] = ldB(j + LF);
+        if (kw == 1 && h + 1 < TH) af[(h + 1) & 3] = ldA(h + 1);
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) {
+          const int kk = h - kh;
+          if (kk >= 0 && kk < TH) {
+            if constexpr (HPM) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc[kh * 3 + kw]) : "v"(af[kk & 3]), "v"(bfr[j & 3]));
+            else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc[kh * 3 + kw]) : "v"(af[kk & 3]), "v"(bfr[j & 3]));
+            __builtin_amdgcn_sched_barrier(0);
+            if (m >= DMA_FIRST && (m - DMA_FIRST) % DMA_STEP == 0) { dma((m - DMA_FIRST) / DMA_STEP); __builtin_amdgcn_sched_barrier(0); }
+            ++m;
+          }
+        }
+      }
+      static_assert((TH * 9 - 1 - DMA_FIRST) / DMA_STEP + 1 >= C::NPIECES, "every piece of the next item has a slot in the MFMA stream");
+    }
+  };
 
   if constexpr (SPLIT) {
     for (int tt = t_begin; tt < t_end; ++tt) {
@@ -222,7 +282,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(PhWgrad p) {
       __syncthreads();
       compute(ldsD, ldsX);
     }
-  } else {
+  } else if constexpr (!LEAN) {
     // perf mode: LDS-DMA (global_load_lds_dwordx4) straight from HBM/L2 into the swizzled LDS image.  The LDS
     // destination of one wave-instruction is linear (base + lane*16 = 8 pixel rows), so the XOR swizzle is
     // applied to the per-lane SOURCE chunk instead; out-of-image pixels read a zero page.  Tile t+1 is issued
@@ -300,6 +360,161 @@ __global__ __launch_bounds__(256) void wgrad_kernel(PhWgrad p) {
       __syncthreads();                                    // ... and everybody's; buffer buf is free again
       buf ^= 1;
     }
+  } else {
+    // perf mode, LEAN: the same LDS image, items, buffers, wait and barrier as above; only HOW a piece's source address is found
+    // changes.  Above, every piece of every tile decodes the tile (two integer divisions), its pixel (a division by HPW) and four
+    // range compares behind two branches: ~350 executed instructions per tile and wave for 10 LDS-DMAs, in front of the MFMAs, where
+    // one wave per SIMD hides none of it.  Here, ONCE per kernel and lane: the byte offset of each of its pieces from the tile's
+    // origin (swizzled source chunk included; strides from PhWgrad, so the strided 1 x 1 view works) and a position word (one bit
+    // for its tile row, one for its column).  Per tile, wave-uniform (scalar): the two 64-bit origins and a validity word (the
+    // rows and columns of the tile inside the image), from (image, tile row, tile column) counters.  Per piece: and + compare of
+    // position and validity word, 64-bit add, select of the zero page - 6 vector instructions, no branch.  (No "tile is interior"
+    // short cut: at the 64 / 32 / 16 pixel maps of ResNet layers 2 - 4 with pad 1, 20 of 32 / 8 of 8 / 2 of 2 tiles touch a border,
+    // and the test would cost a branch to save two instructions per piece.)
+    static_assert(BM * 8 % 256 == 0, "whole dz pieces per wave");
+    constexpr int NDP = C::NDP, NHP = C::NHP, NPC = C::NPIECES;
+    constexpr bool H_TAIL = (C::HPP * 8) % 256 != 0;      // the last halo piece exists for the first waves only
+    typedef typename std::conditional<(HPH + HPW < 32), unsigned, unsigned long long>::type hmask_t;
+    const unsigned lds0 = (unsigned)(size_t)(lds_uchar*)smem;
+    constexpr int BUF = C::D_BYTES + C::X_BYTES;
+    const unsigned char* zero = reinterpret_cast<const unsigned char*>(p.zeros);
+    const int nt = t_end > t_begin ? t_end - t_begin : 0;
+    const bool hi1 = HPM && p.hp_hi_only;
+    const int nitems = (HPM && !hi1) ? 3 * nt : nt;      // (half-pair mode: the three passes as ONE item stream, as above)
+    const int dblk = HPM ? (co0 >> 6) * 128 : co0, xblk = HPM ? (ci0 >> 6) * 128 : ci0;
+    unsigned d_off[NDP], d_pos[NDP], h_off[NHP];
+    hmask_t h_pos[NHP];
+#pragma unroll
+    for (int k = 0; k < NDP; ++k) {
+      const int i = wave * 64 + 256 * k + lane, pix = i >> 3, pos = i & 7;
+      const int ch = sw_piece(pix, pos >> 1) * 2 + (pos & 1);          // source chunk of this LDS slot
+      d_off[k] = (unsigned)((((long)(pix >> 4) * p.OW + (pix & 15)) * dpix + ch * 8) * 2);
+      d_pos[k] = (1u << (pix >> 4)) | (1u << (TH + (pix & 15)));
+    }
+#pragma unroll
+    for (int k = 0; k < NHP; ++k) {
+      const int i = wave * 64 + 256 * k + lane, pix = i >> 3, pos = i & 7;
+      const int ch = sw_piece(pix, pos >> 1) * 2 + (pos & 1);
+      const int hr = pix / HPW, hc = pix - hr * HPW;
+      const bool in = pix < HP;      // (the pixels that pad the halo to whole pieces are never read: the bit no validity word has)
+      h_off[k] = in ? (unsigned)(((long)hr * xrow + (long)hc * xpix + ch * 8) * 2) : 0u;
+      h_pos[k] = in ? ((hmask_t)1 << hr) | ((hmask_t)1 << (HPH + hc)) : (hmask_t)1 << (HPH + HPW);
+    }
+    // tile cursor of the next item to issue: (image, tile row, tile column) counters, the origins kept by ADDING the byte step of a
+    // tile column, tile row or image - the two divisions and the 64-bit products run once per kernel (half-pair mode: once per pass)
+    typedef const unsigned char* bptr;
+    const int b_s = t_begin / tiles_img, ti_s = t_begin - b_s * tiles_img;
+    const int trow_s = ti_s / tiles_w, tcol_s = ti_s - trow_s * tiles_w;
+    auto d_at = [&](int b, int trow, int tcol) {
+      return reinterpret_cast<bptr>(DY) + ((((long)b * p.OH + trow * TH) * p.OW + tcol * TW) * dpix + dblk) * 2;
+    };
+    auto x_at = [&](int b, int trow, int tcol) {
+      return reinterpret_cast<bptr>(X) + ((long)b * ximg + (long)(trow * TH * S - p.pad) * xrow + (long)(tcol * TW * S - p.pad) * xpix + xblk) * 2;
+    };
+    const long d_col = (long)TW * dpix * 2, d_row = (long)TH * p.OW * dpix * 2, d_img = (long)p.OH * p.OW * dpix * 2;
+    const long x_col = (long)TW * S * xpix * 2, x_row = (long)TH * S * xrow * 2, x_img = ximg * 2;
+    int crow = trow_s, ccol = tcol_s, cpass = hi1 ? 2 : 0, cleft = nt;
+    bptr od, od_r, od_i, ox, ox_r, ox_i;      // origins of the cursor's tile, of its tile row's first tile, of its image's first tile
+    unsigned dv_r, dv_c;                      // validity words of the cursor's tile: its row part, its column part
+    hmask_t hv_r, hv_c;
+    auto span = [](int lo, int hi) -> hmask_t {      // bits lo .. hi - 1
+      return hi > lo ? (((hmask_t)1 << hi) - 1) & ~(((hmask_t)1 << lo) - 1) : (hmask_t)0;
+    };
+    auto row_words = [&]() {
+      const int r0 = crow * TH, iy_base = r0 * S - p.pad;
+      dv_r = (unsigned)span(0, min(TH, p.OH - r0));
+      hv_r = span(max(0, -iy_base), min(HPH, p.IH - iy_base));
+    };
+    auto col_words = [&]() {
+      const int c0 = ccol * TW, ix_base = c0 * S - p.pad;
+      dv_c = (unsigned)span(0, min(TW, p.OW - c0)) << TH;
+      hv_c = span(max(0, -ix_base), min(HPW, p.IW - ix_base)) << HPH;
+    };
+    auto to_start = [&]() {
+      crow = trow_s; ccol = tcol_s;
+      od = d_at(b_s, trow_s, tcol_s); od_r = d_at(b_s, trow_s, 0); od_i = d_at(b_s, 0, 0);
+      ox = x_at(b_s, trow_s, tcol_s); ox_r = x_at(b_s, trow_s, 0); ox_i = x_at(b_s, 0, 0);
+      row_words();
+    };
+    to_start();
+    col_words();
+    bptr nx_d = zero, nx_x = zero;      // origins and validity words of the item being issued
+    unsigned nx_dv = 0;
+    hmask_t nx_hv = 0;
+    auto next_item = [&](const bool have) {      // have = false: no validity bit, every lane reads the zero page (into the free buffer)
+      nx_d = od + ((HPM && cpass == 1) ? 128 : 0);      // lo plane of dz' / of x
+      nx_x = ox + ((HPM && cpass == 0) ? 128 : 0);
+      nx_dv = have ? dv_r | dv_c : 0u;
+      nx_hv = have ? hv_r | hv_c : (hmask_t)0;
+      ++ccol; od += d_col; ox += x_col;
+      if (ccol == tiles_w) {
+        ccol = 0; ++crow; od_r += d_row; ox_r += x_row;
+        if (crow == tiles_h) { crow = 0; od_i += d_img; ox_i += x_img; od_r = od_i; ox_r = ox_i; }
+        od = od_r; ox = ox_r;
+        row_words();
+      }
+      if constexpr (HPM) { if (--cleft == 0) { cleft = nt; ++cpass; to_start(); } }
+      col_words();
+    };
+    unsigned ldst = lds0 + wave * 1024;      // LDS byte address of this wave's first dz piece in the buffer being filled
+    auto dma = [&](const int k) __attribute__((always_inline)) {      // piece k: dz pieces first, then the halo's
+#ifndef PH_ABL_WG_NODMA   // timing ablation only (garbage results): no operand traffic
+      if (k < NDP) {
+        const unsigned char* src = (d_pos[k] & nx_dv) == d_pos[k] ? nx_d + d_off[k] : zero;
+        lds_dma16(src, ldst + k * 4096);
+      } else if (k < NPC) {
+        const int e = k - NDP;
+        if (H_TAIL && e == NHP - 1 && wave * 64 + 256 * e >= C::HPP * 8) return;      // (wave-uniform)
+        const unsigned char* src = (h_pos[e] & nx_hv) == h_pos[e] ? nx_x + h_off[e] : zero;
+        lds_dma16(src, ldst + C::D_BYTES + e * 4096);
+      }
+#endif
+    };
+    if (nitems > 0) {
+      next_item(true);
+#pragma unroll
+      for (int k = 0; k < NPC; ++k) dma(k);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    int buf = 0;
+    for (int it = 0; it < nitems; ++it) {
+      next_item(it + 1 < nitems);
+      ldst = lds0 + (buf ^ 1) * BUF + wave * 1024;
+      if constexpr (HPM) {
+        if (!hi1 && it == 2 * nt) {      // the cross terms are complete: weight them before the leading products accumulate
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+              if constexpr (PIPE) {      // (one register at a time, as above)
+                float tmp_;
+                asm volatile("v_accvgpr_read_b32 %1, %0\n\ts_nop 4\n\tv_mul_f32 %1, %2, %1\n\ts_nop 4\n\tv_accvgpr_write_b32 %0, %1\n\ts_nop 4"
+                             : "+a"(acc[t][q]), "=&v"(tmp_) : "v"(PH_HP_LO_INV));
+              } else {
+                acc[t][q] *= PH_HP_LO_INV;
+              }
+            }
+        }
+      }
+      // Buffer discipline (unchanged): the pieces of item it + 1 go to buffer buf ^ 1, whose last reads - the fragment reads of item
+      // it - 1 - every wave completed before it passed the barrier that ended iteration it - 1 (each read was waited for by the MFMA
+      // that consumed it, and all MFMAs precede the barrier).  The fragment reads of item it address bytes [buf * BUF, buf * BUF +
+      // BUF) only and the pieces bytes of the other buffer only, so no read of the current buffer can see a piece of the next item,
+      // wherever in the MFMA stream it is issued; nobody reads buffer buf ^ 1 before the vmcnt(0) + barrier below.
+      if constexpr (PIPE) {
+        compute_l(buf * PBUF, dma);
+      } else {
+        if (it + 1 < nitems) {
+#pragma unroll
+          for (int k = 0; k < NPC; ++k) dma(k);
+        }
+        compute(smem + buf * BUF, smem + buf * BUF + C::D_BYTES);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next item have landed
+      __syncthreads();                                    // ... and everybody's; buffer buf is free again
+      buf ^= 1;
+    }
   }
   // ---- partial slab: acc[t][q] -> row (cout) = (q&3)+8*(q>>2)+4*khalf, col (cin) = lane&31
   float* slab = p.slab + (size_t)chunk * NT * p.Cout * p.Cin;
@@ -325,10 +540,23 @@ __global__ __launch_bounds__(256) void wgrad_kernel(PhWgrad p) {
     }
 }
 
+// the lean loop keeps a piece's source offset from its tile origin in 32 bits (unsigned): true of every tensor whose rows are
+// shorter than ~200 MB; anything else keeps the loop with the 64-bit address arithmetic per piece
 template <typename T, int S, int TH, int KS>
-int launch_wg(const PhWgrad& p, hipStream_t st) {
+bool wg_lean_fits(const PhWgrad& p) {
   using C = WgCfg<T, S, TH, KS>;
-  auto kern = wgrad_kernel<T, S, TH, KS>;
+  const long EW = C::HPM ? 2 : 1;
+  const long xpix = (p.x_pix_stride ? p.x_pix_stride : p.Cin) * EW;
+  const long xrow = (p.x_row_stride ? p.x_row_stride : (long)p.IW * p.Cin) * EW;
+  const long xmax = ((long)C::HPH * xrow + (long)C::HPW * xpix + 128) * 2;
+  const long dmax = (((long)TH * p.OW + C::TW) * p.Cout * EW + 128) * 2;
+  return xrow >= 0 && xpix >= 0 && xmax < (1L << 32) && dmax < (1L << 32);
+}
+
+template <typename T, int S, int TH, int KS, bool LEAN>
+int launch_wg_k(const PhWgrad& p, hipStream_t st) {
+  using C = WgCfg<T, S, TH, KS>;
+  auto kern = wgrad_kernel<T, S, TH, KS, LEAN>;
   static bool attr_done = false;
   if (!attr_done) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -346,6 +574,14 @@ int launch_wg(const PhWgrad& p, hipStream_t st) {
   ph_prof_end(tok, st);
   PH_LAUNCH_CHECK();
   return PH_OK;
+}
+
+template <typename T, int S, int TH, int KS>
+int launch_wg(const PhWgrad& p, hipStream_t st) {
+  if constexpr (!is_f32<T>::value) {
+    if (ph_wg_lean_switch(-1) && wg_lean_fits<T, S, TH, KS>(p)) return launch_wg_k<T, S, TH, KS, true>(p, st);
+  }
+  return launch_wg_k<T, S, TH, KS, false>(p, st);
 }
 
 template <typename T>
