@@ -648,15 +648,32 @@ int ph_tsvd_update_aux_dev(const float* adj, float* aux, float* tnn /* may be NU
  * HOST copy of offsets: it is checked before the launch (offsets[0] = 0, offsets[G] = N, no empty group - else PH_EINVAL).
  * 1 <= G <= N <= 16777216, 1 <= C <= 4096.
  * All three return PH_EINVAL for a NULL pointer or a size outside the stated range before any HIP call.
+ *
+ * ph_group_quantile: the order statistics of the same groups - the median of the survival
+ * aggregation (utils_analysis.py:467) and the percentile form of the grading one (:122) - over the CSR of ph_group_agg.
+ * For one (group, column) with n values, s = the values ascending:  h = (n - 1) q in double, lo = floor(h),
+ * hi = min(lo + 1, n - 1), t = h - lo, a = s[lo], b = s[hi];  out = (float)(t == 0 || a == b ? a : a + (b - a) t), evaluated
+ * in double (a product and a sum, not fused) and rounded once: numpy's percentile with method "linear"; q = 0.5 is pandas'
+ * median, q = 0 the minimum, q = 1 the maximum.  A NaN anywhere in the group's column gives NaN; +-inf are ordinary values
+ * and the expression gives what IEEE gives; the sign of a zero among mixed +-0 is unspecified.  No sort: the element whose
+ * stable rank (#{smaller} + #{equal and earlier in CSR order}) is lo hands over a, the one of rank hi hands over b - one
+ * launch, no workspace, no atomics, independent of scheduling.  The form is chosen per launch from the largest group of
+ * offsets_host: at most 64 rows - one 64-lane wave per (group, column); more - one workgroup of 256 per group, the column
+ * staged in LDS.  The kernels clamp the device offsets and skip a row index outside [0, N).
+ * The limits of ph_group_agg, and every group at most PH_QUANTILE_MAX_GROUP rows, and 0 <= q <= 1 (a NaN q is refused);
+ * anything else, a NULL pointer or an empty group returns PH_EINVAL before any HIP call.
  * ---------------------------------------------------------------------------------------------- */
 #define PH_AGG_MEAN 0
 #define PH_AGG_MAX 1
+#define PH_QUANTILE_MAX_GROUP 4096
 size_t ph_rank_counts_workspace_bytes(int N, int C);
 int ph_rank_counts(const float* pred, const int64_t* grade, int N, int C, int64_t* counts, double* ap_sum, void* workspace,
                    ph_stream_t stream);
 int ph_confusion_counts(const float* pred, const int64_t* grade, int N, int C, int64_t* conf, ph_stream_t stream);
 int ph_group_agg(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C, int G,
                  int fun, float* out, ph_stream_t stream);
+int ph_group_quantile(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C,
+                      int G, double q, float* out, ph_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * In-library kernel timer for bench.py's `roofline` object: HIP events around every MFMA kernel launch on the

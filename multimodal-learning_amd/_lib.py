@@ -79,6 +79,7 @@ SIGNATURES = {
     "ph_rank_counts": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
     "ph_confusion_counts": (i32, [vp, vp, i32, i32, vp, vp]),
     "ph_group_agg": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "ph_group_quantile": (i32, [vp, vp, vp, vp, i32, i32, i32, f64, vp, vp]),
     "ph_pkt_workspace_bytes": (sz, [i32, i32]),
     "ph_pkt_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
     "ph_rkd_workspace_bytes": (sz, [i32, i32]),

@@ -263,9 +263,14 @@ class ResidentPatchLoader:
     `patient`: one hashable id per ROI (None: every ROI its own patient), mapped at construction to dense ids 0..G-1 in
     order of first appearance; a patient whose ROIs carry different grades raises ValueError.  row_patient (int64 [rows],
     device), patients (the ids, host), patient_grade (int64 [G], device), num_patients; group_offsets / group_order: the
-    CSR of the rows per patient that evaluate.aggregate_by_patient hands to ph_group_agg."""
+    CSR of the rows per patient that evaluate.aggregate_by_patient hands to ph_group_agg / ph_group_quantile.
 
-    def __init__(self, opt, tiles_u8, x_omic, grade, patient=None, grid=3, device="cuda"):
+    `censor`, `survtime`: one value per ROI, both or neither (the survival task).  When given, the
+    6-tuple carries them per row at positions 3 and 4 (float32, device) instead of zeros, patient_censor / patient_survtime
+    (float32 [G], device; patient_censor_host / patient_survtime_host: numpy) hold one value per patient, and a patient whose
+    ROIs disagree in either raises ValueError.  Without them the loader is what it was."""
+
+    def __init__(self, opt, tiles_u8, x_omic, grade, patient=None, grid=3, device="cuda", censor=None, survtime=None):
         import numpy as np
         from .ops import group_csr
         self.device = torch.device(device)
@@ -284,15 +289,29 @@ class ResidentPatchLoader:
         ids = list(range(n)) if patient is None else list(patient)
         if len(ids) != n:
             raise ValueError("one patient id per ROI")
-        dense, self.patients, pgrade = {}, [], []
+        if (censor is None) != (survtime is None):
+            raise ValueError("censor and survtime come together: both or neither")
+        self.has_survival = censor is not None
+        if self.has_survival:
+            censor_h, survtime_h = (np.asarray(v.cpu() if torch.is_tensor(v) else v).reshape(-1).astype(np.float32)
+                                    for v in (censor, survtime))
+            if censor_h.shape[0] != n or survtime_h.shape[0] != n:
+                raise ValueError("one censor value and one survival time per ROI")
+        dense, self.patients, pgrade, first = {}, [], [], []
         roi_patient = np.empty(n, dtype=np.int64)
         for i, pid in enumerate(ids):
             if pid not in dense:
                 dense[pid] = len(self.patients)
                 self.patients.append(pid)
                 pgrade.append(int(grade_h[i]))
+                first.append(i)
             elif pgrade[dense[pid]] != int(grade_h[i]):
                 raise ValueError("patient %r has ROIs of different grades (%d and %d)" % (pid, pgrade[dense[pid]], int(grade_h[i])))
+            elif self.has_survival:
+                j = first[dense[pid]]
+                if censor_h[j] != censor_h[i] or survtime_h[j] != survtime_h[i]:
+                    raise ValueError("patient %r has ROIs of different survival data ((censor, survtime) = (%g, %g) and (%g, %g))"
+                                     % (pid, censor_h[j], survtime_h[j], censor_h[i], survtime_h[i]))
             roi_patient[i] = dense[pid]
         self.num_patients = len(self.patients)
         cells = self.grid * self.grid
@@ -316,6 +335,12 @@ class ResidentPatchLoader:
         self.patient_grade = torch.from_numpy(self.patient_grade_host).to(self.device)
         self.x_omic = x_omic.to(self.device).float().contiguous()
         self.grade = torch.from_numpy(grade_h).to(self.device)
+        if self.has_survival:
+            self.censor = torch.from_numpy(censor_h).to(self.device)
+            self.survtime = torch.from_numpy(survtime_h).to(self.device)
+            self.patient_censor_host, self.patient_survtime_host = censor_h[first].copy(), survtime_h[first].copy()
+            self.patient_censor = torch.from_numpy(self.patient_censor_host).to(self.device)
+            self.patient_survtime = torch.from_numpy(self.patient_survtime_host).to(self.device)
         self.group_offsets_host, order = group_csr(row_patient, self.num_patients)
         self.group_offsets = torch.from_numpy(self.group_offsets_host).to(self.device)
         self.group_order = torch.from_numpy(order).to(self.device)
@@ -335,6 +360,8 @@ class ResidentPatchLoader:
         check(lib().ph_augment_apply_v(ptr(self.tiles), None, ptr(roi), ptr(params), outs, None, B, 1, SH, SW, S, stream()),
               "ph_augment_apply_v")
         z = torch.zeros(B, device=self.device)
+        if self.has_survival:
+            return (x_path, z, self.x_omic[roi], self.censor[roi], self.survtime[roi], self.grade[roi])
         return (x_path, z, self.x_omic[roi], z, z, self.grade[roi])
 
     def __iter__(self):

@@ -3,7 +3,9 @@
 //   ph_rank_counts       roc_auc_score / average_precision_score(average="micro")   (core/utils_analysis.py:160-161,
 //                        train_test_path_multi_distill.py:516-526) as exact pair counts,
 //   ph_confusion_counts  f1_score of the arg-max grades (utils_analysis.py:162-163) as the C x C confusion matrix,
-//   ph_group_agg         groupby('TCGA ID').agg(max | mean) of the patch rows per patient (utils_analysis.py:123).
+//   ph_group_agg         groupby('TCGA ID').agg(max | mean) of the patch rows per patient (utils_analysis.py:123),
+//   ph_group_quantile    the order statistics of the same groups: the median of the survival aggregation (utils_analysis.py:467)
+//                        and the percentile form of the grading one (:122) - DESIGN.md section 24.
 // The scores are log-probabilities (negative): nothing here relies on their sign.
 #include "ph_common.h"
 #include "ph_kernels.h"
@@ -16,6 +18,9 @@ constexpr int CONF_THREADS = 256;
 constexpr int CONF_MAX_C = 16;
 constexpr int AGG_MAX_N = 1 << 24;
 constexpr int AGG_MAX_C = 4096;
+constexpr int QUANT_THREADS = 256;
+constexpr int QUANT_MAX_GROUP = 4096;     // PH_QUANTILE_MAX_GROUP: one group's column in LDS (16 KiB)
+constexpr int QUANT_WAVE_MAX_BLOCKS = 1 << 16;
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
@@ -163,6 +168,146 @@ __global__ void group_agg_kernel(const float* __restrict__ x, const int32_t* __r
   }
 }
 
+// ---- ph_group_quantile: numpy's percentile, method "linear", of every column of every group.
+// n values, s ascending:  h = (n - 1) q,  lo = floor(h),  hi = min(lo + 1, n - 1),  t = h - lo,  a = s[lo],  b = s[hi],
+// out = (float)(t == 0 || a == b ? a : a + (b - a) t) in double.  No sort: the stable rank of element k,
+//   rank_k = #{m : x_m < x_k} + #{m before k in CSR order : x_m == x_k},
+// is a permutation of 0 .. n - 1 when no value is a NaN, so exactly one element has rank lo and one has rank hi; they hand
+// a and b over (no atomics: independent of scheduling).  A NaN in the column gives NaN.  A row index outside [0, N) is an
+// absent element (it holds a NaN, which drops out of every comparison, and is not counted in n); the offsets are clamped
+// to [0, N] and the group length to the form's capacity: device data cannot make either kernel read outside x or its LDS.
+struct QuantileSel {
+  int lo, hi;
+  double t;
+};
+
+__device__ __forceinline__ QuantileSel quantile_sel(int n, double q) {
+  const double h = (double)(n - 1) * q, fl = floor(h);
+  QuantileSel s;
+  s.lo = min(max((int)fl, 0), n - 1);
+  s.hi = min(s.lo + 1, n - 1);
+  s.t = h - fl;
+  return s;
+}
+
+// (two roundings, a product and a sum, as the numpy restatement has them: no fused multiply-add)
+__device__ __forceinline__ float quantile_lerp(float a, float b, double t) {
+#pragma clang fp contract(off)
+  const double da = (double)a, db = (double)b;
+  return (float)((t == 0.0 || da == db) ? da : da + (db - da) * t);
+}
+
+// Groups of at most 64 rows: one wave per (group, column), one value per lane, the other lanes' values by cross-lane reads.
+__global__ __launch_bounds__(QUANT_THREADS) void group_quantile_wave_kernel(const float* __restrict__ x,
+                                                                            const int32_t* __restrict__ offsets,
+                                                                            const int32_t* __restrict__ order, int N, int C,
+                                                                            int G, double q, float* __restrict__ out) {
+  constexpr int WAVES = QUANT_THREADS / 64;
+  const int lane = threadIdx.x & 63;
+  const float qnan = __builtin_nanf("");
+  const size_t items = (size_t)G * C, stride = (size_t)gridDim.x * WAVES;
+  for (size_t t = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < items; t += stride) {
+    const int g = (int)(t / C), c = (int)(t - (size_t)g * C);
+    const int lo = min(max(offsets[g], 0), N), hi = min(max(offsets[g + 1], lo), N);
+    const int n = min(hi - lo, 64);
+    float v = qnan;
+    bool valid = false;
+    if (lane < n) {
+      const int r = order[lo + lane];
+      if (r >= 0 && r < N) {
+        v = x[(size_t)r * C + c];
+        valid = true;
+      }
+    }
+    const int n_eff = __popcll(__ballot(valid));
+    const bool has_nan = __ballot(valid && v != v) != 0ull;
+    int rank = 0;
+    for (int m = 0; m < n; ++m) {
+      const float w = __shfl(v, m, 64);
+      rank += (w < v ? 1 : 0) + ((w == v && m < lane) ? 1 : 0);
+    }
+    float res = qnan;
+    if (n_eff > 0 && !has_nan) {        // (wave-uniform)
+      const QuantileSel s = quantile_sel(n_eff, q);
+      const unsigned long long ma = __ballot(valid && rank == s.lo), mb = __ballot(valid && rank == s.hi);
+      if (ma != 0ull && mb != 0ull) {
+        const float a = __shfl(v, __ffsll((long long)ma) - 1, 64), b = __shfl(v, __ffsll((long long)mb) - 1, 64);
+        res = quantile_lerp(a, b, s.t);
+      }
+    }
+    if (lane == 0) out[t] = res;
+  }
+}
+
+// Larger groups (up to QUANT_MAX_GROUP rows): one workgroup per group, the columns looped; the group's column staged in
+// LDS, thread tid ranks the elements tid, tid + 256, .. (four at a time in registers against every staged value).
+__global__ __launch_bounds__(QUANT_THREADS) void group_quantile_block_kernel(const float* __restrict__ x,
+                                                                             const int32_t* __restrict__ offsets,
+                                                                             const int32_t* __restrict__ order, int N, int C,
+                                                                             int G, double q, float* __restrict__ out) {
+  __shared__ float s[QUANT_MAX_GROUP];
+  __shared__ unsigned int red[QUANT_THREADS / 64];
+  __shared__ float sel[2];
+  const int tid = threadIdx.x, g = blockIdx.x;
+  const float qnan = __builtin_nanf("");
+  if (g >= G) return;
+  const int lo = min(max(offsets[g], 0), N), hi = min(max(offsets[g + 1], lo), N);
+  const int n = min(hi - lo, QUANT_MAX_GROUP);
+  for (int c = 0; c < C; ++c) {
+    unsigned int cnt = 0;              // valid elements | NaN values << 16 of this thread
+    for (int k = tid; k < n; k += QUANT_THREADS) {
+      const int r = order[lo + k];
+      float v = qnan;
+      if (r >= 0 && r < N) {
+        v = x[(size_t)r * C + c];
+        cnt += 1u + (v != v ? 1u << 16 : 0u);
+      }
+      s[k] = v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = cnt;
+    if (tid == 0) sel[0] = sel[1] = qnan;
+    __syncthreads();
+    unsigned int tot = 0;
+#pragma unroll
+    for (int w = 0; w < QUANT_THREADS / 64; ++w) tot += red[w];
+    // (at most 4096 of either: the two halves of the packed sum never carry into each other)
+    const int n_eff = (int)(tot & 0xffffu);
+    const bool has_nan = (tot >> 16) != 0u;
+    if (n_eff > 0 && !has_nan) {       // (uniform over the workgroup)
+      const QuantileSel qs = quantile_sel(n_eff, q);
+      for (int k0 = tid; k0 < n; k0 += 4 * QUANT_THREADS) {
+        float xk[4];
+        int rank[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int k = k0 + u * QUANT_THREADS;
+          xk[u] = k < n ? s[k] : qnan;
+          rank[u] = 0;
+        }
+        for (int m = 0; m < n; ++m) {
+          const float w = s[m];
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            rank[u] += (w < xk[u] ? 1 : 0) + ((w == xk[u] && m < k0 + u * QUANT_THREADS) ? 1 : 0);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (xk[u] != xk[u]) continue;        // an absent element (or past the end): no rank
+          if (rank[u] == qs.lo) sel[0] = xk[u];
+          if (rank[u] == qs.hi) sel[1] = xk[u];
+        }
+      }
+      __syncthreads();
+      if (tid == 0) out[(size_t)g * C + c] = quantile_lerp(sel[0], sel[1], qs.t);
+    } else if (tid == 0) {
+      out[(size_t)g * C + c] = qnan;
+    }
+    __syncthreads();                   // s, red and sel are rewritten for the next column
+  }
+}
+
 bool rank_shape_ok(int N, int C) { return N >= 1 && C >= 1 && (int64_t)N * C <= RANK_MAX_M; }
 
 }  // namespace
@@ -209,6 +354,31 @@ int ph_group_agg(const float* x, const int32_t* offsets, const int32_t* order, c
     if (offsets_host[g + 1] <= offsets_host[g]) return PH_EINVAL;        // an empty (or negative) group
   const size_t n = (size_t)G * C;
   hipLaunchKernelGGL(group_agg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, offsets, order, N, C, G, fun, out);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_group_quantile(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C,
+                      int G, double q, float* out, hipStream_t st) {
+  if (!x || !offsets || !order || !offsets_host || !out) return PH_EINVAL;
+  if (N < 1 || N > AGG_MAX_N || C < 1 || C > AGG_MAX_C || G < 1 || G > N) return PH_EINVAL;
+  if (!(q >= 0.0 && q <= 1.0)) return PH_EINVAL;                          // (a NaN q fails both comparisons)
+  if (offsets_host[0] != 0 || offsets_host[G] != N) return PH_EINVAL;
+  int largest = 0;
+  for (int g = 0; g < G; ++g) {
+    const int64_t len = (int64_t)offsets_host[g + 1] - (int64_t)offsets_host[g];
+    if (len <= 0 || len > PH_QUANTILE_MAX_GROUP) return PH_EINVAL;        // empty, negative or larger than the LDS stage
+    if ((int)len > largest) largest = (int)len;
+  }
+  static_assert(PH_QUANTILE_MAX_GROUP == QUANT_MAX_GROUP, "the header's limit is the kernel's LDS stage");
+  if (largest <= 64) {
+    const size_t items = (size_t)G * C, waves = QUANT_THREADS / 64;
+    const size_t blocks = (items + waves - 1) / waves;
+    hipLaunchKernelGGL(group_quantile_wave_kernel, dim3((unsigned)(blocks < (size_t)QUANT_WAVE_MAX_BLOCKS ? blocks : QUANT_WAVE_MAX_BLOCKS)),
+                       dim3(QUANT_THREADS), 0, st, x, offsets, order, N, C, G, q, out);
+  } else {
+    hipLaunchKernelGGL(group_quantile_block_kernel, dim3((unsigned)G), dim3(QUANT_THREADS), 0, st, x, offsets, order, N, C, G, q, out);
+  }
   PH_LAUNCH_CHECK();
   return PH_OK;
 }

@@ -9,6 +9,8 @@ there are exactly four exchanges:
   4. one-off all-reduce of the CRD normalisation sums (first batch only)
 The stage-1 teacher step under the survival task adds one all-gather of its packed survival rows (all_gather_into): the
 Cox risk sets span the global batch.
+The sharded test pass (evaluate.test_patches / test_teacher_patches with sync=) costs one broadcast per dtype of the evaluated
+networks' buffers (broadcast_from0) and one all-gather of the finished rows (all_gather_cat), whatever the batch count.
 BatchNorm keeps per-replica statistics - that IS the DataParallel semantics of the reference.
 Loss normalisers use the GLOBAL batch so summed gradients equal the single-process result."""
 import torch
@@ -116,6 +118,23 @@ class ReplicaSync:
         # as flat vectors: gloo takes the output only as the inputs' concatenation along dim 0, RCCL either form
         dist.all_gather_into_tensor(out.view(-1), inp.contiguous().view(-1), group=self.group)
         return out
+
+    def broadcast_from0(self, tensors):
+        """Rank 0's values into `tensors` on every replica, in place: one broadcast per dtype (the tensors of a dtype travel
+        as one flat buffer).  The sharded test pass (evaluate.test_patches(sync=...)) sends the BatchNorm running
+        statistics (float32) and num_batches_tracked (int64) of the evaluated networks this way: two collectives."""
+        by_dtype = {}
+        for t in tensors:
+            by_dtype.setdefault(t.dtype, []).append(t)
+        for ts in by_dtype.values():
+            flat = torch.cat([t.detach().reshape(-1) for t in ts])
+            dist.broadcast(flat, src=0, group=self.group)
+            at = 0
+            for t in ts:
+                n = t.numel()
+                t.detach().copy_(flat[at:at + n].view_as(t))
+                at += n
+        return tensors
 
     def attach(self, step):
         """Wire the CRD memories of a DistillStep to this group and make every replica start identical."""

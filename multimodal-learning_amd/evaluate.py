@@ -9,7 +9,12 @@ batch); here the per-batch results stay on the device and leave it once, after t
 
 `test_patches` is the protocol the results are reported under: the same pass over the nine-patch
 test loader (`augment.ResidentPatchLoader`), the predictions aggregated per patient (`aggregate_by_patient`), and the four
-numbers taken from count kernels on the device (`grading_metrics_device`) instead of sklearn on copied rows."""
+numbers taken from count kernels on the device (`grading_metrics_device`) instead of sklearn on copied rows.
+`test_teacher_patches` is the same protocol for the stage-1 teacher under both tasks (per-patient hazards, C-indices, log-rank
+p-value under survival), and `sync=` on either pass shards whole batches over data-parallel replicas behind one all-gather
+(DESIGN.md section 24)."""
+import numbers
+
 import numpy as np
 import torch
 
@@ -194,19 +199,134 @@ def grading_metrics_device(pred, grade):
     return metrics_from_counts(host[:4].tolist(), float(host[4:5].view(torch.float64)[0]), host[5:].view(C, C).numpy())
 
 
+def agg_spec(agg):
+    """("mean" | "max", None) or ("quantile", q) for the aggregation names of `aggregate_by_patient`; ValueError otherwise."""
+    if isinstance(agg, str) and agg in ops.AGG_FUN:
+        return agg, None
+    if isinstance(agg, str) and agg == "median":
+        return "quantile", 0.5
+    if isinstance(agg, (tuple, list)) and len(agg) == 2 and isinstance(agg[0], str) and agg[0] == "quantile" \
+            and isinstance(agg[1], numbers.Real) and not isinstance(agg[1], bool) and 0.0 <= float(agg[1]) <= 1.0:
+        return "quantile", float(agg[1])
+    note = ""
+    if agg == "p0.75":
+        note = ('; the reference evaluates the name "p0.75" as np.percentile(x, 0.90), a percent - here that is '
+                '("quantile", 0.009)')
+    raise ValueError('agg must be "mean" or "max", or "median" or ("quantile", q) with q a fraction in [0, 1], got %r%s'
+                     % (agg, note))
+
+
 def aggregate_by_patient(loader, pred, agg="max"):
-    """groupby('TCGA ID').agg(max | mean) of the patch rows (core/utils_analysis.py:79-135, called with agg_type 'max' by
-    evaluation_GBMLGG.py:55-61): pred f32 [rows, C] on the device, in the row order of `loader` (a ResidentPatchLoader) ->
-    device [G, C], patient g = loader.patients[g].  The percentile form (agg_type 'p0.75', which the reference evaluates as
-    np.percentile(x, 0.90)) is not built."""
-    if agg not in ops.AGG_FUN:
-        raise ValueError('agg must be "mean" or "max" (the percentile aggregation is not built), got %r' % (agg,))
+    """groupby('TCGA ID').agg(...) of the patch rows (core/utils_analysis.py:79-135, called with agg_type 'max' by
+    evaluation_GBMLGG.py:55-61; :467 for the hazards of the survival task): pred f32 [rows, C] or [rows] on the device, in
+    the row order of `loader` (a ResidentPatchLoader) -> device [G, C] or [G], patient g = loader.patients[g].
+
+    agg: "mean", "max" (ph_group_agg), "median" (= quantile 0.5, pandas' median) or ("quantile", q) with q a FRACTION in
+    [0, 1] (ph_group_quantile: numpy's percentile, method "linear"; at most 4096 rows per patient).  The reference's
+    percentile form, agg_type 'p0.75', evaluates np.percentile(x, 0.90) - a percent: ("quantile", 0.009)."""
+    fun, q = agg_spec(agg)
     if pred.shape[0] != loader.n_rows:
         raise ValueError("pred has %d rows, the loader %d" % (pred.shape[0], loader.n_rows))
-    return ops.group_agg(pred, loader.group_offsets, loader.group_order, loader.group_offsets_host, agg)
+    if pred.dim() not in (1, 2):
+        raise ValueError("pred is [rows, C] or [rows]")
+    x = pred.reshape(pred.shape[0], -1)
+    if fun == "quantile":
+        out = ops.group_quantile(x, loader.group_offsets, loader.group_order, loader.group_offsets_host, q)
+    else:
+        out = ops.group_agg(x, loader.group_offsets, loader.group_order, loader.group_offsets_host, fun)
+    return out.reshape(-1) if pred.dim() == 1 else out
 
 
-def test_patches(opt, fix_model, model, loader, device, agg="max"):
+# ---- rows sharded over replicas (DESIGN.md section 24).  The loader's batches stay the single-process batches; batch b is run
+# by replica b % W.  The four functions below are index arithmetic and tensor reshapes only (no device call of their own):
+# tests/test_eval_shard_cpu.py drives them on CPU tensors.
+def shard_batches(n_rows, batch_size, rank, world_size):
+    """The batches replica `rank` runs: [(b, lo, hi)] with b = rank, rank + W, .. and rows lo .. hi - 1 of batch b."""
+    nb = -(-n_rows // batch_size)
+    return [(b, b * batch_size, min((b + 1) * batch_size, n_rows)) for b in range(rank, nb, world_size)]
+
+
+def shard_slots(n_rows, batch_size, world_size):
+    """(number of batches, batch slots per replica = ceil(batches / W))."""
+    nb = -(-n_rows // batch_size)
+    return nb, -(-nb // world_size)
+
+
+def pack_shard(rows, losses, n_rows, batch_size, world_size, like=None):
+    """One replica's float32 send buffer: `slots` batch slots of batch_size rows each, then `slots` loss rows; unused
+    slots, and the rows a partial batch leaves free, are zero.  rows: per batch run (in the order of `shard_batches`) a
+    [rows of the batch, width] tensor; losses: per batch a [k] tensor.  `like`: a tensor whose device the buffer takes when
+    the replica ran no batch (width and k then come from `like` = (width, k, device))."""
+    _, slots = shard_slots(n_rows, batch_size, world_size)
+    if rows:
+        width, k, dev = rows[0].shape[1], losses[0].numel(), rows[0].device
+    else:
+        width, k, dev = like
+    buf = torch.zeros(slots * batch_size * width + slots * k, device=dev, dtype=torch.float32)
+    body = buf[:slots * batch_size * width].view(slots, batch_size, width)
+    tail = buf[slots * batch_size * width:].view(slots, k)
+    for s, (r, l) in enumerate(zip(rows, losses)):
+        body[s, :r.shape[0]] = r
+        tail[s] = l.reshape(-1)
+    return buf
+
+
+def undeal_shards(gathered, n_rows, batch_size, world_size, width, k):
+    """The rank-ordered concatenation of every replica's `pack_shard` buffer -> (rows [n_rows, width], losses [batches, k])
+    in the single-process order: slot s of replica r is batch s * W + r."""
+    nb, slots = shard_slots(n_rows, batch_size, world_size)
+    per = slots * batch_size * width + slots * k
+    g = gathered.reshape(world_size, per)
+    body = g[:, :slots * batch_size * width].reshape(world_size, slots, batch_size, width)
+    tail = g[:, slots * batch_size * width:].reshape(world_size, slots, k)
+    rows = body.permute(1, 0, 2, 3).reshape(slots * world_size * batch_size, width)[:n_rows].contiguous()
+    losses = tail.permute(1, 0, 2).reshape(slots * world_size, k)[:nb].contiguous()
+    return rows, losses
+
+
+def _sync_buffers(sync, modules):
+    """Rank 0's buffers (BatchNorm running statistics, num_batches_tracked) on every replica."""
+    bufs = [b for m in modules if m is not None for b in m.buffers()]
+    if bufs:
+        sync.broadcast_from0(bufs)
+
+
+def _collect(loader, sync, one_batch):
+    """Run `one_batch(batch) -> (per-row outputs, loss vector [k])` over the loader; returns (outputs concatenated over
+    the rows, losses [batches, k]).  With `sync`, replica r runs the batches r, r + W, .. and ONE all-gather returns
+    every replica's rows and losses, which `undeal_shards` puts back into row order."""
+    if sync is None:
+        outs, losses = [], []
+        for batch in loader:
+            o, l = one_batch(batch)
+            outs.append(o); losses.append(l)
+        return [torch.cat([o[j] for o in outs]) for j in range(len(outs[0]))], torch.stack(losses)
+    W, n_rows, B = sync.world_size, loader.n_rows, loader.batch_size
+    packed, losses, meta = [], [], None
+    for b, lo, hi in shard_batches(n_rows, B, sync.rank, W):
+        o, l = one_batch(loader.rows(lo, hi))
+        if meta is None:
+            meta = [(tuple(t.shape[1:]), t.dtype) for t in o]
+        packed.append(torch.cat([t.reshape(t.shape[0], -1).float() for t in o], dim=1))
+        losses.append(l)
+    if meta is None:                    # more replicas than batches: this one ran none; its shapes come from one row
+        o, l = one_batch(loader.rows(0, 1))
+        meta = [(tuple(t.shape[1:]), t.dtype) for t in o]
+        like = (sum(t[0].numel() for t in o), l.numel(), o[0].device)
+    else:
+        like = None
+    widths = [int(torch.Size(shape).numel()) for shape, _ in meta]
+    k = l.numel()
+    buf = pack_shard(packed, losses, n_rows, B, W, like=like)
+    rows, loss = undeal_shards(sync.all_gather_cat(buf), n_rows, B, W, sum(widths), k)
+    outs, at = [], 0
+    for (shape, dtype), w in zip(meta, widths):
+        outs.append(rows[:, at:at + w].reshape((n_rows,) + shape).to(dtype).contiguous())
+        at += w
+    return outs, loss
+
+
+def test_patches(opt, fix_model, model, loader, device, agg="max", sync=None):
     """The pass the reference's trainers take their final figures from: `test()` over `test_loader_patches`
     (train_test_path_multi_distill.py:360-366, train_test_MT.py:287-289), then the per-patient aggregation and `calcAggGradMetrics`
     (core/utils_analysis.py:79-135, :152-167) - here over a `augment.ResidentPatchLoader`, with the metric tail on the device.
@@ -216,36 +336,48 @@ def test_patches(opt, fix_model, model, loader, device, agg="max"):
     `grading_metrics_device`.  patient_result: dict(patients, y_label one-hot [G, C], y_pred_path [G, C], y_pred_fuse (None
     without a teacher), metrics_path, metrics_fuse (None without a teacher), agg) - the four numbers of calcAggGradMetrics
     for one split.  `fix_model=None` is the student-only form.  The number of host reads does not depend on the number of
-    batches.  Rows are not sharded over replicas: data-parallel evaluation is out of scope."""
+    batches.  `agg`: the names of `aggregate_by_patient`, echoed in patient_result["agg"].
+
+    `sync` (a dist.ReplicaSync): the rows are sharded over the replicas, whole batches at a time (batch b on replica
+    b % world_size), and every replica returns the single-process result of RANK 0's networks bit for bit.  Training keeps
+    per-replica BatchNorm running statistics; the reference's nn.DataParallel keeps replica 0's.  An evaluation must use
+    one set everywhere, or the replicas' rows do not belong to one model: the buffers of `model` and `fix_model` are
+    first broadcast from rank 0, which OVERWRITES the other replicas' running statistics (train mode never reads them).
+    Then one all-gather per pass returns the rows and the per-batch losses; the metric tail runs on every replica."""
     if opt.task != "grad":
         raise NotImplementedError("evaluation of the survival (Cox) task is out of scope")
-    if agg not in ops.AGG_FUN:
-        raise ValueError('agg must be "mean" or "max" (the percentile aggregation is not built), got %r' % (agg,))
+    agg_spec(agg)
     if fix_model is not None:
         fix_model.eval()
     model.eval()
     dev = torch.device(device)
-    preds_path, preds_fuse, feats, grades, losses = [], [], [], [], []
     with torch.no_grad():
+        if sync is not None:
+            _sync_buffers(sync, (model, fix_model))
         loss_reg = define_reg(opt, model)
-        for x_path, x_grph, x_omic, censor, survtime, grade in loader:
+
+        def one_batch(batch):
+            x_path, x_grph, x_omic, censor, survtime, grade = batch
             x_path = x_path.to(dev, non_blocking=True)
             x_omic = x_omic.to(dev, non_blocking=True)
             grade = grade.to(dev, non_blocking=True)
             _, feat_path, _, pred_path, _ = model(x_path=x_path, x_grph=x_grph, x_omic=x_omic)
-            pred = None
+            outs = [pred_path, feat_path]
             if fix_model is not None:
                 _, _, _, _, _, pred, _, _, _, _, _ = fix_model(x_path=x_path, x_grph=x_grph, x_omic=x_omic)
+                outs.append(pred)
             loss_nll = ops.NLLFn.apply(pred_path, grade, float(pred_path.shape[0]))
-            losses.append((opt.lambda_nll * loss_nll + opt.lambda_reg * loss_reg).reshape(1))
-            preds_path.append(pred_path); preds_fuse.append(pred); feats.append(feat_path); grades.append(grade)
-        d_path = torch.cat(preds_path).float().contiguous()
-        d_fuse = torch.cat(preds_fuse).float().contiguous() if fix_model is not None else None
-        d_grade = torch.cat(grades).reshape(-1)
-        loss_test = float(torch.cat(losses).sum().item()) / len(loader)
+            loss = (opt.lambda_nll * loss_nll + opt.lambda_reg * loss_reg).reshape(1)
+            return (outs + [grade]) if sync is None else outs, loss
+
+        outs, losses = _collect(loader, sync, one_batch)
+        d_path = outs[0].float().contiguous()
+        d_fuse = outs[2].float().contiguous() if fix_model is not None else None
+        d_grade = (outs[-1] if sync is None else loader.grade[loader.row_roi]).reshape(-1)
+        loss_test = float(losses.reshape(-1).sum().item()) / len(loader)
         probs_path = d_path.cpu().numpy()
         probs_all = d_fuse.cpu().numpy() if d_fuse is not None else None
-        feat_path_all = torch.cat(feats).cpu().numpy()
+        feat_path_all = outs[1].cpu().numpy()
         gt = d_grade.cpu().numpy().reshape(-1)
         gt_all = gt.astype(np.float64)
         grad_path_test = float((probs_path.argmax(axis=1) == gt).sum()) / len(loader.dataset)
@@ -271,5 +403,133 @@ def test_patches(opt, fix_model, model, loader, device, agg="max"):
             y_pred_fuse = agg_fuse.cpu().numpy()
         patient_result = dict(patients=list(loader.patients), y_label=y_label, y_pred_path=agg_path.cpu().numpy(),
                               y_pred_fuse=y_pred_fuse, metrics_path=metrics_path, metrics_fuse=metrics_fuse, agg=agg)
-        print("Patient level (%s):" % agg, *metrics_path)
+        print("Patient level (%s):" % (agg,), *metrics_path)
     return patch_result, patient_result
+
+
+CINDEX_MAX_N = 1 << 20                   # ph_cindex_counts: 2 <= N <= 1048576
+
+
+def test_teacher_patches(opt, model, loader, device, agg=None, sync=None):
+    """`test_patches` for the stage-1 teacher (a three-branch PathomicNet, both tasks): the reference's `test()` over
+    `test_loader_patches` (train_test_MT.py:287-289, :340-458), then the per-patient aggregation
+    (core/utils_analysis.py:425-480) - DESIGN.md section 24.  Returns (patch_result, patient_result).
+
+    patch_result: the 16-tuple `test_teacher` returns for the same loader (the same forward calls in the same order: bit
+    for bit), except that under the grading task its twelve all_grad_metrics come from `grading_metrics_device`.  The number
+    of host reads does not depend on the number of batches.
+
+    Grading (agg default "max"): patient_result = dict(patients, y_label one-hot [G, C], y_pred_fuse / _path / _omic [G, C],
+    metrics_fuse / _path / _omic (the four numbers of calcAggGradMetrics each), agg).
+
+    Survival (agg default "mean", the reference's Hazard_mean; "median" and "max" are its other two, utils_analysis.py:467):
+    patient_result = dict(patients, hazard_fuse / _path / _omic (float32 [G], aggregated on the device), survtime, censor
+    (per patient, float64), cindex_fuse / _path / _omic (one ph_cindex_counts launch on the three aggregated vectors,
+    utils.cindex_from_counts), pvalue, surv_acc (the fused branch, utils.cox_log_rank / utils.accuracy_cox), agg).  The loader
+    must carry `censor` and `survtime` (ValueError otherwise), and the number of patients must lie in 2 .. 1048576, the
+    range ph_cindex_counts accepts (ValueError otherwise).
+
+    `sync`: as `test_patches` - rank 0's buffers everywhere, whole batches dealt over the replicas, one all-gather."""
+    from . import utils as U
+    if opt.task not in ("grad", "surv"):
+        raise NotImplementedError("task %r" % opt.task)
+    surv = opt.task == "surv"
+    if agg is None:
+        agg = "mean" if surv else "max"
+    agg_spec(agg)
+    G = loader.num_patients
+    if surv:
+        if not getattr(loader, "has_survival", False):
+            raise ValueError("the survival task needs a loader built with censor= and survtime=")
+        if not 2 <= G <= CINDEX_MAX_N:
+            raise ValueError("the patient-level C-index needs 2 <= patients <= %d (the range of ph_cindex_counts), got %d"
+                             % (CINDEX_MAX_N, G))
+    model.eval()
+    dev = torch.device(device)
+    with torch.no_grad():
+        if sync is not None:
+            _sync_buffers(sync, (model,))
+        loss_reg = define_reg(opt, model)
+
+        def one_batch(batch):
+            x_path, x_grph, x_omic, censor, survtime, grade = batch
+            x_path = x_path.to(dev, non_blocking=True)
+            x_omic = x_omic.to(dev, non_blocking=True)
+            grade = grade.to(dev, non_blocking=True)
+            feat_fuse, feat_path, feat_omic, _, _, pred, pred_path, pred_omic, _, _, _ = model(
+                x_path=x_path, x_grph=x_grph, x_omic=x_omic)
+            if surv:
+                censor = censor.to(dev, torch.float32, non_blocking=True)
+                survtime = survtime.to(dev, torch.float32, non_blocking=True)
+                branch = ops.surv_loss_terms(pred, pred_path, pred_omic, survtime, censor)
+                loss = opt.lambda_cox * branch.sum() + opt.lambda_reg * loss_reg
+            else:
+                bn = float(pred.shape[0])
+                branch = torch.stack([ops.NLLFn.apply(p, grade, bn) for p in (pred, pred_path, pred_omic)])
+                loss = opt.lambda_nll * branch.sum() + opt.lambda_reg * loss_reg
+            return [pred, pred_path, pred_omic, feat_fuse, feat_path, feat_omic], torch.cat([loss.reshape(1), branch])
+
+        outs, losses = _collect(loader, sync, one_batch)
+        nb = len(loader)
+        loss_test, loss_fuse_test, loss_path_test, loss_omic_test = (float(v) / nb for v in
+                                                                     losses.sum(0).double().cpu().numpy())
+        feat_fuse_all, feat_path_all, feat_omic_all = (outs[j].cpu().numpy() for j in (3, 4, 5))
+        d_grade = loader.grade[loader.row_roi]
+        gt_all = d_grade.cpu().numpy().reshape(-1).astype(np.float64)
+        e = np.array([])
+        cindex_test = cindex_path = cindex_omic = pvalue_test = surv_acc_test = None
+        grad_acc_test = grad_path_test = grad_omic_test = all_grad_metrics = None
+        patient_result = dict(patients=list(loader.patients), agg=agg)
+        names = ("fuse", "path", "omic")
+        if surv:
+            risk = [outs[j].reshape(-1) for j in range(3)]
+            t_all, c_all = loader.survtime[loader.row_roi], loader.censor[loader.row_roi]
+            hazard = aggregate_by_patient(loader, torch.stack([r.float() for r in risk], dim=1).contiguous(), agg)
+            hz = [hazard[:, j].contiguous() for j in range(3)]
+            counts = torch.cat([ops.cindex_counts(t_all, c_all, risk),
+                                ops.cindex_counts(loader.patient_survtime, loader.patient_censor, hz)]).cpu().numpy()
+            risk_pred_all, risk_path_all, risk_omic_all = (r.cpu().numpy().astype(np.float64) for r in risk)
+            censor_all, survtime_all = c_all.cpu().numpy().astype(np.float64), t_all.cpu().numpy().astype(np.float64)
+            cindex_test, cindex_path, cindex_omic = (U.cindex_from_counts(c) for c in counts[:3])
+            pvalue_test = U.cox_log_rank(risk_pred_all, censor_all, survtime_all)
+            surv_acc_test = U.accuracy_cox(risk_pred_all, censor_all)
+            pred_test = [risk_pred_all, risk_path_all, risk_omic_all, survtime_all, censor_all, None, None, None, gt_all]
+            hz_host = hazard.cpu().numpy()
+            p_censor = loader.patient_censor_host.astype(np.float64)
+            p_time = loader.patient_survtime_host.astype(np.float64)
+            for j, name in enumerate(names):
+                patient_result["hazard_" + name] = np.ascontiguousarray(hz_host[:, j])
+                patient_result["cindex_" + name] = U.cindex_from_counts(counts[3 + j])
+            h64 = patient_result["hazard_fuse"].astype(np.float64)
+            patient_result.update(survtime=p_time, censor=p_censor, pvalue=U.cox_log_rank(h64, p_censor, p_time),
+                                  surv_acc=U.accuracy_cox(h64, p_censor))
+            print("Patient level (%s): C-index" % (agg,), *(patient_result["cindex_" + n] for n in names))
+        else:
+            d = [outs[j].float().contiguous() for j in range(3)]
+            probs_all, probs_path, probs_omic = (outs[j].cpu().numpy() for j in range(3))
+            n = len(loader.dataset)
+            grad_acc_test, grad_path_test, grad_omic_test = (float((p.argmax(axis=1) == gt_all).sum()) / n
+                                                             for p in (probs_all, probs_path, probs_omic))
+            all_grad_metrics = []
+            for name, p in zip(("Fused", "Path", "Omic"), d):
+                mtr = grading_metrics_device(p, d_grade)
+                print("%s branch:" % name, *mtr)
+                all_grad_metrics.extend(mtr)
+            pred_test = [e, e, e, e, e, probs_all, probs_path, probs_omic, gt_all]
+            C = d[0].shape[1]
+            y_label = np.zeros((G, C), dtype=np.float32)
+            y_label[np.arange(G), loader.patient_grade_host] = 1
+            patient_result["y_label"] = y_label
+            for name, p in zip(names, d):
+                a = aggregate_by_patient(loader, p, agg)
+                patient_result["metrics_" + name] = list(grading_metrics_device(a, loader.patient_grade))
+                patient_result["y_pred_" + name] = a.cpu().numpy()
+            print("Patient level (%s):" % (agg,), *patient_result["metrics_fuse"])
+        grads_test = [None, None, None]
+        feats_test = [feat_fuse_all, feat_path_all, feat_omic_all, gt_all]
+    patch_result = (loss_test, loss_fuse_test, loss_path_test, loss_omic_test, cindex_test, cindex_path, cindex_omic,
+                    pvalue_test, surv_acc_test, grad_acc_test, grad_path_test, grad_omic_test, all_grad_metrics, pred_test,
+                    grads_test, feats_test)
+    return patch_result, patient_result
+
+

@@ -665,6 +665,34 @@ def group_agg(x, offsets_dev, order_dev, offsets_host, fun):
     return out
 
 
+QUANTILE_MAX_GROUP = 4096                 # PH_QUANTILE_MAX_GROUP
+
+
+def group_quantile(x, offsets_dev, order_dev, offsets_host, q):
+    """out [G, C] = the q-quantile (a fraction in [0, 1]; numpy's percentile, method "linear"; 0.5 = pandas' median) of the
+    rows of x [N, C] per group (ph_group_quantile), over the CSR of `group_agg`.  A NaN in a group's column gives NaN.
+    One launch, nothing read back; groups of at most 4096 rows."""
+    import numpy as np
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("group_quantile: q is a fraction in [0, 1], got %r" % (q,))
+    x = _f32(x)
+    oh = np.ascontiguousarray(offsets_host, dtype=np.int32)
+    G = oh.shape[0] - 1
+    if x.dim() != 2 or order_dev.numel() != x.shape[0] or offsets_dev.numel() != G + 1:
+        raise ValueError("group_quantile: x [N, C], order [N], offsets [G + 1]")
+    if offsets_dev.dtype != torch.int32 or order_dev.dtype != torch.int32:
+        raise ValueError("group_quantile: offsets and order are int32")
+    out = torch.empty(G, x.shape[1], device=x.device, dtype=torch.float32)
+    rc = lib().ph_group_quantile(ptr(x), ptr(require_cuda(offsets_dev).contiguous()), ptr(require_cuda(order_dev).contiguous()),
+                                 oh.ctypes.data, x.shape[0], x.shape[1], G, q, ptr(out), stream())
+    if rc == -22:
+        raise ValueError("ph_group_quantile refused the groups: offsets must start at 0, end at N, leave no group empty and "
+                         "none larger than %d rows (N <= 16777216, C <= 4096)" % QUANTILE_MAX_GROUP)
+    check(rc, "ph_group_quantile")
+    return out
+
+
 class L2NormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
