@@ -310,6 +310,22 @@ __global__ __launch_bounds__(QUANT_THREADS) void group_quantile_block_kernel(con
 
 bool rank_shape_ok(int N, int C) { return N >= 1 && C >= 1 && (int64_t)N * C <= RANK_MAX_M; }
 
+// What ph_group_agg and ph_group_quantile check alike: the pointers, the N / C / G ranges and the host offsets (from 0 to N, no
+// group empty or negative, and none longer than max_len where max_len > 0).  *largest: the longest group.
+bool group_args_ok(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C, int G,
+                   const float* out, int max_len, int* largest) {
+  if (!x || !offsets || !order || !offsets_host || !out) return false;
+  if (N < 1 || N > AGG_MAX_N || C < 1 || C > AGG_MAX_C || G < 1 || G > N) return false;
+  if (offsets_host[0] != 0 || offsets_host[G] != N) return false;
+  *largest = 0;
+  for (int g = 0; g < G; ++g) {
+    const int64_t len = (int64_t)offsets_host[g + 1] - (int64_t)offsets_host[g];
+    if (len <= 0 || (max_len > 0 && len > max_len)) return false;
+    if ((int)len > *largest) *largest = (int)len;
+  }
+  return true;
+}
+
 }  // namespace
 
 #include "pathomic_hip.h"
@@ -346,12 +362,9 @@ int ph_confusion_counts(const float* pred, const int64_t* grade, int N, int C, i
 
 int ph_group_agg(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C, int G,
                  int fun, float* out, hipStream_t st) {
-  if (!x || !offsets || !order || !offsets_host || !out) return PH_EINVAL;
-  if (N < 1 || N > AGG_MAX_N || C < 1 || C > AGG_MAX_C || G < 1 || G > N) return PH_EINVAL;
+  int largest;
+  if (!group_args_ok(x, offsets, order, offsets_host, N, C, G, out, 0, &largest)) return PH_EINVAL;
   if (fun != PH_AGG_MEAN && fun != PH_AGG_MAX) return PH_EINVAL;
-  if (offsets_host[0] != 0 || offsets_host[G] != N) return PH_EINVAL;
-  for (int g = 0; g < G; ++g)
-    if (offsets_host[g + 1] <= offsets_host[g]) return PH_EINVAL;        // an empty (or negative) group
   const size_t n = (size_t)G * C;
   hipLaunchKernelGGL(group_agg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, offsets, order, N, C, G, fun, out);
   PH_LAUNCH_CHECK();
@@ -360,16 +373,9 @@ int ph_group_agg(const float* x, const int32_t* offsets, const int32_t* order, c
 
 int ph_group_quantile(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C,
                       int G, double q, float* out, hipStream_t st) {
-  if (!x || !offsets || !order || !offsets_host || !out) return PH_EINVAL;
-  if (N < 1 || N > AGG_MAX_N || C < 1 || C > AGG_MAX_C || G < 1 || G > N) return PH_EINVAL;
+  int largest;                                                            // (a longer group does not fit the LDS stage)
+  if (!group_args_ok(x, offsets, order, offsets_host, N, C, G, out, PH_QUANTILE_MAX_GROUP, &largest)) return PH_EINVAL;
   if (!(q >= 0.0 && q <= 1.0)) return PH_EINVAL;                          // (a NaN q fails both comparisons)
-  if (offsets_host[0] != 0 || offsets_host[G] != N) return PH_EINVAL;
-  int largest = 0;
-  for (int g = 0; g < G; ++g) {
-    const int64_t len = (int64_t)offsets_host[g + 1] - (int64_t)offsets_host[g];
-    if (len <= 0 || len > PH_QUANTILE_MAX_GROUP) return PH_EINVAL;        // empty, negative or larger than the LDS stage
-    if ((int)len > largest) largest = (int)len;
-  }
   static_assert(PH_QUANTILE_MAX_GROUP == QUANT_MAX_GROUP, "the header's limit is the kernel's LDS stage");
   if (largest <= 64) {
     const size_t items = (size_t)G * C, waves = QUANT_THREADS / 64;

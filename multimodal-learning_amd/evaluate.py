@@ -46,47 +46,10 @@ def test(opt, fix_model, model, test_loader, device):
     if opt.task != "grad":
         raise NotImplementedError("evaluation of the survival (Cox) task is out of scope")
     from sklearn.preprocessing import LabelBinarizer
-    if fix_model is not None:
-        fix_model.eval()
-    model.eval()
-    dev = torch.device(device)
-    preds_path, preds_fuse, feats, grades, losses = [], [], [], [], []
-    with torch.no_grad():
-        loss_reg = define_reg(opt, model)
-        for x_path, x_grph, x_omic, censor, survtime, grade in test_loader:
-            x_path = x_path.to(dev, non_blocking=True)
-            x_omic = x_omic.to(dev, non_blocking=True)
-            grade = grade.to(dev, non_blocking=True)
-            _, feat_path, _, pred_path, _ = model(x_path=x_path, x_grph=x_grph, x_omic=x_omic)            # :427
-            pred = None
-            if fix_model is not None:
-                _, _, _, _, _, pred, _, _, _, _, _ = fix_model(x_path=x_path, x_grph=x_grph, x_omic=x_omic)  # :431
-            loss_nll = ops.NLLFn.apply(pred_path, grade, float(pred_path.shape[0]))                        # :439
-            losses.append((opt.lambda_nll * loss_nll + opt.lambda_reg * loss_reg).reshape(1))              # :441
-            preds_path.append(pred_path); preds_fuse.append(pred); feats.append(feat_path); grades.append(grade)
-    nb = len(losses)
-    loss_test = float(torch.cat(losses).sum().item()) / len(test_loader)                                   # :442, :465
-    probs_path = torch.cat(preds_path).cpu().numpy()
-    probs_all = torch.cat(preds_fuse).cpu().numpy() if fix_model is not None else None
-    feat_path_all = torch.cat(feats).cpu().numpy()
-    gt = torch.cat(grades).cpu().numpy().reshape(-1)
-    gt_all = gt.astype(np.float64)                                     # np.concatenate onto np.array([]) (:444)
-    grad_path_test = float((probs_path.argmax(axis=1) == gt).sum()) / len(test_loader.dataset)             # :458, :472
-    enc = LabelBinarizer()
-    enc.fit(gt_all)
-    grad_gt = enc.transform(gt_all)                                                                        # :476-478
-    if fix_model is not None:
-        rocauc_fuse, ap_fuse, f1_micro_fuse, f1_gradeIV_fuse = grading_metrics(grad_gt, probs_all)         # :481
-        print("fixed fuse branch:", rocauc_fuse, ap_fuse, f1_micro_fuse, f1_gradeIV_fuse)
-    rocauc_path, ap_path, f1_micro_path, f1_gradeIV_path = grading_metrics(grad_gt, probs_path)
-    print("Path branch:", rocauc_path, ap_path, f1_micro_path, f1_gradeIV_path)
-    all_grad_metrics = [rocauc_path, ap_path, f1_micro_path, f1_gradeIV_path]
-    e = np.array([])
-    pred_test = [e, e, e, e, e, probs_all, probs_path, None, gt_all]                                       # :491-492
-    grads_test = [None, None, None]
-    feats_test = [None, feat_path_all, None, gt_all]
-    del nb
-    return loss_test, None, None, None, grad_path_test, all_grad_metrics, pred_test, grads_test, feats_test
+    outs, losses = _run(opt, (model, fix_model), test_loader, device, None,
+                        lambda loss_reg, dev: _student_batch(opt, model, fix_model, loss_reg, dev, True))
+    return _student_result(test_loader, outs[0], outs[2] if fix_model is not None else None, outs[1], outs[-1], losses,
+                           _host_metric(lambda gt_all: LabelBinarizer().fit(gt_all).transform(gt_all)))    # :476-478
 
 
 def test_teacher(opt, model, test_loader, device):
@@ -95,69 +58,13 @@ def test_teacher(opt, model, test_loader, device):
     surv_acc_test, grad_acc_test, grad_path_test, grad_omic_test, all_grad_metrics, pred_test, grads_test, feats_test).
     Per-batch losses and outputs stay on the device and leave it once, after the last batch; the survival batch losses are the
     forward-only fused Cox kernel, the three C-indices one concordance-count launch (utils.CIndex_lifeline's rule)."""
-    from . import utils as U
     if opt.task not in ("grad", "surv"):
         raise NotImplementedError("task %r" % opt.task)
     surv = opt.task == "surv"
-    model.eval()
-    dev = torch.device(device)
-    preds, feats, losses, censors, times, grades = [], [], [], [], [], []
-    with torch.no_grad():
-        loss_reg = define_reg(opt, model)
-        for x_path, x_grph, x_omic, censor, survtime, grade in test_loader:
-            x_path = x_path.to(dev, non_blocking=True)
-            x_omic = x_omic.to(dev, non_blocking=True)
-            grade = grade.to(dev, non_blocking=True)
-            feat_fuse, feat_path, feat_omic, _, _, pred, pred_path, pred_omic, _, _, _ = model(
-                x_path=x_path, x_grph=x_grph, x_omic=x_omic)                                                  # :355-356
-            if surv:
-                censor = censor.to(dev, torch.float32, non_blocking=True)
-                survtime = survtime.to(dev, torch.float32, non_blocking=True)
-                branch = ops.surv_loss_terms(pred, pred_path, pred_omic, survtime, censor)               # :366-369
-                loss = opt.lambda_cox * branch.sum() + opt.lambda_reg * loss_reg                         # :379
-                censors.append(censor.reshape(-1)); times.append(survtime.reshape(-1))
-            else:
-                bn = float(pred.shape[0])
-                branch = torch.stack([ops.NLLFn.apply(p, grade, bn) for p in (pred, pred_path, pred_omic)])   # :374-377
-                loss = opt.lambda_nll * branch.sum() + opt.lambda_reg * loss_reg
-            grades.append(grade.reshape(-1))
-            losses.append(torch.cat([loss.reshape(1), branch]))
-            preds.append((pred, pred_path, pred_omic)); feats.append((feat_fuse, feat_path, feat_omic))
-    nb = len(test_loader)
-    loss_test, loss_fuse_test, loss_path_test, loss_omic_test = (float(v) / nb for v in
-                                                                 torch.stack(losses).sum(0).double().cpu().numpy())   # :432-435
-    feat_fuse_all, feat_path_all, feat_omic_all = (torch.cat([f[k] for f in feats]).cpu().numpy() for k in range(3))
-    gt_all = torch.cat(grades).cpu().numpy().reshape(-1).astype(np.float64)                                # :384
-    e = np.array([])
-    cindex_test = cindex_path = cindex_omic = pvalue_test = surv_acc_test = None
-    grad_acc_test = grad_path_test = grad_omic_test = all_grad_metrics = None
-    if surv:
-        risk = [torch.cat([p[k].reshape(-1) for p in preds]) for k in range(3)]
-        t_all, c_all = torch.cat(times), torch.cat(censors)
-        counts = ops.cindex_counts(t_all, c_all, risk).cpu().numpy()                                       # :436-438
-        risk_pred_all, risk_path_all, risk_omic_all = (r.cpu().numpy().astype(np.float64) for r in risk)
-        censor_all, survtime_all = c_all.cpu().numpy().astype(np.float64), t_all.cpu().numpy().astype(np.float64)
-        cindex_test, cindex_path, cindex_omic = (U.cindex_from_counts(c) for c in counts)
-        pvalue_test = U.cox_log_rank(risk_pred_all, censor_all, survtime_all)                              # :439
-        surv_acc_test = U.accuracy_cox(risk_pred_all, censor_all)                                         # :440
-        pred_test = [risk_pred_all, risk_path_all, risk_omic_all, survtime_all, censor_all, None, None, None, gt_all]
-    else:
-        probs_all, probs_path, probs_omic = (torch.cat([p[k] for p in preds]).cpu().numpy() for k in range(3))
-        n = len(test_loader.dataset)
-        grad_acc_test, grad_path_test, grad_omic_test = (float((p.argmax(axis=1) == gt_all).sum()) / n
-                                                         for p in (probs_all, probs_path, probs_omic))       # :389-391, :442-444
-        grad_gt = np.zeros((gt_all.shape[0], opt.label_dim), dtype=np.float32)                           # :452
-        grad_gt[np.arange(gt_all.shape[0]), gt_all.astype(np.int64)] = 1
-        all_grad_metrics = []
-        for name, p in (("Fused", probs_all), ("Path", probs_path), ("Omic", probs_omic)):
-            mtr = grading_metrics(grad_gt, p)
-            print("%s branch:" % name, *mtr)
-            all_grad_metrics.extend(mtr)
-        pred_test = [e, e, e, e, e, probs_all, probs_path, probs_omic, gt_all]
-    grads_test = [None, None, None]
-    feats_test = [feat_fuse_all, feat_path_all, feat_omic_all, gt_all]
-    return (loss_test, loss_fuse_test, loss_path_test, loss_omic_test, cindex_test, cindex_path, cindex_omic, pvalue_test,
-            surv_acc_test, grad_acc_test, grad_path_test, grad_omic_test, all_grad_metrics, pred_test, grads_test, feats_test)
+    outs, losses = _run(opt, (model,), test_loader, device, None,
+                        lambda loss_reg, dev: _teacher_batch(opt, model, loss_reg, dev, surv, True))
+    return _teacher_result(test_loader, outs[:3], outs[3:6], outs[6], (outs[8], outs[7]) if surv else None, losses,
+                           _host_metric(lambda gt_all: _one_hot(gt_all.astype(np.int64), opt.label_dim)))[0]    # :452
 
 
 def metrics_from_counts(counts, ap_sum, conf):
@@ -295,7 +202,7 @@ def _collect(loader, sync, one_batch):
     """Run `one_batch(batch) -> (per-row outputs, loss vector [k])` over the loader; returns (outputs concatenated over
     the rows, losses [batches, k]).  With `sync`, replica r runs the batches r, r + W, .. and ONE all-gather returns
     every replica's rows and losses, which `undeal_shards` puts back into row order."""
-    if sync is None:
+    if sync is None:                    # any iterable loader with __len__ and .dataset
         outs, losses = [], []
         for batch in loader:
             o, l = one_batch(batch)
@@ -326,6 +233,162 @@ def _collect(loader, sync, one_batch):
     return outs, loss
 
 
+def _run(opt, nets, loader, device, sync, make_batch):
+    """The one pass behind `test`, `test_teacher` and the patch forms: `nets` (the first one carries the regulariser; None
+    entries are skipped) in eval mode, under `sync` rank 0's buffers on every replica, then `_collect` over
+    `make_batch(loss_reg, dev)` without a tape."""
+    for net in nets:
+        if net is not None:
+            net.eval()
+    with torch.no_grad():
+        if sync is not None:
+            _sync_buffers(sync, nets)
+        return _collect(loader, sync, make_batch(define_reg(opt, nets[0]), torch.device(device)))
+
+
+def _student_batch(opt, model, fix_model, loss_reg, dev, labels):
+    """one_batch of the stage-2 student (:427-441): outputs [pred_path, feat_path] + [the frozen teacher's fused pred, if
+    there is one] + [grade, if `labels`]; loss [1]."""
+    def one_batch(batch):
+        x_path, x_grph, x_omic, censor, survtime, grade = batch
+        x_path = x_path.to(dev, non_blocking=True)
+        x_omic = x_omic.to(dev, non_blocking=True)
+        grade = grade.to(dev, non_blocking=True)
+        _, feat_path, _, pred_path, _ = model(x_path=x_path, x_grph=x_grph, x_omic=x_omic)                 # :427
+        outs = [pred_path, feat_path]
+        if fix_model is not None:
+            _, _, _, _, _, pred, _, _, _, _, _ = fix_model(x_path=x_path, x_grph=x_grph, x_omic=x_omic)   # :431
+            outs.append(pred)
+        loss_nll = ops.NLLFn.apply(pred_path, grade, float(pred_path.shape[0]))                            # :439
+        loss = (opt.lambda_nll * loss_nll + opt.lambda_reg * loss_reg).reshape(1)                          # :441
+        return (outs + [grade.reshape(-1)]) if labels else outs, loss
+    return one_batch
+
+
+def _teacher_batch(opt, model, loss_reg, dev, surv, labels):
+    """one_batch of the stage-1 teacher (train_test_MT.py:355-379): outputs [pred, pred_path, pred_omic, feat_fuse, feat_path,
+    feat_omic] + [grade (, censor, survtime under `surv`), if `labels`]; loss [4] = (total, fuse, path, omic)."""
+    def one_batch(batch):
+        x_path, x_grph, x_omic, censor, survtime, grade = batch
+        x_path = x_path.to(dev, non_blocking=True)
+        x_omic = x_omic.to(dev, non_blocking=True)
+        grade = grade.to(dev, non_blocking=True)
+        feat_fuse, feat_path, feat_omic, _, _, pred, pred_path, pred_omic, _, _, _ = model(
+            x_path=x_path, x_grph=x_grph, x_omic=x_omic)                                                  # :355-356
+        own = [grade.reshape(-1)]
+        if surv:
+            censor = censor.to(dev, torch.float32, non_blocking=True)
+            survtime = survtime.to(dev, torch.float32, non_blocking=True)
+            branch = ops.surv_loss_terms(pred, pred_path, pred_omic, survtime, censor)                   # :366-369
+            loss = opt.lambda_cox * branch.sum() + opt.lambda_reg * loss_reg                             # :379
+            own += [censor.reshape(-1), survtime.reshape(-1)]
+        else:
+            bn = float(pred.shape[0])
+            branch = torch.stack([ops.NLLFn.apply(p, grade, bn) for p in (pred, pred_path, pred_omic)])   # :374-377
+            loss = opt.lambda_nll * branch.sum() + opt.lambda_reg * loss_reg
+        outs = [pred, pred_path, pred_omic, feat_fuse, feat_path, feat_omic]
+        return (outs + own) if labels else outs, torch.cat([loss.reshape(1), branch])
+    return one_batch
+
+
+def _one_hot(index, width):
+    """float32 [len(index), width], a 1 at column index[i] of row i."""
+    y = np.zeros((len(index), width), dtype=np.float32)
+    y[np.arange(len(index)), index] = 1
+    return y
+
+
+def _host_metric(labels):
+    """The builders' metric(pred, grade, probs, gt_all) of the plain forms: sklearn on the copied rows against
+    labels(gt_all)."""
+    return lambda pred, grade, probs, gt_all: grading_metrics(labels(gt_all), probs)
+
+
+def _device_metric(pred, grade, probs, gt_all):
+    """The builders' metric of the patch forms: the count kernels on the device rows."""
+    return grading_metrics_device(pred, grade)
+
+
+def _student_result(loader, d_path, d_fuse, d_feat, d_grade, losses, metric):
+    """The 9-tuple of `test` from the collected device tensors (d_fuse None without a teacher); each array leaves the
+    device here, once."""
+    loss_test = float(losses.reshape(-1).sum().item()) / len(loader)                                       # :442, :465
+    probs_path = d_path.cpu().numpy()
+    probs_all = d_fuse.cpu().numpy() if d_fuse is not None else None
+    feat_path_all = d_feat.cpu().numpy()
+    gt = d_grade.cpu().numpy().reshape(-1)
+    gt_all = gt.astype(np.float64)                                     # np.concatenate onto np.array([]) (:444)
+    grad_path_test = float((probs_path.argmax(axis=1) == gt).sum()) / len(loader.dataset)                  # :458, :472
+    if d_fuse is not None:
+        print("fixed fuse branch:", *metric(d_fuse, d_grade, probs_all, gt_all))                           # :481
+    all_grad_metrics = list(metric(d_path, d_grade, probs_path, gt_all))
+    print("Path branch:", *all_grad_metrics)
+    e = np.array([])
+    pred_test = [e, e, e, e, e, probs_all, probs_path, None, gt_all]                                       # :491-492
+    return (loss_test, None, None, None, grad_path_test, all_grad_metrics, pred_test, [None, None, None],
+            [None, feat_path_all, None, gt_all])
+
+
+def _teacher_result(loader, d_preds, d_feats, d_grade, surv_cols, losses, metric, more_counts=None):
+    """(the 16-tuple of `test_teacher`, host `more_counts`) from the collected device tensors: d_preds and d_feats in the
+    order fuse, path, omic; surv_cols = the rows' (survtime, censor) under the survival task, None under grading.
+    `more_counts`: further int64 [k, 3] concordance counts on the device, read in the one copy of the rows' three.  Each
+    array leaves the device here, once."""
+    from . import utils as U
+    nb = len(loader)
+    loss_test, loss_fuse_test, loss_path_test, loss_omic_test = (float(v) / nb for v in
+                                                                 losses.sum(0).double().cpu().numpy())    # :432-435
+    feat_fuse_all, feat_path_all, feat_omic_all = (f.cpu().numpy() for f in d_feats)
+    gt_all = d_grade.cpu().numpy().reshape(-1).astype(np.float64)                                          # :384
+    e = np.array([])
+    cindex_test = cindex_path = cindex_omic = pvalue_test = surv_acc_test = None
+    grad_acc_test = grad_path_test = grad_omic_test = all_grad_metrics = None
+    if surv_cols is not None:
+        risk = [p.reshape(-1) for p in d_preds]
+        t_all, c_all = surv_cols
+        counts = ops.cindex_counts(t_all, c_all, risk)                                                     # :436-438
+        if more_counts is not None:
+            counts = torch.cat([counts, more_counts])
+        counts = counts.cpu().numpy()
+        counts, more_counts = counts[:3], counts[3:]
+        risk_pred_all, risk_path_all, risk_omic_all = (r.cpu().numpy().astype(np.float64) for r in risk)
+        censor_all, survtime_all = c_all.cpu().numpy().astype(np.float64), t_all.cpu().numpy().astype(np.float64)
+        cindex_test, cindex_path, cindex_omic = (U.cindex_from_counts(c) for c in counts)
+        pvalue_test = U.cox_log_rank(risk_pred_all, censor_all, survtime_all)                              # :439
+        surv_acc_test = U.accuracy_cox(risk_pred_all, censor_all)                                         # :440
+        pred_test = [risk_pred_all, risk_path_all, risk_omic_all, survtime_all, censor_all, None, None, None, gt_all]
+    else:
+        probs = [p.cpu().numpy() for p in d_preds]
+        n = len(loader.dataset)
+        grad_acc_test, grad_path_test, grad_omic_test = (float((p.argmax(axis=1) == gt_all).sum()) / n
+                                                         for p in probs)                                   # :389-391, :442-444
+        all_grad_metrics = []
+        for name, d, p in zip(("Fused", "Path", "Omic"), d_preds, probs):
+            mtr = metric(d, d_grade, p, gt_all)
+            print("%s branch:" % name, *mtr)
+            all_grad_metrics.extend(mtr)
+        pred_test = [e, e, e, e, e] + probs + [gt_all]
+    grads_test = [None, None, None]
+    feats_test = [feat_fuse_all, feat_path_all, feat_omic_all, gt_all]
+    return (loss_test, loss_fuse_test, loss_path_test, loss_omic_test, cindex_test, cindex_path, cindex_omic, pvalue_test,
+            surv_acc_test, grad_acc_test, grad_path_test, grad_omic_test, all_grad_metrics, pred_test, grads_test,
+            feats_test), more_counts
+
+
+def _patient_grading(loader, agg, branches):
+    """The patient level of the grading task (core/utils_analysis.py:79-135, :152-167) for branches = ((name, device pred
+    [rows, C] or None), ..): dict(y_label one-hot [G, C], y_pred_<name> (`aggregate_by_patient`), metrics_<name> (the four
+    numbers of calcAggGradMetrics, `grading_metrics_device`)); both entries of a None branch are None."""
+    out = dict(y_label=_one_hot(loader.patient_grade_host, branches[0][1].shape[1]))
+    for name, d in branches:
+        out["metrics_" + name] = out["y_pred_" + name] = None
+        if d is not None:
+            a = aggregate_by_patient(loader, d, agg)
+            out["metrics_" + name] = list(grading_metrics_device(a, loader.patient_grade))
+            out["y_pred_" + name] = a.cpu().numpy()
+    return out
+
+
 def test_patches(opt, fix_model, model, loader, device, agg="max", sync=None):
     """The pass the reference's trainers take their final figures from: `test()` over `test_loader_patches`
     (train_test_path_multi_distill.py:360-366, train_test_MT.py:287-289), then the per-patient aggregation and `calcAggGradMetrics`
@@ -347,63 +410,15 @@ def test_patches(opt, fix_model, model, loader, device, agg="max", sync=None):
     if opt.task != "grad":
         raise NotImplementedError("evaluation of the survival (Cox) task is out of scope")
     agg_spec(agg)
-    if fix_model is not None:
-        fix_model.eval()
-    model.eval()
-    dev = torch.device(device)
-    with torch.no_grad():
-        if sync is not None:
-            _sync_buffers(sync, (model, fix_model))
-        loss_reg = define_reg(opt, model)
-
-        def one_batch(batch):
-            x_path, x_grph, x_omic, censor, survtime, grade = batch
-            x_path = x_path.to(dev, non_blocking=True)
-            x_omic = x_omic.to(dev, non_blocking=True)
-            grade = grade.to(dev, non_blocking=True)
-            _, feat_path, _, pred_path, _ = model(x_path=x_path, x_grph=x_grph, x_omic=x_omic)
-            outs = [pred_path, feat_path]
-            if fix_model is not None:
-                _, _, _, _, _, pred, _, _, _, _, _ = fix_model(x_path=x_path, x_grph=x_grph, x_omic=x_omic)
-                outs.append(pred)
-            loss_nll = ops.NLLFn.apply(pred_path, grade, float(pred_path.shape[0]))
-            loss = (opt.lambda_nll * loss_nll + opt.lambda_reg * loss_reg).reshape(1)
-            return (outs + [grade]) if sync is None else outs, loss
-
-        outs, losses = _collect(loader, sync, one_batch)
-        d_path = outs[0].float().contiguous()
-        d_fuse = outs[2].float().contiguous() if fix_model is not None else None
-        d_grade = (outs[-1] if sync is None else loader.grade[loader.row_roi]).reshape(-1)
-        loss_test = float(losses.reshape(-1).sum().item()) / len(loader)
-        probs_path = d_path.cpu().numpy()
-        probs_all = d_fuse.cpu().numpy() if d_fuse is not None else None
-        feat_path_all = outs[1].cpu().numpy()
-        gt = d_grade.cpu().numpy().reshape(-1)
-        gt_all = gt.astype(np.float64)
-        grad_path_test = float((probs_path.argmax(axis=1) == gt).sum()) / len(loader.dataset)
-        metrics_fuse = None
-        if d_fuse is not None:
-            print("fixed fuse branch:", *grading_metrics_device(d_fuse, d_grade))
-        all_grad_metrics = list(grading_metrics_device(d_path, d_grade))
-        print("Path branch:", *all_grad_metrics)
-        e = np.array([])
-        patch_result = (loss_test, None, None, None, grad_path_test, all_grad_metrics,
-                        [e, e, e, e, e, probs_all, probs_path, None, gt_all], [None, None, None],
-                        [None, feat_path_all, None, gt_all])
-        # per patient
-        G, C = loader.num_patients, d_path.shape[1]
-        y_label = np.zeros((G, C), dtype=np.float32)
-        y_label[np.arange(G), loader.patient_grade_host] = 1
-        agg_path = aggregate_by_patient(loader, d_path, agg)
-        metrics_path = list(grading_metrics_device(agg_path, loader.patient_grade))
-        y_pred_fuse = None
-        if d_fuse is not None:
-            agg_fuse = aggregate_by_patient(loader, d_fuse, agg)
-            metrics_fuse = list(grading_metrics_device(agg_fuse, loader.patient_grade))
-            y_pred_fuse = agg_fuse.cpu().numpy()
-        patient_result = dict(patients=list(loader.patients), y_label=y_label, y_pred_path=agg_path.cpu().numpy(),
-                              y_pred_fuse=y_pred_fuse, metrics_path=metrics_path, metrics_fuse=metrics_fuse, agg=agg)
-        print("Patient level (%s):" % (agg,), *metrics_path)
+    outs, losses = _run(opt, (model, fix_model), loader, device, sync,
+                        lambda loss_reg, dev: _student_batch(opt, model, fix_model, loss_reg, dev, sync is None))
+    d_path = outs[0].float().contiguous()
+    d_fuse = outs[2].float().contiguous() if fix_model is not None else None
+    d_grade = (outs[-1] if sync is None else loader.grade[loader.row_roi]).reshape(-1)
+    patch_result = _student_result(loader, d_path, d_fuse, outs[1], d_grade, losses, _device_metric)
+    patient_result = dict(patients=list(loader.patients), agg=agg,
+                          **_patient_grading(loader, agg, (("path", d_path), ("fuse", d_fuse))))
+    print("Patient level (%s):" % (agg,), *patient_result["metrics_path"])
     return patch_result, patient_result
 
 
@@ -444,92 +459,31 @@ def test_teacher_patches(opt, model, loader, device, agg=None, sync=None):
         if not 2 <= G <= CINDEX_MAX_N:
             raise ValueError("the patient-level C-index needs 2 <= patients <= %d (the range of ph_cindex_counts), got %d"
                              % (CINDEX_MAX_N, G))
-    model.eval()
-    dev = torch.device(device)
-    with torch.no_grad():
-        if sync is not None:
-            _sync_buffers(sync, (model,))
-        loss_reg = define_reg(opt, model)
-
-        def one_batch(batch):
-            x_path, x_grph, x_omic, censor, survtime, grade = batch
-            x_path = x_path.to(dev, non_blocking=True)
-            x_omic = x_omic.to(dev, non_blocking=True)
-            grade = grade.to(dev, non_blocking=True)
-            feat_fuse, feat_path, feat_omic, _, _, pred, pred_path, pred_omic, _, _, _ = model(
-                x_path=x_path, x_grph=x_grph, x_omic=x_omic)
-            if surv:
-                censor = censor.to(dev, torch.float32, non_blocking=True)
-                survtime = survtime.to(dev, torch.float32, non_blocking=True)
-                branch = ops.surv_loss_terms(pred, pred_path, pred_omic, survtime, censor)
-                loss = opt.lambda_cox * branch.sum() + opt.lambda_reg * loss_reg
-            else:
-                bn = float(pred.shape[0])
-                branch = torch.stack([ops.NLLFn.apply(p, grade, bn) for p in (pred, pred_path, pred_omic)])
-                loss = opt.lambda_nll * branch.sum() + opt.lambda_reg * loss_reg
-            return [pred, pred_path, pred_omic, feat_fuse, feat_path, feat_omic], torch.cat([loss.reshape(1), branch])
-
-        outs, losses = _collect(loader, sync, one_batch)
-        nb = len(loader)
-        loss_test, loss_fuse_test, loss_path_test, loss_omic_test = (float(v) / nb for v in
-                                                                     losses.sum(0).double().cpu().numpy())
-        feat_fuse_all, feat_path_all, feat_omic_all = (outs[j].cpu().numpy() for j in (3, 4, 5))
-        d_grade = loader.grade[loader.row_roi]
-        gt_all = d_grade.cpu().numpy().reshape(-1).astype(np.float64)
-        e = np.array([])
-        cindex_test = cindex_path = cindex_omic = pvalue_test = surv_acc_test = None
-        grad_acc_test = grad_path_test = grad_omic_test = all_grad_metrics = None
-        patient_result = dict(patients=list(loader.patients), agg=agg)
-        names = ("fuse", "path", "omic")
-        if surv:
-            risk = [outs[j].reshape(-1) for j in range(3)]
-            t_all, c_all = loader.survtime[loader.row_roi], loader.censor[loader.row_roi]
-            hazard = aggregate_by_patient(loader, torch.stack([r.float() for r in risk], dim=1).contiguous(), agg)
-            hz = [hazard[:, j].contiguous() for j in range(3)]
-            counts = torch.cat([ops.cindex_counts(t_all, c_all, risk),
-                                ops.cindex_counts(loader.patient_survtime, loader.patient_censor, hz)]).cpu().numpy()
-            risk_pred_all, risk_path_all, risk_omic_all = (r.cpu().numpy().astype(np.float64) for r in risk)
-            censor_all, survtime_all = c_all.cpu().numpy().astype(np.float64), t_all.cpu().numpy().astype(np.float64)
-            cindex_test, cindex_path, cindex_omic = (U.cindex_from_counts(c) for c in counts[:3])
-            pvalue_test = U.cox_log_rank(risk_pred_all, censor_all, survtime_all)
-            surv_acc_test = U.accuracy_cox(risk_pred_all, censor_all)
-            pred_test = [risk_pred_all, risk_path_all, risk_omic_all, survtime_all, censor_all, None, None, None, gt_all]
-            hz_host = hazard.cpu().numpy()
-            p_censor = loader.patient_censor_host.astype(np.float64)
-            p_time = loader.patient_survtime_host.astype(np.float64)
-            for j, name in enumerate(names):
-                patient_result["hazard_" + name] = np.ascontiguousarray(hz_host[:, j])
-                patient_result["cindex_" + name] = U.cindex_from_counts(counts[3 + j])
-            h64 = patient_result["hazard_fuse"].astype(np.float64)
-            patient_result.update(survtime=p_time, censor=p_censor, pvalue=U.cox_log_rank(h64, p_censor, p_time),
-                                  surv_acc=U.accuracy_cox(h64, p_censor))
-            print("Patient level (%s): C-index" % (agg,), *(patient_result["cindex_" + n] for n in names))
-        else:
-            d = [outs[j].float().contiguous() for j in range(3)]
-            probs_all, probs_path, probs_omic = (outs[j].cpu().numpy() for j in range(3))
-            n = len(loader.dataset)
-            grad_acc_test, grad_path_test, grad_omic_test = (float((p.argmax(axis=1) == gt_all).sum()) / n
-                                                             for p in (probs_all, probs_path, probs_omic))
-            all_grad_metrics = []
-            for name, p in zip(("Fused", "Path", "Omic"), d):
-                mtr = grading_metrics_device(p, d_grade)
-                print("%s branch:" % name, *mtr)
-                all_grad_metrics.extend(mtr)
-            pred_test = [e, e, e, e, e, probs_all, probs_path, probs_omic, gt_all]
-            C = d[0].shape[1]
-            y_label = np.zeros((G, C), dtype=np.float32)
-            y_label[np.arange(G), loader.patient_grade_host] = 1
-            patient_result["y_label"] = y_label
-            for name, p in zip(names, d):
-                a = aggregate_by_patient(loader, p, agg)
-                patient_result["metrics_" + name] = list(grading_metrics_device(a, loader.patient_grade))
-                patient_result["y_pred_" + name] = a.cpu().numpy()
-            print("Patient level (%s):" % (agg,), *patient_result["metrics_fuse"])
-        grads_test = [None, None, None]
-        feats_test = [feat_fuse_all, feat_path_all, feat_omic_all, gt_all]
-    patch_result = (loss_test, loss_fuse_test, loss_path_test, loss_omic_test, cindex_test, cindex_path, cindex_omic,
-                    pvalue_test, surv_acc_test, grad_acc_test, grad_path_test, grad_omic_test, all_grad_metrics, pred_test,
-                    grads_test, feats_test)
+    outs, losses = _run(opt, (model,), loader, device, sync,
+                        lambda loss_reg, dev: _teacher_batch(opt, model, loss_reg, dev, surv, False))
+    d_grade = loader.grade[loader.row_roi]
+    patient_result = dict(patients=list(loader.patients), agg=agg)
+    names = ("fuse", "path", "omic")
+    if surv:
+        risk = [outs[j].reshape(-1) for j in range(3)]
+        hazard = aggregate_by_patient(loader, torch.stack([r.float() for r in risk], dim=1).contiguous(), agg)
+        hz = [hazard[:, j].contiguous() for j in range(3)]
+        patch_result, counts = _teacher_result(
+            loader, outs[:3], outs[3:6], d_grade, (loader.survtime[loader.row_roi], loader.censor[loader.row_roi]), losses,
+            _device_metric, more_counts=ops.cindex_counts(loader.patient_survtime, loader.patient_censor, hz))
+        hz_host = hazard.cpu().numpy()
+        p_censor = loader.patient_censor_host.astype(np.float64)
+        p_time = loader.patient_survtime_host.astype(np.float64)
+        for j, name in enumerate(names):
+            patient_result["hazard_" + name] = np.ascontiguousarray(hz_host[:, j])
+            patient_result["cindex_" + name] = U.cindex_from_counts(counts[j])
+        h64 = patient_result["hazard_fuse"].astype(np.float64)
+        patient_result.update(survtime=p_time, censor=p_censor, pvalue=U.cox_log_rank(h64, p_censor, p_time),
+                              surv_acc=U.accuracy_cox(h64, p_censor))
+        print("Patient level (%s): C-index" % (agg,), *(patient_result["cindex_" + n] for n in names))
+    else:
+        d = [outs[j].float().contiguous() for j in range(3)]
+        patch_result, _ = _teacher_result(loader, d, outs[3:6], d_grade, None, losses, _device_metric)
+        patient_result.update(_patient_grading(loader, agg, tuple(zip(names, d))))
+        print("Patient level (%s):" % (agg,), *patient_result["metrics_fuse"])
     return patch_result, patient_result
-
-

@@ -643,26 +643,33 @@ def group_csr(group_of_row, num_groups):
     return offsets, order
 
 
-def group_agg(x, offsets_dev, order_dev, offsets_host, fun):
-    """out [G, C] = mean or max of the rows of x [N, C] per group (ph_group_agg); offsets_host: the numpy int32 copy of
-    offsets_dev (the entry checks it on the host: an empty group raises)."""
+def _group_call(name, entry, x, offsets_dev, order_dev, offsets_host, scalar, refusal):
+    """The body of `group_agg` and `group_quantile`: the checks of x and the CSR, out [G, C], the C call `entry` with its
+    one extra `scalar`, and its -22 as a ValueError with the text `refusal`."""
     import numpy as np
-    if fun not in AGG_FUN:
-        raise ValueError('agg must be "mean" or "max", got %r' % (fun,))
     x = _f32(x)
     oh = np.ascontiguousarray(offsets_host, dtype=np.int32)
     G = oh.shape[0] - 1
     if x.dim() != 2 or order_dev.numel() != x.shape[0] or offsets_dev.numel() != G + 1:
-        raise ValueError("group_agg: x [N, C], order [N], offsets [G + 1]")
+        raise ValueError("%s: x [N, C], order [N], offsets [G + 1]" % name)
     if offsets_dev.dtype != torch.int32 or order_dev.dtype != torch.int32:
-        raise ValueError("group_agg: offsets and order are int32")
+        raise ValueError("%s: offsets and order are int32" % name)
     out = torch.empty(G, x.shape[1], device=x.device, dtype=torch.float32)
-    rc = lib().ph_group_agg(ptr(x), ptr(require_cuda(offsets_dev).contiguous()), ptr(require_cuda(order_dev).contiguous()),
-                            oh.ctypes.data, x.shape[0], x.shape[1], G, AGG_FUN[fun], ptr(out), stream())
+    rc = entry(ptr(x), ptr(require_cuda(offsets_dev).contiguous()), ptr(require_cuda(order_dev).contiguous()),
+               oh.ctypes.data, x.shape[0], x.shape[1], G, scalar, ptr(out), stream())
     if rc == -22:
-        raise ValueError("ph_group_agg refused the groups: offsets must start at 0, end at N and leave no group empty")
-    check(rc, "ph_group_agg")
+        raise ValueError("ph_%s refused the groups: %s" % (name, refusal))
+    check(rc, "ph_" + name)
     return out
+
+
+def group_agg(x, offsets_dev, order_dev, offsets_host, fun):
+    """out [G, C] = mean or max of the rows of x [N, C] per group (ph_group_agg); offsets_host: the numpy int32 copy of
+    offsets_dev (the entry checks it on the host: an empty group raises)."""
+    if fun not in AGG_FUN:
+        raise ValueError('agg must be "mean" or "max", got %r' % (fun,))
+    return _group_call("group_agg", lib().ph_group_agg, x, offsets_dev, order_dev, offsets_host, AGG_FUN[fun],
+                       "offsets must start at 0, end at N and leave no group empty")
 
 
 QUANTILE_MAX_GROUP = 4096                 # PH_QUANTILE_MAX_GROUP
@@ -672,25 +679,12 @@ def group_quantile(x, offsets_dev, order_dev, offsets_host, q):
     """out [G, C] = the q-quantile (a fraction in [0, 1]; numpy's percentile, method "linear"; 0.5 = pandas' median) of the
     rows of x [N, C] per group (ph_group_quantile), over the CSR of `group_agg`.  A NaN in a group's column gives NaN.
     One launch, nothing read back; groups of at most 4096 rows."""
-    import numpy as np
     q = float(q)
     if not 0.0 <= q <= 1.0:
         raise ValueError("group_quantile: q is a fraction in [0, 1], got %r" % (q,))
-    x = _f32(x)
-    oh = np.ascontiguousarray(offsets_host, dtype=np.int32)
-    G = oh.shape[0] - 1
-    if x.dim() != 2 or order_dev.numel() != x.shape[0] or offsets_dev.numel() != G + 1:
-        raise ValueError("group_quantile: x [N, C], order [N], offsets [G + 1]")
-    if offsets_dev.dtype != torch.int32 or order_dev.dtype != torch.int32:
-        raise ValueError("group_quantile: offsets and order are int32")
-    out = torch.empty(G, x.shape[1], device=x.device, dtype=torch.float32)
-    rc = lib().ph_group_quantile(ptr(x), ptr(require_cuda(offsets_dev).contiguous()), ptr(require_cuda(order_dev).contiguous()),
-                                 oh.ctypes.data, x.shape[0], x.shape[1], G, q, ptr(out), stream())
-    if rc == -22:
-        raise ValueError("ph_group_quantile refused the groups: offsets must start at 0, end at N, leave no group empty and "
-                         "none larger than %d rows (N <= 16777216, C <= 4096)" % QUANTILE_MAX_GROUP)
-    check(rc, "ph_group_quantile")
-    return out
+    return _group_call("group_quantile", lib().ph_group_quantile, x, offsets_dev, order_dev, offsets_host, q,
+                       "offsets must start at 0, end at N, leave no group empty and none larger than %d rows "
+                       "(N <= 16777216, C <= 4096)" % QUANTILE_MAX_GROUP)
 
 
 class L2NormFn(torch.autograd.Function):

@@ -124,3 +124,37 @@ class Report:
             if err > tol:
                 bad.append(what)
         assert not bad, f"{self.title}: out of tolerance: {bad}"
+
+
+def assert_same(a, b, path="r"):
+    """Exact equality of two nested results (dicts, lists / tuples, numpy arrays with dtype, floats, None)."""
+    if isinstance(a, dict):
+        assert isinstance(b, dict) and set(a) == set(b), path
+        for k in a:
+            assert_same(a[k], b[k], "%s[%r]" % (path, k))
+    elif isinstance(a, (list, tuple)):
+        assert type(a) is type(b) and len(a) == len(b), path
+        for k, (x, y) in enumerate(zip(a, b)):
+            assert_same(x, y, "%s[%d]" % (path, k))
+    elif isinstance(a, np.ndarray):
+        assert isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=True), path
+    elif isinstance(a, float) and a != a:
+        assert b != b, path
+    else:
+        assert type(a) is type(b) and a == b, (path, a, b)
+
+
+def count_host_reads(monkeypatch):
+    """Wrap torch.Tensor's cpu / item / tolist / numpy so that each call counts; returns the dict whose "n" is the count."""
+    calls = {"n": 0}
+
+    def counted(name):
+        orig = getattr(torch.Tensor, name)
+
+        def f(self, *a, **k):
+            calls["n"] += 1
+            return orig(self, *a, **k)
+        return f
+    for name in ("cpu", "item", "tolist", "numpy"):
+        monkeypatch.setattr(torch.Tensor, name, counted(name))
+    return calls

@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_util import assert_same
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -72,24 +74,6 @@ def _nets(opt, perturb=0.0):
                     elif name.endswith("num_batches_tracked"):
                         b.add_(7)
     return student, teacher
-
-
-def _same(a, b, path="r"):
-    """Exact equality of two nested results (dicts, lists / tuples, numpy arrays with dtype, floats, None)."""
-    if isinstance(a, dict):
-        assert isinstance(b, dict) and set(a) == set(b), path
-        for k in a:
-            _same(a[k], b[k], "%s[%r]" % (path, k))
-    elif isinstance(a, (list, tuple)):
-        assert type(a) is type(b) and len(a) == len(b), path
-        for k, (x, y) in enumerate(zip(a, b)):
-            _same(x, y, "%s[%d]" % (path, k))
-    elif isinstance(a, np.ndarray):
-        assert isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=True), path
-    elif isinstance(a, float) and a != a:
-        assert b != b, path
-    else:
-        assert type(a) is type(b) and a == b, (path, a, b)
 
 
 class LocalGroup:
@@ -184,8 +168,8 @@ def test_grading_replicas_equal_the_single_process_pass_of_rank_0(store, batch, 
         return a, b
     outs, group = _run_replicas(W, fn)
     for r in range(W):
-        _same(outs[r][0], single_p, "rank%d.test_patches" % r)
-        _same(outs[r][1], single_t, "rank%d.test_teacher_patches" % r)
+        assert_same(outs[r][0], single_p, "rank%d.test_patches" % r)
+        assert_same(outs[r][1], single_t, "rank%d.test_teacher_patches" % r)
         assert counts[(r, 0)] == (1, 1) and counts[(r, 1)] == (2, 2), (r, counts)       # one gather per pass
         for net, ref in zip(nets[r], ref_buffers):
             for b, want in zip(net.buffers(), ref):
@@ -204,7 +188,7 @@ def test_survival_replicas_equal_the_single_process_pass_of_rank_0(store):
     nets = [t0, _nets(opt, 0.05)[1]]
     outs, group = _run_replicas(W, lambda r, sync: m.evaluate.test_teacher_patches(opt, nets[r], ld, "cuda", agg="median", sync=sync))
     for r in range(W):
-        _same(outs[r], single, "rank%d" % r)
+        assert_same(outs[r], single, "rank%d" % r)
     assert group.gathers == [1, 1]
     for b, want in zip(nets[1].buffers(), t0.buffers()):
         assert torch.equal(b, want)
@@ -228,15 +212,15 @@ def _rank_child(store_path, out_path):
         sync = ReplicaSync()
         assert sync.world_size == 1 and sync.rank == 0
         before = [b.clone() for b in t0.buffers()]
-        _same(m.evaluate.test_patches(opt, t0, s0, ld, "cuda", agg="median", sync=sync),
-              m.evaluate.test_patches(opt, t0, s0, ld, "cuda", agg="median"), "test_patches")
-        _same(m.evaluate.test_teacher_patches(opt, t0, ld, "cuda", sync=sync),
-              m.evaluate.test_teacher_patches(opt, t0, ld, "cuda"), "test_teacher_patches")
+        assert_same(m.evaluate.test_patches(opt, t0, s0, ld, "cuda", agg="median", sync=sync),
+                    m.evaluate.test_patches(opt, t0, s0, ld, "cuda", agg="median"), "test_patches")
+        assert_same(m.evaluate.test_teacher_patches(opt, t0, ld, "cuda", sync=sync),
+                    m.evaluate.test_teacher_patches(opt, t0, ld, "cuda"), "test_teacher_patches")
         sopt = _opt(8, task="surv", act_type="Sigmoid", label_dim=1)
         sld = _loader(store, sopt, surv=True)
         _, st = _nets(sopt)
-        _same(m.evaluate.test_teacher_patches(sopt, st, sld, "cuda", sync=sync),
-              m.evaluate.test_teacher_patches(sopt, st, sld, "cuda"), "test_teacher_patches(surv)")
+        assert_same(m.evaluate.test_teacher_patches(sopt, st, sld, "cuda", sync=sync),
+                    m.evaluate.test_teacher_patches(sopt, st, sld, "cuda"), "test_teacher_patches(surv)")
         assert all(torch.equal(a, b) for a, b in zip(before, t0.buffers()))
         torch.cuda.synchronize()
         with open(out_path, "w") as f:

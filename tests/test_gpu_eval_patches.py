@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import eval_emulation as E
+from tests.gpu_util import count_host_reads
 
 pytestmark = pytest.mark.gpu
 
@@ -156,17 +157,7 @@ def test_student_only_form(passes, nets):
 def test_host_reads_do_not_depend_on_the_number_of_batches(store, nets, monkeypatch):
     import multimodal_learning_amd as m
     student, teacher = nets
-    calls = {"n": 0}
-
-    def counted(name):
-        orig = getattr(torch.Tensor, name)
-
-        def f(self, *a, **k):
-            calls["n"] += 1
-            return orig(self, *a, **k)
-        return f
-    for name in ("cpu", "item", "tolist", "numpy"):
-        monkeypatch.setattr(torch.Tensor, name, counted(name))
+    calls = count_host_reads(monkeypatch)
     reads = {}
     for bs in (36, 8):
         opt = _opt()
