@@ -46,5 +46,6 @@ class CRDLoss(nn.Module):
             raise RuntimeError("contrast_idx must be [B, nce_k + 1] (CRD_criterion.py:42 views it so)")
         f_s = self.embed_s(f_s)
         f_t = self.embed_t(f_t)
-        sample_loss = _CRDCoreFn.apply(f_s, f_t, self.contrast, idx, contrast_idx, None, True)   # [B], already / bsz
+        call = self.contrast.plan(contrast_idx, per_sample=True)
+        sample_loss = _CRDCoreFn.apply(f_s, f_t, self.contrast, idx, call)   # [B], already / bsz
         return sample_loss.sum(0, keepdim=True)                                                  # s_loss + t_loss, [1]

@@ -13,47 +13,31 @@ this project's own instead, `ph_crd_kmeans_centers`: fart
 (default 16) Lloyd iterations on the device, the nce_p - 1 centres of every class behind the bank rows.  It is not sklearn's
 k-means++ and claims no draw parity; on a bank whose clustering is not in doubt it gives the reference's numbers
 (tests/golden/make_golden_mia2023_kmeans.py)."""
-import math
+import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .CRD_loss import Embed, Normalize   # noqa: F401
-from .memory_new import _CRDCoreFn, check_feat_dim
+from .memory_new import ContrastBank, CrdCall, _CRDCoreFn, check_feat_dim
 from .._lib import lib, check, ptr, stream
 
 eps = 1e-7
 
 
-class ContrastMemory(nn.Module):
-    """CRD_criterion_v10.py:20-43: params = [K, T, Z_v1, Z_v2, momentum] + the class of every bank row."""
+class ContrastMemory(ContrastBank):
+    """CRD_criterion_v10.py:20-43: params = [K, T, Z_v1, Z_v2, momentum] + the class of every bank row.  The list widths are
+    per call (CRDLoss.neighbor_columns / center_columns)."""
 
     def __init__(self, inputSize, outputSize, train_class_idx, K, T=0.07, momentum=0.5):
-        super().__init__()
-        self.nLem = outputSize
-        self.K = K
+        super().__init__(inputSize, outputSize, K, T, momentum)
         self.class_idx = train_class_idx
         labels = torch.zeros(outputSize, dtype=torch.int32)
         for c, members in enumerate(train_class_idx):
             labels[torch.as_tensor(np.asarray(members)).long()] = c
         self.register_buffer("all_sample_labels", labels, persistent=False)
-        self.T = T
-        self.select_neg_pairs = "False"
-        self.register_buffer("params", torch.tensor([K, T, -1, -1, momentum], dtype=torch.float32))
-        stdv = 1.0 / math.sqrt(inputSize / 3)
-        self.register_buffer("memory_v1", torch.rand(outputSize, inputSize).mul_(2 * stdv).add_(-stdv))
-        self.register_buffer("memory_v2", torch.rand(outputSize, inputSize).mul_(2 * stdv).add_(-stdv))
-        self._z_set = False
-        self.sync = None
-        self.batch_norm_size = None
-        self.verbose = True
-        self.last = None
         self.center_k = 1          # centre rows per class behind the bank (CRDLoss sets nce_p - 1)
-
-    def _load_from_state_dict(self, *a, **k):
-        super()._load_from_state_dict(*a, **k)
-        self._z_set = bool((self.params[2:4] > 0).all().item())
 
     def ensure_center_rows(self, dev):
         """`pos_extra == "centers"`: re-home both banks into allocations with len(class_idx) * center_k extra rows behind the
@@ -133,30 +117,25 @@ class CRDLoss(nn.Module):
             self.contrast.center_k = self.num_pos - 1
         self.criterion_t = ContrastLoss_v2(n_data)
         self.criterion_s = ContrastLoss_v2(n_data)
-        import os
         self._scan_override = os.environ.get("PH_CRD_SCAN")      # (read once: the numerics do not follow later changes)
 
     def forward(self, sample_weights, f_s, f_t, batch_label, idx, contrast_idx=None):
         mem = self.contrast
-        NP, K = self.num_pos, mem.K
-        if contrast_idx is None or contrast_idx.shape[1] != K + 1:
+        if contrast_idx is None or contrast_idx.shape[1] != mem.K + 1:
             raise RuntimeError("contrast_idx must be [B, nce_k + 1]")
         v1 = self.embed_s(f_s)
         v2 = self.embed_t(f_t)
-        B = v1.shape[0]
+        B, D = v1.shape
         dev = v1.device
         contrast_idx = contrast_idx.contiguous()
         batch_label = batch_label.to(dev).long().contiguous()
         if self.pos_extra == "centers":
-            return self._forward_centers(sample_weights, v1, v2, batch_label, idx, contrast_idx)
-        idx1, knn = self.neighbor_columns(B, v1.shape[1], batch_label, contrast_idx)
-        rows = _CRDCoreFn.apply(v1, v2, mem, idx, idx1, None, True)          # [B]: (s + t) sample losses / bsz
+            call, knn = self.center_columns(B, D, batch_label, contrast_idx), {}
+        else:
+            call, knn = self.neighbor_columns(B, D, batch_label, contrast_idx)
+        rows = _CRDCoreFn.apply(v1, v2, mem, idx, call)                      # [B]: (s + t) sample losses / bsz
         mem.last.update(knn)
-        w = sample_weights.to(dev).reshape(-1) if torch.is_tensor(sample_weights) else float(sample_weights)
-        bn = float(mem.batch_norm_size or B)                                 # global batch under data parallelism
-        sample_loss = w * rows * bn                                          # the reference's per-sample values
-        return sample_loss.sum(0) / bn, sample_loss
-
+        return _weighted(sample_weights, rows, mem, B)
 
     SCAN_MIN_ROWS = 8192
 
@@ -169,7 +148,6 @@ class CRDLoss(nn.Module):
         gathered form.  `override` "0" / "1" forces one form (tests, A/B); the default reads PH_CRD_SCAN from the
         environment - a CRDLoss instance reads it ONCE, at construction."""
         if override == "env":
-            import os
             override = os.environ.get("PH_CRD_SCAN")
         if override in ("0", "1"):
             return override == "1"
@@ -177,9 +155,9 @@ class CRDLoss(nn.Module):
 
     def neighbor_columns(self, B, D, batch_label, contrast_idx):
         """`pos_extra == "neighbors"` (:72-80, :110-117): the num_pos same-class nearest bank rows of every query in either
-        bank (ph_crd_bank_topk) in front of the K sampled negatives.  Sets the memory module up for the fused CRD kernels
-        (column list of bank 2, similarity weights of the positives) and returns (column list of bank 1, the KNN tensors);
-        shared by forward() and the closed-form loss head (loss_head.FusedMia2023LossFn)."""
+        bank (ph_crd_bank_topk) in front of the K sampled negatives.  -> (the CrdCall of the fused CRD kernels: a column list
+        per bank, the similarity weights of the positives; the KNN tensors); shared by forward() and the closed-form loss head
+        (loss_head.FusedMia2023LossFn)."""
         mem = self.contrast
         NP, K = self.num_pos, mem.K
         dev = contrast_idx.device
@@ -189,24 +167,21 @@ class CRDLoss(nn.Module):
         check(lib().ph_crd_bank_topk(ptr(mem.memory_v1), ptr(mem.memory_v2), ptr(mem.all_sample_labels),
                                      ptr(contrast_idx), K + 1, ptr(batch_label), B, mem.nLem, NP, D, ptr(nb1),
                                      ptr(nb2), ptr(sim1), ptr(sim2), ptr(ws), stream()), "ph_crd_bank_topk")
-        # out_s = out_v1 comes from bank 2 and is weighted by the bank-2 similarities (:226), and vice versa (:227)
-        mem.P, mem.P2, mem.K2 = NP, NP, K
         if self.scan_negatives(K, mem.nLem, self._scan_override):
             # nce_k at or above the number of bank rows (configs[4] read as 65 536 negatives per query): the negatives' terms are
             # summed over the whole bank weighted by multiplicity (memory_new._crd_core_scan); only the positives are gathered
-            idx1, idx2 = nb1, nb2
-            mem._scan_neg = dict(idx=contrast_idx, col0=1, K=K)
+            idx1, idx2, scan = nb1, nb2, dict(idx=contrast_idx, col0=1, K=K)
         else:
             # column lists: [num_pos KNN rows of that bank] + [the K sampled negatives]  (:80, :117)
             idx1 = torch.cat((nb1, contrast_idx[:, 1:]), 1).contiguous()
             idx2 = torch.cat((nb2, contrast_idx[:, 1:]), 1).contiguous()
-            mem._scan_neg = None
-        mem._idx_bank2 = idx2
-        mem._posw_s = (sim2 / sim2.sum(1, keepdim=True)).contiguous()
-        mem._posw_t = (sim1 / sim1.sum(1, keepdim=True)).contiguous()
-        return idx1, dict(nb1=nb1, nb2=nb2, sim1=sim1, sim2=sim2, _ws=ws)
+            scan = None
+        # out_s = out_v1 comes from bank 2 and is weighted by the bank-2 similarities (:226), and vice versa (:227)
+        call = CrdCall(NP, K, NP, K, idx1, idx_bank2=idx2, scan=scan, posw_s=(sim2 / sim2.sum(1, keepdim=True)).contiguous(),
+                       posw_t=(sim1 / sim1.sum(1, keepdim=True)).contiguous(), per_sample=True)
+        return call, dict(nb1=nb1, nb2=nb2, sim1=sim1, sim2=sim2, _ws=ws)
 
-    def _forward_centers(self, sample_weights, v1, v2, batch_label, idx, contrast_idx):
+    def center_columns(self, B, D, batch_label, contrast_idx):
         """:81-101 / :118-139 and ContrastLoss (:241-277) for P = num_pos: columns = [the P - 1 centres of the query's class,
         the K + 1 sampled rows (the first is the query's own), the (C - 1)(P - 1) centres of the other classes, classes
         ascending, centres ascending]; the first P are the positives.  ContrastLoss with P > 1 is
@@ -214,20 +189,19 @@ class CRDLoss(nn.Module):
         what the fused kernels compute for posw = None.  P == 2: the class means (ph_crd_class_centers); P > 2: the device
         k-means (ph_crd_kmeans_centers), both banks in one call, from the PRE-update bank like the means.  Under ReplicaSync
         the banks are replicated and the k-means is deterministic - the same bits on every replica - so no exchange is
-        needed."""
+        needed.  -> the CrdCall."""
         mem = self.contrast
-        K, n, dev = mem.K, mem.nLem, v1.device
-        B = v1.shape[0]
+        K, n, dev = mem.K, mem.nLem, contrast_idx.device
         C = len(mem.class_idx)
         mem.ensure_center_rows(dev)
         P, ck = self.num_pos, self.num_pos - 1
         if ck == 1:
             for bank in (mem.memory_v1, mem.memory_v2):
                 check(lib().ph_crd_class_centers(ptr(bank), ptr(mem._members), ptr(mem._member_off), C, mem._max_class, n,
-                                                 v1.shape[1], ptr(mem._center_ws), stream()), "ph_crd_class_centers")
+                                                 D, ptr(mem._center_ws), stream()), "ph_crd_class_centers")
         else:
             check(lib().ph_crd_kmeans_centers(ptr(mem.memory_v1), ptr(mem.memory_v2), ptr(mem._members), ptr(mem._member_off),
-                                              C, mem._max_class, n, v1.shape[1], ck, self.kmeans_iters, None, None,
+                                              C, mem._max_class, n, D, ck, self.kmeans_iters, None, None,
                                               ptr(mem._kmeans_ws), stream()), "ph_crd_kmeans_centers")
         # the other classes in ascending order (np.argwhere(onehot == 0)[:, 1], :63-64)
         others = mem._others[batch_label]                                          # [B, C - 1]
@@ -238,20 +212,16 @@ class CRDLoss(nn.Module):
             own = n + batch_label.view(B, 1) * ck + j                              # [B, P - 1]
             neg = (n + others.view(B, C - 1, 1) * ck + j).view(B, (C - 1) * ck)
             cols = torch.cat((own, contrast_idx, neg), 1).contiguous()
-        mem.P, mem.P2, mem.K2 = P, P, K + (C - 1) * ck
-        mem._idx_bank2 = None
-        mem._scan_neg = None
-        mem._posw_s = mem._posw_t = None                                           # ContrastLoss: 1 / P each
-        K_saved = mem.K
-        mem.K = K + (C - 1) * ck                                                   # crd_core reads P + K as the list width
-        try:
-            rows = _CRDCoreFn.apply(v1, v2, mem, idx, cols, None, True)
-        finally:
-            mem.K = K_saved
-        w = sample_weights.to(dev).reshape(-1) if torch.is_tensor(sample_weights) else float(sample_weights)
-        bn = float(mem.batch_norm_size or B)
-        sample_loss = w * rows * bn
-        return sample_loss.sum(0) / bn, sample_loss
+        Kn = K + (C - 1) * ck
+        return CrdCall(P, Kn, P, Kn, cols, per_sample=True)                       # (no weights - ContrastLoss: 1 / P each)
+
+
+def _weighted(sample_weights, rows, mem, B):
+    """`rows` [B] = (s + t) sample losses / bsz under the trainer's sample weights -> (loss, the reference's per-sample values)."""
+    w = sample_weights.to(rows.device).reshape(-1) if torch.is_tensor(sample_weights) else float(sample_weights)
+    bn = float(mem.batch_norm_size or B)                                     # global batch under data parallelism
+    sample_loss = w * rows * bn
+    return sample_loss.sum(0) / bn, sample_loss
 
 
 class ContrastLoss_v2(nn.Module):

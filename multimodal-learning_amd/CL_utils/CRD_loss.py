@@ -26,7 +26,7 @@ class CRDLoss(nn.Module):
         # --sample_KD True (options.py:69): both criteria return the [B] per-sample losses of ContrastLoss_v2's second branch
         # (:246-250) and forward() their sum s_loss + t_loss, shape [B] - the same fused kernel, rows left un-normalised
         self.sample_KD = getattr(opt, "sample_KD", "False")
-        self.contrast.sample_KD = self.sample_KD == "True"
+        self.contrast.sample_KD = self.sample_KD == "True"      # (the bank's own flag, False by default: ContrastBank)
         self.criterion_t = ContrastLoss_v2(n_data, sample_KD=opt.sample_KD)
         self.criterion_s = ContrastLoss_v2(n_data, sample_KD=opt.sample_KD)
         self.select_pos_mode = opt.select_pos_mode

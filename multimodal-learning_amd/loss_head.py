@@ -29,7 +29,7 @@ import torch
 
 from . import ops
 from ._lib import lib, check, ptr, stream
-from .CL_utils.memory_new import crd_core
+from .CL_utils.memory_new import FEAT_DIMS, crd_core
 
 
 class LossHeadCtx:
@@ -160,8 +160,8 @@ class FusedDistillLossFn(torch.autograd.Function):
 
         def chain(k):                                                  # row 3 + k: d CRD_k / d feat
             crd, tf, rk = chains[k]
-            return _crd_chain(crd, feat, tf, G[3 + k], lambda v1, v2: crd_core(v1, v2, crd.contrast, H.index, H.sample_idx, rk,
-                                                                               False, loss_out=Lb[3 + k]))
+            call = crd.contrast.plan(H.sample_idx, rk)
+            return _crd_chain(crd, feat, tf, G[3 + k], lambda v1, v2: crd_core(v1, v2, crd.contrast, H.index, call, loss_out=Lb[3 + k]))
         done = step._two_chains(lambda: chain(0), lambda: chain(1))
         gram = torch.empty(25, device=dev, dtype=torch.float32)
         check(L.ph_gram(ptr(G), ptr(gram), 5, B * D, st), "ph_gram")
@@ -220,9 +220,9 @@ class FusedMia2023LossFn(torch.autograd.Function):
         opt = step.opt
         L = lib()
         st = stream()
-        if feat.shape[1] not in (64, 128, 256):      # before anything runs: the CRD chains below update the banks
-            raise ValueError("MIA-2023 loss head: feature rows of width %d; ph_gk_rows is built for the widths [64, 128, 256]"
-                             % feat.shape[1])
+        if feat.shape[1] not in FEAT_DIMS:      # before anything runs: the CRD chains below update the banks
+            raise ValueError("MIA-2023 loss head: feature rows of width %d; ph_gk_rows is built for the widths %s"
+                             % (feat.shape[1], list(FEAT_DIMS)))
         # Lb: batch means of KL to the fused teacher, to the EMA teacher, CE; dl: d (those means) / d logits
         feat, logits, pred, Lb, dl, yts, grade = _logit_losses(H, feat, 3)
         B, D = feat.shape
@@ -247,10 +247,10 @@ class FusedMia2023LossFn(torch.autograd.Function):
             crd, tf = chains[k]
 
             def core(v1, v2):
-                idx1, knn = crd.neighbor_columns(B, v1.shape[1], grade, H.sample_idx)
-                rows, dv1, dv2 = crd_core(v1, v2, crd.contrast, H.index, idx1, None, True)     # rows: (s + t) losses / bsz per sample
+                call, knn = crd.neighbor_columns(B, v1.shape[1], grade, H.sample_idx)
+                rows, dv1, dv2 = crd_core(v1, v2, crd.contrast, H.index, call)     # rows: (s + t) losses / bsz per sample
                 crd.contrast.last.update(knn)
-                return (rows, dv1, dv2, idx1, *knn.values())
+                return (rows, dv1, dv2, call.idx, *knn.values())
             return _crd_chain(crd, feat, tf, G[2 + k], core)
         done = step._two_chains(lambda: chain(0), lambda: chain(1))
         lossp = [c[1] for c in done]

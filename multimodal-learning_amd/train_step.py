@@ -1009,8 +1009,7 @@ class DistillStep:
                     # (memory_new.py:311): without them a resumed run with step(None) / step.sampler draws other batches
                     input_rng=self._input_rng_state(),
                     # step counters / seeds of the `contrast_idx is None` draws (CL_utils/memory_new.draw_uniform_indices)
-                    crd_draw_steps=[(None if getattr(c.contrast, "_draw_step", None) is None else c.contrast._draw_step.clone(),
-                                     getattr(c.contrast, "_draw_seed", None))
+                    crd_draw_steps=[(None if c.contrast._draw_step is None else c.contrast._draw_step.clone(), c.contrast._draw_seed)
                                     for c in (self.criterion_kd, self.criterion_kd_path)])
 
     def _input_rng_state(self, load=None):
@@ -1052,8 +1051,7 @@ class DistillStep:
         self.ema_model.load_state_dict(sd["ema_model_state_dict"])
         self.fix_model.load_state_dict(sd["teacher_state_dict"])
         for crd, key in ((self.criterion_kd, "crd_kd_state_dict"), (self.criterion_kd_path, "crd_kd_path_state_dict")):
-            crd.load_state_dict(sd[key])
-            crd.contrast._z_set = bool((crd.contrast.params[2:4] > 0).all().item())
+            crd.load_state_dict(sd[key])      # (the bank's _load_from_state_dict tells from Z whether the first call is past)
         self.optimizer.load_state_dict(sd["optimizer_state_dict"])
         self.scheduler.load_state_dict(sd["scheduler_state_dict"])
         self.iter_num = sd["iter_num"]

@@ -216,7 +216,7 @@ def test_mia2023_bank_scan_form_equals_gathered_form(g, D, monkeypatch):
             f_t = torch.randn(B, S, generator=gen).relu_().cuda()
             w = (torch.rand(B, generator=gen) + 0.5).cuda()
             loss, sl = crd(w, f_s, f_t, labels[index].cuda(), index.cuda(), sidx.cuda())
-            assert (crd.contrast._scan_neg is not None) == (form == "scan")
+            assert (crd.contrast.last["call"].scan is not None) == (form == "scan")
             gs = torch.autograd.grad(loss, [f_s, crd.embed_t.linear.weight])
             rec.append(dict(loss=loss.detach(), sl=sl.detach(), g_fs=gs[0], g_wt=gs[1], params=crd.contrast.params.clone(),
                             rows=crd.contrast.memory_v1[index.cuda()].clone()))

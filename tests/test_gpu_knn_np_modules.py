@@ -124,7 +124,8 @@ def test_mia2023_step_with_16_neighbours_fused_head_equals_autograd_path():
             step = _step(fused)
             out = step.step(_batch(600), epoch=2)
             assert step._fused_head_ok() == fused
-            assert step.criterion_kd.contrast.P == NP_STEP and tuple(step.criterion_kd.contrast._posw_s.shape) == (B, NP_STEP)
+            call = step.criterion_kd.contrast.last["call"]
+            assert call.P == NP_STEP and tuple(call.posw_s.shape) == (B, NP_STEP)
             rec.append(_record(step, out))
     finally:
         m.set_precision("bf16")

@@ -353,7 +353,7 @@ def test_mia2023_crd_v10_with_as_many_negatives_as_bank_rows(n_data, K, B, form,
         fg = f_s.cuda().requires_grad_(True)
         loss, sl = crd(w.cuda(), fg, f_t.cuda(), grade.cuda(), index.cuda(), sidx.cuda())
         gg = torch.autograd.grad(loss, [fg, crd.embed_t.linear.weight])
-        assert (crd.contrast._scan_neg is not None) == (form == "scan")
+        assert (crd.contrast.last["call"].scan is not None) == (form == "scan")
         R.close(lo.detach().numpy(), loss, 1e-4, 1e-5, f"loss call {it}")
         R.close(slo.detach().numpy(), sl, 1e-3, 1e-5, f"sample_loss call {it}")
         R.close(go.numpy(), gg[0], 1e-6, 2e-3, f"d f_s call {it}")
