@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(PhStem p) {
       }
     }
   }
-  if (p.stats) {   // one partial row per workgroup
+  if (p.stats) {   // one partial row per block of STEM_TPW tiles
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);   // [4 waves][2][64]
 #pragma unroll
@@ -1151,6 +1151,12 @@ int set_lds(K kern, int bytes, bool& done) {
   return PH_OK;
 }
 
+// PhStem::grid_cap (the test entries): the strided block walk at a grid of the caller's choosing
+inline void cap_grid(PhStem& q, dim3& grid) {
+  q.vblocks = (int)grid.x;
+  if ((int)grid.x > q.grid_cap) grid.x = q.grid_cap;
+}
+
 }  // namespace
 
 int ph_stem_stat_parts(int B, int OH, int OW) { return cdiv(B * cdiv(OH, TH) * cdiv(OW, TW), STEM_TPW); }
@@ -1170,7 +1176,8 @@ int ph_stem_fwd_launch(const PhStem* p, int prec, hipStream_t st) {
     // workgroup: 173 -> 165 us per launch, two alternations on one box; 2 x: 185, 4 x: 209.  PH_STEM_VB16=n overrides, 0 = one block each
     static const int vb16 = [] { const char* e = getenv("PH_STEM_VB16"); return e ? atoi(e) : 3; }();
     PhStem q = *p;
-    if (vb16 > 0 && (int)grid.x > vb16 * ph_num_cus()) { q.vblocks = (int)grid.x; grid.x = vb16 * ph_num_cus(); }
+    if (p->grid_cap > 0) cap_grid(q, grid);
+    else if (vb16 > 0 && (int)grid.x > vb16 * ph_num_cus()) { q.vblocks = (int)grid.x; grid.x = vb16 * ph_num_cus(); }
     hipLaunchKernelGGL(stem_fwd_kernel<bf16>, grid, dim3(256), lds, st, q);
   } else if (PH_IS_SPLIT_PREC(prec)) {
     static bool done = false;
@@ -1178,6 +1185,7 @@ int ph_stem_fwd_launch(const PhStem* p, int prec, hipStream_t st) {
     if (set_lds(stem_fwd_kernel<float>, lds, done)) return PH_ELAUNCH;
     PhStem q = *p;
     q.prod6 = prec == PH_PREC_BF16X6;
+    if (p->grid_cap > 0) cap_grid(q, grid);
     hipLaunchKernelGGL(stem_fwd_kernel<float>, grid, dim3(256), lds, st, q);
   } else if (prec == PH_PREC_FP16X3) {
     static bool done = false;
@@ -1188,7 +1196,8 @@ int ph_stem_fwd_launch(const PhStem* p, int prec, hipStream_t st) {
     static const int vb_mul = [] { const char* e = getenv("PH_STEM_VB"); return e ? atoi(e) : 1; }();
     PhStem q = *p;
     const int cap = vb_mul * ph_num_cus();
-    if (vb_mul > 0 && (int)grid.x > cap) { q.vblocks = (int)grid.x; grid.x = cap; }
+    if (p->grid_cap > 0) cap_grid(q, grid);
+    else if (vb_mul > 0 && (int)grid.x > cap) { q.vblocks = (int)grid.x; grid.x = cap; }
     hipLaunchKernelGGL(stem_fwd_kernel<hp16>, grid, dim3(256), lds, st, q);
   } else {
     return PH_EINVAL;
@@ -1272,3 +1281,125 @@ int ph_stem_wgrad_reduce_launch(const float* slab, float* dw, int nchunks, const
   PH_LAUNCH_CHECK();
   return PH_OK;
 }
+
+// ---------------------------------------------------------------- test entry points (tests/test_gpu_stem.py)
+// ph_debug_stem_*: C-linked doors to the four launchers above for the operator-level sweep, after the ph_debug_bn_* entries of
+// bn_act.hip (images are packed with ph_debug_bn_pack_input).  Not part of the public C-ABI.  Each one builds the launcher's struct
+// from plain arguments, as the plan does, and forwards to the launcher; it returns PH_EINVAL, and launches nothing, for
+//   - a NULL pointer (every pointer is required; `unscale` alone is optional),
+//   - B, IH or IW < 1, grid_cap < 0, tiles_per_chunk < 0,
+//   - a `prec` the entry does not take: the weight packer and the forward PH_PREC_BF16, _BF16X6, _BF16X3, _FP16X3; the weight gradient those and
+//     PH_PREC_FP16X1; the pooled forward and the fused weight gradient PH_PREC_BF16 alone,
+//   - a tensor that is not 16-byte aligned, or a half-pair tensor (PH_PREC_FP16X3 / _FP16X1: x4, the weight gradient's dy) that is
+//     not 256-byte aligned.
+// Tensors: x4 [B][IH][IW][4] of the mode's activation type (half-pair modes: the two fp16 planes of ph_pack_input_launch), packed
+// weights ph_debug_stem_weight_bytes() bytes, conv map OH = (IH - 1) / 2 + 1 (OW likewise), pooled map PH = (OH + 1) / 2.
+namespace {
+inline bool dbg_al(const void* p, size_t a) { return p && reinterpret_cast<uintptr_t>(p) % a == 0; }
+inline bool dbg_is_hp(int prec) { return prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1; }
+inline bool dbg_fwd_prec(int prec) {
+  return prec == PH_PREC_BF16 || prec == PH_PREC_BF16X6 || prec == PH_PREC_BF16X3 || prec == PH_PREC_FP16X3;
+}
+inline bool dbg_dims_ok(int B, int IH, int IW) { return B >= 1 && IH >= 1 && IW >= 1; }
+inline int dbg_conv(int I) { return (I - 1) / 2 + 1; }
+// chunks of the weight gradient over `ntiles` tiles: tiles_per_chunk == 0 - the plan's rule
+inline int dbg_chunks(int B, int OH, int OW, int* tpc) {
+  if (*tpc == 0) return ph_stem_wgrad_chunks(B, OH, OW, tpc);
+  return cdiv(B * cdiv(OH, TH) * cdiv(OW, TW), *tpc);
+}
+}  // namespace
+
+extern "C" {
+
+size_t ph_debug_stem_weight_bytes(void) { return (size_t)PH_NPLANES * 7 * 64 * 32 * sizeof(bf16); }
+
+// w_oihw [64][3][7][7] fp32 -> the packed stem weights of the mode, by the packer ph_resnet_pack_weights runs for unit 0
+int ph_debug_stem_pack_weights(const float* w_oihw, void* packed, int prec, hipStream_t st) {
+  if (!dbg_al(w_oihw, 16) || !dbg_al(packed, 16) || !dbg_fwd_prec(prec)) return PH_EINVAL;
+  return dbg_is_hp(prec) ? ph_pack_w_stem_hp_launch(w_oihw, packed, st) : ph_pack_w_stem_launch(w_oihw, packed, st);
+}
+
+// rows of [2][64] the forward / the pooled forward write at an OH x OW conv map
+int ph_debug_stem_stat_parts(int B, int OH, int OW) {
+  if (!dbg_dims_ok(B, OH, OW)) return PH_EINVAL;
+  return ph_stem_stat_parts(B, OH, OW);
+}
+int ph_debug_stem_pool_stat_parts(int B, int OH, int OW) {
+  if (!dbg_dims_ok(B, OH, OW)) return PH_EINVAL;
+  return ph_stem_pool_stat_parts(B, OH, OW);
+}
+
+// out [B][OH][OW][64] (bf16 in PH_PREC_BF16, else fp32), stats [ph_stem_stat_parts][2][64].  grid_cap: PhStem::grid_cap
+int ph_debug_stem_fwd(const void* x4, const void* w, void* out, float* stats, int B, int IH, int IW, int prec, int grid_cap,
+                      hipStream_t st) {
+  if (!dbg_dims_ok(B, IH, IW) || !dbg_fwd_prec(prec) || grid_cap < 0) return PH_EINVAL;
+  if (!dbg_al(x4, dbg_is_hp(prec) ? 256 : 16) || !dbg_al(w, 16) || !dbg_al(out, 16) || !dbg_al(stats, 16)) return PH_EINVAL;
+  PhStem s{};
+  s.x4 = x4; s.w = w; s.wplane = 7 * 64 * 32;
+  s.out = out; s.stats = stats;
+  s.B = B; s.IH = IH; s.IW = IW; s.OH = dbg_conv(IH); s.OW = dbg_conv(IW);
+  s.grid_cap = grid_cap;
+  return ph_stem_fwd_launch(&s, prec, st);
+}
+
+// pooled [B][PH][PW][64] bf16, stats [ph_stem_pool_stat_parts][2][64], gamma [64]
+int ph_debug_stem_fwd_pool(const void* x4, const void* w, void* pooled, float* stats, const float* gamma, int B, int IH, int IW,
+                           int prec, hipStream_t st) {
+  if (!dbg_dims_ok(B, IH, IW) || prec != PH_PREC_BF16) return PH_EINVAL;
+  if (!dbg_al(x4, 16) || !dbg_al(w, 16) || !dbg_al(pooled, 16) || !dbg_al(stats, 16) || !dbg_al(gamma, 16)) return PH_EINVAL;
+  PhStemPool s{};
+  s.x4 = x4; s.w = w; s.wplane = 7 * 64 * 32;
+  s.pooled = pooled; s.stats = stats; s.gamma = gamma;
+  s.B = B; s.IH = IH; s.IW = IW; s.OH = dbg_conv(IH); s.OW = dbg_conv(IW); s.PH = (s.OH + 1) / 2; s.PW = (s.OW + 1) / 2;
+  return ph_stem_fwd_pool_launch(&s, st);
+}
+
+// bytes of the slab [chunks][7][64][32] fp32 of a weight gradient chunked by tiles_per_chunk (0: the plan's rule); 0 = bad arguments
+size_t ph_debug_stem_wgrad_slab_bytes(int B, int IH, int IW, int tiles_per_chunk) {
+  if (!dbg_dims_ok(B, IH, IW) || tiles_per_chunk < 0) return 0;
+  return (size_t)dbg_chunks(B, dbg_conv(IH), dbg_conv(IW), &tiles_per_chunk) * 7 * 64 * 32 * sizeof(float);
+}
+
+namespace {
+int dbg_wgrad(PhStemWgrad& w, float* dw, int prec, int tiles_per_chunk, const float* unscale, hipStream_t st) {
+  w.OH = dbg_conv(w.IH); w.OW = dbg_conv(w.IW);
+  w.tiles_per_chunk = tiles_per_chunk;
+  w.nchunks = dbg_chunks(w.B, w.OH, w.OW, &w.tiles_per_chunk);
+  if (int rc = ph_stem_wgrad_launch(&w, prec, st)) return rc;
+  return ph_stem_wgrad_reduce_launch(w.slab, dw, w.nchunks, unscale, st);
+}
+}  // namespace
+
+// dy [B][OH][OW][64] of the mode's gradient type (bf16 | fp32 | the [hi 64 | lo 64] fp16 records of the half-pair modes) ->
+// slab (ph_debug_stem_wgrad_slab_bytes) and dw [64][3][7][7] fp32 = the chunks' sum (times unscale[1])
+int ph_debug_stem_wgrad(const void* x4, const void* dy, float* slab, float* dw, int B, int IH, int IW, int prec,
+                        int tiles_per_chunk, const float* unscale, hipStream_t st) {
+  if (!dbg_dims_ok(B, IH, IW) || !(dbg_fwd_prec(prec) || prec == PH_PREC_FP16X1) || tiles_per_chunk < 0) return PH_EINVAL;
+  const size_t a = dbg_is_hp(prec) ? 256 : 16;
+  if (!dbg_al(x4, a) || !dbg_al(dy, a) || !dbg_al(slab, 16) || !dbg_al(dw, 16)) return PH_EINVAL;
+  PhStemWgrad w{};
+  w.x4 = x4; w.dy = dy; w.slab = slab;
+  w.B = B; w.IH = IH; w.IW = IW;
+  return dbg_wgrad(w, dw, prec, tiles_per_chunk, unscale, st);
+}
+
+// the fused form (PH_PREC_BF16): dz is formed in the kernel from y0 [B][OH][OW][64], dpool [B][PH][PW][64], the arg codes idx and
+// the seven constant rows of ph_stem_bwd_apply_launch
+int ph_debug_stem_wgrad_fused(const void* x4, const void* y0, const void* dpool, const uint8_t* idx, const float* mean,
+                              const float* invstd, const float* scale, const float* shift, const float* gamma, const float* c1,
+                              const float* c2, float* slab, float* dw, int B, int IH, int IW, int prec, int tiles_per_chunk,
+                              const float* unscale, hipStream_t st) {
+  if (!dbg_dims_ok(B, IH, IW) || prec != PH_PREC_BF16 || tiles_per_chunk < 0) return PH_EINVAL;
+  if (!dbg_al(x4, 16) || !dbg_al(y0, 16) || !dbg_al(dpool, 16) || !dbg_al(idx, 16) || !dbg_al(slab, 16) || !dbg_al(dw, 16))
+    return PH_EINVAL;
+  if (!mean || !invstd || !scale || !shift || !gamma || !c1 || !c2) return PH_EINVAL;
+  PhStemWgrad w{};
+  w.x4 = x4; w.slab = slab;
+  w.B = B; w.IH = IH; w.IW = IW;
+  w.y0 = y0; w.dpool = dpool; w.idx = idx;
+  w.mean = mean; w.invstd = invstd; w.scale = scale; w.shift = shift; w.gamma = gamma; w.c1 = c1; w.c2 = c2;
+  w.PH = (dbg_conv(IH) + 1) / 2; w.PW = (dbg_conv(IW) + 1) / 2;
+  return dbg_wgrad(w, dw, prec, tiles_per_chunk, unscale, st);
+}
+
+}  // extern "C"

@@ -248,11 +248,14 @@ struct PhStem {
   const void* w;         // [nplanes][7][64][32] bf16: k = kw*4 + ch, kw==7 and ch==3 are zero
   size_t wplane;
   void* out;             // [B][OH][OW][64]
-  float* stats;          // [B*tiles][2][64]
+  float* stats;          // [ph_stem_stat_parts()][2][64]: row vb = [sum, sum of squares] of the fp32 values (before the bf16 rounding
+                         // of the perf mode) over the valid pixels of tiles 8 vb .. 8 vb + 7, tiles numbered image-major
   int B, IH, IW, OH, OW;
   int prod6;             // split-plane modes: six products or the three leading ones (set by the launcher)
   int vblocks;           // > 0: the grid is smaller than the `vblocks` blocks of STEM_TPW tiles - workgroup b walks blocks b, b + grid, ..
                          // (one statistics row per BLOCK either way: rows and summation order do not depend on the grid)
+  int grid_cap;          // test entries only (the plan leaves 0 = the launcher's own rule): > 0 - at most this many workgroups walk
+                         // the blocks, `vblocks` set, in every arithmetic
 };
 int ph_stem_fwd_launch(const PhStem* p, int prec, hipStream_t st);
 int ph_stem_stat_parts(int B, int OH, int OW);
@@ -284,6 +287,8 @@ struct PhStemWgrad {
   int PH, PW;
 };
 int ph_stem_wgrad_launch(const PhStemWgrad* p, int prec, hipStream_t st);
+// the plan's chunking of that launch (resnet_plan.hip): the chunk count, *tiles_per_chunk tiles each
+int ph_stem_wgrad_chunks(int B, int OH, int OW, int* tiles_per_chunk);
 // input gradient of the 7x7/2 stem conv: dy [B][H/2][W/2][64] (type of the mode) -> dx [B][3][H][W] f32 (stem_dgrad.hip)
 int ph_stem_dgrad_launch(const void* dy, const float* w_oihw, float* dx_nchw, int B, int H, int W, int prec, hipStream_t st);
 int ph_stem_wgrad_reduce_launch(const float* slab, float* dw_oihw, int nchunks, const float* unscale, hipStream_t st);

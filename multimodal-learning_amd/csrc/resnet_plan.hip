@@ -145,6 +145,9 @@ struct Grads {
 
 }  // namespace
 
+// (the stem test entries of conv_stem.hip chunk as the plan does)
+int ph_stem_wgrad_chunks(int B, int OH, int OW, int* tiles_per_chunk) { return stem_chunks(B, OH, OW, tiles_per_chunk); }
+
 extern "C" {
 
 PhResnetPlan* ph_resnet_plan_create_layers(int B, int H, int W, int prec, const int* layers4) {
