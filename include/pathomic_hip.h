@@ -662,6 +662,32 @@ int ph_tsvd_update_aux_dev(const float* adj, float* aux, float* tnn /* may be NU
  * staged in LDS.  The kernels clamp the device offsets and skip a row index outside [0, N).
  * The limits of ph_group_agg, and every group at most PH_QUANTILE_MAX_GROUP rows, and 0 <= q <= 1 (a NaN q is refused);
  * anything else, a NULL pointer or an empty group returns PH_EINVAL before any HIP call.
+ *
+ * ph_rank_counts_classes: the one-vs-rest counts of EVERY column in one call - what
+ * roc_auc_score / average_precision_score(average="macro" | "weighted" | None) are made of (calcGradMetrics /
+ * calcAggGradMetrics(..., avg), core/utils_analysis.py:138-167).  Class c: element n has score pred[n][c] and label
+ * grade[n] == c.  counts int64 [C][4] = {P_c, concordant_c, tied_c, bad_c} as ph_rank_counts defines them over the N elements
+ * of the column; bad_c = the non-finite scores of column c, and for c == 0 also the labels outside [0, C).  ap_sum float64
+ * [C]: the sum of ge_pos / ge_all over the positives of column c, added in the fixed order of ph_rank_counts (a tree over each
+ * block of 256 ROWS, then block t, t + 256, .. per thread and the same tree): two runs agree bitwise.  With Q_c = N - P_c:
+ * AUC_c = (concordant_c + tied_c / 2) / (P_c Q_c), AP_c = ap_sum_c / P_c.  A row is a positive of its own class only, so
+ * thread = row n compares pred[n][grade[n]] with that column of every row; one workgroup stages its 256 x C tile once for
+ * all classes.  1 <= N <= 1048576, 1 <= C <= 16; workspace: ph_rank_counts_classes_workspace_bytes (0 for a refused shape).
+ * A memset and two launches whatever C is; no host read.
+ *
+ * ph_roc_points (section 26): the integer points of roc_curve (makeAUROCPlot, core/utils_analysis.py:172-215) at every
+ * distinct threshold.  cls in [0, C): the one-vs-rest problem of that column, M = N elements, element n with score
+ * pred[n][cls] and label grade[n] == cls.  cls == -1: the micro problem over the M = N * C pairs in the pair order of ph_rank_counts.  For the
+ * k-th largest distinct score t_k:  thr[k] = t_k,  tps[k] = #{positive j: s_j >= t_k},  fps[k] = #{negative j: s_j >= t_k}
+ * (int32), k = 0 .. npoints[0] - 1; entries from npoints[0] on are left unwritten.  npoints int32 [2]: [0] the number of
+ * points, [1] the bad count (non-finite scores and labels outside [0, C), a label once per row).  A NaN score compares false
+ * everywhere and takes part in nothing; +-inf are ordinary scores.  No sort: element i represents its score when no EARLIER
+ * element has an equal one, and its slot is the number of representatives with a larger score - two all-pairs passes over LDS
+ * tiles of 256, integers and copied floats only: bit for bit independent of scheduling.  fps, tps, thr hold M entries each.
+ * 1 <= N <= 1048576, 1 <= C <= 16, M <= 1048576; workspace: ph_roc_points_workspace_bytes = 12 bytes per element of the
+ * largest problem the shape admits (N * C, or N where N * C > 1048576 and only cls >= 0 is served; 0 for a refused shape).
+ * A memset and two launches; no host read.
+ * Both return PH_EINVAL for a NULL pointer, a size outside the stated range or a cls outside [-1, C) before any HIP call.
  * ---------------------------------------------------------------------------------------------- */
 #define PH_AGG_MEAN 0
 #define PH_AGG_MAX 1
@@ -674,6 +700,12 @@ int ph_group_agg(const float* x, const int32_t* offsets, const int32_t* order, c
                  int fun, float* out, ph_stream_t stream);
 int ph_group_quantile(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C,
                       int G, double q, float* out, ph_stream_t stream);
+size_t ph_rank_counts_classes_workspace_bytes(int N, int C);
+int ph_rank_counts_classes(const float* pred, const int64_t* grade, int N, int C, int64_t* counts, double* ap_sum,
+                           void* workspace, ph_stream_t stream);
+size_t ph_roc_points_workspace_bytes(int N, int C);
+int ph_roc_points(const float* pred, const int64_t* grade, int N, int C, int cls, int32_t* fps, int32_t* tps, float* thr,
+                  int32_t* npoints, void* workspace, ph_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * In-library kernel timer for bench.py's `roofline` object: HIP events around every MFMA kernel launch on the

@@ -80,6 +80,10 @@ SIGNATURES = {
     "ph_confusion_counts": (i32, [vp, vp, i32, i32, vp, vp]),
     "ph_group_agg": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "ph_group_quantile": (i32, [vp, vp, vp, vp, i32, i32, i32, f64, vp, vp]),
+    "ph_rank_counts_classes_workspace_bytes": (sz, [i32, i32]),
+    "ph_rank_counts_classes": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
+    "ph_roc_points_workspace_bytes": (sz, [i32, i32]),
+    "ph_roc_points": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "ph_pkt_workspace_bytes": (sz, [i32, i32]),
     "ph_pkt_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
     "ph_rkd_workspace_bytes": (sz, [i32, i32]),

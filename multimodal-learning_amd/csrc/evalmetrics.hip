@@ -6,6 +6,8 @@
 //   ph_group_agg         groupby('TCGA ID').agg(max | mean) of the patch rows per patient (utils_analysis.py:123),
 //   ph_group_quantile    the order statistics of the same groups: the median of the survival aggregation (utils_analysis.py:467)
 //                        and the percentile form of the grading one (:122) - DESIGN.md section 24.
+//   ph_rank_counts_classes  the same counts per one-vs-rest column: average="macro" | "weighted" | None (utils_analysis.py:138-167),
+//   ph_roc_points        the integer points of roc_curve per grade and micro (makeAUROCPlot, :172-215) - DESIGN.md section 26.
 // The scores are log-probabilities (negative): nothing here relies on their sign.
 #include "ph_common.h"
 #include "ph_kernels.h"
@@ -112,6 +114,193 @@ __global__ __launch_bounds__(RANK_TILE) void rank_finish_kernel(const double* __
   for (int b = threadIdx.x; b < nblocks; b += RANK_TILE) v += part[b];
   const double s = tile_tree_sum(v, red);
   if (threadIdx.x == 0) ap_sum[0] = s;
+}
+
+// ---- ph_rank_counts_classes: the counts of rank_counts_kernel for every one-vs-rest column at once.
+// Row n is a positive of class g = grade[n] only (of none when g lies outside [0, C)), so thread = row n with
+// s_i = pred[n][g]; the rows j stream through LDS in tiles of 256 rows x C columns (staged once for all classes) and the
+// thread reads column g of each: w = sj[jj][g], positive when gj[jj] == g.  The last tile is padded with NaN scores, which
+// drop out of every comparison.  acc[c][0..3] collects P, concordant, tied, bad of the block per class in LDS (32-bit: at
+// most 256 * 2^20 per block), then 64-bit atomics into counts; part[block][c] = the tile tree over the block's terms of class c.
+__global__ __launch_bounds__(RANK_TILE) void rank_counts_classes_kernel(const float* __restrict__ pred,
+                                                                        const int64_t* __restrict__ grade, int N, int C,
+                                                                        unsigned long long* __restrict__ counts,
+                                                                        double* __restrict__ part) {
+  __shared__ float sj[RANK_TILE * CONF_MAX_C];
+  __shared__ int gj[RANK_TILE];
+  __shared__ double red[RANK_TILE];
+  __shared__ unsigned int acc[CONF_MAX_C * 4];
+  const int tid = threadIdx.x;
+  const int n = blockIdx.x * RANK_TILE + tid;
+  const float qnan = __builtin_nanf("");
+  if (tid < C * 4) acc[tid] = 0;
+  __syncthreads();
+  int g = -1;                  // the class this row is a positive of
+  float si = 0.f;
+  if (n < N) {
+    const int64_t g64 = grade[n];
+    const bool in_range = g64 >= 0 && g64 < (int64_t)C;
+    if (in_range) {
+      g = (int)g64;
+      si = pred[(size_t)n * C + g];
+      atomicAdd(&acc[g * 4 + 0], 1u);
+    } else {
+      atomicAdd(&acc[3], 1u);                      // (class 0 carries the labels out of range, as the micro kernel has it)
+    }
+    for (int c = 0; c < C; ++c)
+      if (!isfinite(pred[(size_t)n * C + c])) atomicAdd(&acc[c * 4 + 3], 1u);
+  }
+  const bool pos = g >= 0;
+  unsigned int ge_pos = 0, ge_all = 0, below = 0, equal = 0;
+  const int tile_words = RANK_TILE * C;
+  for (int j0 = 0; j0 < N; j0 += RANK_TILE) {
+    __syncthreads();
+    const int rows = min(RANK_TILE, N - j0);
+    for (int k = tid; k < tile_words; k += RANK_TILE) sj[k] = k < rows * C ? pred[(size_t)j0 * C + k] : qnan;
+    {
+      int lab = -1;
+      if (tid < rows) {
+        const int64_t v = grade[j0 + tid];
+        if (v >= 0 && v < (int64_t)C) lab = (int)v;
+      }
+      gj[tid] = lab;
+    }
+    __syncthreads();
+    if (!pos) continue;        // (no early exit: every thread takes part in the barriers)
+#pragma unroll 8
+    for (int jj = 0; jj < RANK_TILE; ++jj) {
+      const float w = sj[jj * C + g];
+      const bool p = gj[jj] == g;
+      ge_all += w >= si ? 1u : 0u;
+      ge_pos += (p && w >= si) ? 1u : 0u;
+      below += (!p && w < si) ? 1u : 0u;
+      equal += (!p && w == si) ? 1u : 0u;
+    }
+  }
+  if (pos) {
+    if (below) atomicAdd(&acc[g * 4 + 1], below);
+    if (equal) atomicAdd(&acc[g * 4 + 2], equal);
+  }
+  // ge_all >= 1 for a positive whose score is not a NaN (j = n); a NaN positive has ge_all = 0: its term is left out
+  const double term = (pos && ge_all > 0) ? (double)ge_pos / (double)ge_all : 0.0;
+  for (int c = 0; c < C; ++c) {
+    const double tsum = tile_tree_sum(g == c ? term : 0.0, red);
+    if (tid == 0) part[(size_t)blockIdx.x * C + c] = tsum;
+    __syncthreads();           // red is rewritten for the next class
+  }
+  if (tid < C * 4 && acc[tid]) atomicAdd(&counts[tid], (unsigned long long)acc[tid]);
+}
+
+// Workgroup c: the fixed-order finish of rank_finish_kernel over part[b][c], b = 0 .. nblocks - 1.
+__global__ __launch_bounds__(RANK_TILE) void rank_finish_classes_kernel(const double* __restrict__ part, int nblocks, int C,
+                                                                        double* __restrict__ ap_sum) {
+  __shared__ double red[RANK_TILE];
+  const int c = blockIdx.x;
+  double v = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += RANK_TILE) v += part[(size_t)b * C + c];
+  const double s = tile_tree_sum(v, red);
+  if (threadIdx.x == 0) ap_sum[c] = s;
+}
+
+// ---- ph_roc_points.  Element i of the selected problem: cls >= 0 - score pred[i][cls], label
+// grade[i] == cls, M = N; cls == -1 - pair i = n * C + c of rank_counts_kernel, M = N * C.
+struct RocElem {
+  float s;
+  int lab;                     // 1 positive, 0 negative
+  unsigned int bad;
+};
+
+__device__ __forceinline__ RocElem roc_elem(const float* __restrict__ pred, const int64_t* __restrict__ grade, int i, int C,
+                                            int cls) {
+  RocElem e;
+  int n, c;
+  if (cls >= 0) { n = i; c = cls; } else { n = i / C; c = i - n * C; }
+  e.s = pred[(size_t)n * C + c];
+  const int64_t g = grade[n];
+  e.lab = g == (int64_t)c ? 1 : 0;
+  const bool count_label = cls >= 0 || c == 0;       // a label outside [0, C) once per row
+  e.bad = (isfinite(e.s) ? 0u : 1u) + ((count_label && (g < 0 || g >= (int64_t)C)) ? 1u : 0u);
+  return e;
+}
+
+// Pass 1, thread = element i, the j elements in LDS tiles (.x = the score of a positive j, .y = of a negative one, the other
+// half and the padding NaN).  tp_i / fp_i = #{positive / negative j: s_j >= s_i}; i represents its score when its score is
+// not a NaN and no j < i has an equal one.  rep[i] = s_i for a representative, NaN otherwise; tpfp[i] = (tp_i, fp_i).
+// npoints[0] += representatives, npoints[1] += bad (integer atomics: independent of the order).
+__global__ __launch_bounds__(RANK_TILE) void roc_count_kernel(const float* __restrict__ pred, const int64_t* __restrict__ grade,
+                                                              int M, int C, int cls, float* __restrict__ rep,
+                                                              int2* __restrict__ tpfp, int* __restrict__ npoints) {
+  __shared__ float2 sj[RANK_TILE];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * RANK_TILE + tid;
+  const bool live = i < M;
+  const float qnan = __builtin_nanf("");
+  float si = qnan;
+  unsigned int bad = 0;
+  if (live) {
+    const RocElem e = roc_elem(pred, grade, i, C, cls);
+    si = e.s;
+    bad = e.bad;
+  }
+  unsigned int tp = 0, fp = 0, before = 0;
+  for (int j0 = 0; j0 < M; j0 += RANK_TILE) {
+    const int j = j0 + tid;
+    float2 v = make_float2(qnan, qnan);
+    if (j < M) {
+      const RocElem e = roc_elem(pred, grade, j, C, cls);
+      if (e.lab) v.x = e.s; else v.y = e.s;
+    }
+    __syncthreads();
+    sj[tid] = v;
+    __syncthreads();
+    const int lim = i - j0;                           // the elements jj < lim of this tile come before i
+#pragma unroll 8
+    for (int jj = 0; jj < RANK_TILE; ++jj) {
+      const float2 w = sj[jj];
+      tp += w.x >= si ? 1u : 0u;
+      fp += w.y >= si ? 1u : 0u;
+      before += (jj < lim && (w.x == si || w.y == si)) ? 1u : 0u;
+    }
+  }
+  const bool is_rep = live && si == si && before == 0;
+  if (live) {
+    rep[i] = is_rep ? si : qnan;
+    tpfp[i] = make_int2((int)tp, (int)fp);
+  }
+  const unsigned long long r = wave_sum_u64(is_rep ? 1ull : 0ull), b = wave_sum_u64(bad);
+  if ((tid & 63) == 0) {
+    if (r) atomicAdd(&npoints[0], (int)r);
+    if (b) atomicAdd(&npoints[1], (int)b);
+  }
+}
+
+// Pass 2: the slot of a representative = the number of representatives with a larger score (distinct scores: a permutation
+// of 0 .. points - 1), where it leaves its threshold and counts.
+__global__ __launch_bounds__(RANK_TILE) void roc_place_kernel(const float* __restrict__ rep, const int2* __restrict__ tpfp, int M,
+                                                              int* __restrict__ fps, int* __restrict__ tps,
+                                                              float* __restrict__ thr) {
+  __shared__ float sj[RANK_TILE];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * RANK_TILE + tid;
+  const float qnan = __builtin_nanf("");
+  const float si = i < M ? rep[i] : qnan;
+  const bool is_rep = si == si;
+  unsigned int slot = 0;
+  for (int j0 = 0; j0 < M; j0 += RANK_TILE) {
+    const int j = j0 + tid;
+    __syncthreads();
+    sj[tid] = j < M ? rep[j] : qnan;
+    __syncthreads();
+    if (!is_rep) continue;     // (no early exit: every thread takes part in the barriers)
+#pragma unroll 8
+    for (int jj = 0; jj < RANK_TILE; ++jj) slot += sj[jj] > si ? 1u : 0u;
+  }
+  if (is_rep && slot < (unsigned int)M) {
+    const int2 c = tpfp[i];
+    thr[slot] = si;
+    tps[slot] = c.x;
+    fps[slot] = c.y;
+  }
 }
 
 // conf[t * C + p] += 1 for every row whose label t lies in [0, C), p = the first maximum of the row (np.argmax: a later equal
@@ -310,6 +499,9 @@ __global__ __launch_bounds__(QUANT_THREADS) void group_quantile_block_kernel(con
 
 bool rank_shape_ok(int N, int C) { return N >= 1 && C >= 1 && (int64_t)N * C <= RANK_MAX_M; }
 
+// ph_rank_counts_classes and ph_roc_points: the per-column problems have N elements each
+bool class_shape_ok(int N, int C) { return N >= 1 && N <= RANK_MAX_M && C >= 1 && C <= CONF_MAX_C; }
+
 // What ph_group_agg and ph_group_quantile check alike: the pointers, the N / C / G ranges and the host offsets (from 0 to N, no
 // group empty or negative, and none longer than max_len where max_len > 0).  *largest: the longest group.
 bool group_args_ok(const float* x, const int32_t* offsets, const int32_t* order, const int32_t* offsets_host, int N, int C, int G,
@@ -347,6 +539,46 @@ int ph_rank_counts(const float* pred, const int64_t* grade, int N, int C, int64_
                      reinterpret_cast<unsigned long long*>(counts), part);
   PH_LAUNCH_CHECK();
   hipLaunchKernelGGL(rank_finish_kernel, dim3(1), dim3(RANK_TILE), 0, st, part, nblocks, ap_sum);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+size_t ph_rank_counts_classes_workspace_bytes(int N, int C) {
+  if (!class_shape_ok(N, C)) return 0;
+  return sizeof(double) * (size_t)cdiv(N, RANK_TILE) * (size_t)C;
+}
+
+int ph_rank_counts_classes(const float* pred, const int64_t* grade, int N, int C, int64_t* counts, double* ap_sum,
+                           void* workspace, hipStream_t st) {
+  if (!pred || !grade || !counts || !ap_sum || !workspace || !class_shape_ok(N, C)) return PH_EINVAL;
+  const int nblocks = cdiv(N, RANK_TILE);
+  if (hipMemsetAsync(counts, 0, sizeof(int64_t) * 4 * C, st) != hipSuccess) return PH_ELAUNCH;
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(rank_counts_classes_kernel, dim3(nblocks), dim3(RANK_TILE), 0, st, pred, grade, N, C,
+                     reinterpret_cast<unsigned long long*>(counts), part);
+  PH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rank_finish_classes_kernel, dim3(C), dim3(RANK_TILE), 0, st, part, nblocks, C, ap_sum);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+size_t ph_roc_points_workspace_bytes(int N, int C) {
+  if (!class_shape_ok(N, C)) return 0;
+  const int64_t pairs = (int64_t)N * C;                 // (the micro problem is served only where it fits)
+  return (sizeof(int2) + sizeof(float)) * (size_t)(pairs <= RANK_MAX_M ? pairs : (int64_t)N);
+}
+
+int ph_roc_points(const float* pred, const int64_t* grade, int N, int C, int cls, int32_t* fps, int32_t* tps, float* thr,
+                  int32_t* npoints, void* workspace, hipStream_t st) {
+  if (!pred || !grade || !fps || !tps || !thr || !npoints || !workspace || !class_shape_ok(N, C)) return PH_EINVAL;
+  if (cls < -1 || cls >= C || (cls == -1 && (int64_t)N * C > RANK_MAX_M)) return PH_EINVAL;
+  const int M = cls >= 0 ? N : N * C, nblocks = cdiv(M, RANK_TILE);
+  if (hipMemsetAsync(npoints, 0, sizeof(int32_t) * 2, st) != hipSuccess) return PH_ELAUNCH;
+  int2* tpfp = static_cast<int2*>(workspace);           // [M] (tp, fp), then rep [M]
+  float* rep = reinterpret_cast<float*>(tpfp + M);
+  hipLaunchKernelGGL(roc_count_kernel, dim3(nblocks), dim3(RANK_TILE), 0, st, pred, grade, M, C, cls, rep, tpfp, npoints);
+  PH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(roc_place_kernel, dim3(nblocks), dim3(RANK_TILE), 0, st, rep, tpfp, M, fps, tps, thr);
   PH_LAUNCH_CHECK();
   return PH_OK;
 }

@@ -12,7 +12,8 @@ test loader (`augment.ResidentPatchLoader`), the predictions aggregated per pati
 numbers taken from count kernels on the device (`grading_metrics_device`) instead of sklearn on copied rows.
 `test_teacher_patches` is the same protocol for the stage-1 teacher under both tasks (per-patient hazards, C-indices, log-rank
 p-value under survival), and `sync=` on either pass shards whole batches over data-parallel replicas behind one all-gather
-(DESIGN.md section 24)."""
+(DESIGN.md section 24).  `grading_metrics_device(avg=)` and `roc_curve_device` are the reference's `avg` argument and the
+curves of its `makeAUROCPlot` on the device; `avg=` / `curves=` carry them through both patch passes."""
 import numbers
 
 import numpy as np
@@ -88,22 +89,122 @@ def metrics_from_counts(counts, ap_sum, conf):
     return ((conc + tied / 2.0) / (float(P) * float(Q)), float(ap_sum) / P, float(2.0 * tp.sum() / (2.0 * n)), float(f1[2]))
 
 
-def grading_metrics_device(pred, grade):
-    """`grading_metrics` (micro average only) without sklearn and without copying the rows: pred f32 [N, C] and grade [N]
-    stay on the device, two count kernels (ph_rank_counts, ph_confusion_counts) fill 5 + C * C words, and ONE host read of
-    those gives (rocauc, ap, f1_micro, f1_gradeIV) - sklearn's values, ties included.
+AVERAGES = ("micro", "macro", "weighted", None)
 
-    Raises ValueError for a non-finite score or a label outside [0, C), and when there is no positive or no negative pair
-    (sklearn raises in those cases).  Every column of pred takes part whether or not its class occurs among the labels;
-    the reference's LabelBinarizer would drop an absent class and then fail on the shape mismatch with pred.  Likewise
-    f1_gradeIV is the F1 of class 2 (0.0 if it is neither a label nor a prediction), where sklearn's `average=None`
-    indexes the classes that occur."""
+
+def _check_avg(avg):
+    if not (avg is None or (isinstance(avg, str) and avg in AVERAGES)):
+        raise ValueError('avg must be "micro", "macro", "weighted" or None (per class), got %r' % (avg,))
+
+
+def metrics_from_class_counts(counts, ap_sum, conf, avg="macro"):
+    """Host arithmetic on the integers of ph_rank_counts_classes (counts [C, 4] = P_c, concordant_c, tied_c, bad_c over the
+    N = conf.sum() elements of each one-vs-rest column; ap_sum [C]) and ph_confusion_counts, as sklearn's
+    average="macro" | "weighted" | None computes them -
+    AUC_c = (concordant_c + tied_c / 2) / (P_c Q_c) with Q_c = N - P_c, AP_c = ap_sum_c / P_c, F1_c = 2 tp / (true + predicted);
+    "macro" the plain mean over the classes, "weighted" the mean with the supports P_c as weights (F1 too), None the three
+    float64 [C] arrays.  Returns (rocauc, ap, f1, f1_gradeIV); f1_gradeIV is the F1 of class 2 in every form."""
+    _check_avg(avg)
+    if avg == "micro":
+        raise ValueError('the micro average comes from the pair counts: metrics_from_counts')
+    conf = np.asarray(conf, dtype=np.int64)
+    C = conf.shape[0]
+    counts = np.asarray(counts, dtype=np.int64).reshape(C, 4)
+    ap_sum = np.asarray(ap_sum, dtype=np.float64).reshape(C)
+    bad = int(counts[:, 3].sum())
+    if bad:
+        raise ValueError("%d non-finite scores or labels outside [0, %d)" % (bad, C))
+    if C < 3:
+        raise ValueError("the F1 of grade IV is the F1 of class 2: label_dim >= 3")
+    n = int(conf.sum())
+    P = counts[:, 0]
+    Q = n - P
+    for c in range(C):
+        if P[c] == 0 or Q[c] == 0:
+            raise ValueError("class %d: ROC-AUC and average precision need a positive and a negative element "
+                             "(P = %d, Q = %d)" % (c, P[c], Q[c]))
+    Pf, Qf = P.astype(np.float64), Q.astype(np.float64)
+    auc = (counts[:, 1].astype(np.float64) + counts[:, 2].astype(np.float64) / 2.0) / (Pf * Qf)
+    ap = ap_sum / Pf
+    tp = np.diag(conf).astype(np.float64)
+    denom = (conf.sum(axis=1) + conf.sum(axis=0)).astype(np.float64)
+    f1 = np.divide(2.0 * tp, denom, out=np.zeros(C), where=denom > 0)
+    if avg is None:
+        return auc, ap, f1, float(f1[2])
+    w = Pf if avg == "weighted" else None
+    return float(np.average(auc, weights=w)), float(np.average(ap, weights=w)), float(np.average(f1, weights=w)), float(f1[2])
+
+
+def grading_metrics_device(pred, grade, avg="micro"):
+    """`grading_metrics` without sklearn and without copying the rows: pred f32 [N, C] and grade [N] stay on the device,
+    two count kernels fill a few words, and ONE host read of those gives (rocauc, ap, f1, f1_gradeIV) - sklearn's values,
+    ties included.  avg = "micro": ph_rank_counts and ph_confusion_counts, 5 + C * C words.
+    avg = "macro" | "weighted" | None: ph_rank_counts_classes and ph_confusion_counts, 5 C + C * C words, the averages of
+    `metrics_from_class_counts` (None: three float64 [C] arrays and f1_gradeIV) - DESIGN.md section 26.
+
+    Raises ValueError for an unknown avg, for a non-finite score or a label outside [0, C), and when there is no positive or
+    no negative pair - per class, naming the class, under the other averages (sklearn raises in those cases).  Every column
+    of pred takes part whether or not its class occurs among the labels; the reference's LabelBinarizer would drop an absent
+    class and then fail on the shape mismatch with pred.  Likewise f1_gradeIV is the F1 of class 2 (0.0 if it is neither a
+    label nor a prediction), where sklearn's `average=None` indexes the classes that occur."""
+    _check_avg(avg)
     C = pred.shape[1]
-    buf = torch.empty(5 + C * C, device=pred.device, dtype=torch.int64)
-    ops.rank_counts(pred, grade, out=buf[:5])
-    ops.confusion_counts(pred, grade, out=buf[5:].view(C, C))
+    if avg == "micro":
+        buf = torch.empty(5 + C * C, device=pred.device, dtype=torch.int64)
+        ops.rank_counts(pred, grade, out=buf[:5])
+        ops.confusion_counts(pred, grade, out=buf[5:].view(C, C))
+        host = buf.cpu()
+        return metrics_from_counts(host[:4].tolist(), float(host[4:5].view(torch.float64)[0]), host[5:].view(C, C).numpy())
+    buf = torch.empty(5 * C + C * C, device=pred.device, dtype=torch.int64)
+    ops.rank_counts_classes(pred, grade, out=buf[:5 * C])
+    ops.confusion_counts(pred, grade, out=buf[5 * C:].view(C, C))
     host = buf.cpu()
-    return metrics_from_counts(host[:4].tolist(), float(host[4:5].view(torch.float64)[0]), host[5:].view(C, C).numpy())
+    return metrics_from_class_counts(host[:4 * C].view(C, 4).numpy(), host[4 * C:5 * C].view(torch.float64).numpy(),
+                                     host[5 * C:].view(C, C).numpy(), avg)
+
+
+def roc_curve_from_points(fps, tps, thr, drop_intermediate=True):
+    """sklearn's roc_curve from the integer points of ph_roc_points (descending thresholds): with `drop_intermediate` (and
+    more than two points) keep the points where the second difference of fps or of tps is not zero, and both ends - applied
+    BEFORE the origin is prepended; then prepend (0, 0, inf) and divide by the last fps / tps.  -> (fpr, tpr, thresholds),
+    float64."""
+    fps, tps = np.asarray(fps, dtype=np.float64), np.asarray(tps, dtype=np.float64)
+    thr = np.asarray(thr, dtype=np.float64)
+    if drop_intermediate and fps.shape[0] > 2:
+        keep = np.where(np.r_[True, np.logical_or(np.diff(fps, 2), np.diff(tps, 2)), True])[0]
+        fps, tps, thr = fps[keep], tps[keep], thr[keep]
+    fps, tps, thr = np.r_[0.0, fps], np.r_[0.0, tps], np.r_[np.inf, thr]
+    if fps[-1] <= 0 or tps[-1] <= 0:
+        raise ValueError("a ROC curve needs a positive and a negative element (P = %d, Q = %d)" % (tps[-1], fps[-1]))
+    return fps / fps[-1], tps / tps[-1], thr
+
+
+def roc_curve_device(pred, grade, cls="micro", drop_intermediate=True):
+    """sklearn's roc_curve(label, score, drop_intermediate=...) of column `cls` of pred [N, C] one-vs-rest, or with
+    cls = "micro" of all N * C (score, label) pairs (the curves makeAUROCPlot draws, core/utils_analysis.py:172-215), the
+    points counted on the device (ph_roc_points) and read in ONE host copy: (fpr, tpr, thresholds), float64, thresholds
+    descending from inf.  Raises ValueError for a non-finite score or a label outside [0, C), and when the problem has no
+    positive or no negative element."""
+    buf = ops.roc_points(pred, grade, cls)
+    M = (buf.shape[0] - 2) // 3
+    host = buf.cpu()
+    npts, bad = int(host[0]), int(host[1])
+    if bad:
+        raise ValueError("%d non-finite scores or labels outside [0, %d)" % (bad, pred.shape[1]))
+    h = host.numpy()
+    try:
+        return roc_curve_from_points(h[2:2 + npts], h[2 + M:2 + M + npts], h[2 + 2 * M:2 + 2 * M + npts].view(np.float32),
+                                     drop_intermediate)
+    except ValueError as e:
+        raise ValueError("class %r: %s" % (cls, e)) from None
+
+
+def roc_auc_from_curve(fpr, tpr):
+    """The area under a curve by the trapezoid rule, as sklearn.metrics.auc(fpr, tpr) computes it for an increasing fpr."""
+    fpr, tpr = np.asarray(fpr, dtype=np.float64), np.asarray(tpr, dtype=np.float64)
+    if fpr.shape[0] < 2 or fpr.shape != tpr.shape:
+        raise ValueError("at least two points, as many fpr as tpr")
+    return float((np.diff(fpr) * (tpr[1:] + tpr[:-1]) / 2.0).sum())
 
 
 def agg_spec(agg):
@@ -304,9 +405,9 @@ def _host_metric(labels):
     return lambda pred, grade, probs, gt_all: grading_metrics(labels(gt_all), probs)
 
 
-def _device_metric(pred, grade, probs, gt_all):
-    """The builders' metric of the patch forms: the count kernels on the device rows."""
-    return grading_metrics_device(pred, grade)
+def _device_metric(avg="micro"):
+    """The builders' metric of the patch forms: the count kernels on the device rows, under the average `avg`."""
+    return lambda pred, grade, probs, gt_all: grading_metrics_device(pred, grade, avg)
 
 
 def _student_result(loader, d_path, d_fuse, d_feat, d_grade, losses, metric):
@@ -375,21 +476,29 @@ def _teacher_result(loader, d_preds, d_feats, d_grade, surv_cols, losses, metric
             feats_test), more_counts
 
 
-def _patient_grading(loader, agg, branches):
+def _patient_grading(loader, agg, branches, avg="micro", curves=False):
     """The patient level of the grading task (core/utils_analysis.py:79-135, :152-167) for branches = ((name, device pred
     [rows, C] or None), ..): dict(y_label one-hot [G, C], y_pred_<name> (`aggregate_by_patient`), metrics_<name> (the four
-    numbers of calcAggGradMetrics, `grading_metrics_device`)); both entries of a None branch are None."""
-    out = dict(y_label=_one_hot(loader.patient_grade_host, branches[0][1].shape[1]))
+    numbers of calcAggGradMetrics, `grading_metrics_device` under `avg`)); both entries of a None branch are None.  With
+    `avg` other than "micro" the dict carries it as `avg`; with `curves`, roc_<name> = {0: (fpr, tpr, thresholds), ..,
+    C - 1: .., "micro": ..} (`roc_curve_device` on the aggregated rows: the data makeAUROCPlot plots, :172-215) for every
+    branch that has predictions."""
+    C = branches[0][1].shape[1]
+    out = dict(y_label=_one_hot(loader.patient_grade_host, C))
+    if avg != "micro":
+        out["avg"] = avg
     for name, d in branches:
         out["metrics_" + name] = out["y_pred_" + name] = None
         if d is not None:
             a = aggregate_by_patient(loader, d, agg)
-            out["metrics_" + name] = list(grading_metrics_device(a, loader.patient_grade))
+            out["metrics_" + name] = list(grading_metrics_device(a, loader.patient_grade, avg))
             out["y_pred_" + name] = a.cpu().numpy()
+            if curves:
+                out["roc_" + name] = {c: roc_curve_device(a, loader.patient_grade, c) for c in list(range(C)) + ["micro"]}
     return out
 
 
-def test_patches(opt, fix_model, model, loader, device, agg="max", sync=None):
+def test_patches(opt, fix_model, model, loader, device, agg="max", sync=None, avg="micro", curves=False):
     """The pass the reference's trainers take their final figures from: `test()` over `test_loader_patches`
     (train_test_path_multi_distill.py:360-366, train_test_MT.py:287-289), then the per-patient aggregation and `calcAggGradMetrics`
     (core/utils_analysis.py:79-135, :152-167) - here over a `augment.ResidentPatchLoader`, with the metric tail on the device.
@@ -406,18 +515,24 @@ def test_patches(opt, fix_model, model, loader, device, agg="max", sync=None):
     per-replica BatchNorm running statistics; the reference's nn.DataParallel keeps replica 0's.  An evaluation must use
     one set everywhere, or the replicas' rows do not belong to one model: the buffers of `model` and `fix_model` are
     first broadcast from rank 0, which OVERWRITES the other replicas' running statistics (train mode never reads them).
-    Then one all-gather per pass returns the rows and the per-batch losses; the metric tail runs on every replica."""
+    Then one all-gather per pass returns the rows and the per-batch losses; the metric tail runs on every replica.
+
+    `avg` ("micro", "macro", "weighted" or None = per class; the `avg` of the reference's grading_metrics and
+    calcAggGradMetrics): the average of the patch-level and patient-level metric lists; other than "micro" it is echoed in
+    patient_result["avg"].  `curves=True` adds patient_result["roc_path"] (and "roc_fuse" with a teacher): per class and
+    "micro" the (fpr, tpr, thresholds) of `roc_curve_device` on the aggregated patient rows."""
     if opt.task != "grad":
         raise NotImplementedError("evaluation of the survival (Cox) task is out of scope")
     agg_spec(agg)
+    _check_avg(avg)
     outs, losses = _run(opt, (model, fix_model), loader, device, sync,
                         lambda loss_reg, dev: _student_batch(opt, model, fix_model, loss_reg, dev, sync is None))
     d_path = outs[0].float().contiguous()
     d_fuse = outs[2].float().contiguous() if fix_model is not None else None
     d_grade = (outs[-1] if sync is None else loader.grade[loader.row_roi]).reshape(-1)
-    patch_result = _student_result(loader, d_path, d_fuse, outs[1], d_grade, losses, _device_metric)
+    patch_result = _student_result(loader, d_path, d_fuse, outs[1], d_grade, losses, _device_metric(avg))
     patient_result = dict(patients=list(loader.patients), agg=agg,
-                          **_patient_grading(loader, agg, (("path", d_path), ("fuse", d_fuse))))
+                          **_patient_grading(loader, agg, (("path", d_path), ("fuse", d_fuse)), avg, curves))
     print("Patient level (%s):" % (agg,), *patient_result["metrics_path"])
     return patch_result, patient_result
 
@@ -425,7 +540,7 @@ def test_patches(opt, fix_model, model, loader, device, agg="max", sync=None):
 CINDEX_MAX_N = 1 << 20                   # ph_cindex_counts: 2 <= N <= 1048576
 
 
-def test_teacher_patches(opt, model, loader, device, agg=None, sync=None):
+def test_teacher_patches(opt, model, loader, device, agg=None, sync=None, avg="micro", curves=False):
     """`test_patches` for the stage-1 teacher (a three-branch PathomicNet, both tasks): the reference's `test()` over
     `test_loader_patches` (train_test_MT.py:287-289, :340-458), then the per-patient aggregation
     (core/utils_analysis.py:425-480) - DESIGN.md section 24.  Returns (patch_result, patient_result).
@@ -444,7 +559,9 @@ def test_teacher_patches(opt, model, loader, device, agg=None, sync=None):
     must carry `censor` and `survtime` (ValueError otherwise), and the number of patients must lie in 2 .. 1048576, the
     range ph_cindex_counts accepts (ValueError otherwise).
 
-    `sync`: as `test_patches` - rank 0's buffers everywhere, whole batches dealt over the replicas, one all-gather."""
+    `sync`: as `test_patches` - rank 0's buffers everywhere, whole batches dealt over the replicas, one all-gather.
+    `avg`, `curves`: as `test_patches`, for the grading task (roc_fuse / roc_path / roc_omic); the survival task has no
+    grading metrics and ignores both."""
     from . import utils as U
     if opt.task not in ("grad", "surv"):
         raise NotImplementedError("task %r" % opt.task)
@@ -452,6 +569,7 @@ def test_teacher_patches(opt, model, loader, device, agg=None, sync=None):
     if agg is None:
         agg = "mean" if surv else "max"
     agg_spec(agg)
+    _check_avg(avg)
     G = loader.num_patients
     if surv:
         if not getattr(loader, "has_survival", False):
@@ -470,7 +588,7 @@ def test_teacher_patches(opt, model, loader, device, agg=None, sync=None):
         hz = [hazard[:, j].contiguous() for j in range(3)]
         patch_result, counts = _teacher_result(
             loader, outs[:3], outs[3:6], d_grade, (loader.survtime[loader.row_roi], loader.censor[loader.row_roi]), losses,
-            _device_metric, more_counts=ops.cindex_counts(loader.patient_survtime, loader.patient_censor, hz))
+            _device_metric(avg), more_counts=ops.cindex_counts(loader.patient_survtime, loader.patient_censor, hz))
         hz_host = hazard.cpu().numpy()
         p_censor = loader.patient_censor_host.astype(np.float64)
         p_time = loader.patient_survtime_host.astype(np.float64)
@@ -483,7 +601,7 @@ def test_teacher_patches(opt, model, loader, device, agg=None, sync=None):
         print("Patient level (%s): C-index" % (agg,), *(patient_result["cindex_" + n] for n in names))
     else:
         d = [outs[j].float().contiguous() for j in range(3)]
-        patch_result, _ = _teacher_result(loader, d, outs[3:6], d_grade, None, losses, _device_metric)
-        patient_result.update(_patient_grading(loader, agg, tuple(zip(names, d))))
+        patch_result, _ = _teacher_result(loader, d, outs[3:6], d_grade, None, losses, _device_metric(avg))
+        patient_result.update(_patient_grading(loader, agg, tuple(zip(names, d)), avg, curves))
         print("Patient level (%s):" % (agg,), *patient_result["metrics_fuse"])
     return patch_result, patient_result

@@ -618,6 +618,49 @@ def rank_counts(pred, grade, out=None):
     return out
 
 
+def rank_counts_classes(pred, grade, out=None):
+    """The counts of `rank_counts` for every one-vs-rest column of pred [N, C] in one call (ph_rank_counts_classes; a memset
+    and two launches whatever C is): an int64 [5 * C] device tensor, words 4 c .. 4 c + 3 = {P_c, concordant_c, tied_c, bad_c}
+    and word 4 C + c the BITS of the float64 ap_sum_c (`out[4 * C:].view(torch.float64)`).  `out`: 5 C int64 words of a
+    caller's buffer to fill instead."""
+    pred, grade = _pred_grade(pred, grade, "rank_counts_classes")
+    N, C = pred.shape
+    nbytes = lib().ph_rank_counts_classes_workspace_bytes(N, C)
+    if nbytes == 0:
+        raise ValueError("rank_counts_classes: 1 <= N <= 1048576 and 1 <= C <= 16 (got %d x %d)" % (N, C))
+    if out is None:
+        out = torch.empty(5 * C, device=pred.device, dtype=torch.int64)
+    ws = torch.empty(nbytes // 8, device=pred.device, dtype=torch.float64)
+    check(lib().ph_rank_counts_classes(ptr(pred), ptr(grade), N, C, ptr(out), out.data_ptr() + 32 * C, ptr(ws), stream()),
+          "ph_rank_counts_classes")
+    return out
+
+
+def roc_points(pred, grade, cls):
+    """The ROC curve's integer points at every distinct threshold (ph_roc_points) of column `cls` of pred [N, C] one-vs-rest
+    (M = N elements), or with cls = "micro" (or -1) of all M = N * C (score, label) pairs: an int32 [2 + 3 * M] device tensor
+    {points, bad, fps [M], tps [M], thr [M] (the BITS of the float32 thresholds: `.view(torch.float32)`)}; the first `points`
+    entries of the three arrays are the curve in descending threshold order, the rest is left unwritten."""
+    pred, grade = _pred_grade(pred, grade, "roc_points")
+    N, C = pred.shape
+    if isinstance(cls, str):
+        if cls != "micro":
+            raise ValueError('roc_points: cls is a class index or "micro", got %r' % (cls,))
+        cls = -1
+    cls = int(cls)
+    nbytes = lib().ph_roc_points_workspace_bytes(N, C)
+    if nbytes == 0 or not -1 <= cls < C or (cls == -1 and N * C > 1 << 20):
+        raise ValueError("roc_points: 1 <= N <= 1048576, 1 <= C <= 16, cls in [0, C) or \"micro\" with N * C <= 1048576 "
+                         "(got %d x %d, cls %d)" % (N, C, cls))
+    M = N if cls >= 0 else N * C
+    out = torch.empty(2 + 3 * M, device=pred.device, dtype=torch.int32)
+    ws = torch.empty(nbytes // 4, device=pred.device, dtype=torch.int32)
+    base = out.data_ptr()
+    check(lib().ph_roc_points(ptr(pred), ptr(grade), N, C, cls, base + 8, base + 8 + 4 * M, base + 8 + 8 * M, base, ptr(ws),
+                              stream()), "ph_roc_points")
+    return out
+
+
 def confusion_counts(pred, grade, out=None):
     """int64 [C, C] device tensor: row = true grade, column = arg-max of the row of pred (first maximum), ph_confusion_counts."""
     pred, grade = _pred_grade(pred, grade, "confusion_counts")
