@@ -118,12 +118,12 @@ int plan_dgrad(const Conv& v, int prec, PhTapConv* t, PhTapConv cls[4], int* ncl
   return PH_OK;
 }
 
-// dgrad weights in layout w_frag, and the plane-1 fragment copy when launch t reads it
-int pack_dgrad(const float* w, bf16* hi, const PhTapConv* t, const Conv& v, int prec, hipStream_t st) {
+// the weights of convolution v at `hi` in the orientation and layout launch t (stride S) reads: the half-pair layout t->w_frag, the
+// split planes, or perf-mode plane 0 with the plane-1 fragment copy when the launch's kernel reads it
+int pack_one(const float* w, bf16* hi, const PhTapConv* t, int S, const Conv& v, int dgrad, int prec, hipStream_t st) {
   const bool hp = prec == PH_PREC_FP16X3 || prec == PH_PREC_FP16X1;
-  const int rc = hp ? ph_pack_w_hp_launch(w, hi, v.Cout, v.Cin, v.KS, 1, t->w_frag, st) : ph_pack_w_dgrad_launch(w, hi, v.Cout, v.Cin, v.KS, st);
-  if (rc || !ph_tapconv_needs_frag_copy(t, 1, prec)) return rc;
-  return ph_frag7_repack_launch(hi, v.Cin, v.Cout, 9, st);
+  const int frag = hp ? t->w_frag : (ph_tapconv_needs_frag_copy(t, S, prec) ? PH_WFRAG_COPY : PH_WFRAG_ROW);
+  return ph_pack_w_launch(w, hi, v.Cout, v.Cin, v.KS, dgrad, hp ? -3 : (prec == PH_PREC_BF16 ? 1 : 3), frag, st);
 }
 }  // namespace
 
@@ -138,10 +138,7 @@ int ph_conv2d_fwd(const void* x, const float* w, void* y, float* ch_sum, float* 
   int rc = plan_fwd(Conv{B, Cin, IH, IW, Cout, KS, stride, pad}, prec, &t, &S);
   if (rc) return rc;
   t.stats = reinterpret_cast<float*>(ws + up(PH_NPLANES * t.wplane * sizeof(bf16)));
-  rc = prec == PH_PREC_FP16X3 ? ph_pack_w_hp_launch(w, hi, Cout, Cin, KS, 0, t.w_frag, st) : ph_pack_w_fwd_launch(w, hi, Cout, Cin, KS, st);
-  if (rc) return rc;
-  // perf mode, conv_tap7.hip / conv_tap6b.hip: the fragment-major copy in plane 1 (a split plane this mode does not read)
-  if (ph_tapconv_needs_frag_copy(&t, S, prec) && (rc = ph_frag7_repack_launch(hi, Cout, Cin, 9, st))) return rc;
+  if ((rc = pack_one(w, hi, &t, S, Conv{B, Cin, IH, IW, Cout, KS, stride, pad}, 0, prec, st))) return rc;
   if ((rc = ph_tapconv_launch(&t, S, prec, st))) return rc;
   if (ch_sum || ch_sumsq) {
     hipLaunchKernelGGL(parts_sum_kernel, dim3(cdiv(Cout, 64)), dim3(64), 0, st, t.stats,
@@ -166,7 +163,7 @@ int dgrad_common(const void* dy, const float* w, void* dx, const void* res_g, co
   int rc = plan_dgrad(v, prec, &t, cls, &ncls, &tapless);
   if (rc) return rc;
   if (tapless && res_g && (res_g != dx || res_a)) return PH_EINVAL;
-  if ((rc = pack_dgrad(w, hi, &cls[0], v, prec, st))) return rc;
+  if ((rc = pack_one(w, hi, &cls[0], 1, v, 1, prec, st))) return rc;
   if (tapless && !res_g) {
     const size_t es = prec == PH_PREC_BF16 ? 2 : 4;
     if (hipMemsetAsync(dx, 0, (size_t)B * IH * IW * Cin * es, st) != hipSuccess) return PH_ELAUNCH;
@@ -211,13 +208,13 @@ int ph_conv2d_fwd_fused_in(const void* x, const float* in_scale, const float* in
   unsigned char* ws = reinterpret_cast<unsigned char*>(ws_);
   const size_t plane = (size_t)9 * Cin * Cout;
   bf16* hi = reinterpret_cast<bf16*>(ws);
-  int rc = ph_pack_w_fwd_launch(w, hi, Cout, Cin, 3, st);
-  if (rc) return rc;
   PhTapConv t{};
   t.in = x; t.w = hi; t.wplane = plane; t.out = y; t.in_scale = in_scale; t.in_shift = in_shift;
   t.stats = reinterpret_cast<float*>(ws + up(PH_NPLANES * plane * sizeof(bf16)));
   t.B = B;
   ph_conv_fwd_geometry(&t, Cin, IH, IW, Cout, 3, 1, 1);
+  int rc = pack_one(w, hi, &t, 1, Conv{B, Cin, IH, IW, Cout, 3, 1, 1}, 0, PH_PREC_BF16, st);
+  if (rc) return rc;
   if ((rc = ph_tapconv_launch(&t, 1, PH_PREC_BF16, st))) return rc;
   if (ch_sum || ch_sumsq) {
     hipLaunchKernelGGL(parts_sum_kernel, dim3(cdiv(Cout, 64)), dim3(64), 0, st, t.stats, ph_tapconv_stat_parts(&t, 1, PH_PREC_BF16), Cout,
@@ -245,7 +242,7 @@ int ph_conv2d_dgrad_bnstat(const void* dy, const float* w, void* dx, const void*
   t.bst_y = bst_y; t.bst_a = bst_a; t.bst_y2 = bst_y2; t.bst_scale = bst_scale; t.bst_shift = bst_shift;
   t.bst_mean = bst_mean; t.bst_mean2 = bst_mean2;
   t.stats = reinterpret_cast<float*>(ws + up(PH_NPLANES * plane * sizeof(bf16)));
-  int rc = pack_dgrad(w, hi, &t, Conv{B, Cin, IH, IW, Cout, 3, 1, 1}, PH_PREC_BF16, st);
+  int rc = pack_one(w, hi, &t, 1, Conv{B, Cin, IH, IW, Cout, 3, 1, 1}, 1, PH_PREC_BF16, st);
   if (rc) return rc;
   if ((rc = ph_tapconv_launch(&t, 1, PH_PREC_BF16, st))) return rc;
   const int nparts = ph_tapconv_stat_parts(&t, 1, PH_PREC_BF16);

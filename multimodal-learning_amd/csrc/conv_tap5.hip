@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void tapconv5_kernel(PhTapConv p) {
   PH_TILE_LIST(tile_id, total);
 
   // ---- weights: tap slab t = wtap[0] + t * (wtap[1] - wtap[0]) (forward 0..8, dgrad 8..0).  The 64 -> 64 slabs are packed
-  // FRAGMENT-MAJOR for this kernel (conv_wgrad.hip: pack_all_tiled_hp_kernel, ph5_frag_index below): per tap
+  // FRAGMENT-MAJOR for this kernel (pack_weights.hip: pack_all_tiled_hp_kernel, frag64_index): per tap
   // [block 3][k-step 2][N tile 4][lane 64][8 fp16] - the fragment of N tile n / k-step ks (row 4 li + n, k = 32 ks + 8 lg ..) of
   // all 64 lanes is ONE contiguous KiB, so a load instruction touches 8 full cache lines.  (In the row-major layout [row][192]
   // a fragment is 16 rows x 64 B = 16 half lines: the same bytes took the vector L1 twice as long - a slice with weight loads

@@ -401,27 +401,17 @@ __global__ __launch_bounds__(256) void tapconv7_kernel(PhTapConv p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // pieces / fragments issued past the end of the stream must not outlive the workgroup
 }
 
-// row-major perf-mode weights [tap][R][K] (plane 0) -> the fragment-major copy (plane 1): one thread per 16-byte chunk
-__global__ void frag7_repack_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst, int R, int K, int ntaps) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // chunk index: [tap][r][k / 8]
-  const size_t n = (size_t)ntaps * R * (K >> 3);
-  if (i >= n) return;
-  const int k8 = (int)(i % (K >> 3));
-  const int r = (int)((i / (K >> 3)) % R);
-  const int tp = (int)(i / ((size_t)(K >> 3) * R));
-  const int k = k8 * 8;
-  const size_t d = (size_t)tp * R * K + (size_t)((r >> 6) * (K >> 6) + (k >> 6)) * 4096 +
-                   (size_t)((((k & 63) >> 5) * 4 + (r & 3)) * 512 + (((((k & 63) >> 3) & 3) << 4) + ((r & 63) >> 2)) * 8);
-  *reinterpret_cast<u32x4*>(dst + d) = *reinterpret_cast<const u32x4*>(src + ((size_t)tp * R + r) * K + k);
-}
-
 }  // namespace
 
+
+// the weight shapes ([rows][K] per tap, either orientation) the kernel takes: 3x3, rows = K a multiple of 128 up to 512.  Units of
+// this shape carry the fragment-major copy the kernel reads (ph_kernels.h)
+bool ph_tapconv7_wshape(int rows, int K, int ntaps) { return ntaps == 9 && rows == K && K >= 128 && K <= 512 && K % 128 == 0; }
 
 // eligible: conv_tap3.hip's perf-mode configuration without the in-LDS input BatchNorm (dense 3x3 stride-1 over the whole map,
 // Cin = Cout in 128 .. 512) on a dense NHWC tensor
 bool ph_tapconv7_eligible(const PhTapConv* p) {
-  return ph_tapconv3_eligible(p) && !p->in_scale && !p->m_groups && !p->ncls && p->Cin == p->Cout && p->os == 1 && p->oa_h == 0 &&
+  return ph_tapconv7_wshape(p->Cout, p->Cin, p->ntaps) && ph_tapconv3_eligible(p) && !p->in_scale && !p->m_groups && !p->ncls && p->os == 1 && p->oa_h == 0 &&
          p->oa_w == 0 && p->OHt == p->OH && p->OWt == p->OW && p->IH == p->OH && p->IW == p->OW && p->iy0 == -1 && p->ix0 == -1 &&
          !p->in_pix_stride && !p->in_row_stride && !p->in_img_stride && p->wplane == (size_t)9 * p->Cin * p->Cout &&
          (long)p->OH * p->OW * p->Cout * 2 < 0x7ffffff0L;
@@ -442,14 +432,4 @@ int ph_tapconv7_launch(const PhTapConv* p, hipStream_t st) {
     return p->bst_y2 ? launch7<3>(p, st) : launch7<2>(p, st);
   }
   return p->stats ? launch7<0>(p, st) : launch7<-1>(p, st);
-}
-
-// the fragment-major copy of ONE convolution's packed perf-mode weights (test hooks, c_api.hip): plane 0 -> plane 1
-int ph_frag7_repack_launch(void* packed, int R, int K, int ntaps, hipStream_t st) {
-  if ((R & 63) || (K & 63)) return PH_EINVAL;
-  bf16* base = reinterpret_cast<bf16*>(packed);
-  const size_t n = (size_t)ntaps * R * (K >> 3);
-  hipLaunchKernelGGL(frag7_repack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, base, base + (size_t)ntaps * R * K, R, K, ntaps);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
 }

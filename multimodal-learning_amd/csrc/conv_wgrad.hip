@@ -1,4 +1,4 @@
-// Weight-gradient (wgrad) of the 3x3 / 1x1 convolutions on MFMA, plus weight packing kernels.
+// Weight-gradient (wgrad) of the 3x3 / 1x1 convolutions on MFMA.
 //
 //   dW[tap][cout][cin] = sum_{b,r,c} dY[b,r,c,cout] * X[b, r*S + kh - pad, c*S + kw - pad, cin]
 // GEMM view: M = cout, N = cin, K = pixels (huge).  Both operands are K-major in HBM (NHWC: pixel is the
@@ -625,246 +625,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-__global__ void pack_w_kernel(const float* __restrict__ w, bf16* __restrict__ planes, int O, int I, int NT,
-                              int dgrad) {
-  // w OIHW [O][I][NT].  fwd layout [tap][O][I]; dgrad layout [tap][I][O]
-  const size_t n = (size_t)NT * O * I;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  int t, o, ii;
-  if (!dgrad) { ii = i % I; o = (i / I) % O; t = i / ((size_t)I * O); }
-  else        { o = i % O; ii = (i / O) % I; t = i / ((size_t)I * O); }
-  const float v = w[((size_t)o * I + ii) * NT + t];
-  bf16 a, b, c;
-  split3_bf16(v, a, b, c);
-  planes[i] = a; planes[n + i] = b; planes[2 * n + i] = c;
-}
-
-__global__ void pack_w_stem_kernel(const float* __restrict__ w, bf16* __restrict__ planes) {
-  // w [64][3][7][7] -> [kh 7][cout 64][kw 8 x ch 4], zero padded
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 7 * 64 * 32) return;
-  const int k = i & 31, co = (i >> 5) & 63, kh = i >> 11;
-  const int kw = k >> 2, ch = k & 3;
-  float v = 0.f;
-  if (kw < 7 && ch < 3) v = w[((co * 3 + ch) * 7 + kh) * 7 + kw];
-  bf16 a, b, c;
-  split3_bf16(v, a, b, c);
-  planes[i] = a; planes[7 * 64 * 32 + i] = b; planes[2 * 7 * 64 * 32 + i] = c;
-}
-
-// all conv weights of one network in ONE launch: thread i walks the concatenated fwd-layout index space
-__global__ void pack_all_kernel(PhPackAll t, bf16* __restrict__ packed, int nplanes) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= t.total) return;
-  int u = 0;
-#pragma unroll 1
-  while (u + 1 < t.n && i >= t.start[u + 1]) ++u;
-  const size_t e = i - t.start[u];
-  const int O = t.O[u], I = t.I[u], NT = t.NT[u];
-  const size_t n = (size_t)NT * O * I;
-  const int ii = e % I, o = (e / I) % O, tp = e / ((size_t)I * O);
-  const float v = t.w[u][((size_t)o * I + ii) * NT + tp];
-  bf16 a, b, c;
-  split3_bf16(v, a, b, c);
-  const size_t fdst = t.dst_fwd[u] + e;                                     // [tap][O][I]
-  const size_t ddst = t.dst_dg[u] + ((size_t)tp * I + ii) * O + o;          // [tap][I][O]
-  packed[fdst] = a; packed[ddst] = a;
-  if (nplanes == 3) {
-    packed[fdst + n] = b; packed[fdst + 2 * n] = c;
-    packed[ddst + n] = b; packed[ddst + 2 * n] = c;
-  }
-}
-
-// The same, tiled through LDS: one workgroup per (conv, 32 output channels, 32 input channels), all taps.  The
-// element-per-thread kernel above writes the dgrad layout [tap][I][O] as 2-byte words scattered with a stride of O
-// elements (110 us for the 11 M weights of a ResNet-18, twice per step); here the OIHW rows are read as contiguous
-// runs of 32*NT floats and both layouts leave as 64-byte runs.
-struct PackTiles { int tstart[21]; };
-// fragment-major order of a 64 x 64 (row, k) block for the register-window kernels (conv_tap5/6/7.hip): [k-step 2][N tile 4][lane 64][8]:
-// row r = 4 li + n, k = 32 ks + 8 lg + j, lane = 16 lg + li
-__device__ __forceinline__ size_t frag64_index(int r, int k) {
-  return (size_t)(((k >> 5) * 4 + (r & 3)) * 512 + ((((k >> 3) & 3) << 4) + (r >> 2)) * 8 + (k & 7));
-}
-template <int NP>
-__global__ __launch_bounds__(256) void pack_all_tiled_kernel(PhPackAll t, PackTiles pt, bf16* __restrict__ packed) {
-  __shared__ bf16 sh[NP][32][32 * 9 + 2];
-  int u = 0;
-#pragma unroll 1
-  while (u + 1 < t.n && (int)blockIdx.x >= pt.tstart[u + 1]) ++u;
-  const int O = t.O[u], I = t.I[u], NT = t.NT[u];
-  const int tile = (int)blockIdx.x - pt.tstart[u];
-  const int itiles = I >> 5;
-  const int o0 = (tile / itiles) << 5, i0 = (tile % itiles) << 5;
-  const size_t n = (size_t)NT * O * I;
-  const int run = 32 * NT;   // contiguous floats per output-channel row of the tile
-  for (int idx = threadIdx.x; idx < 32 * run; idx += 256) {
-    const int o = idx / run, r = idx - o * run;
-    const float v = t.w[u][((size_t)(o0 + o) * I + i0) * NT + r];
-    if constexpr (NP == 1) {
-      sh[0][o][r] = (bf16)v;
-    } else {
-      bf16 a, b, c;
-      split3_bf16(v, a, b, c);
-      sh[0][o][r] = a; sh[1][o][r] = b; sh[2][o][r] = c;
-    }
-  }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < 32 * run; idx += 256) {
-    const int x = idx & 31, y = (idx >> 5) & 31, tp = idx >> 10;
-    // forward layout [tap][O][I]: x = input channel (fastest), y = output channel
-    const size_t fdst = t.dst_fwd[u] + ((size_t)tp * O + o0 + y) * I + i0 + x;
-    // dgrad layout [tap][I][O]: x = output channel (fastest), y = input channel
-    const size_t ddst = t.dst_dg[u] + ((size_t)tp * I + i0 + y) * O + o0 + x;
-#pragma unroll
-    for (int pl = 0; pl < NP; ++pl) {
-      packed[fdst + pl * n] = sh[pl][y][x * NT + tp];
-      packed[ddst + pl * n] = sh[pl][x][y * NT + tp];
-    }
-    // perf mode, dense 3x3 stride-1 units with Cin = Cout >= 128 (ResNet layers 2-4: what conv_tap7.hip takes): a fragment-major
-    // copy of both orientations in plane 1 of the unit's region (unused in this mode): [tap][rows / 64][K / 64] x 4096 elements
-    if constexpr (NP == 1) {
-      if (NT == 9 && O == 2 * I) {      // the stride-2 units, forward orientation (conv_tap6b.hip)
-        const int o = o0 + y, i = i0 + x;
-        packed[t.dst_fwd[u] + n + (size_t)tp * O * I + (size_t)((o >> 6) * (I >> 6) + (i >> 6)) * 4096 + frag64_index(o & 63, i & 63)] = sh[0][y][x * NT + tp];
-      }
-      if (NT == 9 && O == I && I >= 128) {
-        const int o = o0 + y, i = i0 + x;      // forward: row o, k i
-        packed[t.dst_fwd[u] + n + (size_t)tp * O * I + (size_t)((o >> 6) * (I >> 6) + (i >> 6)) * 4096 + frag64_index(o & 63, i & 63)] = sh[0][y][x * NT + tp];
-        const int r = i0 + y, k = o0 + x;      // dgrad: row = input channel, k = output channel
-        packed[t.dst_dg[u] + n + (size_t)tp * I * O + (size_t)((r >> 6) * (O >> 6) + (k >> 6)) * 4096 + frag64_index(r & 63, k & 63)] = sh[0][x][y * NT + tp];
-      }
-    }
-  }
-}
-
-// PH_PREC_FP16X3 layout: per (tap, output row) the K direction holds, for every 64-channel slice, the three fp16 blocks
-// [hi * 2^11 | lo | hi] of the weights' half-pair split (w ~= hi + lo * 2^-11): the K loop of a convolution multiplies them
-// with the activation blocks (hi, hi, lo) and accumulates 2^11 * (x * w) in ONE accumulator set.  |w| < 32 (hi * 2^11 is fp16).
-__device__ __forceinline__ size_t hp_k(int k) { return (size_t)(k >> 6) * 192 + (k & 63); }
-__device__ __forceinline__ void hp_w3(float v, f16& b0, f16& b1, f16& b2) {
-  hp_split(v, b2, b1);
-  b0 = (f16)((float)b2 * PH_HP_LO);
-}
-// conv_tap5.hip's layout of a 64 x 64 x 9 slab set: per tap [block 3][k-step 2][N tile 4][lane 64][8]: row r = 4 li + n, k = 32 ks + 8 lg + j,
-// lane = 16 lg + li -> element index inside the tap (block 0); blocks are 4096 elements apart.  The layout of each unit is the host's
-// decision (PhPackAll::frag, PH_WFRAG_*: the same eligibility and switch state that picks the kernel, ph_tapconv_hp_wfrag)
-__device__ __forceinline__ size_t ph5_frag_index(int r, int k) { return frag64_index(r, k); }
-template <bool ONE>
-__global__ __launch_bounds__(256) void pack_all_tiled_hp_kernel(PhPackAll t, PackTiles pt, f16* __restrict__ packed, int dgrad_only) {
-  __shared__ float sh[32][32 * 9 + 1];
-  int u = 0;
-#pragma unroll 1
-  while (u + 1 < t.n && (int)blockIdx.x >= pt.tstart[u + 1]) ++u;
-  const int O = t.O[u], I = t.I[u], NT = t.NT[u];
-  const int ffwd = t.frag[u] & 3, fdg = (t.frag[u] >> 2) & 3;
-  const int tile = (int)blockIdx.x - pt.tstart[u];
-  const int itiles = I >> 5;
-  const int o0 = (tile / itiles) << 5, i0 = (tile % itiles) << 5;
-  const int run = 32 * NT;
-  for (int idx = threadIdx.x; idx < 32 * run; idx += 256) {
-    const int o = idx / run, r = idx - o * run;
-    sh[o][r] = t.w[u][((size_t)(o0 + o) * I + i0) * NT + r];
-  }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < 32 * run; idx += 256) {
-    const int x = idx & 31, y = (idx >> 5) & 31, tp = idx >> 10;
-    f16 b0, b1, b2;
-    if (!ONE || dgrad_only == 0) {   // forward layout [tap][O][3 I]: x = input channel (fastest), y = output channel
-      hp_w3(sh[y][x * NT + tp], b0, b1, b2);
-      if (ffwd == PH_WFRAG_TAP5) {
-        f16* d = packed + t.dst_fwd[u] + (size_t)tp * 12288 + ph5_frag_index(o0 + y, i0 + x);
-        d[0] = b0; d[4096] = b1; d[8192] = b2;
-      } else if (ffwd == PH_WFRAG_TAP6) {
-        // conv_tap6.hip (the stride-2 convolutions, forward orientation only): [tap][O / 64][I / 64][block 3] x 4096 elements
-        const int o = o0 + y, i = i0 + x;
-        f16* d = packed + t.dst_fwd[u] + (size_t)tp * O * 3 * I + (size_t)(((o >> 6) * (I >> 6) + (i >> 6)) * 3) * 4096 + ph5_frag_index(o & 63, i & 63);
-        d[0] = b0; d[4096] = b1; d[8192] = b2;
-      } else {
-        f16* d = packed + t.dst_fwd[u] + ((size_t)tp * O + o0 + y) * (3 * (size_t)I) + hp_k(i0 + x);
-        d[0] = b0; d[64] = b1; d[128] = b2;
-      }
-    }
-    if (!ONE || dgrad_only == 1) {   // dgrad layout [tap][I][3 O]: x = output channel (fastest), y = input channel
-      hp_w3(sh[x][y * NT + tp], b0, b1, b2);
-      if (fdg == PH_WFRAG_TAP5) {
-        f16* d = packed + t.dst_dg[u] + (size_t)tp * 12288 + ph5_frag_index(i0 + y, o0 + x);
-        d[0] = b0; d[4096] = b1; d[8192] = b2;
-      } else {
-        f16* d = packed + t.dst_dg[u] + ((size_t)tp * I + i0 + y) * (3 * (size_t)O) + hp_k(o0 + x);
-        d[0] = b0; d[64] = b1; d[128] = b2;
-      }
-    }
-  }
-}
-
-// stem, PH_PREC_FP16X3: three fp16 planes [3][kh 7][cout 64][kw 8 x ch 4] = w hi * 2^11, w lo, w hi (the layout of the
-// three bf16 split planes): the kernel multiplies them with the activation planes (hi, hi, lo)
-__global__ void pack_w_stem_hp_kernel(const float* __restrict__ w, f16* __restrict__ packed) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 7 * 64 * 32) return;
-  const int k = i & 31, co = (i >> 5) & 63, kh = i >> 11;
-  const int kw = k >> 2, ch = k & 3;
-  float v = 0.f;
-  if (kw < 7 && ch < 3) v = w[((co * 3 + ch) * 7 + kh) * 7 + kw];
-  f16 b0, b1, b2;
-  hp_w3(v, b0, b1, b2);
-  packed[i] = b0; packed[7 * 64 * 32 + i] = b1; packed[2 * 7 * 64 * 32 + i] = b2;
-}
-
 }  // namespace
-
-int ph_pack_w_stem_hp_launch(const float* w, void* packed, hipStream_t st) {
-  hipLaunchKernelGGL(pack_w_stem_hp_kernel, dim3((7 * 64 * 32 + 255) / 256), dim3(256), 0, st, w, (f16*)packed);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
-}
-
-// one convolution in the PH_PREC_FP16X3 layout (forward or dgrad orientation) at the start of `packed` (test hooks)
-int ph_pack_w_hp_launch(const float* w, void* packed, int O, int I, int KS, int dgrad, int wfrag, hipStream_t st) {
-  if ((O & 31) || (I & 31) || (KS != 1 && KS != 3)) return PH_EINVAL;
-  // (the fragment-major layouts exist for the shapes of their kernels only)
-  if (wfrag == PH_WFRAG_TAP5 && !(O == 64 && I == 64 && KS == 3)) return PH_EINVAL;
-  if (wfrag == PH_WFRAG_TAP6 && !(O == 2 * I && KS == 3 && !dgrad)) return PH_EINVAL;
-  if (wfrag < 0 || wfrag > PH_WFRAG_TAP6) return PH_EINVAL;
-  PhPackAll t{};
-  t.n = 1; t.w[0] = w; t.O[0] = O; t.I[0] = I; t.NT[0] = KS * KS; t.dst_fwd[0] = 0; t.dst_dg[0] = 0;
-  t.frag[0] = dgrad ? wfrag << 2 : wfrag;
-  t.start[0] = 0; t.start[1] = t.total = (size_t)KS * KS * O * I;
-  PackTiles pt;
-  pt.tstart[0] = 0; pt.tstart[1] = (O >> 5) * (I >> 5);
-  hipLaunchKernelGGL(pack_all_tiled_hp_kernel<true>, dim3(pt.tstart[1]), dim3(256), 0, st, t, pt, (f16*)packed, dgrad ? 1 : 0);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
-}
-
-int ph_pack_all_launch(const PhPackAll* t, void* packed, int nplanes, hipStream_t st) {
-  bool tiled = t->n <= 20;
-  PackTiles pt;
-  pt.tstart[0] = 0;
-  for (int u = 0; u < t->n && tiled; ++u) {
-    if ((t->O[u] & 31) || (t->I[u] & 31) || t->NT[u] > 9) tiled = false;
-    pt.tstart[u + 1] = pt.tstart[u] + (t->O[u] >> 5) * (t->I[u] >> 5);
-  }
-  if (nplanes == -3) {
-    if (!tiled) return PH_EINVAL;
-    for (int u = 0; u < t->n; ++u) {      // (the fragment-major layouts exist for the shapes of their kernels only)
-      const int ff = t->frag[u] & 3, fd = (t->frag[u] >> 2) & 3;
-      if ((ff == PH_WFRAG_TAP5 || fd == PH_WFRAG_TAP5) && !(t->O[u] == 64 && t->I[u] == 64 && t->NT[u] == 9)) return PH_EINVAL;
-      if (ff == PH_WFRAG_TAP6 && !(t->O[u] == 2 * t->I[u] && t->NT[u] == 9)) return PH_EINVAL;
-      if (ff == 3 || fd == 3 || fd == PH_WFRAG_TAP6) return PH_EINVAL;
-    }
-    hipLaunchKernelGGL(pack_all_tiled_hp_kernel<false>, dim3(pt.tstart[t->n]), dim3(256), 0, st, *t, pt, (f16*)packed, 0);
-  } else if (tiled && nplanes == 1)
-    hipLaunchKernelGGL(pack_all_tiled_kernel<1>, dim3(pt.tstart[t->n]), dim3(256), 0, st, *t, pt, (bf16*)packed);
-  else if (tiled && nplanes == 3)
-    hipLaunchKernelGGL(pack_all_tiled_kernel<3>, dim3(pt.tstart[t->n]), dim3(256), 0, st, *t, pt, (bf16*)packed);
-  else
-    hipLaunchKernelGGL(pack_all_kernel, dim3((unsigned)((t->total + 255) / 256)), dim3(256), 0, st, *t, (bf16*)packed,
-                       nplanes);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
-}
 
 int ph_wgrad_tile_h(int S) { return S == 1 ? 8 : 4; }
 
@@ -891,26 +652,6 @@ int ph_wgrad_reduce_launch(const float* slab, float* dw, int nchunks, int KS, in
   const size_t n = (size_t)KS * KS * Cout * Cin;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, slab, dw, nchunks,
                      KS * KS, Cout, Cin, unscale);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
-}
-
-int ph_pack_w_fwd_launch(const float* w, void* planes, int O, int I, int KS, hipStream_t st) {
-  const size_t n = (size_t)KS * KS * O * I;
-  hipLaunchKernelGGL(pack_w_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, (bf16*)planes, O, I,
-                     KS * KS, 0);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
-}
-int ph_pack_w_dgrad_launch(const float* w, void* planes, int O, int I, int KS, hipStream_t st) {
-  const size_t n = (size_t)KS * KS * O * I;
-  hipLaunchKernelGGL(pack_w_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, (bf16*)planes, O, I,
-                     KS * KS, 1);
-  PH_LAUNCH_CHECK();
-  return PH_OK;
-}
-int ph_pack_w_stem_launch(const float* w, void* planes, hipStream_t st) {
-  hipLaunchKernelGGL(pack_w_stem_kernel, dim3((7 * 64 * 32 + 255) / 256), dim3(256), 0, st, w, (bf16*)planes);
   PH_LAUNCH_CHECK();
   return PH_OK;
 }

@@ -96,6 +96,8 @@ struct PhTapConv {
 #define PH_WFRAG_ROW 0       // [tap][O][3 I] (forward) / [tap][I][3 O] (dgrad)
 #define PH_WFRAG_TAP5 1      // conv_tap5.hip's 64 x 64 x 9 fragment-major slabs (3x3 stride-1, Cin = Cout = 64)
 #define PH_WFRAG_TAP6 2      // conv_tap6.hip's [tap][O / 64][I / 64][block 3] slabs (3x3 / stride 2 forward, Cout = 2 Cin)
+// perf mode (the pack only: PhPackAll::frag, never PhTapConv::w_frag): row-major in plane 0 and a fragment-major copy in plane 1
+#define PH_WFRAG_COPY 1
 
 // ---- kernel selection (conv_select.hip): the ONE place that combines the kernels' own predicates (ph_tapconvN_eligible,
 // ph_tapconv2_tile_h) with the A/B switches (PH_TAP3 .. PH_TAP7) and judges a descriptor.  The launcher, the BatchNorm row count,
@@ -125,7 +127,7 @@ extern "C" int ph_tapconv_stat_parts_bound(int B, int OH, int OW, int Cout, int 
 // the layout to PACK for a half-pair convolution over descriptor p (the only reader of PH_TAP5 / PH_TAP6: after the pack the
 // descriptor's w_frag decides)
 int ph_tapconv_hp_wfrag(const PhTapConv* p, int S, int prec);
-// the launch reads the fragment-major copy of its perf-mode weights in plane 1 (conv_tap7.hip, conv_tap6b.hip: ph_frag7_repack_launch)
+// the launch reads the fragment-major copy of its perf-mode weights in plane 1 (conv_tap7.hip, conv_tap6b.hip: PH_WFRAG_COPY)
 bool ph_tapconv_needs_frag_copy(const PhTapConv* p, int S, int prec);
 
 // ---- descriptor builders of the convolution entry points and the ResNet plan (conv_select.hip).  A convolution is given by plain
@@ -198,18 +200,19 @@ int ph_tapconv5_launch(const PhTapConv* p, hipStream_t st);
 int ph_tapconv5_stat_parts(const PhTapConv* p);
 // perf-mode kernel of the dense 3x3 stride-1 convolutions with Cin = Cout >= 128 (conv_tap7.hip: conv_tap3.hip's plain form on the
 // register-window machinery, bitwise the same outputs); reads the fragment-major copy of the weights in plane 1 of the unit's packed
-// region (p->w + p->wplane elements; pack_all_tiled_kernel<1> writes it, ph_frag7_repack_launch for a single convolution);
-// PH_TAP7=0 keeps conv_tap3.hip
+// region (p->w + p->wplane elements; pack_weights.hip writes it for every unit of the kernel's weight shapes, ph_tapconv7_wshape:
+// the weight-shape part of the eligibility, rows = K for either orientation); PH_TAP7=0 keeps conv_tap3.hip
+bool ph_tapconv7_wshape(int rows, int K, int ntaps);
 bool ph_tapconv7_eligible(const PhTapConv* p);
 int ph_tapconv7_launch(const PhTapConv* p, hipStream_t st);
-int ph_frag7_repack_launch(void* packed, int R, int K, int ntaps, hipStream_t st);
 // half-pair kernel of the 3x3 / stride-2 forward convolutions (conv_tap6.hip: parity-plane images through four LDS buffers on a
 // compile-time DMA schedule, conv_tap5.hip's weight window; reads PH_WFRAG_TAP6 weights); PH_TAP6=0 at pack time keeps the first generation
 bool ph_tapconv6_eligible(const PhTapConv* p);
 int ph_tapconv6_launch(const PhTapConv* p, hipStream_t st);
 int ph_tapconv6_stat_parts(const PhTapConv* p);
-// ... and its perf-mode (bf16) form (conv_tap6b.hip); reads the fragment-major copy in plane 1 of the unit's packed region; PH_TAP6B=0
-// keeps conv_tap2.hip's masked grid
+// ... and its perf-mode (bf16) form (conv_tap6b.hip); reads the fragment-major copy in plane 1 of the unit's packed region, which the
+// forward orientation of every unit of its weight shapes (ph_tapconv6b_wshape) carries; PH_TAP6B=0 keeps conv_tap2.hip's masked grid
+bool ph_tapconv6b_wshape(int Cout, int Cin, int ntaps);
 bool ph_tapconv6b_eligible(const PhTapConv* p);
 int ph_tapconv6b_launch(const PhTapConv* p, hipStream_t st);
 int ph_tapconv6b_stat_parts(const PhTapConv* p);
@@ -293,24 +296,28 @@ int ph_stem_wgrad_chunks(int B, int OH, int OW, int* tiles_per_chunk);
 int ph_stem_dgrad_launch(const void* dy, const float* w_oihw, float* dx_nchw, int B, int H, int W, int prec, hipStream_t st);
 int ph_stem_wgrad_reduce_launch(const float* slab, float* dw_oihw, int nchunks, const float* unscale, hipStream_t st);
 
-// weight packing (OIHW fp32 -> MFMA-friendly bf16, 3 split planes of `plane` elements each)
-int ph_pack_w_fwd_launch(const float* w, void* planes, int O, int I, int KS, hipStream_t st);   // [tap][O][I]
-int ph_pack_w_dgrad_launch(const float* w, void* planes, int O, int I, int KS, hipStream_t st); // [tap][I][O]
-int ph_pack_w_stem_launch(const float* w, void* planes, hipStream_t st);                        // [7][64][32]
-
-// all 3x3 / 1x1 conv weights of one network in one launch (stem handled by ph_pack_w_stem_launch)
+// ---- weight packing (pack_weights.hip): OIHW fp32 -> the layouts the kernels read, PH_NPLANES planes per orientation of a unit
+int ph_pack_w_stem_launch(const float* w, void* planes, hipStream_t st);                        // three bf16 split planes [7][64][32]
+int ph_pack_w_stem_hp_launch(const float* w, void* packed, hipStream_t st);                     // PH_PREC_FP16X3
+// up to 20 3x3 / 1x1 convolutions in one launch (the table is a kernel argument): the forward layout [tap][O][I] at element dst_fwd,
+// the dgrad layout [tap][I][O] at dst_dg
 struct PhPackAll {
   const float* w[20];
-  size_t dst_fwd[20], dst_dg[20], start[21];
+  size_t dst_fwd[20], dst_dg[20];
+  size_t start[21];      // (unread, like `total`: the table keeps the argument layout its kernels were compiled for)
   int O[20], I[20], NT[20];
-  int frag[20];          // nplanes = -3: PH_WFRAG_* of the forward layout (bits 0-1) | (PH_WFRAG_* of the dgrad layout) << 2
+  // the layout of the forward orientation (bits 0-1) | the dgrad orientation's << 2, the caller's decision: PH_WFRAG_* of the half-pair
+  // kernels (nplanes = -3), PH_WFRAG_ROW / PH_WFRAG_COPY (nplanes = 1), 0 (nplanes = 3)
+  int frag[20];
   int n;
   size_t total;
 };
-// nplanes: 1 (bf16), 3 (three bf16 split planes), -3 (PH_PREC_FP16X3: fp16 [hi 2^11 | lo | hi] per 64-channel K slice, (hi, lo) = the half-pair split)
+// nplanes: 1 (bf16), 3 (three bf16 split planes), -3 (PH_PREC_FP16X3: fp16 [hi 2^11 | lo | hi] per 64-channel K slice, (hi, lo) = the
+// half-pair split).  PH_EINVAL: a table the kernels cannot tile, or a layout that does not exist for its unit's shape
 int ph_pack_all_launch(const PhPackAll* t, void* packed, int nplanes, hipStream_t st);
-int ph_pack_w_hp_launch(const float* w, void* packed, int O, int I, int KS, int dgrad, int wfrag, hipStream_t st);   // one conv, layout PH_WFRAG_*
-int ph_pack_w_stem_hp_launch(const float* w, void* packed, hipStream_t st);
+// one convolution, as a one-entry table: the forward (dgrad = 0) or the dgrad orientation alone at the start of `packed`, in that
+// orientation's layout `frag`
+int ph_pack_w_launch(const float* w, void* packed, int O, int I, int KS, int dgrad, int nplanes, int frag, hipStream_t st);
 
 // ---- BatchNorm / elementwise (bn_act.hip).  `prec` selects the activation type (bf16 | float).
 int ph_pack_input_launch(const float* x_nchw, void* x4, int B, int H, int W, int prec, hipStream_t st);

@@ -30,8 +30,10 @@ struct Unit {
   size_t wplane;           // elements per plane (lo plane follows hi)
   size_t y_off;            // byte offset of raw conv output in ws
   size_t st_off;           // byte offset of [mean, invstd, scale, shift] (4*C floats)
-  // PH_PREC_FP16X3: layouts (PH_WFRAG_*) of the fwd / dgrad weights, chosen at pack time from the descriptors below
+  // layouts of the fwd / dgrad weights (refresh_layouts).  PH_PREC_FP16X3: PH_WFRAG_*, chosen at pack time under the switches;
+  // perf mode: copy_f / copy_d, the orientation carries the plane-1 fragment copy
   mutable int wfrag_f = 0, wfrag_d = 0;
+  mutable bool copy_f = false, copy_d = false;
 };
 
 struct Block {
@@ -106,8 +108,10 @@ int stem_chunks(int B, int OH, int OW, int* tpc) {
   return cdiv(ntiles, *tpc);
 }
 
-// the half-pair weight layout of every unit (Unit::wfrag_f / wfrag_d) under the current switches, and its signature: a packed
-// buffer is valid for every plan whose signature equals the one it was packed under (ph_resnet_plan_layout_sig)
+// The one place that fills a unit's weight layouts.  Half-pair modes: Unit::wfrag_f / wfrag_d under the current switches, and their
+// signature: a packed buffer is valid for every plan whose signature equals the one it was packed under (ph_resnet_plan_layout_sig).
+// Perf mode: Unit::copy_f / copy_d from the weight shape alone, by the kernels' own predicates - no switch and no map size enters,
+// so PH_TAP7 / PH_TAP6B can be toggled over a packed buffer, every plan of a network shares it, and the signature has nothing to record.
 unsigned long long refresh_layouts(const PhResnetPlan* P) {
   unsigned long long sig = 1469598103934665603ull;      // FNV-1a over (unit, fwd layout, dgrad layout)
   for (size_t i = 1; i < P->units.size(); ++i) {
@@ -117,6 +121,9 @@ unsigned long long refresh_layouts(const PhResnetPlan* P) {
     u.wfrag_f = ph_tapconv_hp_wfrag(&f, u.S, P->prec);
     u.wfrag_d = PH_WFRAG_ROW;
     if (u.S == 1) { ph_conv_dgrad_s1_geometry(&d, u.Cin, u.IH, u.IW, u.Cout, u.KS, u.pad); u.wfrag_d = ph_tapconv_hp_wfrag(&d, 1, P->prec); }
+    const int NT = u.KS * u.KS;
+    u.copy_f = P->prec == PH_PREC_BF16 && (ph_tapconv7_wshape(u.Cout, u.Cin, NT) || ph_tapconv6b_wshape(u.Cout, u.Cin, NT));
+    u.copy_d = P->prec == PH_PREC_BF16 && ph_tapconv7_wshape(u.Cin, u.Cout, NT);
     for (unsigned long long v : {(unsigned long long)i, (unsigned long long)u.wfrag_f, (unsigned long long)u.wfrag_d}) {
       sig ^= v;
       sig *= 1099511628211ull;
@@ -284,20 +291,15 @@ int ph_resnet_pack_weights(const PhResnetPlan* P, const void* const* params_, vo
   constexpr size_t PER = std::size(PhPackAll{}.w);
   for (size_t i0 = 1; i0 < P->units.size(); i0 += PER) {
     PhPackAll t{};
-    size_t acc = 0;
     for (size_t i = i0; i < P->units.size() && i < i0 + PER; ++i) {
       const Unit& u = P->units[i];
       const int k = t.n++;
       t.w[k] = params.w((int)i);
       t.dst_fwd[k] = u.wf_off; t.dst_dg[k] = u.wd_off;
       t.O[k] = u.Cout; t.I[k] = u.Cin; t.NT[k] = u.KS * u.KS;
-      // the layouts the kernels of this unit's launches read (refresh_layouts above: the eligibility and switch state that picks them)
-      t.frag[k] = u.wfrag_f | (u.wfrag_d << 2);
-      t.start[k] = acc;
-      acc += u.wplane;
+      // the layouts the kernels of this unit's launches read (refresh_layouts above)
+      t.frag[k] = P->prec == PH_PREC_BF16 ? (u.copy_f ? PH_WFRAG_COPY : 0) | (u.copy_d ? PH_WFRAG_COPY << 2 : 0) : u.wfrag_f | (u.wfrag_d << 2);
     }
-    t.start[t.n] = acc;
-    t.total = acc;
     if ((rc = ph_pack_all_launch(&t, pk, P->prec == PH_PREC_BF16 ? 1 : (P->prec == PH_PREC_FP16X3 ? -3 : 3), st))) return rc;
   }
   return PH_OK;
