@@ -710,7 +710,6 @@ __global__ __launch_bounds__(256) void stem_bwd_reduce_raw_kernel(const T* __res
   }
 }
 
-inline unsigned nblk(size_t n, int t = 256) { return (unsigned)((n + t - 1) / t); }
 // blocks of the grid-stride elementwise passes: ~PH_EW_ITEMS eight-channel vectors per thread once the tensor is large enough to
 // fill the chip anyway (>= 2048 blocks = one wave of 8 blocks per CU); A/B: PH_EW_ITEMS=1 restores one element per thread
 inline unsigned ew_grid(size_t n8, int C8) {

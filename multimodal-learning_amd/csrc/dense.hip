@@ -4,6 +4,7 @@
 #include "ph_common.h"
 #include "ph_dense.h"
 #include "ph_kernels.h"
+#include "ph_reduce.h"
 
 namespace {
 
@@ -25,6 +26,77 @@ __global__ void bn1d_eval_bwd_kernel(const float* __restrict__ g, const float* _
 #define PH_BN1D_NC 16      // channels per workgroup of the BatchNorm1d kernels (256 / PH_BN1D_NC row lanes)
 #endif
 constexpr int GT = 64, GK = 32;   // all global loads of a K step are issued before any is consumed
+
+// the epilogue activation of the GEMMs (PH_ACT_*; anything else: none)
+__device__ __forceinline__ float act_apply(float v, int act) {
+  if (act == PH_ACT_RELU) v = v > 0.f ? v : 0.f;
+  else if (act == PH_ACT_ELU) v = v > 0.f ? v : expm1f(v);
+  else if (act == PH_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+  return v;
+}
+
+// Operand staging of the three SGEMM kernels, 256 threads over a TF x TK tile (TF rows of M or N, TK of K).
+// Element e of the tile: the operand's unit-stride direction is the fast thread index.
+template <int TF, int TK>
+__device__ __forceinline__ void tile_coord(int e, bool kfast, int& f, int& k) {
+  if (kfast) { k = e % TK; f = e / TK; } else { f = e % TF; k = e / TF; }
+}
+// global -> registers for both operands of the K step at k0, every load in flight together; 0 outside M x kend (A) and
+// kend x N (B), kend = K or the end of a split-K slab
+template <int TF, int TK>
+__device__ __forceinline__ void stage_fetch(const float* A, const float* Bm, int tid, int m0, int n0, int k0, int M, int N, int kend,
+                                            long sam, long sak, long sbk, long sbn, bool a_kfast, bool b_nfast,
+                                            float (&ra)[TF * TK / 256], float (&rb)[TF * TK / 256]) {
+#pragma unroll
+  for (int q = 0; q < TF * TK / 256; ++q) {
+    const int e = tid + q * 256;
+    int m, k, n, kk;
+    tile_coord<TF, TK>(e, a_kfast, m, k);
+    const int gm = m0 + m, gk = k0 + k;
+    ra[q] = (gm < M && gk < kend) ? A[gm * sam + gk * sak] : 0.f;
+    tile_coord<TF, TK>(e, !b_nfast, n, kk);
+    const int gn = n0 + n, gk2 = k0 + kk;
+    rb[q] = (gn < N && gk2 < kend) ? Bm[gk2 * sbk + gn * sbn] : 0.f;
+  }
+}
+// registers -> LDS: element e of a tile kept as S[k][f] (KMAJOR) or S[f][k].  One element per call: with the loop over a
+// thread's elements inside a helper the compiler gives sgemm_small_kernel two more VGPRs than it has with the loop written out.
+template <int TF, int TK, bool KMAJOR, int LD>
+__device__ __forceinline__ void tile_put(float (*S)[LD], int e, bool kfast, float v) {
+  int f, k;
+  tile_coord<TF, TK>(e, kfast, f, k);
+  (KMAJOR ? S[k][f] : S[f][k]) = v;
+}
+
+// The 4 x 4 outputs of a thread in a GT x GT tile (sgemm_kernel, sgemm_splitk_kernel): rows ak = As[k], bk = Bs[k] of a
+// staged K step (the loop over k stays in the kernel, as for tile_put) ...
+__device__ __forceinline__ void mac_4x4(const float* ak, const float* bk, int ty, int tx, float (&acc)[4][4]) {
+  float a[4], b[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] = ak[ty * 4 + i];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) b[j] = bk[tx * 4 + j];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+}
+// ... and put(acc[i][j], out[gm * ld + gn], gn) for those of them inside M x N
+template <class Put>
+__device__ __forceinline__ void store_4x4(const float (&acc)[4][4], float* out, long ld, int m0, int n0, int ty, int tx, int M,
+                                          int N, Put put) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int gm = m0 + ty * 4 + i;
+    if (gm >= M) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int gn = n0 + tx * 4 + j;
+      if (gn < N) put(acc[i][j], out[gm * ld + gn], gn);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void sgemm_kernel(const float* __restrict__ A, const float* __restrict__ Bm,
                                                     const float* __restrict__ bias, float* __restrict__ Cm, int M,
                                                     int N, int K, long sam, long sak, long sbk, long sbn, long ldc,
@@ -38,64 +110,25 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const float* __restrict__ A,
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-  // loader mapping: pick the unit-stride direction of each operand as the fast thread index
   const bool a_kfast = (sak == 1), b_nfast = (sbn == 1);
   for (int k0 = 0; k0 < K; k0 += GK) {
-    constexpr int PER = GT * GK / 256;
-    float ra[PER], rb[PER];
+    float ra[GT * GK / 256], rb[GT * GK / 256];
+    stage_fetch<GT, GK>(A, Bm, tid, m0, n0, k0, M, N, K, sam, sak, sbk, sbn, a_kfast, b_nfast, ra, rb);
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {          // phase 1: every load in flight together
-      const int e = tid + q * 256;
-      int m, k;
-      if (a_kfast) { k = e % GK; m = e / GK; } else { m = e % GT; k = e / GT; }
-      const int gm = m0 + m, gk = k0 + k;
-      ra[q] = (gm < M && gk < K) ? A[gm * sam + gk * sak] : 0.f;
-      int n, kk;
-      if (b_nfast) { n = e % GT; kk = e / GT; } else { kk = e % GK; n = e / GK; }
-      const int gn = n0 + n, gk2 = k0 + kk;
-      rb[q] = (gn < N && gk2 < K) ? Bm[gk2 * sbk + gn * sbn] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {          // phase 2: LDS
-      const int e = tid + q * 256;
-      int m, k;
-      if (a_kfast) { k = e % GK; m = e / GK; } else { m = e % GT; k = e / GT; }
-      As[k][m] = ra[q];
-      int n, kk;
-      if (b_nfast) { n = e % GT; kk = e / GT; } else { kk = e % GK; n = e / GK; }
-      Bs[kk][n] = rb[q];
+    for (int q = 0; q < GT * GK / 256; ++q) {
+      tile_put<GT, GK, true>(As, tid + q * 256, a_kfast, ra[q]);
+      tile_put<GT, GK, true>(Bs, tid + q * 256, !b_nfast, rb[q]);
     }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < GK; ++k) {
-      float a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = As[k][ty * 4 + i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = Bs[k][tx * 4 + j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
-    }
+    for (int k = 0; k < GK; ++k) mac_4x4(As[k], Bs[k], ty, tx, acc);
     __syncthreads();
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int gm = m0 + ty * 4 + i;
-    if (gm >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int gn = n0 + tx * 4 + j;
-      if (gn >= N) continue;
-      float v = acc[i][j] + (bias ? bias[gn] : 0.f);
-      if (act == PH_ACT_RELU) v = v > 0.f ? v : 0.f;
-      else if (act == PH_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-      else if (act == PH_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
-      if (accumulate) v += Cm[gm * ldc + gn];
-      Cm[gm * ldc + gn] = v;
-    }
-  }
+  store_4x4(acc, Cm, ldc, m0, n0, ty, tx, M, N, [&](float v, float& c, int gn) {
+    v = act_apply(v + (bias ? bias[gn] : 0.f), act);
+    if (accumulate) v += c;
+    c = v;
+  });
 }
 
 // Small problems (the heads, the SNN, the embeds: at most 128 x 128 outputs, 32 + 12 launches per step on one or two
@@ -110,35 +143,18 @@ __global__ __launch_bounds__(256) void sgemm_small_kernel(const float* __restric
   __shared__ __attribute__((aligned(16))) float Bs[ST][SLD];
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int m0 = blockIdx.y * ST, n0 = blockIdx.x * ST;
-  constexpr int PER = ST * SK / 256;
   const bool a_kfast = (sak == 1), b_nfast = (sbn == 1);
-  float ra[PER], rb[PER];
+  float ra[ST * SK / 256], rb[ST * SK / 256];
   auto load_regs = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int e = tid + q * 256;
-      int m, k;
-      if (a_kfast) { k = e % SK; m = e / SK; } else { m = e % ST; k = e / ST; }
-      const int gm = m0 + m, gk = k0 + k;
-      ra[q] = (gm < M && gk < K) ? A[gm * sam + gk * sak] : 0.f;
-      int n, kk;
-      if (b_nfast) { n = e % ST; kk = e / ST; } else { kk = e % SK; n = e / SK; }
-      const int gn = n0 + n, gk2 = k0 + kk;
-      rb[q] = (gn < N && gk2 < K) ? Bm[gk2 * sbk + gn * sbn] : 0.f;
-    }
+    stage_fetch<ST, SK>(A, Bm, tid, m0, n0, k0, M, N, K, sam, sak, sbk, sbn, a_kfast, b_nfast, ra, rb);
   };
   float acc = 0.f;
   load_regs(0);
   for (int k0 = 0; k0 < K; k0 += SK) {
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int e = tid + q * 256;
-      int m, k;
-      if (a_kfast) { k = e % SK; m = e / SK; } else { m = e % ST; k = e / ST; }
-      As[m][k] = ra[q];
-      int n, kk;
-      if (b_nfast) { n = e % ST; kk = e / ST; } else { kk = e % SK; n = e / SK; }
-      Bs[n][kk] = rb[q];
+    for (int q = 0; q < ST * SK / 256; ++q) {
+      tile_put<ST, SK, false>(As, tid + q * 256, a_kfast, ra[q]);
+      tile_put<ST, SK, false>(Bs, tid + q * 256, !b_nfast, rb[q]);
     }
     __syncthreads();
     if (k0 + SK < K) load_regs(k0 + SK);   // in flight during the FMAs below
@@ -152,10 +168,7 @@ __global__ __launch_bounds__(256) void sgemm_small_kernel(const float* __restric
   }
   const int gm = m0 + ty, gn = n0 + tx;
   if (gm < M && gn < N) {
-    float v = acc + (bias ? bias[gn] : 0.f);
-    if (act == PH_ACT_RELU) v = v > 0.f ? v : 0.f;
-    else if (act == PH_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-    else if (act == PH_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+    float v = act_apply(acc + (bias ? bias[gn] : 0.f), act);
     if (accumulate) v += Cm[gm * ldc + gn];
     Cm[gm * ldc + gn] = v;
   }
@@ -179,61 +192,25 @@ __global__ __launch_bounds__(256) void sgemm_splitk_kernel(const float* __restri
   // (round 6) the loads of K step s + 1 are in flight while step s is multiplied: a workgroup has only ~5 steps (K / nsplit / GK),
   // and as load -> LDS -> multiply one after the other every step exposed a full memory round trip (16-18 us for the fusion
   // head's three 8.5 MB weight matrices on the fused teacher's tail)
-  constexpr int PER = GT * GK / 256;
-  float ra[PER], rb[PER];
+  float ra[GT * GK / 256], rb[GT * GK / 256];
   auto load_step = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {          // every load in flight together
-      const int e = tid + q * 256;
-      int m, k;
-      if (a_kfast) { k = e % GK; m = e / GK; } else { m = e % GT; k = e / GT; }
-      const int gm = m0 + m, gk = k0 + k;
-      ra[q] = (gm < M && gk < ke) ? A[gm * sam + gk * sak] : 0.f;
-      int n, kk;
-      if (b_nfast) { n = e % GT; kk = e / GT; } else { kk = e % GK; n = e / GK; }
-      const int gn = n0 + n, gk2 = k0 + kk;
-      rb[q] = (gn < N && gk2 < ke) ? Bm[gk2 * sbk + gn * sbn] : 0.f;
-    }
+    stage_fetch<GT, GK>(A, Bm, tid, m0, n0, k0, M, N, ke, sam, sak, sbk, sbn, a_kfast, b_nfast, ra, rb);
   };
   if (kb < ke) load_step(kb);
   for (int k0 = kb; k0 < ke; k0 += GK) {
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {          // LDS
-      const int e = tid + q * 256;
-      int m, k;
-      if (a_kfast) { k = e % GK; m = e / GK; } else { m = e % GT; k = e / GT; }
-      As[k][m] = ra[q];
-      int n, kk;
-      if (b_nfast) { n = e % GT; kk = e / GT; } else { kk = e % GK; n = e / GK; }
-      Bs[kk][n] = rb[q];
+    for (int q = 0; q < GT * GK / 256; ++q) {
+      tile_put<GT, GK, true>(As, tid + q * 256, a_kfast, ra[q]);
+      tile_put<GT, GK, true>(Bs, tid + q * 256, !b_nfast, rb[q]);
     }
     __syncthreads();
     if (k0 + GK < ke) load_step(k0 + GK);      // next step's operands travel while this one is multiplied
 #pragma unroll
-    for (int k = 0; k < GK; ++k) {
-      float a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = As[k][ty * 4 + i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = Bs[k][tx * 4 + j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
-    }
+    for (int k = 0; k < GK; ++k) mac_4x4(As[k], Bs[k], ty, tx, acc);
     __syncthreads();
   }
   float* P = part + (size_t)blockIdx.z * M * N;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int gm = m0 + ty * 4 + i;
-    if (gm >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int gn = n0 + tx * 4 + j;
-      if (gn < N) P[(size_t)gm * N + gn] = acc[i][j];
-    }
-  }
+  store_4x4(acc, P, N, m0, n0, ty, tx, M, N, [](float v, float& c, int) { c = v; });
 }
 
 // four lanes per output element (each sums every fourth slab in a fixed order, then a fixed-order combine): with one thread per
@@ -252,11 +229,7 @@ __global__ void splitk_finish_kernel(const float* __restrict__ part, const float
   const float s23 = __shfl_xor(s01, 2, 64);
   if (!live || q != 0) return;
   const int m = i / N, n = i % N;
-  float v = (bias ? bias[n] : 0.f) + (s01 + s23);
-  if (act == PH_ACT_RELU) v = v > 0.f ? v : 0.f;
-  else if (act == PH_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-  else if (act == PH_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
-  Cm[m * ldc + n] = v;
+  Cm[m * ldc + n] = act_apply((bias ? bias[n] : 0.f) + (s01 + s23), act);
 }
 
 // ------------------------------------------------------------------ BatchNorm1d (train mode), thread per channel
@@ -361,13 +334,50 @@ __global__ __launch_bounds__(256) void bn1d_bwd_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------ row ops on [B][C<=64]
+// Softmax statistics of one row y[o .. o + C) (o: the row's offset as the kernels index it, 32-bit): the maximum, then the
+// sum of exp(y - max) - of the row itself, of y / T, and of a student's and a teacher's row of y / T side by side in the
+// same two loops (the form the four kl_* kernels have; two calls of the one-row form make them half as long again).  The
+// three forms are kept apart: dividing by a run-time T = 1 is exact but is other code.  (row_stats_t has no offset: its one
+// caller, logit_losses_kernel, walks row pointers.)
+__device__ __forceinline__ void row_stats(const float* y, int o, int C, float& mx, float& s) {
+  float m = -INFINITY;
+  for (int c = 0; c < C; ++c) m = fmaxf(m, y[o + c]);
+  float t = 0.f;
+  for (int c = 0; c < C; ++c) t += expf(y[o + c] - m);
+  mx = m; s = t;
+}
+__device__ __forceinline__ void row_stats_t(const float* y, int C, float T, float& mx, float& s) {
+  float m = -INFINITY;
+  for (int c = 0; c < C; ++c) m = fmaxf(m, y[c] / T);
+  float t = 0.f;
+  for (int c = 0; c < C; ++c) t += expf(y[c] / T - m);
+  mx = m; s = t;
+}
+__device__ __forceinline__ void row_stats_t2(const float* ys, const float* yt, int o, int C, float T, float& ms, float& ss, float& mt,
+                                             float& st) {
+  float a = -INFINITY, b = -INFINITY;
+  for (int c = 0; c < C; ++c) { a = fmaxf(a, ys[o + c] / T); b = fmaxf(b, yt[o + c] / T); }
+  float u = 0.f, v = 0.f;
+  for (int c = 0; c < C; ++c) { u += expf(ys[o + c] / T - a); v += expf(yt[o + c] / T - b); }
+  ms = a; mt = b; ss = u; st = v;
+}
+// s += p_t (log p_t - log p_s) of one class, ls / lt = max + log(sum) of the two rows; a teacher probability that underflowed
+// to 0 adds nothing (0 * -inf otherwise)
+__device__ __forceinline__ void kl_term_add(float& s, float ys, float yt, float T, float ls, float lt) {
+  const float lpt = yt / T - lt, lps = ys / T - ls;
+  const float pt = expf(lpt);
+  if (pt > 0.f) s += pt * (lpt - lps);
+}
+// k (softmax(ys / T) - softmax(yt / T)) of one class
+__device__ __forceinline__ float kl_grad(float k, float ys, float yt, float T, float ms, float ss, float mt, float st) {
+  return k * (expf(ys / T - ms) / ss - expf(yt / T - mt) / st);
+}
+
 __global__ void log_softmax_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int C) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float mx = -INFINITY;
-  for (int c = 0; c < C; ++c) mx = fmaxf(mx, x[b * C + c]);
-  float s = 0.f;
-  for (int c = 0; c < C; ++c) s += expf(x[b * C + c] - mx);
+  float mx, s;
+  row_stats(x, b * C, C, mx, s);
   const float l = mx + logf(s);
   for (int c = 0; c < C; ++c) y[b * C + c] = x[b * C + c] - l;
 }
@@ -380,24 +390,13 @@ __global__ void log_softmax_bwd_kernel(const float* __restrict__ g, const float*
   for (int c = 0; c < C; ++c) dx[b * C + c] = g[b * C + c] - expf(y[b * C + c]) * s;
 }
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < nw; ++i) t += sh[i];
-  __syncthreads();
-  return t;
-}
-
 // loss = -(1/Bnorm) sum_b pred[b][grade[b]]
 __global__ void nll_fwd_kernel(const float* __restrict__ pred, const int64_t* __restrict__ grade, float* loss, int B,
                                int C, float inv_bnorm) {
   __shared__ float sh[16];
   float s = 0.f;
   for (int b = threadIdx.x; b < B; b += blockDim.x) s -= pred[b * C + (int)grade[b]];
-  s = block_sum(s, sh);
+  s = block_sum_waves(s, sh);
   if (threadIdx.x == 0) *loss = s * inv_bnorm;
 }
 __global__ void nll_bwd_kernel(const float* __restrict__ gs, const int64_t* __restrict__ grade, float* dpred, int B,
@@ -414,18 +413,12 @@ __global__ void kl_fwd_kernel(const float* __restrict__ ys, const float* __restr
   __shared__ float sh[16];
   float s = 0.f;
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    float ms = -INFINITY, mt = -INFINITY;
-    for (int c = 0; c < C; ++c) { ms = fmaxf(ms, ys[b * C + c] / T); mt = fmaxf(mt, yt[b * C + c] / T); }
-    float ss = 0.f, st = 0.f;
-    for (int c = 0; c < C; ++c) { ss += expf(ys[b * C + c] / T - ms); st += expf(yt[b * C + c] / T - mt); }
+    float ms, ss, mt, st;
+    row_stats_t2(ys, yt, b * C, C, T, ms, ss, mt, st);
     const float ls = ms + logf(ss), lt = mt + logf(st);
-    for (int c = 0; c < C; ++c) {
-      const float lpt = yt[b * C + c] / T - lt, lps = ys[b * C + c] / T - ls;
-      const float pt = expf(lpt);
-      if (pt > 0.f) s += pt * (lpt - lps);
-    }
+    for (int c = 0; c < C; ++c) kl_term_add(s, ys[b * C + c], yt[b * C + c], T, ls, lt);
   }
-  s = block_sum(s, sh);
+  s = block_sum_waves(s, sh);
   if (threadIdx.x == 0) *loss = s * T * T * inv_bnorm;
 }
 // d loss / d ys = gs * T/Bnorm * (softmax(ys/T) - softmax(yt/T))
@@ -434,17 +427,14 @@ __global__ void kl_bwd_kernel(const float* __restrict__ gs, const float* __restr
                               float inv_bnorm) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float ms = -INFINITY, mt = -INFINITY;
-  for (int c = 0; c < C; ++c) { ms = fmaxf(ms, ys[b * C + c] / T); mt = fmaxf(mt, yt[b * C + c] / T); }
-  float ss = 0.f, st = 0.f;
-  for (int c = 0; c < C; ++c) { ss += expf(ys[b * C + c] / T - ms); st += expf(yt[b * C + c] / T - mt); }
+  float ms, ss, mt, st;
+  row_stats_t2(ys, yt, b * C, C, T, ms, ss, mt, st);
   const float k = (*gs) * T * inv_bnorm;
-  for (int c = 0; c < C; ++c)
-    dys[b * C + c] = k * (expf(ys[b * C + c] / T - ms) / ss - expf(yt[b * C + c] / T - mt) / st);
+  for (int c = 0; c < C; ++c) dys[b * C + c] = kl_grad(k, ys[b * C + c], yt[b * C + c], T, ms, ss, mt, st);
 }
 
 // The logit-level part of the stage-2 loss block in ONE launch (loss_head.py): log-softmax of the student logits, the
-// two DistillKL terms and the NLL, and d(each loss)/d(logits) for a unit upstream gradient - the same arithmetic, row
+// two DistillKL terms and the NLL, and d(each loss)/d(logits) for a unit upstream gradient - the same functions, row
 // by row and in the same order, as log_softmax / kl_fwd / kl_bwd / nll_fwd / nll_bwd / log_softmax_bwd above (which it
 // replaces inside DistillStep: 8 dependent launches of ~5 us).  losses[0..2] = KL(t1), KL(t2), NLL; dl = [3][B][C].
 __global__ __launch_bounds__(256) void logit_losses_kernel(const float* __restrict__ ys, const float* __restrict__ yt1,
@@ -458,10 +448,8 @@ __global__ __launch_bounds__(256) void logit_losses_kernel(const float* __restri
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
     const float* y = ys + (size_t)b * C;
     // log-softmax of the raw logits (log_softmax_kernel)
-    float mx = -INFINITY;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, y[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(y[c] - mx);
+    float mx, se;
+    row_stats(y, 0, C, mx, se);
     const float l = mx + logf(se);
     const int gb = (int)grade[b];
     for (int c = 0; c < C; ++c) pred[(size_t)b * C + c] = y[c] - l;
@@ -471,34 +459,28 @@ __global__ __launch_bounds__(256) void logit_losses_kernel(const float* __restri
     for (int c = 0; c < C; ++c)
       dl[((size_t)2 * B + b) * C + c] = (c == gb ? -inv_bnorm : 0.f) - expf(y[c] - l) * gsum;
     // temperature softmax of the student (kl_*_kernel)
-    float ms = -INFINITY;
-    for (int c = 0; c < C; ++c) ms = fmaxf(ms, y[c] / T);
-    float ss = 0.f;
-    for (int c = 0; c < C; ++c) ss += expf(y[c] / T - ms);
+    float ms, ss;
+    row_stats_t(y, C, T, ms, ss);
     const float ls = ms + logf(ss);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const float* t = (k ? yt2 : yt1) + (size_t)b * C;
-      float mt = -INFINITY;
-      for (int c = 0; c < C; ++c) mt = fmaxf(mt, t[c] / T);
-      float st = 0.f;
-      for (int c = 0; c < C; ++c) st += expf(t[c] / T - mt);
+      float mt, st;
+      row_stats_t(t, C, T, mt, st);
       const float lt = mt + logf(st);
       float acc = 0.f;
       for (int c = 0; c < C; ++c) {
-        const float lpt = t[c] / T - lt, lps = y[c] / T - ls;
-        const float pt = expf(lpt);
-        if (pt > 0.f) acc += pt * (lpt - lps);
-        dl[((size_t)k * B + b) * C + c] = kk * (expf(y[c] / T - ms) / ss - expf(t[c] / T - mt) / st);
+        kl_term_add(acc, y[c], t[c], T, ls, lt);
+        dl[((size_t)k * B + b) * C + c] = kl_grad(kk, y[c], t[c], T, ms, ss, mt, st);
       }
       if (k) s2 += acc; else s1 += acc;
     }
   }
-  s1 = block_sum(s1, sh);
+  s1 = block_sum_waves(s1, sh);
   __syncthreads();
-  s2 = block_sum(s2, sh);
+  s2 = block_sum_waves(s2, sh);
   __syncthreads();
-  s3 = block_sum(s3, sh);
+  s3 = block_sum_waves(s3, sh);
   if (threadIdx.x == 0) {
     losses[0] = s1 * T * T * inv_bnorm;
     losses[1] = s2 * T * T * inv_bnorm;
@@ -511,17 +493,11 @@ __global__ void kl_rows_fwd_kernel(const float* __restrict__ ys, const float* __
                                    float* __restrict__ sample_loss, int B, int C, float T) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float ms = -INFINITY, mt = -INFINITY;
-  for (int c = 0; c < C; ++c) { ms = fmaxf(ms, ys[b * C + c] / T); mt = fmaxf(mt, yt[b * C + c] / T); }
-  float ss = 0.f, st = 0.f;
-  for (int c = 0; c < C; ++c) { ss += expf(ys[b * C + c] / T - ms); st += expf(yt[b * C + c] / T - mt); }
+  float ms, ss, mt, st;
+  row_stats_t2(ys, yt, b * C, C, T, ms, ss, mt, st);
   const float ls = ms + logf(ss), lt = mt + logf(st);
   float s = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float lpt = yt[b * C + c] / T - lt, lps = ys[b * C + c] / T - ls;
-    const float pt = expf(lpt);
-    if (pt > 0.f) s += pt * (lpt - lps);
-  }
+  for (int c = 0; c < C; ++c) kl_term_add(s, ys[b * C + c], yt[b * C + c], T, ls, lt);
   sample_loss[b] = s * T * T;
 }
 // d sample_loss_b / d ys[b] = T (softmax(ys/T) - softmax(yt/T)); g = upstream gradient per sample
@@ -529,13 +505,10 @@ __global__ void kl_rows_bwd_kernel(const float* __restrict__ g, const float* __r
                                    const float* __restrict__ yt, float* __restrict__ dys, int B, int C, float T) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float ms = -INFINITY, mt = -INFINITY;
-  for (int c = 0; c < C; ++c) { ms = fmaxf(ms, ys[b * C + c] / T); mt = fmaxf(mt, yt[b * C + c] / T); }
-  float ss = 0.f, st = 0.f;
-  for (int c = 0; c < C; ++c) { ss += expf(ys[b * C + c] / T - ms); st += expf(yt[b * C + c] / T - mt); }
+  float ms, ss, mt, st;
+  row_stats_t2(ys, yt, b * C, C, T, ms, ss, mt, st);
   const float k = g[b] * T;
-  for (int c = 0; c < C; ++c)
-    dys[b * C + c] = k * (expf(ys[b * C + c] / T - ms) / ss - expf(yt[b * C + c] / T - mt) / st);
+  for (int c = 0; c < C; ++c) dys[b * C + c] = kl_grad(k, ys[b * C + c], yt[b * C + c], T, ms, ss, mt, st);
 }
 // assign_sample_weights (".../train_test_path_multi_distill.py":131-158) on logits: conf = log p_gt - log max_{c != gt} p_c,
 // discrepancy = min(max(conf_t - conf_s, 0), max_discrep)
@@ -548,11 +521,9 @@ __global__ void conf_discrepancy_kernel(const float* __restrict__ logit_s, const
   float conf[2];
   for (int w = 0; w < 2; ++w) {
     const float* y = (w ? logit_t : logit_s) + b * C;
-    float mx = -INFINITY;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, y[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += expf(y[c] - mx);
-    float top2 = 0.f;                                  // max over c != gt of p_c   (p * (1 - onehot) has 0 at gt)
+    float mx, s;
+    row_stats(y, 0, C, mx, s);
+    float top2 = 0.f;                                 // max over c != gt of p_c   (p * (1 - onehot) has 0 at gt)
     for (int c = 0; c < C; ++c) if (c != g) top2 = fmaxf(top2, expf(y[c] - mx) / s);
     conf[w] = logf(expf(y[g] - mx) / s) - logf(top2);
   }
@@ -645,19 +616,21 @@ __device__ __forceinline__ float u01(uint64_t seed, uint64_t idx) {
   z = z ^ (z >> 31);
   return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
-// nn.Dropout / nn.AlphaDropout in training mode (fusion.py:22-32, networks_new.py:193-211)
+// nn.Dropout / nn.AlphaDropout in training mode (fusion.py:22-32, networks_new.py:193-211) of one element, or (backward)
+// g * d(out)/d(in): plain keep / (1 - p) both ways; alpha a * (keep ? v : alpha') + b forward, a * keep backward
+__device__ __forceinline__ float dropout_value(float v, bool keep, float p, int alpha, bool backward) {
+  if (!alpha) return keep ? v / (1.f - p) : 0.f;
+  const float ap = -1.7580993408473766f;
+  const float a = rsqrtf((1.f - p) * (1.f + p * ap * ap));
+  if (backward) return keep ? a * v : 0.f;
+  const float b = -a * ap * p;
+  return a * (keep ? v : ap) + b;
+}
 __global__ void dropout_kernel(float* __restrict__ x, size_t n, float p, uint64_t seed, uint64_t offset, int alpha) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const bool keep = u01(seed, offset + i) >= p;
-  if (!alpha) {
-    x[i] = keep ? x[i] / (1.f - p) : 0.f;
-  } else {
-    const float ap = -1.7580993408473766f;
-    const float a = rsqrtf((1.f - p) * (1.f + p * ap * ap));
-    const float b = -a * ap * p;
-    x[i] = a * (keep ? x[i] : ap) + b;
-  }
+  x[i] = dropout_value(keep ? x[i] : 0.f, keep, p, alpha, false);      // (a dropped element is not read)
 }
 
 // graph-replayable variant: the per-step part of the RNG counter lives in device memory
@@ -669,15 +642,7 @@ __global__ void dropout_bwd_dev_kernel(const float* src, float* g, size_t n, flo
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t ctr = (*step_ctr << 34) ^ (site_offset + i);
-  const bool keep = u01(seed, ctr) >= p;
-  const float v = src[i];
-  if (!alpha) {
-    g[i] = keep ? v / (1.f - p) : 0.f;
-  } else {
-    const float ap = -1.7580993408473766f;
-    const float a = rsqrtf((1.f - p) * (1.f + p * ap * ap));
-    g[i] = keep ? a * v : 0.f;
-  }
+  g[i] = dropout_value(src[i], u01(seed, ctr) >= p, p, alpha, true);
 }
 
 // backward of y = sigmoid(z) * h  (fusion.py:44-45,51-52)
@@ -715,16 +680,7 @@ __global__ void dropout_dev_kernel(const float* src, float* x, size_t n, float p
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t ctr = (*step_ctr << 34) ^ (site_offset + i);
-  const bool keep = u01(seed, ctr) >= p;
-  const float v = src[i];
-  if (!alpha) {
-    x[i] = keep ? v / (1.f - p) : 0.f;
-  } else {
-    const float ap = -1.7580993408473766f;
-    const float a = rsqrtf((1.f - p) * (1.f + p * ap * ap));
-    const float b = -a * ap * p;
-    x[i] = a * (keep ? v : ap) + b;
-  }
+  x[i] = dropout_value(src[i], u01(seed, ctr) >= p, p, alpha, false);
 }
 __global__ void counter_inc_kernel(uint64_t* c) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *c += 1;
@@ -734,11 +690,9 @@ __global__ void sum_kernel(const float* __restrict__ x, float* out, int n, float
   __shared__ float sh[16];
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += blockDim.x) s += x[i];
-  s = block_sum(s, sh);
+  s = block_sum_waves(s, sh);
   if (threadIdx.x == 0) *out = s * scale;
 }
-
-inline unsigned nblk(size_t n, int t = 256) { return (unsigned)((n + t - 1) / t); }
 
 }  // namespace
 

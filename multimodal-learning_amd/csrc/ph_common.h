@@ -170,3 +170,4 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline unsigned nblk(size_t n, int t = 256) { return (unsigned)((n + t - 1) / t); }   // workgroups of t threads over n elements

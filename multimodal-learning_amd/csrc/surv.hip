@@ -4,6 +4,7 @@
 // CL_utils/KD_losses.py:20-22) and the concordance counts behind the evaluation's C-index (utils.py:424-425).
 #include "ph_common.h"
 #include "ph_kernels.h"
+#include "ph_reduce.h"
 
 namespace {
 
@@ -11,20 +12,6 @@ constexpr int SURV_MAX_B = 4096;        // one workgroup, everything in LDS (as 
 constexpr int SURV_THREADS = 1024;
 constexpr int CIDX_TILE = 256;          // rows per workgroup and j-tile length of the concordance counts
 constexpr int CIDX_MAX_N = 1 << 20;
-
-// fixed-tree block reduction; every thread gets the total.  red: >= blockDim.x floats
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  const int tid = threadIdx.x, n = blockDim.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int o = n >> 1; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const float t = red[0];
-  __syncthreads();
-  return t;
-}
 
 // pred = sigmoid(h) * range[0] + shift[0]; sigma kept for the backward.  range / shift are the module's parameters
 // (device memory: the EMA update and load_state_dict change them like any other parameter).
@@ -110,7 +97,7 @@ __device__ __forceinline__ void surv_stage1_body(const Rows& rows, int B, int nt
   }
   float cox[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) cox[k] = -block_sum(l[k], red) / (float)B;     // (block_sum ends with a barrier: w is complete)
+  for (int k = 0; k < 3; ++k) cox[k] = -block_sum_tree(l[k], red) / (float)B;     // (block_sum_tree ends with a barrier: w is complete)
   // consistency terms; m[a][b] = mse(p_a, q_b) for the pairs the teacher count uses
   float kd[3] = {0.f, 0.f, 0.f};
   if (nt > 0) {
@@ -133,16 +120,16 @@ __device__ __forceinline__ void surv_stage1_body(const Rows& rows, int B, int nt
     for (int a = 0; a < 3; ++a)
 #pragma unroll
       for (int b = 0; b < 3; ++b) m[a][b] = 0.f;
-    m[0][0] = block_sum(part[0][0], red) / (float)B;
-    m[1][1] = block_sum(part[1][1], red) / (float)B;
-    m[2][2] = block_sum(part[2][2], red) / (float)B;
+    m[0][0] = block_sum_tree(part[0][0], red) / (float)B;
+    m[1][1] = block_sum_tree(part[1][1], red) / (float)B;
+    m[2][2] = block_sum_tree(part[2][2], red) / (float)B;
     if (nt >= 2) {
-      m[1][0] = block_sum(part[1][0], red) / (float)B;
-      m[2][0] = block_sum(part[2][0], red) / (float)B;
+      m[1][0] = block_sum_tree(part[1][0], red) / (float)B;
+      m[2][0] = block_sum_tree(part[2][0], red) / (float)B;
     }
     if (nt == 3) {
-      m[1][2] = block_sum(part[1][2], red) / (float)B;
-      m[2][1] = block_sum(part[2][1], red) / (float)B;
+      m[1][2] = block_sum_tree(part[1][2], red) / (float)B;
+      m[2][1] = block_sum_tree(part[2][1], red) / (float)B;
     }
     kd[0] = m[0][0];
     if (nt == 1) {

@@ -6,28 +6,9 @@
 // ph_rkd_one_workgroup_fits' LDS rule): latency-bound.
 #include "ph_common.h"
 #include "ph_kernels.h"
+#include "ph_reduce.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// fixed-tree block reduction; every thread gets the total.  red: >= blockDim.x floats
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  const int tid = threadIdx.x, n = blockDim.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int o = n >> 1; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const float t = red[0];
-  __syncthreads();
-  return t;
-}
 
 // ------------------------------------------------------------------------------------------------ PKT
 // rows: y = x / (||x|| + eps) for the student and the teacher rows
@@ -86,7 +67,7 @@ __global__ __launch_bounds__(1024) void pkt_finish_kernel(const float* __restric
   __shared__ float red[1024];
   float l = 0.f;
   for (int i = threadIdx.x; i < B; i += 1024) l += loss_rows[i];
-  l = block_sum(l, red);
+  l = block_sum_tree(l, red);
   if (threadIdx.x == 0) loss[0] = l / ((float)B * (float)B);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int row = wave; row < B; row += 16) {
@@ -117,7 +98,7 @@ __global__ __launch_bounds__(1024) void rkd_dist_kernel(const float* __restrict_
     st += sqrtf(fmaxf(gt[i * B + i] + gt[j * B + j] - 2.f * gt[e], eps));
   }
   const float N = (float)B * (float)(B - 1);
-  const float md = block_sum(sd, red) / N, mt = block_sum(st, red) / N;
+  const float md = block_sum_tree(sd, red) / N, mt = block_sum_tree(st, red) / N;
   float l = 0.f, ud = 0.f;
   for (int e = tid; e < n; e += 1024) {
     const int i = e / B, j = e % B;
@@ -129,8 +110,8 @@ __global__ __launch_bounds__(1024) void rkd_dist_kernel(const float* __restrict_
     ud += fminf(fmaxf(z, -1.f), 1.f) * d;
   }
   const float inv_n2 = 1.f / (float)n;
-  l = block_sum(l, red) * inv_n2;
-  const float corr = block_sum(ud, red) * inv_n2 / N;       // (1/N) sum_kl u_kl dhat_kl
+  l = block_sum_tree(l, red) * inv_n2;
+  const float corr = block_sum_tree(ud, red) * inv_n2 / N;       // (1/N) sum_kl u_kl dhat_kl
   for (int e = tid; e < n; e += 1024) {
     const int i = e / B, j = e % B;
     float w = 0.f;
@@ -196,7 +177,7 @@ __global__ __launch_bounds__(1024) void rkd_angle_kernel(const float* __restrict
     l += az < 1.f ? 0.5f * z * z : az - 0.5f;
     A[j * LDA + k] = fminf(fmaxf(z, -1.f), 1.f) * inv_n3;
   }
-  l = block_sum(l, red);     // (also orders the writes of U before the reads below)
+  l = block_sum_tree(l, red);     // (also orders the writes of U before the reads below)
   if (tid == 0) part[i] = w_a * l * inv_n3;
   // G_j = 2 sum_k U_jk e_ik ;  dv_ij = (G_j - e_ij (e_ij . G_j)) / ||v_ij||   (zero for j == i: v_ii == 0 identically)
   for (int j = wave; j < B; j += 16) {
@@ -266,7 +247,7 @@ __global__ __launch_bounds__(1024) void cox_kernel(const float* __restrict__ the
     w[i] = c[i] / s;
     l += (theta[i] - logf(s)) * c[i];
   }
-  l = block_sum(l, red);
+  l = block_sum_tree(l, red);
   if (tid == 0) loss[0] = -l / (float)B;
   if (dtheta) {
     // times 1 / B, not over B: the form of surv_stage1_body (csrc/surv.hip), whose gradient rows at lambda_cox = 1 are these bit for bit

@@ -17,6 +17,7 @@
 // two runs give the same bits.
 #include "ph_common.h"
 #include "ph_kernels.h"
+#include "ph_reduce.h"
 
 namespace {
 
@@ -28,26 +29,7 @@ constexpr int RP_LD1 = 33;        // LDS row stride of the 32-column operand til
 constexpr int RP_LD2 = 96;        // ... of the 64-column E_k tile of dE += G E_k
 constexpr int RP_LDG = 66;        // ... of G
 constexpr float RP_EPS = 1e-12f;
-
-__device__ __forceinline__ float rp_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// fixed-tree sum over the 256 threads of a workgroup; every thread gets the total
-__device__ __forceinline__ float rp_block_sum(float v, float* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const float t = red[0];
-  __syncthreads();
-  return t;
-}
+constexpr int RP_THREADS = 256;   // every kernel here that sums over its workgroup is launched with 256 threads: block_sum_tree's extent
 
 __device__ __forceinline__ float rp_huber(float z) {
   const float az = fabsf(z);
@@ -121,7 +103,7 @@ __global__ __launch_bounds__(256) void rkd_part_rowsum_kernel(const float* __res
     a += sqrtf(fmaxf(N2s[(size_t)i * Bg + k], RP_EPS));
     b += sqrtf(fmaxf(N2t[(size_t)i * Bg + k], RP_EPS));
   }
-  a = rp_wave_sum(a); b = rp_wave_sum(b);
+  a = wave_sum(a); b = wave_sum(b);
   if (lane == 0) { rs[i] = a; rt[i] = b; }
 }
 
@@ -137,7 +119,7 @@ __global__ __launch_bounds__(256) void rkd_part_dist_rows_kernel(const float* __
   float a = 0.f, b = 0.f;
   for (int k = tid; k < Bg; k += 256) { a += rs[k]; b += rt[k]; }
   const float N = (float)Bg * (float)(Bg - 1);
-  const float md = rp_block_sum(a, red) / N, mt = rp_block_sum(b, red) / N;
+  const float md = block_sum_tree<RP_THREADS>(a, red) / N, mt = block_sum_tree<RP_THREADS>(b, red) / N;
   float l = 0.f, ud = 0.f;
   for (int j = tid; j < Bg; j += 256) {
     if (j == i) continue;
@@ -147,7 +129,7 @@ __global__ __launch_bounds__(256) void rkd_part_dist_rows_kernel(const float* __
     l += rp_huber(z);
     ud += fminf(fmaxf(z, -1.f), 1.f) * d;
   }
-  l = rp_block_sum(l, red); ud = rp_block_sum(ud, red);
+  l = block_sum_tree<RP_THREADS>(l, red); ud = block_sum_tree<RP_THREADS>(ud, red);
   if (tid == 0) {
     lrow[blockIdx.x] = l; udrow[blockIdx.x] = ud;
     if (blockIdx.x == 0) { sc[0] = md; sc[1] = mt; }
@@ -168,7 +150,7 @@ __global__ __launch_bounds__(256) void rkd_part_dist_grad_kernel(const float* __
   float c = 0.f;
   for (int k = tid; k < na; k += 256) c += udrow[k];
   const float inv_n2 = 1.f / ((float)Bg * (float)Bg), N = (float)Bg * (float)(Bg - 1);
-  const float corr = rp_block_sum(c, red) * inv_n2 / N;
+  const float corr = block_sum_tree<RP_THREADS>(c, red) * inv_n2 / N;
   const float md = sc[0], mt = sc[1];
   const float m_in = (m >= lo && m < lo + na) ? 1.f : 0.f;
   for (int l = tid; l < Bg; l += 256) {
@@ -318,7 +300,7 @@ __global__ __launch_bounds__(256) void rkd_part_angle_kernel(const float* __rest
       }
     }
   }
-  lsum = rp_block_sum(lsum, red);
+  lsum = block_sum_tree<RP_THREADS>(lsum, red);
   if (tid == 0) apart[(size_t)(part_off + blockIdx.y) * gridDim.x + blockIdx.x] = w_a * inv_n3 * lsum;
   // dv_ij = 2 w_a (dE_j - e_ij (e_ij . dE_j)) / |v_ij|: the dot product spans this wave's columns, its 32-lane halves and
   // the wave holding the other column half
@@ -406,7 +388,7 @@ __global__ __launch_bounds__(256) void rkd_part_loss_kernel(const float* __restr
   float l = 0.f, a = 0.f;
   for (int k = threadIdx.x; k < na; k += 256) l += lrow[k];
   for (int k = threadIdx.x; k < n_apart; k += 256) a += apart[k];
-  l = rp_block_sum(l, red); a = rp_block_sum(a, red);
+  l = block_sum_tree<RP_THREADS>(l, red); a = block_sum_tree<RP_THREADS>(a, red);
   if (threadIdx.x == 0) loss[0] = w_d * l / ((float)Bg * (float)Bg) + a;
 }
 

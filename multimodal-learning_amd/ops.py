@@ -107,6 +107,29 @@ def linear_fwd(x, w, b, act=ACT_NONE):
     return sgemm(x, w, b, y, Bn, N, K, K, 1, 1, K, act)
 
 
+def _bias_grad(g):
+    """db[N] = 1^T dY of dY [B, N]"""
+    Bn, N = g.shape
+    db = torch.empty(N, device=g.device, dtype=torch.float32)
+    return sgemm(_ones(Bn, g.device), g, None, db, 1, N, Bn, 0, 1, N, 1)
+
+
+def _linear_grads(needs, g, x, w, has_bias):
+    """(dx, dw, db) of y = x @ w^T + b for dY = g, each None where needs[i] is false (db also without a bias)"""
+    Bn, K = x.shape
+    N = w.shape[0]
+    dx = dw = db = None
+    if needs[0]:
+        dx = torch.empty_like(x)
+        sgemm(g, w, None, dx, Bn, K, N, N, 1, K, 1)              # dX = dY @ W
+    if needs[1]:
+        dw = torch.empty_like(w)
+        sgemm(g, x, None, dw, N, K, Bn, 1, N, K, 1)              # dW = dY^T @ X
+    if has_bias and needs[2]:
+        db = _bias_grad(g)
+    return dx, dw, db
+
+
 class LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):
@@ -117,20 +140,7 @@ class LinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        g = _f32(g)
-        Bn, K = x.shape
-        N = w.shape[0]
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            sgemm(g, w, None, dx, Bn, K, N, N, 1, K, 1)              # dX = dY @ W
-        if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            sgemm(g, x, None, dw, N, K, Bn, 1, N, K, 1)              # dW = dY^T @ X
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = torch.empty(N, device=g.device, dtype=torch.float32)
-            sgemm(_ones(Bn, g.device), g, None, db, 1, N, Bn, 0, 1, N, 1)   # db = 1^T dY
-        return dx, dw, db
+        return _linear_grads(ctx.needs_input_grad, _f32(g), x, w, ctx.has_bias)
 
 
 # ---- a linear map over a row-wise concatenation (x_0 | x_1 | ...), some blocks followed by a column of ones, without forming
@@ -201,8 +211,7 @@ class CatLinearFn(torch.autograd.Function):
             for c in ones:
                 sgemm(g, one, None, dw[:, c:], N, 1, Bn, 1, N, 0, 0, ldc=Kt)       # dW[:, c] = dY^T 1
         if ctx.has_bias and ctx.needs_input_grad[1]:
-            db = torch.empty(N, device=g.device, dtype=torch.float32)
-            sgemm(_ones(Bn, g.device), g, None, db, 1, N, Bn, 0, 1, N, 1)
+            db = _bias_grad(g)
         return (dw, db, None) + tuple(dxs)
 
 
@@ -232,19 +241,7 @@ class LinearActFn(torch.autograd.Function):
             g = eltwise(g, y, EW_ELU_BWD)
         elif ctx.act != ACT_NONE:
             raise NotImplementedError("LinearActFn backward: activation %d" % ctx.act)
-        Bn, K = x.shape
-        N = w.shape[0]
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            sgemm(g, w, None, dx, Bn, K, N, N, 1, K, 1)
-        if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            sgemm(g, x, None, dw, N, K, Bn, 1, N, K, 1)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = torch.empty(N, device=g.device, dtype=torch.float32)
-            sgemm(_ones(Bn, g.device), g, None, db, 1, N, Bn, 0, 1, N, 1)
-        return dx, dw, db, None
+        return _linear_grads(ctx.needs_input_grad, g, x, w, ctx.has_bias) + (None,)
 
 
 class ReluFn(torch.autograd.Function):
@@ -487,6 +484,32 @@ def apply_act(act, hazard, owner):
                               % type(act).__name__)
 
 
+# ---- what the two survival autograd functions share
+def _surv_prepare(pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic, survtime, censor):
+    """-> the eight flattened rows in the order the C entries take them (an absent teacher row is None), out [9] and
+    d [3, n] = d total / d (pred, pred_path, pred_omic) for the entry to fill"""
+    ps = [_f32(p).reshape(-1) for p in (pred, pred_path, pred_omic)]
+    qs = [None if q is None else _f32(q.detach()).reshape(-1) for q in (ema_pred, ema_pred_path, ema_pred_omic)]
+    rows = ps + qs + [_f32(survtime).reshape(-1), _f32(censor).reshape(-1)]
+    out = torch.empty(9, device=ps[0].device, dtype=torch.float32)
+    d = torch.empty(3, ps[0].shape[0], device=ps[0].device, dtype=torch.float32)
+    return rows, out, d
+
+
+def _surv_result(ctx, preds, out, d):
+    """(total, terms[8]) from `out`; d and the predictions' shapes kept for _surv_backward"""
+    ctx.save_for_backward(d)
+    ctx.shapes = tuple(p.shape for p in preds)
+    terms = out[:8]
+    ctx.mark_non_differentiable(terms)
+    return out[8], terms
+
+
+def _surv_backward(ctx, g):
+    d, = ctx.saved_tensors
+    return tuple((d[k] * g).reshape(ctx.shapes[k]) for k in range(3))
+
+
 class SurvStage1LossFn(torch.autograd.Function):
     """The survival block of the stage-1 teacher step in one launch (ph_surv_stage1_loss_grad): the three Cox terms
     (train_test_MT.py:149-152) and the MSE consistency terms (:180-201, KD_losses.py:20-22).  Returns (total, terms[6]) with
@@ -497,26 +520,14 @@ class SurvStage1LossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic, survtime, censor, num_teachers,
                 lambda_cox, kd_weight):
-        ps = [_f32(p).reshape(-1) for p in (pred, pred_path, pred_omic)]
-        qs = [None if q is None else _f32(q.detach()).reshape(-1) for q in (ema_pred, ema_pred_path, ema_pred_omic)]
-        B = ps[0].shape[0]
-        t, c = _f32(survtime).reshape(-1), _f32(censor).reshape(-1)
-        out = torch.empty(9, device=ps[0].device, dtype=torch.float32)
-        d = torch.empty(3, B, device=ps[0].device, dtype=torch.float32)
-        check(lib().ph_surv_stage1_loss_grad(ptr(ps[0]), ptr(ps[1]), ptr(ps[2]), ptr(qs[0]), ptr(qs[1]), ptr(qs[2]), ptr(t),
-                                             ptr(c), B, int(num_teachers), float(lambda_cox), float(kd_weight), ptr(out),
-                                             ptr(d), stream()), "ph_surv_stage1_loss_grad")
-        ctx.save_for_backward(d)
-        ctx.shapes = (pred.shape, pred_path.shape, pred_omic.shape)
-        terms = out[:8]
-        ctx.mark_non_differentiable(terms)
-        return out[8], terms
+        rows, out, d = _surv_prepare(pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic, survtime, censor)
+        check(lib().ph_surv_stage1_loss_grad(*map(ptr, rows), d.shape[1], int(num_teachers), float(lambda_cox), float(kd_weight),
+                                             ptr(out), ptr(d), stream()), "ph_surv_stage1_loss_grad")
+        return _surv_result(ctx, (pred, pred_path, pred_omic), out, d)
 
     @staticmethod
     def backward(ctx, g, g_terms):
-        d, = ctx.saved_tensors
-        return ((d[0] * g).reshape(ctx.shapes[0]), (d[1] * g).reshape(ctx.shapes[1]), (d[2] * g).reshape(ctx.shapes[2]),
-                None, None, None, None, None, None, None, None)
+        return _surv_backward(ctx, g) + (None,) * 8
 
 
 def surv_gather_buffers(n, world, device):
@@ -540,32 +551,20 @@ class SurvStage1GatheredFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic, survtime, censor, num_teachers,
                 lambda_cox, kd_weight, sync, staging, gathered):
-        ps = [_f32(p).reshape(-1) for p in (pred, pred_path, pred_omic)]
-        qs = [None if q is None else _f32(q.detach()).reshape(-1) for q in (ema_pred, ema_pred_path, ema_pred_omic)]
-        n = ps[0].shape[0]
-        t, c = _f32(survtime).reshape(-1), _f32(censor).reshape(-1)
-        W, nt = sync.world_size, int(num_teachers)
+        rows, out, d = _surv_prepare(pred, pred_path, pred_omic, ema_pred, ema_pred_path, ema_pred_omic, survtime, censor)
+        n, W, nt = d.shape[1], sync.world_size, int(num_teachers)
         if tuple(staging.shape) != (8, n) or tuple(gathered.shape) != (W, 8, n):
             raise ValueError("SurvStage1GatheredFn: staging must be [8, %d] and gathered [%d, 8, %d], got %s and %s"
                              % (n, W, n, tuple(staging.shape), tuple(gathered.shape)))
-        check(lib().ph_surv_pack_rows(ptr(ps[0]), ptr(ps[1]), ptr(ps[2]), ptr(qs[0]), ptr(qs[1]), ptr(qs[2]), ptr(t), ptr(c),
-                                      n, nt, ptr(staging), stream()), "ph_surv_pack_rows")
+        check(lib().ph_surv_pack_rows(*map(ptr, rows), n, nt, ptr(staging), stream()), "ph_surv_pack_rows")
         sync.all_gather_into(gathered, staging)
-        out = torch.empty(9, device=ps[0].device, dtype=torch.float32)
-        d = torch.empty(3, n, device=ps[0].device, dtype=torch.float32)
         check(lib().ph_surv_stage1_loss_grad_gathered(ptr(gathered), W, n, sync.rank, nt, float(lambda_cox), float(kd_weight),
                                                       ptr(out), ptr(d), stream()), "ph_surv_stage1_loss_grad_gathered")
-        ctx.save_for_backward(d)
-        ctx.shapes = (pred.shape, pred_path.shape, pred_omic.shape)
-        terms = out[:8]
-        ctx.mark_non_differentiable(terms)
-        return out[8], terms
+        return _surv_result(ctx, (pred, pred_path, pred_omic), out, d)
 
     @staticmethod
     def backward(ctx, g, g_terms):
-        d, = ctx.saved_tensors
-        return ((d[0] * g).reshape(ctx.shapes[0]), (d[1] * g).reshape(ctx.shapes[1]), (d[2] * g).reshape(ctx.shapes[2]),
-                None, None, None, None, None, None, None, None, None, None, None)
+        return _surv_backward(ctx, g) + (None,) * 11
 
 
 def surv_loss_terms(pred, pred_path, pred_omic, survtime, censor):
