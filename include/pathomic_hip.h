@@ -231,6 +231,16 @@ int ph_crd_select(const float* diff, const float* out1, const float* out2, const
                   float* xs, float* xt /* gathered raw scores [B][P2+K2] */, int B, int P, int K, int P2, int K2,
                   int select_neg, int select_pos /* 0: keep every positive column in order (v3 / v10 banks) */,
                   ph_stream_t stream);
+/* DSCD selection of the MIA-2022 tree ("MIA 2022/CL_utils/memory_new.py": ContrastMemory_v4 :471-527, ContrastMemory_mono
+ * :630-670): the P positives ranked by diff - ascending = 1 (v4: t_relation - s_relation descending with mem1 the student bank)
+ * or 0 (mono: mem1 the teacher bank), the lower column first among equal keys, -0 == +0 - P2 of them at `ranks` (NULL: the first
+ * P2 ranks), slot 0 forced to column 0, then ALL K negatives in order: sel / xs / xt are [B][P2 + K].  neg_reweight = 1 (v4
+ * :510-517): xs / xt of negative column P + k are out * (1.0f + diff), one rounded add then one rounded multiply, in both
+ * directions.  LDS holds the positives alone (2 P words).  PH_EINVAL before any launch for a NULL pointer (ranks excepted), B < 1,
+ * P < 1, K < 1, P2 outside 1..P, a flag outside {0, 1} or a positive list above 160 KiB of LDS (P > 20480). */
+int ph_crd_select_dscd(const float* diff, const float* out1, const float* out2, const int* ranks, int* sel /* [B][P2+K] */,
+                       float* xs, float* xt /* [B][P2+K] */, int B, int P, int K, int P2, int ascending, int neg_reweight,
+                       ph_stream_t stream);
 int ph_crd_zsum(const float* xs, const float* xt, float* sums2, int n, ph_stream_t stream);
 int ph_crd_setz(float* params, const float* sums2, float count, float n_data, ph_stream_t stream);
 /* loss partials lossp[B] (sum = s_loss + t_loss) and d loss/d v1, d loss/d v2 [B][feat_dim] */
@@ -240,6 +250,15 @@ int ph_crd_loss_grad(const float* xs, const float* xt, const int* sel, const int
                      const float* posw_s, const float* posw_t, const float* mem1, const float* mem2,
                      const float* params, float* lossp, float* dv1, float* dv2, int B, int PK, int P2, int K2,
                      int feat_dim, float n_data, float inv_bnorm, void* workspace /* may be NULL */, ph_stream_t stream);
+/* The one-directional half of ph_crd_loss_grad, for ContrastMemory_mono / CRDLoss_v2 ("MIA 2022/CL_utils/memory_new.py":565-698,
+ * "MIA 2022/CL_utils/CRD_loss_v2.py":95-101): xt / mem (= memory_v1) / Z_v2 -> lossp [B] and dv = d loss / d v2 [B][feat_dim], bit
+ * for bit the dv2 of ph_crd_loss_grad on the same xt, sel, idx, mem and Z_v2, in the one-workgroup and the split form (same
+ * workspace size).  params = that bank's [P, K, T, Z_v2, momentum]: only params[3] is read, T is the argument.  posw: optional
+ * [B][P2] weights of the positives.  PH_EINVAL for a NULL pointer (posw and workspace excepted), T <= 0 and what ph_crd_loss_grad
+ * refuses. */
+int ph_crd_loss_grad_one(const float* xt, const int* sel, const int64_t* idx, const float* posw, const float* mem,
+                         const float* params, float T, float* lossp, float* dv, int B, int PK, int P2, int K2, int feat_dim,
+                         float n_data, float inv_bnorm, void* workspace /* may be NULL */, ph_stream_t stream);
 size_t ph_crd_loss_grad_workspace_bytes(int B);                        /* the size at feat_dim 128 */
 size_t ph_crd_loss_grad_workspace_bytes_w(int B, int feat_dim);        /* the size at any supported width */
 /* Bank-scan form of the CRD negatives: BASELINE configs[4] read as nce_k = 65536 negatives per query (SURVEY 8-e assumption (i);

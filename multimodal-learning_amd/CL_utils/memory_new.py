@@ -5,7 +5,9 @@ momentum update).  The forward returns (out_v1, out_v2) like the reference when 
 CRDLoss the fused loss+gradient kernel is used instead (nothing [B,P+K,128]-sized is materialised).
 
 Also the home of what every CRD criterion of the package shares: `ContrastBank`, the base of the
-three memory modules; `CrdCall`, what one call consists of; `crd_core`, the fused step over a bank and a call."""
+memory modules; `CrdCall`, what one call consists of; `crd_core`, the fused step over a bank and a call.
+`ContrastMemory_v4` and `ContrastMemory_mono` at the end of the file are the banks of the MIA-2022 tree's DSCD criteria
+("MIA 2022/CL_utils/memory_new.py":398-561 and :565-698; CL_utils/CRD_loss_v2.py)."""
 import math
 
 import numpy as np
@@ -34,13 +36,23 @@ class CrdCall:
     `posw_s` / `posw_t` [B, P] float32: weights of the positives in the student's / the teacher's term (None: 1 / P2 each);
     `scan`: None, or dict(idx [B, >= col0 + K] int64, col0, K) - the bank-scan form, the K negatives are columns
     col0 .. col0 + K of that tensor and `idx` / `idx_bank2` hold the P positives alone; `per_sample`: the [B] losses, not
-    their sum."""
+    their sum.
+    The DSCD criteria of the MIA-2022 tree: `rank_ascending` None = the selection above; True / False =
+    ph_crd_select_dscd - the P positives ranked by the discrepancy ascending (ContrastMemory_v4) or descending
+    (ContrastMemory_mono), every one of the K negatives kept (K2 == K); `neg_reweight`: their scores times 1 + discrepancy;
+    `one_direction`: only out_v2 / Z_v2 / d loss / d v2 exist (ContrastMemory_mono)."""
     __slots__ = ("P", "K", "P2", "K2", "select_pos", "select_neg", "idx", "idx_bank2", "posw_s", "posw_t", "scan", "ranks",
-                 "per_sample")
+                 "per_sample", "rank_ascending", "neg_reweight", "one_direction")
 
     def __init__(self, P, K, P2, K2, idx, select_pos=False, select_neg=False, idx_bank2=None, posw_s=None, posw_t=None,
-                 scan=None, ranks=None, per_sample=False):
+                 scan=None, ranks=None, per_sample=False, rank_ascending=None, neg_reweight=False, one_direction=False):
         self.P, self.K, self.P2, self.K2 = int(P), int(K), int(P2), int(K2)
+        self.rank_ascending = None if rank_ascending is None else bool(rank_ascending)
+        self.neg_reweight, self.one_direction = bool(neg_reweight), bool(one_direction)
+        if self.rank_ascending is None and (self.neg_reweight or self.one_direction):
+            raise ValueError("CrdCall: neg_reweight / one_direction belong to the DSCD selection (rank_ascending True or False)")
+        if self.rank_ascending is not None and (self.K2 != self.K or scan is not None or idx_bank2 is not None):
+            raise ValueError("CrdCall: the DSCD selection keeps every negative (K2 == K) of one gathered index list")
         self.select_pos, self.select_neg = bool(select_pos), bool(select_neg)
         self.idx, self.idx_bank2, self.posw_s, self.posw_t = idx, idx_bank2, posw_s, posw_t
         self.scan, self.ranks, self.per_sample = scan, ranks, bool(per_sample)
@@ -84,7 +96,8 @@ def _set_z_once(mem, sums, count):
     mem._z_set = True
     if mem.verbose:   # the reference prints Z once (memory_new.py:371,375); costs one host sync
         z = mem.params[2:4].tolist()
-        print("normalization constant Z_v1 is set to {:.1f}".format(z[0]))
+        if not mem.one_direction:      # (ContrastMemory_mono has Z_v2 alone, "MIA 2022/CL_utils/memory_new.py":674-677)
+            print("normalization constant Z_v1 is set to {:.1f}".format(z[0]))
         print("normalization constant Z_v2 is set to {:.1f}".format(z[1]))
 
 
@@ -133,8 +146,12 @@ def crd_core(v1, v2, mem, y, call, loss_out=None, outputs_only=False):
     sel = torch.empty(B, S2, device=dev, dtype=torch.int32)
     xs = torch.empty(B, S2, device=dev, dtype=torch.float32)
     xt = torch.empty_like(xs)
-    check(L.ph_crd_select(ptr(diff), ptr(out1), ptr(out2), ptr(call.ranks), ptr(sel), ptr(xs), ptr(xt), B, P, K, P2, K2,
-                          int(call.select_neg), int(call.select_pos), st), "ph_crd_select")
+    if call.rank_ascending is None:
+        check(L.ph_crd_select(ptr(diff), ptr(out1), ptr(out2), ptr(call.ranks), ptr(sel), ptr(xs), ptr(xt), B, P, K, P2, K2,
+                              int(call.select_neg), int(call.select_pos), st), "ph_crd_select")
+    else:
+        check(L.ph_crd_select_dscd(ptr(diff), ptr(out1), ptr(out2), ptr(call.ranks), ptr(sel), ptr(xs), ptr(xt), B, P, K, P2,
+                                   int(call.rank_ascending), int(call.neg_reweight), st), "ph_crd_select_dscd")
     if not mem._z_set:
         sums = torch.empty(2, device=dev, dtype=torch.float32)
         check(L.ph_crd_zsum(ptr(xs), ptr(xt), ptr(sums), B * S2, st), "ph_crd_zsum")
@@ -149,14 +166,19 @@ def crd_core(v1, v2, mem, y, call, loss_out=None, outputs_only=False):
         result = (o1, o2, rows1, rows2)
     else:
         lossp = torch.empty(B, device=dev, dtype=torch.float32)
-        dv1 = torch.empty(B, D, device=dev, dtype=torch.float32)
-        dv2 = torch.empty_like(dv1)
+        dv2 = torch.empty(B, D, device=dev, dtype=torch.float32)
+        dv1 = None if call.one_direction else torch.empty_like(dv2)
         # long column lists (nce_k = 4096 of the MIA trainers) are dealt to several workgroups per sample through a workspace
         lg_ws = (torch.empty(L.ph_crd_loss_grad_workspace_bytes_w(B, D), device=dev, dtype=torch.uint8) if P2 + K2 >= 1024 else None)
-        check(L.ph_crd_loss_grad(ptr(xs), ptr(xt), ptr(sel), ptr(idx), ptr(idx2), ptr(call.posw_s), ptr(call.posw_t),
-                                 ptr(mem.memory_v1), ptr(mem.memory_v2),
-                                 ptr(mem.params), ptr(lossp), ptr(dv1), ptr(dv2), B, PK, P2, K2, D, float(mem.nLem),
-                                 1.0 / _loss_divisor(mem, B), ptr(lg_ws), st), "ph_crd_loss_grad")
+        if call.one_direction:      # ContrastMemory_mono: v2 is the student, memory_v1 the teacher bank, T where that buffer keeps it
+            check(L.ph_crd_loss_grad_one(ptr(xt), ptr(sel), ptr(idx), ptr(call.posw_t), ptr(mem.memory_v1), ptr(mem.params),
+                                         float(mem.T), ptr(lossp), ptr(dv2), B, PK, P2, K2, D, float(mem.nLem),
+                                         1.0 / _loss_divisor(mem, B), ptr(lg_ws), st), "ph_crd_loss_grad_one")
+        else:
+            check(L.ph_crd_loss_grad(ptr(xs), ptr(xt), ptr(sel), ptr(idx), ptr(idx2), ptr(call.posw_s), ptr(call.posw_t),
+                                     ptr(mem.memory_v1), ptr(mem.memory_v2),
+                                     ptr(mem.params), ptr(lossp), ptr(dv1), ptr(dv2), B, PK, P2, K2, D, float(mem.nLem),
+                                     1.0 / _loss_divisor(mem, B), ptr(lg_ws), st), "ph_crd_loss_grad")
         result = (_finish_loss(lossp, call.per_sample, loss_out), dv1, dv2)
     _crd_update(mem, y, v1, v2, D)
     mem.last = dict(sel=sel, xs=xs, xt=xt, diff=diff, call=call)
@@ -236,7 +258,7 @@ class _CRDCoreFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v1, v2, mem, y, call):
         loss, dv1, dv2 = crd_core(v1, v2, mem, y, call)
-        ctx.save_for_backward(dv1, dv2)
+        ctx.save_for_backward(dv1, dv2)      # (dv1 None under call.one_direction)
         ctx.per_sample = call.per_sample
         return loss
 
@@ -245,7 +267,7 @@ class _CRDCoreFn(torch.autograd.Function):
         dv1, dv2 = ctx.saved_tensors
         if ctx.per_sample:
             g = g.reshape(-1, 1)      # d loss_b / d v_b is row b of dv
-        return dv1 * g, dv2 * g, None, None, None
+        return (None if dv1 is None else dv1 * g), dv2 * g, None, None, None      # (no dv1: the one-directional criterion)
 
 
 class _CRDOutputsFn(torch.autograd.Function):
@@ -271,6 +293,30 @@ class _CRDOutputsFn(torch.autograd.Function):
         check(lib().ph_crd_outputs_bwd(ptr(g1), ptr(g2), ptr(o1), ptr(o2), ptr(rows1), ptr(rows2), ctx.T, ptr(dv1), ptr(dv2),
                                        B, S2, D, stream()), "ph_crd_outputs_bwd")
         return dv1, dv2, None, None, None
+
+
+class _CRDOutputsMonoFn(torch.autograd.Function):
+    """(v1, v2) -> out_v2 [B, P2+K, 1] of ContrastMemory_mono.forward ("MIA 2022/CL_utils/memory_new.py":590-698):
+    out_v2 = exp(memory_v1[sel] . v2 / T) / Z_v2; v1 (the teacher's feature) only ranks the positives and updates its bank."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, mem, y, call):
+        _, o2, rows1, _ = crd_core(v1, v2, mem, y, call, outputs_only=True)
+        ctx.save_for_backward(o2, rows1)
+        ctx.T = float(mem.T)
+        return o2.unsqueeze(-1)
+
+    @staticmethod
+    def backward(ctx, g2):
+        o2, rows1 = ctx.saved_tensors
+        B, S2 = o2.shape
+        D = rows1.shape[2]
+        g2 = ops._f32(g2).reshape(B, S2).contiguous()
+        dv1 = torch.empty(B, D, device=o2.device, dtype=torch.float32)      # (zeros: the NULL gradient of direction 1)
+        dv2 = torch.empty_like(dv1)
+        check(lib().ph_crd_outputs_bwd(None, ptr(g2), ptr(o2), ptr(o2), ptr(rows1), ptr(rows1), ctx.T, ptr(dv1), ptr(dv2),
+                                       B, S2, D, stream()), "ph_crd_outputs_bwd")
+        return None, dv2, None, None, None
 
 
 def draw_uniform_indices(mem, y, width):
@@ -307,12 +353,15 @@ class ContrastBank(nn.Module):
     of a bank whose calls all look alike (`plan`); None where the criterion builds every call itself (CRD_criterion_v10)."""
 
     def __init__(self, inputSize, outputSize, K, T, momentum, P=None, P2=None, K2=None, select_pos_pairs=False,
-                 select_neg_pairs="False", params_P=False):
+                 select_neg_pairs="False", params_P=False, params=None):
         super().__init__()
         self.nLem, self.K, self.T = outputSize, K, T
         self.P, self.P2, self.K2 = P, P2, K2
         self.select_pos_pairs, self.select_neg_pairs = select_pos_pairs, select_neg_pairs
-        self.register_buffer("params", torch.tensor([K, T, -1, -1, momentum] + ([P] if params_P else []), dtype=torch.float32))
+        self.one_direction = False     # ContrastMemory_mono: Z_v2 and d loss / d v2 alone
+        # `params`: a bank with a layout of its own (ContrastMemory_mono) - Z_v2 and the momentum stay at indices 3 and 4
+        self.register_buffer("params", torch.tensor(params if params is not None else
+                                                    [K, T, -1, -1, momentum] + ([P] if params_P else []), dtype=torch.float32))
         stdv = 1.0 / math.sqrt(inputSize / 3)
         self.register_buffer("memory_v1", torch.rand(outputSize, inputSize).mul_(2 * stdv).add_(-stdv))
         self.register_buffer("memory_v2", torch.rand(outputSize, inputSize).mul_(2 * stdv).add_(-stdv))
@@ -384,3 +433,118 @@ class ContrastMemory_v3(ContrastBank):
         list of the `mid` / `random` / `curriculum` modes comes from numpy's global RNG exactly as in the reference
         (:311-322) unless `ranks` is given."""
         return _CRDOutputsFn.apply(v1, v2, self, y, self._plan(epoch, v1.device, y, idx, select_pos_mode, ranks))
+
+
+def _draw_ranks(P, P2, epoch, select_pos_mode, mid):
+    """The host-RNG rank draws of the DSCD banks ("MIA 2022/CL_utils/memory_new.py":480-495 and :646-658; numpy's global RNG, like
+    the reference); `mid`: that bank's own draw.  A rank at or above P fails as ContrastMemory_v3.draw_ranks does."""
+    if select_pos_mode == "hard":
+        return None
+    if select_pos_mode == "mid":
+        r = mid()
+    elif select_pos_mode == "random":
+        r = np.random.randint(0, P, P2)
+    elif select_pos_mode == "curriculum":
+        interval = 4 - np.ceil(3 * epoch)
+        r = np.random.randint(50 * (interval - 1), 50 * interval, P2)
+    else:
+        raise NotImplementedError(select_pos_mode)
+    if r.max() >= P or r.min() < 0:
+        raise RuntimeError("select_pos_mode '%s' needs nce_p > %d" % (select_pos_mode, int(r.max())))
+    return torch.as_tensor(np.asarray(r), dtype=torch.int32)
+
+
+class _DscdBank(ContrastBank):
+    """What ContrastMemory_v4 and ContrastMemory_mono share: the reference's constructor arguments and attributes, the plan of a
+    call (the P positives ranked by ph_crd_select_dscd, all K negatives kept: select_neg_pairs and K2 are stored and never read,
+    as there), the rank draws, the `idx is None` draw."""
+    rank_ascending = None      # the subclass's direction of the positive ranking
+
+    def _init_dscd(self, P2, K2, select_neg_pairs, neg_reweight):
+        self.P2, self.K2 = P2, K2
+        self.select_neg_pairs, self.neg_reweight = select_neg_pairs, neg_reweight
+
+    def draw_indices(self, y):
+        return draw_uniform_indices(self, y, self.P + self.K)
+
+    def plan(self, idx, ranks=None, per_sample=False):
+        """The call over the columns `idx` [B, P + K] (what the fused loss head of DistillStep asks a bank for)."""
+        if not torch.is_tensor(idx) or idx.dim() != 2 or idx.shape[1] != self.P + self.K:
+            raise RuntimeError("contrast_idx must be [B, nce_p + nce_k] = [B, %d + %d], got %s"
+                               % (self.P, self.K, tuple(idx.shape) if torch.is_tensor(idx) else type(idx).__name__))
+        return CrdCall(self.P, self.K, self.P2, self.K, idx, ranks=ranks, per_sample=per_sample,
+                       rank_ascending=self.rank_ascending, neg_reweight=self.neg_reweight == "True" and not self.one_direction,
+                       one_direction=self.one_direction)
+
+    def _plan(self, epoch, dev, y, idx, select_pos_mode, ranks, per_sample=False):
+        if idx is None:
+            idx = self.draw_indices(y)
+        if ranks is None:
+            ranks = self.draw_ranks(epoch, select_pos_mode)
+        if ranks is not None:
+            if not torch.is_tensor(ranks):
+                ranks = torch.as_tensor(np.asarray(ranks), dtype=torch.int32)
+            if not ranks.is_cuda:      # (a device tensor is a graph input: checked where it was drawn)
+                if ranks.numel() != self.P2 or int(ranks.max()) >= self.P or int(ranks.min()) < 0:
+                    raise RuntimeError("ranks must be %d values below nce_p = %d" % (self.P2, self.P))
+                ranks = ranks.to(torch.int32).to(dev, non_blocking=True)
+        return self.plan(idx, ranks, per_sample)
+
+    def loss(self, epoch, v1, v2, y, idx, select_pos_mode="hard", ranks=None):
+        """The criterion's loss in one fused pass (what CRD_loss_v2.CRDLoss / CRDLoss_v2 call)."""
+        return _CRDCoreFn.apply(v1, v2, self, y, self._plan(epoch, v1.device, y, idx, select_pos_mode, ranks, self.sample_KD))
+
+
+class ContrastMemory_v4(_DscdBank):
+    """"MIA 2022/CL_utils/memory_new.py":398-561.  params = [K, T, Z_v1, Z_v2, momentum, P]; called as (epoch, student, teacher, y,
+    idx, mode), so memory_v1 is the student bank.  Positives by t_relation - s_relation descending (:473-476) = the discrepancy
+    of ph_crd_score ASCENDING; all K negatives, under neg_reweight == "True" weighted by 1 + discrepancy in both directions
+    (:510-517).  Where the reference fails at its first call (UnboundLocalError: out_v2_pos for select_pos_pairs other than True,
+    out_v2_neg for a neg_reweight outside "True" / "False"), this fails at construction."""
+    rank_ascending = True
+
+    def __init__(self, inputSize, outputSize, P, K, T=0.07, momentum=0.5, select_pos_pairs=True, P2=10,
+                 select_neg_pairs=False, neg_reweight=True, K2=512):
+        if not (select_pos_pairs == True):      # noqa: E712  (the reference's own comparison, :471)
+            raise UnboundLocalError("local variable 'out_v2_pos' referenced before assignment")
+        if neg_reweight not in ("True", "False"):
+            raise UnboundLocalError("local variable 'out_v2_neg' referenced before assignment")
+        super().__init__(inputSize, outputSize, K, T, momentum, P, P2, K, select_pos_pairs, select_neg_pairs, params_P=True)
+        self._init_dscd(P2, K2, select_neg_pairs, neg_reweight)
+
+    def draw_ranks(self, epoch, select_pos_mode):
+        return _draw_ranks(self.P, self.P2, epoch, select_pos_mode,
+                           lambda: np.random.choice(np.arange(30, 100, 1), self.P2, replace=False))      # :484
+
+    def forward(self, epoch, v1, v2, y, idx=None, select_pos_mode="mid", ranks=None):
+        """:422-561 as written: (out_v1, out_v2), each [B, P2+K, 1], differentiable w.r.t. v1 / v2."""
+        return _CRDOutputsFn.apply(v1, v2, self, y, self._plan(epoch, v1.device, y, idx, select_pos_mode, ranks))
+
+
+class ContrastMemory_mono(_DscdBank):
+    """"MIA 2022/CL_utils/memory_new.py":565-698, the one-directional bank.  params = [P, K, T, Z_v2, momentum] (:584: its own
+    order; Z_v2 and the momentum sit where the kernels read them, T is passed).  Called as (epoch, teacher, student, y, idx,
+    mode): memory_v1 is the TEACHER bank, only out_v2 = exp(memory_v1[idx] . v2 / T) exists.  Positives by the discrepancy
+    descending (:632-642), `mid` draws randint(50, 100) (:649); all K negatives, unweighted - neg_reweight is stored and unused.
+    forward returns (out_v2, memory_v1) (:698)."""
+    rank_ascending = False
+
+    def __init__(self, inputSize, outputSize, P, K, T=0.07, momentum=0.5, select_pos_pairs=True, P2=10,
+                 select_neg_pairs=False, neg_reweight=True, K2=512):
+        if not (select_pos_pairs == True):      # noqa: E712  (:630: without it the reference keeps all P + K columns as positives-first)
+            raise NotImplementedError("ContrastMemory_mono without select_pos_pairs (options.py:44-45: always on)")
+        super().__init__(inputSize, outputSize, K, T, momentum, P, P2, K, select_pos_pairs, select_neg_pairs,
+                         params=[P, K, T, -1, momentum])
+        self._init_dscd(P2, K2, select_neg_pairs, neg_reweight)
+        self.one_direction = True
+
+    def _load_from_state_dict(self, *a, **k):
+        super()._load_from_state_dict(*a, **k)
+        self._z_set = bool((self.params[3] > 0).item())
+
+    def draw_ranks(self, epoch, select_pos_mode):
+        return _draw_ranks(self.P, self.P2, epoch, select_pos_mode, lambda: np.random.randint(50, 100, self.P2))      # :649
+
+    def forward(self, epoch, v1, v2, y, idx=None, select_pos_mode="hard", ranks=None):
+        out_v2 = _CRDOutputsMonoFn.apply(v1, v2, self, y, self._plan(epoch, v1.device, y, idx, select_pos_mode, ranks))
+        return out_v2, self.memory_v1

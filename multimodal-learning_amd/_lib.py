@@ -112,6 +112,8 @@ SIGNATURES = {
     "ph_tsvd_update_aux_dev": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "ph_crd_score": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]),
     "ph_crd_select": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "ph_crd_select_dscd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "ph_crd_loss_grad_one": (i32, [vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp]),
     "ph_crd_bank_topk_workspace_bytes": (sz, [i32, i32]),
     "ph_crd_bank_topk_workspace_bytes_np": (sz, [i32, i32, i32]),
     "ph_crd_bank_topk": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),

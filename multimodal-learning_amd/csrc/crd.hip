@@ -6,6 +6,9 @@
 //   crd_select  : per-sample rank-by-counting in LDS (replaces two full torch.sort calls): P2 positives at the
 //                 requested ranks of (student-sim - teacher-sim) descending, slot 0 forced to the exact
 //                 positive; K2 negatives with the smallest discrepancy (ascending order kept)
+//   crd_select_dscd : the selection of the MIA-2022 tree's DSCD criteria ("MIA 2022/CL_utils/memory_new.py":398-698,
+//                 ContrastMemory_v4 / ContrastMemory_mono): positives ranked in either direction from 2 P words of LDS, every
+//                 negative kept and optionally weighted by 1 + discrepancy; crd_loss_grad<D, ONE> is mono's one-directional loss
 //   crd_zsum/crd_setz : first-call normalisation constants Z (memory_new.py:368-375)
 //   crd_loss_grad: NCE loss + analytic d loss / d (v1, v2) as a weighted gather-sum of the *pre-update*
 //                 bank rows (the bank is momentum-updated right after, as in the reference)
@@ -149,6 +152,68 @@ __global__ __launch_bounds__(1024) void crd_select_kernel(const float* __restric
   }
 }
 
+// DSCD selection ("MIA 2022/CL_utils/memory_new.py": ContrastMemory_v4 :471-527, ContrastMemory_mono :630-670; the criteria of
+// "MIA 2022/CL_utils/CRD_loss_v2.py").  One block per sample.  Only the P positives are ranked, so LDS holds 2 P words (keys,
+// rank_to_col) whatever K.  With diff = cos(mem1, v1) - cos(mem2, v2) as crd_score writes it:
+//   v4   sorts t_relation - s_relation = -diff descending (:460-464, :476; mem1 is the STUDENT bank there)  -> ascending = 1
+//   mono sorts t_relation - s_relation = +diff descending (:632-642; mem1 is the TEACHER bank there)        -> ascending = 0
+// The keys go to LDS negated when ascending, so one descending count serves both: the lower column first among equal keys,
+// -0 == +0.  P2 columns at `ranks` (NULL: ranks 0..P2-1, "hard"), slot 0 forced to column 0 (:498 / :661).  Then ALL K
+// negatives in order (select_neg_pairs / nce_k2 are never read): S2 = P2 + K.  neg_reweight (v4, :510-517): the scores of
+// negative column P + k are multiplied in BOTH directions by s_relation - t_relation + 1 = 1 + diff - one rounded add, one
+// rounded multiply, never distributed.
+__global__ __launch_bounds__(1024) void crd_select_dscd_kernel(const float* __restrict__ diff, const float* __restrict__ out1,
+                                                              const float* __restrict__ out2, const int* __restrict__ ranks,
+                                                              int* __restrict__ sel, float* __restrict__ xs,
+                                                              float* __restrict__ xt, int P, int K, int P2, int ascending,
+                                                              int neg_reweight) {
+  extern __shared__ __attribute__((aligned(16))) float sk[];   // [P] keys, then int rank_to_col[P]
+  const int b = blockIdx.x, PK = P + K, S2 = P2 + K;
+  int* r2c = reinterpret_cast<int*>(sk + P);
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    const float d = diff[(size_t)b * PK + i];
+    sk[i] = ascending ? -d : d;
+    r2c[i] = 0;      // (a NaN key ranks nothing: no slot is left unwritten)
+  }
+  __syncthreads();
+  // rank by counting, the list read from LDS four keys at a time; a P above the block is walked with the block's stride
+  const int P4 = P & ~3;
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    const float v = sk[i];
+    int r = 0;
+    for (int q = 0; q < P4; q += 4) {
+      const f32x4 w = *reinterpret_cast<const f32x4*>(sk + q);
+      r += (w[0] > v) || (w[0] == v && q < i);
+      r += (w[1] > v) || (w[1] == v && q + 1 < i);
+      r += (w[2] > v) || (w[2] == v && q + 2 < i);
+      r += (w[3] > v) || (w[3] == v && q + 3 < i);
+    }
+    for (int q = P4; q < P; ++q) { const float w = sk[q]; r += (w > v) || (w == v && q < i); }
+    r2c[r] = i;
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < P2; t += blockDim.x) {
+    int rk = ranks ? ranks[t] : t;
+    rk = (unsigned)rk < (unsigned)P ? rk : P - 1;      // (the host refuses a rank at or above P; never an index past the list)
+    const int col = t == 0 ? 0 : r2c[rk];
+    sel[(size_t)b * S2 + t] = col;
+    xs[(size_t)b * S2 + t] = out1[(size_t)b * PK + col];
+    xt[(size_t)b * S2 + t] = out2[(size_t)b * PK + col];
+  }
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    const size_t c = (size_t)b * PK + P + k, o = (size_t)b * S2 + P2 + k;
+    float a1 = out1[c], a2 = out2[c];
+    if (neg_reweight) {
+      const float w = __fadd_rn(1.0f, diff[c]);
+      a1 = __fmul_rn(a1, w);
+      a2 = __fmul_rn(a2, w);
+    }
+    sel[o] = P + k;
+    xs[o] = a1;
+    xt[o] = a2;
+  }
+}
+
 // sums[0] = sum(xs), sums[1] = sum(xt) over n elements (single block, deterministic)
 __global__ __launch_bounds__(1024) void crd_zsum_kernel(const float* __restrict__ xs, const float* __restrict__ xt,
                                                         float* sums, int n) {
@@ -176,7 +241,11 @@ __global__ void crd_setz_kernel(float* params, const float* sums, float count, f
 //   loss_s = -(1/Bn) [ sum_p log(x/(x+c)) / P2 + sum_n log(mPn/(x+c)) ],  x = xs/Z_v1, c = K2/n_data + eps
 //   d loss_s / d dot_j = -(1/(Bn P2)) (c/(x+c))/T  (positives) ;  +(1/Bn) (x/(x+c))/T  (negatives)
 //   dv1[b] = sum_j coef_s[j] mem2[idx[b][sel_j]] ; dv2[b] = sum_j coef_t[j] mem1[idx[b][sel_j]]
-template <int D>
+// ONE: the one-directional criterion (ContrastMemory_mono / CRDLoss_v2, "MIA 2022/CL_utils/memory_new.py":565-698 and
+// "MIA 2022/CL_utils/CRD_loss_v2.py":95-101): only out_v2 = exp(mem1[idx] . v2 / T) / Z_v2 exists, so only the xt / mem1 / Z_v2 -> dv2
+// half runs - the same column walk, split and reduce order, the same expressions, so dv2 is bit for bit the two-directional
+// one.  That bank keeps params = [P, K, T, Z_v2, momentum]: Z_v2 is where it always was, T arrives as `T_one`.
+template <int D, bool ONE = false>
 __global__ __launch_bounds__(1024) void crd_loss_grad_kernel(const float* __restrict__ xs,
                                                             const float* __restrict__ xt,
                                                             const int* __restrict__ sel,
@@ -189,13 +258,14 @@ __global__ __launch_bounds__(1024) void crd_loss_grad_kernel(const float* __rest
                                                             const float* __restrict__ params,
                                                             float* __restrict__ lossp, float* __restrict__ dv1,
                                                             float* __restrict__ dv2, int PK, int P2, int K2, int m_neg,
-                                                            float n_data, float inv_bnorm, float* __restrict__ part) {
+                                                            float n_data, float inv_bnorm, float* __restrict__ part,
+                                                            float T_one) {
   // gridDim.y > 1 (long column lists, e.g. nce_k = 4096): the columns of a sample are dealt to gridDim.y workgroups whose
   // partial sums go to `part` and are added in a fixed order by crd_loss_grad_reduce_kernel
   constexpr int G = D / 4;
   const int b = blockIdx.x, S2 = P2 + K2;
   const int hw = threadIdx.x / G, l = threadIdx.x % G;
-  const float invT = 1.f / params[1], Z1 = params[2], Z2 = params[3];
+  const float invT = 1.f / (ONE ? T_one : params[1]), Z1 = ONE ? 1.f : params[2], Z2 = params[3];
   const float mPn = (float)m_neg / n_data, c = mPn + 1e-7f;      // m = the number of negatives of the loss (= K2 unless they are scanned)
   f32x4 g1 = {0.f, 0.f, 0.f, 0.f}, g2 = {0.f, 0.f, 0.f, 0.f};
   float ls = 0.f;
@@ -204,26 +274,44 @@ __global__ __launch_bounds__(1024) void crd_loss_grad_kernel(const float* __rest
   // 16 row groups, and sh[NHW][2][D] is 32 KiB whichever
   constexpr int NHW = 1024 / G;
   for (int j = blockIdx.y * NHW + hw; j < S2; j += NHW * gridDim.y) {
-    const float x1 = xs[(size_t)b * S2 + j] / Z1, x2 = xt[(size_t)b * S2 + j] / Z2;
-    float c1, c2;
-    if (j < P2) {
-      // weight of positive j: 1/P2 (MICCAI / v3) or similarity_j / sum_p similarity_p (MIA-2023 ContrastLoss_v2)
-      const float w1 = posw_s ? posw_s[(size_t)b * P2 + j] : 1.f / (float)P2;
-      const float w2 = posw_t ? posw_t[(size_t)b * P2 + j] : 1.f / (float)P2;
-      ls += logf(x1 / (x1 + c)) * w1 + logf(x2 / (x2 + c)) * w2;
-      c1 = -(c / (x1 + c)) * invT * inv_bnorm * w1;
-      c2 = -(c / (x2 + c)) * invT * inv_bnorm * w2;
-    } else {
-      ls += logf(mPn / (x1 + c)) + logf(mPn / (x2 + c));
-      c1 = (x1 / (x1 + c)) * invT * inv_bnorm;
-      c2 = (x2 / (x2 + c)) * invT * inv_bnorm;
-    }
-    const int col = sel[(size_t)b * S2 + j];
-    const int64_t row = idx[(size_t)b * PK + col], row2 = idx_b2[(size_t)b * PK + col];
-    const f32x4 m2 = *reinterpret_cast<const f32x4*>(mem2 + row2 * D + l * 4);
-    const f32x4 m1 = *reinterpret_cast<const f32x4*>(mem1 + row * D + l * 4);
+    if constexpr (!ONE) {
+      const float x1 = xs[(size_t)b * S2 + j] / Z1, x2 = xt[(size_t)b * S2 + j] / Z2;
+      float c1, c2;
+      if (j < P2) {
+        // weight of positive j: 1/P2 (MICCAI / v3) or similarity_j / sum_p similarity_p (MIA-2023 ContrastLoss_v2)
+        const float w1 = posw_s ? posw_s[(size_t)b * P2 + j] : 1.f / (float)P2;
+        const float w2 = posw_t ? posw_t[(size_t)b * P2 + j] : 1.f / (float)P2;
+        ls += logf(x1 / (x1 + c)) * w1 + logf(x2 / (x2 + c)) * w2;
+        c1 = -(c / (x1 + c)) * invT * inv_bnorm * w1;
+        c2 = -(c / (x2 + c)) * invT * inv_bnorm * w2;
+      } else {
+        ls += logf(mPn / (x1 + c)) + logf(mPn / (x2 + c));
+        c1 = (x1 / (x1 + c)) * invT * inv_bnorm;
+        c2 = (x2 / (x2 + c)) * invT * inv_bnorm;
+      }
+      const int col = sel[(size_t)b * S2 + j];
+      const int64_t row = idx[(size_t)b * PK + col], row2 = idx_b2[(size_t)b * PK + col];
+      const f32x4 m2 = *reinterpret_cast<const f32x4*>(mem2 + row2 * D + l * 4);
+      const f32x4 m1 = *reinterpret_cast<const f32x4*>(mem1 + row * D + l * 4);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { g1[k] += c1 * m2[k]; g2[k] += c2 * m1[k]; }
+      for (int k = 0; k < 4; ++k) { g1[k] += c1 * m2[k]; g2[k] += c2 * m1[k]; }
+    } else {      // the x2 / c2 / g2 expressions of the branch above, alone
+      const float x2 = xt[(size_t)b * S2 + j] / Z2;
+      float c2;
+      if (j < P2) {
+        const float w2 = posw_t ? posw_t[(size_t)b * P2 + j] : 1.f / (float)P2;
+        ls += logf(x2 / (x2 + c)) * w2;
+        c2 = -(c / (x2 + c)) * invT * inv_bnorm * w2;
+      } else {
+        ls += logf(mPn / (x2 + c));
+        c2 = (x2 / (x2 + c)) * invT * inv_bnorm;
+      }
+      const int col = sel[(size_t)b * S2 + j];
+      const int64_t row = idx[(size_t)b * PK + col];
+      const f32x4 m1 = *reinterpret_cast<const f32x4*>(mem1 + row * D + l * 4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g2[k] += c2 * m1[k];
+    }
   }
   __shared__ float sh[NHW][2][D];
   __shared__ float shl[NHW];
@@ -231,7 +319,7 @@ __global__ __launch_bounds__(1024) void crd_loss_grad_kernel(const float* __rest
   for (int k = 0; k < 4; ++k) { sh[hw][0][l * 4 + k] = g1[k]; sh[hw][1][l * 4 + k] = g2[k]; }
   if (l == 0) shl[hw] = ls;
   __syncthreads();
-  if (threadIdx.x < 2 * D) {
+  if (threadIdx.x < 2 * D && !(ONE && threadIdx.x < D)) {
     const int which = threadIdx.x / D, d = threadIdx.x % D;
     float t = 0.f;
 #pragma unroll
@@ -247,14 +335,16 @@ __global__ __launch_bounds__(1024) void crd_loss_grad_kernel(const float* __rest
   }
 }
 
-template <int D>      // block 2 D
+template <int D, bool ONE = false>      // block 2 D
 __global__ __launch_bounds__(2 * D) void crd_loss_grad_reduce_kernel(const float* __restrict__ part, float* __restrict__ lossp,
                                                                      float* __restrict__ dv1, float* __restrict__ dv2, int NS,
                                                                      float inv_bnorm) {
   const int b = blockIdx.x, which = threadIdx.x / D, d = threadIdx.x % D;
-  float t = 0.f;
-  for (int y = 0; y < NS; ++y) t += part[(((size_t)b * NS + y) * 2 + which) * D + d];
-  (which ? dv2 : dv1)[(size_t)b * D + d] = t;
+  if (!(ONE && which == 0)) {      // (ONE: the dv1 half of `part` was never written)
+    float t = 0.f;
+    for (int y = 0; y < NS; ++y) t += part[(((size_t)b * NS + y) * 2 + which) * D + d];
+    (which ? dv2 : dv1)[(size_t)b * D + d] = t;
+  }
   if (threadIdx.x == 0) {
     float l = 0.f;
     for (int y = 0; y < NS; ++y) l += part[(size_t)gridDim.x * NS * 2 * D + (size_t)b * NS + y];
@@ -1113,6 +1203,28 @@ int ph_crd_select(const float* diff, const float* out1, const float* out2, const
   return PH_OK;
 }
 
+int ph_crd_select_dscd(const float* diff, const float* out1, const float* out2, const int* ranks, int* sel, float* xs,
+                       float* xt, int B, int P, int K, int P2, int ascending, int neg_reweight, hipStream_t st) {
+  if (!diff || !out1 || !out2 || !sel || !xs || !xt) return PH_EINVAL;
+  if (B < 1 || P < 1 || K < 1 || P2 < 1 || P2 > P) return PH_EINVAL;
+  if ((ascending != 0 && ascending != 1) || (neg_reweight != 0 && neg_reweight != 1)) return PH_EINVAL;
+  const size_t lds = (size_t)P * 2 * sizeof(float);      // keys + rank_to_col: the positives alone
+  if (lds > 160 * 1024) return PH_EINVAL;
+  if (lds > 64 * 1024) {      // above the default dynamic-LDS limit of a launch: opt in once, up to the LDS of a CU
+    static std::once_flag attr_once;
+    static hipError_t attr_rc = hipSuccess;
+    std::call_once(attr_once, [] {
+      attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(crd_select_dscd_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
+    if (attr_rc != hipSuccess) return PH_ELAUNCH;
+  }
+  hipLaunchKernelGGL(crd_select_dscd_kernel, dim3(B), dim3(1024), lds, st, diff, out1, out2, ranks, sel, xs, xt, P, K, P2,
+                     ascending, neg_reweight);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
 int ph_crd_zsum(const float* xs, const float* xt, float* sums, int n, hipStream_t st) {
   if (n < 1) return PH_EINVAL;
   hipLaunchKernelGGL(crd_zsum_kernel, dim3(1), dim3(1024), 0, st, xs, xt, sums, n);
@@ -1133,7 +1245,8 @@ size_t ph_crd_loss_grad_workspace_bytes(int B) { return ph_crd_loss_grad_workspa
 static int crd_loss_grad_impl(const float* xs, const float* xt, const int* sel, const int64_t* idx, const int64_t* idx_bank2,
                               const float* posw_s, const float* posw_t, const float* mem1, const float* mem2,
                               const float* params, float* lossp, float* dv1, float* dv2, int B, int PK, int P2, int K2, int m_neg,
-                              int feat_dim, float n_data, float inv_bnorm, void* workspace, hipStream_t st);
+                              int feat_dim, float n_data, float inv_bnorm, void* workspace, hipStream_t st, bool one = false,
+                              float T_one = 0.f);
 int ph_crd_loss_grad(const float* xs, const float* xt, const int* sel, const int64_t* idx, const int64_t* idx_bank2,
                      const float* posw_s, const float* posw_t, const float* mem1, const float* mem2,
                      const float* params, float* lossp, float* dv1, float* dv2, int B, int PK, int P2, int K2,
@@ -1153,7 +1266,8 @@ int ph_crd_loss_grad_pos(const float* xs, const float* xt, const int* sel, const
 static int crd_loss_grad_impl(const float* xs, const float* xt, const int* sel, const int64_t* idx, const int64_t* idx_bank2,
                               const float* posw_s, const float* posw_t, const float* mem1, const float* mem2,
                               const float* params, float* lossp, float* dv1, float* dv2, int B, int PK, int P2, int K2, int m_neg,
-                              int feat_dim, float n_data, float inv_bnorm, void* workspace, hipStream_t st) {
+                              int feat_dim, float n_data, float inv_bnorm, void* workspace, hipStream_t st, bool one,
+                              float T_one) {
   if (!crd_width_ok(feat_dim) || B < 1 || P2 < 1 || K2 < 0 || P2 + K2 > PK) return PH_EINVAL;
   const int D = feat_dim;
   int ns = workspace ? (P2 + K2) / 512 : 1;     // one workgroup per 512 columns of a sample, at most LG_SPLIT_MAX
@@ -1161,17 +1275,33 @@ static int crd_loss_grad_impl(const float* xs, const float* xt, const int* sel, 
   void* tok = nullptr;
   if (ph_prof_on())   // algorithmic bytes: the selected rows of both banks + the two gradient rows per sample
     ph_prof_begin(PH_CLS_CRD_LOSSGRAD, 2.0 * B * (P2 + K2) * D * 4 + 2.0 * B * D * 4 + 2.0 * B * (P2 + K2) * 4, st, &tok);
-  PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(crd_loss_grad_kernel<DW>, dim3(B, ns), dim3(1024), 0, st, xs, xt, sel, idx,
-                                               idx_bank2 ? idx_bank2 : idx, posw_s, posw_t, mem1, mem2, params, lossp, dv1, dv2,
-                                               PK, P2, K2, m_neg, n_data, inv_bnorm, reinterpret_cast<float*>(workspace)));
-  PH_LAUNCH_CHECK();
-  if (ns > 1) {
-    PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL(crd_loss_grad_reduce_kernel<DW>, dim3(B), dim3(2 * DW), 0, st,
-                                                 reinterpret_cast<const float*>(workspace), lossp, dv1, dv2, ns, inv_bnorm));
-    PH_LAUNCH_CHECK();
-  }
+  // (ONE: the two-directional kernels, or their one-directional instantiation)
+#define PH_CRD_LG(ONE)                                                                                                          \
+  do {                                                                                                                          \
+    PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL((crd_loss_grad_kernel<DW, ONE>), dim3(B, ns), dim3(1024), 0, st, xs, xt, sel,  \
+                                                 idx, idx_bank2 ? idx_bank2 : idx, posw_s, posw_t, mem1, mem2, params, lossp,    \
+                                                 dv1, dv2, PK, P2, K2, m_neg, n_data, inv_bnorm,                                 \
+                                                 reinterpret_cast<float*>(workspace), T_one));                                  \
+    PH_LAUNCH_CHECK();                                                                                                          \
+    if (ns > 1) {                                                                                                               \
+      PH_CRD_DISPATCH(feat_dim, hipLaunchKernelGGL((crd_loss_grad_reduce_kernel<DW, ONE>), dim3(B), dim3(2 * DW), 0, st,        \
+                                                   reinterpret_cast<const float*>(workspace), lossp, dv1, dv2, ns, inv_bnorm)); \
+      PH_LAUNCH_CHECK();                                                                                                        \
+    }                                                                                                                           \
+  } while (0)
+  if (one) PH_CRD_LG(true);
+  else PH_CRD_LG(false);
+#undef PH_CRD_LG
   ph_prof_end(tok, st);
   return PH_OK;
+}
+// the xt / mem1 / Z_v2 -> dv half alone (ContrastMemory_mono): params[3] = Z_v2 in that bank's layout too, T is an argument
+int ph_crd_loss_grad_one(const float* xt, const int* sel, const int64_t* idx, const float* posw, const float* mem, const float* params,
+                         float T, float* lossp, float* dv, int B, int PK, int P2, int K2, int feat_dim, float n_data,
+                         float inv_bnorm, void* workspace, hipStream_t st) {
+  if (!xt || !sel || !idx || !mem || !params || !lossp || !dv || !(T > 0.f)) return PH_EINVAL;
+  return crd_loss_grad_impl(nullptr, xt, sel, idx, nullptr, nullptr, posw, mem, nullptr, params, lossp, nullptr, dv, B, PK, P2, K2, K2,
+                            feat_dim, n_data, inv_bnorm, workspace, st, true, T);
 }
 // ---- bank-scan form of the negatives (kernels above).  idx + col0: the K sampled negatives of query b are idx[b * row_stride + col0 ..]
 int ph_crd_neg_hist(const int64_t* idx, long row_stride, int col0, int K, int B, int n_data, int* mult, hipStream_t st) {

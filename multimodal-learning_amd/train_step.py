@@ -413,7 +413,8 @@ def _validate_opt(opt, who, surv_ok=False):
 #               "crd1" (one call, through criterion_kd whichever teacher is chosen), "zoo" (a distiller_zoo criterion on the
 #               fused teacher's feature) or "none"
 #   weighting   "gk" (the variant's GK-Refine) or "sum" (fixed weights alpha / beta)
-#   rank_draws  host RNG rank draws per step (memory_new.py:311): one per CRD call of the MICCAI-2022 bank, else 0
+#   rank_draws  host RNG rank draws per step (memory_new.py:311): one per CRD call of the MICCAI-2022 bank and of the DSCD banks
+#               of the MIA-2022 tree (opt.crd_criterion "dscd" / "dscd_mono"), else 0
 #   unused      names of the CRD criteria whose embedding heads sit in the optimiser without ever receiving a gradient
 #   crd_heads   whether the CRD embedding heads are in the optimiser's parameter list at all
 #   report      what the returned loss terms are: "scaled" (alpha * div, beta * kd), "unscaled_rows" (div, kd as computed, plus
@@ -422,6 +423,22 @@ def _validate_opt(opt, who, surv_ok=False):
 LossPlan = collections.namedtuple("LossPlan", "kl feat weighting rank_draws unused crd_heads report kd_global")
 
 ZOO_DISTILL = ("kd", "feats_KL", "rkd", "pkt", "similarity")      # `--distill` baselines of the MIA-2022 trainer (kd: no criterion)
+
+# opt.crd_criterion of variant "mia2022": the three import lines of "MIA 2022/train_test_path_multi_distill_v2.py":24-26 -
+# CRD_criterion_v3.CRDLoss (the one left uncommented there, the default), CRD_loss_v2.CRDLoss (DSCD over ContrastMemory_v4) and
+# CRD_loss_v2.CRDLoss_v2 (its one-directional form; the trainer's set-up keeps it in comments at :333-337)
+CRD_CRITERIA = ("v3", "dscd", "dscd_mono")
+
+
+def crd_criterion_of(opt, variant):
+    """The resolved opt.crd_criterion (absent: "v3"); anything else, or a DSCD criterion outside variant "mia2022", is a
+    ValueError."""
+    crit = getattr(opt, "crd_criterion", "v3")
+    if crit not in CRD_CRITERIA:
+        raise ValueError("crd_criterion %r: one of %s" % (crit, list(CRD_CRITERIA)))
+    if crit != "v3" and variant != "mia2022":
+        raise ValueError("crd_criterion %r belongs to variant 'mia2022' (the MIA-2022 tree's CRD_loss_v2.py)" % crit)
+    return crit
 
 
 def distill_loss_plan(opt, variant, sync=None):
@@ -476,7 +493,9 @@ def distill_loss_plan(opt, variant, sync=None):
     calls = {"crd2": 2, "crd1": 1, "none": 0}[feat]
     # only the MIA-2023 body with both CRD calls reports its terms unscaled, with the per-sample values
     report = "unscaled_rows" if variant == "mia2023" and feat == "crd2" else "scaled"
-    return LossPlan(kl, feat, "gk" if gk else "sum", calls if variant == "miccai2022" else 0, unused, True, report, False)
+    # host-drawn ranks: the MICCAI-2022 bank and the DSCD banks of the MIA-2022 tree (they enter a captured graph as inputs)
+    ranked = variant == "miccai2022" or crd_criterion_of(opt, variant) != "v3"
+    return LossPlan(kl, feat, "gk" if gk else "sum", calls if ranked else 0, unused, True, report, False)
 
 
 # ----------------------------------------------------------------------------------------- the hot loop
@@ -500,24 +519,31 @@ class DistillStep:
                  train_class_idx=None):
         """variant "miccai2022": MICCAI-2022/train_test_path_multi_distill.py:242-330 (DC-Distill CRD + GK-Refine);
         variant "mia2022": "MIA 2022/train_test_path_multi_distill_v2.py":388-500 (vanilla K+1 CRD bank of
-        CRD_criterion_v3 with the epoch weight, momentum GK-Refine carried over the iterations, row a17);
+        CRD_criterion_v3 with the epoch weight, momentum GK-Refine carried over the iterations, row a17; opt.crd_criterion
+        "dscd" / "dscd_mono": that tree's CRD_loss_v2 criteria over a [B, nce_p + nce_k] index tensor, DESIGN.md section 28);
         variant "mia2023": "MIA 2023/stage2_unimodal_student/train_test_path_multi_distill.py":307-448 (per-sample KL
         rows, confidence-discrepancy query weights, the class-aware KNN bank of CRD_criterion_v10 - needs
         `train_class_idx`, the per-class lists of bank rows - and the per-sample GK-Refine, row a18)."""
         from .networks_new import define_net, define_optimizer, define_scheduler
         from .kd_loss import DistillKL
+        if variant not in ("miccai2022", "mia2022", "mia2023"):
+            raise ValueError("variant must be 'miccai2022', 'mia2022' or 'mia2023'")
+        self.crd_criterion = crd_criterion_of(opt, variant)
         if variant == "mia2022":
-            from .CL_utils.CRD_criterion_v3 import CRDLoss
+            if self.crd_criterion == "v3":
+                from .CL_utils.CRD_criterion_v3 import CRDLoss
+            elif self.crd_criterion == "dscd":
+                from .CL_utils.CRD_loss_v2 import CRDLoss
+            else:
+                from .CL_utils.CRD_loss_v2 import CRDLoss_v2 as CRDLoss
         elif variant == "miccai2022":
             from .CL_utils import CRDLoss
-        elif variant == "mia2023":
+        else:
             from .CL_utils.CRD_criterion_v10 import CRDLoss as _CRDv10
             from .mia2023 import DistillKL
             if train_class_idx is None:
                 raise ValueError("variant 'mia2023' needs train_class_idx (CRD_criterion_v10.py:25)")
             CRDLoss = lambda o, n: _CRDv10(o, n, train_class_idx)    # noqa: E731
-        else:
-            raise ValueError("variant must be 'miccai2022', 'mia2022' or 'mia2023'")
         self.variant = variant
         _validate_opt(opt, "DistillStep")
         if variant == "mia2023" and getattr(opt, "path_dim", 128) not in (64, 128, 256):
@@ -547,8 +573,11 @@ class DistillStep:
         self.criterion_div = DistillKL(opt.kd_T)                                   # :197
         self.criterion_kd = CRDLoss(opt, n_data).to(self.device)                   # :202
         self.criterion_kd_path = CRDLoss(opt, n_data).to(self.device)              # :206
-        self.module_list = nn.ModuleList([self.model, self.criterion_kd.embed_s, self.criterion_kd.embed_t,
-                                          self.criterion_kd_path.embed_s, self.criterion_kd_path.embed_t])
+        if self.crd_criterion == "dscd_mono":      # CRDLoss_v2 has no embed_t (v2 trainer :336-337)
+            self.module_list = nn.ModuleList([self.model, self.criterion_kd.embed_s, self.criterion_kd_path.embed_s])
+        else:
+            self.module_list = nn.ModuleList([self.model, self.criterion_kd.embed_s, self.criterion_kd.embed_t,
+                                              self.criterion_kd_path.embed_s, self.criterion_kd_path.embed_t])
         # the option combination decides the loss path ONCE (or raises where the reference's body, or this package, cannot run it)
         self.plan = plan = distill_loss_plan(opt, variant, sync)
         self.zoo_kd = None        # the feature-level baseline criterion of the MIA-2022 trainer's other `--distill` choices
@@ -565,7 +594,8 @@ class DistillStep:
         # the reference, where their .grad stays None and the update skips them
         unused = [getattr(self, c) for c in plan.unused]
         if unused and hasattr(self.optimizer, "set_inactive"):
-            self.optimizer.set_inactive([p for c in unused for m_ in (c.embed_s, c.embed_t) for p in m_.parameters()])
+            self.optimizer.set_inactive([p for c in unused for m_ in (c.embed_s, getattr(c, "embed_t", None)) if m_ is not None
+                                         for p in m_.parameters()])
         self.iter_num = opt.global_step
         self._want_graph = False
         self._static = None       # the input set of the last graph step
@@ -757,6 +787,9 @@ class DistillStep:
             """One CRD call -> (loss, per-sample rows or None)."""
             if v == "miccai2022":
                 return criterion(e, path_feat, t_feat.detach(), index, sample_idx, ranks=ranks), None       # :278-279
+            if v == "mia2022" and self.crd_criterion != "v3":
+                # CRD_loss_v2: (epoch fraction, f_s, f_t, idx, contrast_idx) -> 0-d, no epoch weight on the term
+                return criterion(self._epoch_frac, path_feat, t_feat.detach(), index, sample_idx, ranks=ranks), None
             if v == "mia2022":
                 # v2 trainer :436-437: the first argument is the epoch weight of the per-sample CRD loss; result shape [1]
                 return criterion(e, path_feat, t_feat.detach(), index, sample_idx).reshape(()), None
@@ -852,6 +885,10 @@ class DistillStep:
             return False
         if self.variant == "mia2023" and getattr(opt, "pos_extra", "neighbors") != "neighbors":
             return False
+        if self.crd_criterion == "dscd_mono":
+            # one direction, no embed_t: the closed form's CRD chain and head-gradient tail are written for two heads per
+            # criterion - the one-directional criterion stays on the generic path
+            return False
         return (getattr(opt, "fused_loss_head", True) and plan.feat == "crd2" and plan.weighting == "gk"
                 and bool(opt.CE_grads)
                 and isinstance(getattr(self.model, "fc_new2", None), nn.Linear)
@@ -916,12 +953,19 @@ class DistillStep:
         self.criterion_kd.contrast.batch_norm_size = bnorm
         self.criterion_kd_path.contrast.batch_norm_size = bnorm
         e, rk = self._draw_ranks(epoch, ranks)
+        self._epoch_frac = e
+        if self.crd_criterion != "v3" and sample_idx.shape[1] != opt.nce_p + opt.nce_k:
+            raise RuntimeError("crd_criterion %r: sample_idx must be [B, nce_p + nce_k] = [B, %d + %d], got width %d (the v3 "
+                               "criterion's width is nce_k + 1 = %d)" % (self.crd_criterion, opt.nce_p, opt.nce_k,
+                                                                          sample_idx.shape[1], opt.nce_k + 1))
         if self.variant != "miccai2022":
             # the epoch weight multiplies the CRD loss on the device (mia2022) / switches the re-weighting on (mia2023, :373):
             # one persistent scalar so a captured graph reads the current value instead of baking the capture-time epoch in
             if self._e_dev is None:
                 self._e_dev = torch.zeros(1, device=dev, dtype=torch.float32)
-            self._e_dev.fill_(float(e) if self.variant == "mia2022" else 0.0 if epoch < opt.start_reweight else 1.0)
+            # (the DSCD criteria carry no epoch weight: the scalar ph_gk_finish_momentum multiplies in is 1)
+            self._e_dev.fill_((float(e) if self.crd_criterion == "v3" else 1.0) if self.variant == "mia2022"
+                              else 0.0 if epoch < opt.start_reweight else 1.0)
             e = self._e_dev
         self.optimizer.ema_alpha = min(1 - 1 / (self.iter_num + 1), opt.ema_decay)                          # :36
         use_graph = self._want_graph and self.iter_num - opt.global_step >= 2
@@ -1003,6 +1047,7 @@ class DistillStep:
                     crd_kd_state_dict=self.criterion_kd.state_dict(),
                     crd_kd_path_state_dict=self.criterion_kd_path.state_dict(),
                     scheduler_state_dict=self.scheduler.state_dict(), iter_num=self.iter_num,
+                    crd_criterion=self.crd_criterion,
                     teacher_rng_steps=rng,
                     gk_momentum_scale=None if self._mo_state is None else self._mo_state.clone(),
                     # draw counters of the on-device input pipeline and the host RNG behind the CRD rank draws
@@ -1047,6 +1092,9 @@ class DistillStep:
             np.random.set_state(st)
 
     def load_state_dict(self, sd):
+        if sd.get("crd_criterion", "v3") != self.crd_criterion:      # (a checkpoint from before the option: "v3")
+            raise ValueError("the checkpoint was written under crd_criterion %r, this step runs %r"
+                             % (sd.get("crd_criterion", "v3"), self.crd_criterion))
         self.model.load_state_dict(sd["model_state_dict"])
         self.ema_model.load_state_dict(sd["ema_model_state_dict"])
         self.fix_model.load_state_dict(sd["teacher_state_dict"])
