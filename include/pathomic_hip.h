@@ -727,6 +727,58 @@ int ph_roc_points(const float* pred, const int64_t* grade, int N, int C, int cls
                   int32_t* npoints, void* workspace, ph_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The survival side of the patient-level test pass: risk strata, the event table per stratum, the
+ * log-rank sums between strata and the Kaplan-Meier estimate per stratum (core/utils_analysis.py:259-263, :398-418, :719-780;
+ * numpy and lifelines on the host there).  No sort: ranks and slots are exact counts from all-pairs passes over LDS tiles
+ * of 256; each entry is a fixed number of memsets and launches whatever N is, and reads nothing back.
+ *
+ * ph_surv_strata: hazard f32 [N] (device); q double [K] (HOST, percent).  cuts double [K] (device):
+ * cuts[i] = np.percentile(hazard.astype(float64), q[i]), method "linear", restated exactly:  h = (N - 1) (q / 100) in double,
+ * lo = floor(h), hi = min(lo + 1, N - 1), t = h - lo, a and b the values of stable rank lo and hi (#{smaller} + #{equal and
+ * earlier}, counted over the whole vector);  t == 0 or a == b: a;  t < 0.5: a + (b - a) t;  else b - (b - a) (1 - t) - numpy's
+ * _lerp with both of its forms, products and sums unfused, never rounded to float32.  (One divergence: with t == 0 or a == b
+ * numpy still evaluates a + (b - a) t and returns NaN when a or b is infinite; this entry returns a.  Finite order statistics
+ * give numpy's bits.)  Then the reference's patch (:412, :722):
+ * K == 2 and cuts[0] == cuts[1] sets cuts[0] = 2.99997.  group int32 [N]: the FIRST i with (double)hazard[n] < cuts[i], else K
+ * (the first-i rule of hazard2grade, not a count of cuts: the patch can leave the cuts non-ascending).  sizes int32 [K + 1]: the rows per group.
+ * bad int32 [1]: the non-finite hazards.  A NaN hazard makes every cut NaN (numpy's rule) and every row falls in group K;
+ * +-inf are ordinary values and the expression gives what IEEE gives.  2 <= N <= 1048576, 1 <= K <= 7, every q finite in
+ * [0, 100]; workspace: ph_surv_strata_workspace_bytes = 64.  Three memsets and two launches.
+ *
+ * ph_surv_table: lifelines' event table per group over every distinct observed time (event or censored), ascending.
+ * survtime, event f32 [N] (an event is event > 0), group int32 [N], G groups.  For slot k with time times[k]:
+ * at_risk[k][g] = #{j in g: t_j >= times[k]}, observed[k][g] = #{j in g: t_j == times[k], event}, censored[k][g] the same for
+ * the rows with no event (int32 [N][G] each, times f32 [N]); k = 0 .. npoints[0] - 1, entries from npoints[0] on are left
+ * unwritten.  npoints int32 [2]: [0] the number of slots, [1] the rows that take part in nothing (group outside [0, G) or a
+ * NaN time).  A row represents its time when no EARLIER row has an equal one; its slot is the number of representatives with
+ * a smaller time.  Integers and copied floats only: bit for bit independent of scheduling and of the row order.  Times compare
+ * as float32.  2 <= N <= 1048576, 1 <= G <= 8; workspace: ph_surv_table_workspace_bytes = 4 N.  A memset and two launches.
+ *
+ * ph_surv_logrank_km: from the table (at_risk, observed, npoints on the device; N = the capacity of the arrays).
+ * pairs int32 [P][2] (HOST): for pair (a, b) the log-rank test over the members of a and b only - per slot, with
+ * n = n_a + n_b and d = d_a + d_b, where d > 0:  O - E += d_a - (d n_a) / n,  and for n > 1
+ * V += n_a (n - n_a) d (n - d) / (n n (n - 1))  (float64, evaluated left to right as written);  stat double [P][2] = (O - E, V),
+ * chi2 = (O - E)^2 / V with one degree of freedom.  The sums have a fixed shape (a tree over each tile of 256 slots, then tile
+ * t, t + 256, .. per thread and the same tree): two runs agree bitwise.  surv double [N][G]:
+ * surv[k][g] = prod over j <= k with at_risk[j][g] > 0 of (1 - observed[j][g] / at_risk[j][g]), the Kaplan-Meier estimate at
+ * every slot (the product of the tiles before, then the slots of the tile in order); entries from npoints[0] on are left
+ * unwritten.  Limits of ph_surv_table, 0 <= P <= 28 (pairs and stat may be NULL when P == 0), every pair index in [0, G) and
+ * a != b; workspace: ph_surv_logrank_km_workspace_bytes = 8 ceil(N / 256) (2 P + 2 G).  Three launches.
+ *
+ * All three return PH_EINVAL for a NULL pointer or a value outside the stated ranges before any HIP call, and each
+ * workspace query returns 0 for a refused shape.
+ * ---------------------------------------------------------------------------------------------- */
+size_t ph_surv_strata_workspace_bytes(int N, int K);
+int ph_surv_strata(const float* hazard, int N, const double* q, int K, double* cuts, int32_t* group, int32_t* sizes, int32_t* bad,
+                   void* workspace, ph_stream_t stream);
+size_t ph_surv_table_workspace_bytes(int N, int G);
+int ph_surv_table(const float* survtime, const float* event, const int32_t* group, int N, int G, float* times, int32_t* at_risk,
+                  int32_t* observed, int32_t* censored, int32_t* npoints, void* workspace, ph_stream_t stream);
+size_t ph_surv_logrank_km_workspace_bytes(int N, int G, int P);
+int ph_surv_logrank_km(const int32_t* at_risk, const int32_t* observed, const int32_t* npoints, int N, int G, const int32_t* pairs,
+                       int P, double* stat, double* surv, void* workspace, ph_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * In-library kernel timer for bench.py's `roofline` object: HIP events around every MFMA kernel launch on the
  * launch stream.  Classes: 0 first-generation tap-conv Cout=64 (dgrad parity classes), 1 first-generation tap-conv
  * Cout>=128 stride 1 (1x1, dgrad parity classes), 2 tap-conv stride 2, 3 wgrad, 4 stem forward, 5 stem wgrad,

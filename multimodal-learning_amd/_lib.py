@@ -84,6 +84,12 @@ SIGNATURES = {
     "ph_rank_counts_classes": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
     "ph_roc_points_workspace_bytes": (sz, [i32, i32]),
     "ph_roc_points": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "ph_surv_strata_workspace_bytes": (sz, [i32, i32]),
+    "ph_surv_strata": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "ph_surv_table_workspace_bytes": (sz, [i32, i32]),
+    "ph_surv_table": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "ph_surv_logrank_km_workspace_bytes": (sz, [i32, i32, i32]),
+    "ph_surv_logrank_km": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     "ph_pkt_workspace_bytes": (sz, [i32, i32]),
     "ph_pkt_loss_grad": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
     "ph_rkd_workspace_bytes": (sz, [i32, i32]),

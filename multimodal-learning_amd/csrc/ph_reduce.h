@@ -19,9 +19,9 @@ __device__ __forceinline__ float block_sum_waves(float v, float* sh) {
 
 // Fixed LDS tree: thread t adds element t + o for o = n / 2, n / 4, .. 1 over n = blockDim.x threads (a power of two), or
 // over the compile-time N of a kernel whose workgroup size is fixed.  red: n floats.  Ends with a barrier: red may be
-// reused at once.
-template <int N = 0>
-__device__ __forceinline__ float block_sum_tree(float v, float* red) {
+// reused at once.  T: float, or double for the float64 sums of survstrata.hip (red: n values of T).
+template <int N = 0, typename T = float>
+__device__ __forceinline__ T block_sum_tree(T v, T* red) {
   const int tid = threadIdx.x, n = N ? N : (int)blockDim.x;
   red[tid] = v;
   __syncthreads();
@@ -29,7 +29,7 @@ __device__ __forceinline__ float block_sum_tree(float v, float* red) {
     if (tid < o) red[tid] += red[tid + o];
     __syncthreads();
   }
-  const float t = red[0];
+  const T t = red[0];
   __syncthreads();
   return t;
 }

@@ -13,7 +13,10 @@ numbers taken from count kernels on the device (`grading_metrics_device`) instea
 `test_teacher_patches` is the same protocol for the stage-1 teacher under both tasks (per-patient hazards, C-indices, log-rank
 p-value under survival), and `sync=` on either pass shards whole batches over data-parallel replicas behind one all-gather
 (DESIGN.md section 24).  `grading_metrics_device(avg=)` and `roc_curve_device` are the reference's `avg` argument and the
-curves of its `makeAUROCPlot` on the device; `avg=` / `curves=` carry them through both patch passes."""
+curves of its `makeAUROCPlot` on the device; `avg=` / `curves=` carry them through both patch passes.
+`survival_strata_device` is the survival side of the same analysis (risk strata at the percentile cuts, log-rank p-values
+between adjacent strata, Kaplan-Meier tables; `km_step_function` for a curve's layout), and `strata=` carries it through
+`test_teacher_patches`."""
 import numbers
 
 import numpy as np
@@ -205,6 +208,114 @@ def roc_auc_from_curve(fpr, tpr):
     if fpr.shape[0] < 2 or fpr.shape != tpr.shape:
         raise ValueError("at least two points, as many fpr as tpr")
     return float((np.diff(fpr) * (tpr[1:] + tpr[:-1]) / 2.0).sum())
+
+
+def check_percentile(percentile):
+    """The tuple of 1 to 7 ascending percents in [0, 100] that `survival_strata_device` accepts; ValueError otherwise."""
+    ok = isinstance(percentile, (tuple, list)) and 1 <= len(percentile) <= ops.SURV_MAX_K
+    ok = ok and all(isinstance(v, numbers.Real) and not isinstance(v, bool) and 0.0 <= float(v) <= 100.0 for v in percentile)
+    ok = ok and all(float(a) <= float(b) for a, b in zip(percentile[:-1], percentile[1:]))
+    if not ok:
+        raise ValueError("percentile must be 1 to %d ascending percents in [0, 100], got %r" % (ops.SURV_MAX_K, percentile))
+    return tuple(float(v) for v in percentile)
+
+
+def logrank_pvalue(o_minus_e, var):
+    """p = erfc(sqrt(chi2 / 2)) of the one-degree-of-freedom log-rank statistic chi2 = (O - E)^2 / V; NaN where V <= 0 (an empty
+    stratum, no event, one risk time) - the rule of utils.cox_log_rank."""
+    import math
+    if not var > 0.0:
+        return float("nan")
+    return math.erfc(math.sqrt(o_minus_e * o_minus_e / var / 2.0))
+
+
+def _strata_layout(N, K, Gn, P):
+    """The one buffer of `survival_strata_device`: (name, numpy dtype, entries) in storage order, the float64 fields first
+    so that every field is aligned.  It drives the device views and the host views alike."""
+    return (("cuts", np.float64, K), ("stat", np.float64, 2 * P), ("survival", np.float64, N * Gn),
+            ("npoints", np.int32, 2), ("bad", np.int32, 1), ("sizes", np.int32, K + 1), ("group", np.int32, N),
+            ("times", np.float32, N), ("at_risk", np.int32, N * Gn), ("observed", np.int32, N * Gn),
+            ("censored", np.int32, N * Gn))
+
+
+_TORCH_OF = {np.float64: torch.float64, np.float32: torch.float32, np.int32: torch.int32}
+
+
+def survival_strata_device(hazard, survtime, censor, percentile=(33, 66), group=None, G=None):
+    """The survival analysis of core/utils_analysis.py on the device: the risk strata of the hazards at
+    the percentile cuts (the first-i rule on np.percentile(hazard, percentile), with the reference's 2.99997 patch), lifelines'
+    event table per stratum, the log-rank p-values between adjacent strata (getPValAggSurv_GBMLGG_Binary / _Multi) and the
+    Kaplan-Meier estimate per stratum (makeKaplanMeierPlot).  hazard, survtime, censor: device tensors [N] (an event is
+    censor > 0).  `group=` (an int device tensor [N]) with `G=` (its number of groups, 1 .. 8) replaces the percentile stage:
+    the per-grade curves of makeKaplanMeierPlot; rows whose group lies outside [0, G) take part in nothing.
+
+    Returns a dict of host arrays: cuts float64 [K] (empty with group=), group int32 [N], sizes int64 [K + 1] (or [G]),
+    pvalues float64 [groups - 1] (the adjacent pairs (0, 1), (1, 2), .. in that order; NaN where V <= 0), stat float64
+    [groups - 1, 2] = (O - E, V), times float32 [npoints], at_risk / observed / censored int32 [npoints, groups], survival
+    float64 [npoints, groups], bad (non-finite hazards + rows left out of the table).
+
+    Device work whatever N is: seven kernel launches and four memsets of the three C entries (2 + 2 + 3 launches, 3 + 1 + 0
+    memsets) and no torch kernel; with group= five launches and one memset of the entries plus ONE torch copy (the groups,
+    converted to int32, into the buffer).  ONE device-to-host copy, of the whole buffer at its capacity of N slots."""
+    hazard = ops._f32(hazard).reshape(-1) if hazard is not None else None
+    survtime, censor = ops._f32(survtime).reshape(-1), ops._f32(censor).reshape(-1)
+    N = survtime.shape[0]
+    if group is None:
+        q = check_percentile(percentile)
+        K, Gn = len(q), len(q) + 1
+        if hazard is None or hazard.shape[0] != N or censor.shape[0] != N:
+            raise ValueError("hazard, survtime and censor are [N] device tensors")
+    else:
+        if G is None or not 1 <= int(G) <= ops.SURV_MAX_G or group.numel() != N or censor.shape[0] != N:
+            raise ValueError("group= needs one group per row and G= in 1 .. %d" % ops.SURV_MAX_G)
+        K, Gn = 0, int(G)
+    if not 2 <= N <= ops.SURV_MAX_N:
+        raise ValueError("the survival strata need 2 <= N <= %d rows, got %d" % (ops.SURV_MAX_N, N))
+    P = Gn - 1
+    layout = _strata_layout(N, K, Gn, P)
+    buf = torch.empty(sum(np.dtype(dt).itemsize * n for _, dt, n in layout), device=survtime.device, dtype=torch.uint8)
+
+    def views(raw, view):
+        out, at = {}, 0
+        for name, dt, n in layout:
+            nbytes = np.dtype(dt).itemsize * n
+            out[name] = view(raw[at:at + nbytes], dt)
+            at += nbytes
+        return out
+    d = views(buf, lambda b, dt: b.view(_TORCH_OF[dt]))
+    if group is None:
+        ops.surv_strata(hazard, q, d["cuts"], d["group"], d["sizes"], d["bad"])
+    else:
+        d["group"].copy_(ops.require_cuda(group, "group").reshape(-1))
+    ops.surv_table(survtime, censor, d["group"], Gn, d["times"], d["at_risk"], d["observed"], d["censored"], d["npoints"])
+    ops.surv_logrank_km(d["at_risk"], d["observed"], d["npoints"], Gn, [(g, g + 1) for g in range(P)], d["stat"], d["survival"])
+    h = views(buf.cpu().numpy(), lambda b, dt: b.view(dt))
+    npts, left_out = int(h["npoints"][0]), int(h["npoints"][1])
+    out = {name: h[name][:npts * Gn].reshape(npts, Gn).copy() for name in ("at_risk", "observed", "censored", "survival")}
+    stat = h["stat"].reshape(P, 2).copy()
+    grp = h["group"].copy()
+    if group is None:                                   # (with group= the entry that fills sizes and bad did not run)
+        sizes, bad = h["sizes"].astype(np.int64), int(h["bad"][0])
+    else:
+        sizes, bad = np.bincount(grp[(grp >= 0) & (grp < Gn)], minlength=Gn).astype(np.int64), 0
+    out.update(cuts=h["cuts"].copy(), group=grp, sizes=sizes, stat=stat, times=h["times"][:npts].copy(), bad=bad + left_out,
+               pvalues=np.array([logrank_pvalue(float(v[0]), float(v[1])) for v in stat], dtype=np.float64))
+    return out
+
+
+def km_step_function(times, survival_column, at_risk_column):
+    """One group's Kaplan-Meier curve as lifelines' `survival_function_` lays it out, from a column of the `survival` and
+    `at_risk` arrays of `survival_strata_device`: (timeline, S) float64, the timeline starting at 0 with S = 1, the slots
+    at which the group is no longer at risk dropped.  (A first time of 0 is the timeline's first entry, not a second one.)"""
+    times = np.asarray(times, dtype=np.float64).reshape(-1)
+    s = np.asarray(survival_column, dtype=np.float64).reshape(-1)
+    keep = np.asarray(at_risk_column).reshape(-1) > 0
+    if not (times.shape == s.shape == keep.shape):
+        raise ValueError("times, survival_column and at_risk_column have one entry per slot")
+    t, s = times[keep], s[keep]
+    if t.shape[0] and t[0] == 0.0:
+        return t, s
+    return np.r_[0.0, t], np.r_[1.0, s]
 
 
 def agg_spec(agg):
@@ -540,7 +651,8 @@ def test_patches(opt, fix_model, model, loader, device, agg="max", sync=None, av
 CINDEX_MAX_N = 1 << 20                   # ph_cindex_counts: 2 <= N <= 1048576
 
 
-def test_teacher_patches(opt, model, loader, device, agg=None, sync=None, avg="micro", curves=False):
+def test_teacher_patches(opt, model, loader, device, agg=None, sync=None, avg="micro", curves=False, strata=None,
+                         grade_classes=None):
     """`test_patches` for the stage-1 teacher (a three-branch PathomicNet, both tasks): the reference's `test()` over
     `test_loader_patches` (train_test_MT.py:287-289, :340-458), then the per-patient aggregation
     (core/utils_analysis.py:425-480) - DESIGN.md section 24.  Returns (patch_result, patient_result).
@@ -561,11 +673,23 @@ def test_teacher_patches(opt, model, loader, device, agg=None, sync=None, avg="m
 
     `sync`: as `test_patches` - rank 0's buffers everywhere, whole batches dealt over the replicas, one all-gather.
     `avg`, `curves`: as `test_patches`, for the grading task (roc_fuse / roc_path / roc_omic); the survival task has no
-    grading metrics and ignores both."""
+    grading metrics and ignores both.
+
+    `strata` (survival task only; ValueError under grading): a percentile tuple of `survival_strata_device`, e.g. (33, 66) or
+    (50,).  Adds strata_fuse / _path / _omic - the dict of `survival_strata_device` on each aggregated hazard vector (cuts,
+    strata, adjacent log-rank p-values, event table, Kaplan-Meier estimates) - and km_grade, the same table and curves with
+    group = loader.patient_grade and G = `grade_classes`, the number of grade classes (1 .. 8; None: the largest patient grade
+    of this loader + 1, which is narrower than the reference's table when the split has no patient of the top grade): the
+    "ground truth" curves of makeKaplanMeierPlot.  None returns the dict of before.  With `sync`, every replica
+    computes them on the gathered, aggregated hazards: no further collective."""
     from . import utils as U
     if opt.task not in ("grad", "surv"):
         raise NotImplementedError("task %r" % opt.task)
     surv = opt.task == "surv"
+    if strata is not None:
+        if not surv:
+            raise ValueError("strata= belongs to the survival task; the grading task has no hazards to stratify")
+        strata = check_percentile(strata)
     if agg is None:
         agg = "mean" if surv else "max"
     agg_spec(agg)
@@ -577,6 +701,13 @@ def test_teacher_patches(opt, model, loader, device, agg=None, sync=None, avg="m
         if not 2 <= G <= CINDEX_MAX_N:
             raise ValueError("the patient-level C-index needs 2 <= patients <= %d (the range of ph_cindex_counts), got %d"
                              % (CINDEX_MAX_N, G))
+        if strata is not None:                          # (at least two patients from here on)
+            top = int(loader.patient_grade_host.max())
+            n_grades = top + 1 if grade_classes is None else int(grade_classes)
+            if int(loader.patient_grade_host.min()) < 0 or not 1 <= n_grades <= ops.SURV_MAX_G or top >= n_grades:
+                raise ValueError("km_grade needs patient grades in [0, grade_classes) with 1 <= grade_classes <= %d, got "
+                                 "grades %d .. %d and grade_classes=%r"
+                                 % (ops.SURV_MAX_G, int(loader.patient_grade_host.min()), top, grade_classes))
     outs, losses = _run(opt, (model,), loader, device, sync,
                         lambda loss_reg, dev: _teacher_batch(opt, model, loss_reg, dev, surv, False))
     d_grade = loader.grade[loader.row_roi]
@@ -599,6 +730,12 @@ def test_teacher_patches(opt, model, loader, device, agg=None, sync=None, avg="m
         patient_result.update(survtime=p_time, censor=p_censor, pvalue=U.cox_log_rank(h64, p_censor, p_time),
                               surv_acc=U.accuracy_cox(h64, p_censor))
         print("Patient level (%s): C-index" % (agg,), *(patient_result["cindex_" + n] for n in names))
+        if strata is not None:
+            for j, name in enumerate(names):
+                patient_result["strata_" + name] = survival_strata_device(hz[j], loader.patient_survtime, loader.patient_censor,
+                                                                          strata)
+            patient_result["km_grade"] = survival_strata_device(None, loader.patient_survtime, loader.patient_censor,
+                                                                group=loader.patient_grade, G=n_grades)
     else:
         d = [outs[j].float().contiguous() for j in range(3)]
         patch_result, _ = _teacher_result(loader, d, outs[3:6], d_grade, None, losses, _device_metric(avg))

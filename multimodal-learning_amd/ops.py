@@ -660,6 +660,79 @@ def roc_points(pred, grade, cls):
     return out
 
 
+SURV_MAX_N, SURV_MAX_K, SURV_MAX_G, SURV_MAX_P = 1 << 20, 7, 8, 28      # the limits of csrc/survstrata.hip
+
+
+def _i32_out(t, n, what):
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+        raise ValueError("%s: a contiguous int32 tensor of %d entries" % (what, n))
+    return require_cuda(t, what)
+
+
+def surv_strata(hazard, q, cuts, group, sizes, bad):
+    """Risk strata of hazard f32 [N] at the percentiles q (a host sequence of K percents): ph_surv_strata fills the caller's
+    device tensors cuts float64 [K] (numpy's linear percentile of the float64 hazards, with the reference's 2.99997 patch),
+    group int32 [N] (the first i with hazard < cuts[i], else K), sizes int32 [K + 1] and bad int32 [1] (non-finite hazards).
+    Nothing is read back."""
+    import numpy as np
+    hazard = _f32(hazard).reshape(-1)
+    qh = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+    N, K = hazard.shape[0], qh.shape[0]
+    nbytes = lib().ph_surv_strata_workspace_bytes(N, K)
+    if nbytes == 0 or not bool(np.all((qh >= 0.0) & (qh <= 100.0))):
+        raise ValueError("surv_strata: 2 <= N <= 1048576 and 1 to 7 percentiles in [0, 100] (got N = %d, q = %r)" % (N, qh.tolist()))
+    if cuts.dtype != torch.float64 or cuts.numel() != K or not cuts.is_contiguous():
+        raise ValueError("surv_strata: cuts is a contiguous float64 tensor of %d entries" % K)
+    _i32_out(group, N, "group"); _i32_out(sizes, K + 1, "sizes"); _i32_out(bad, 1, "bad")
+    ws = torch.empty(nbytes, device=hazard.device, dtype=torch.uint8)
+    check(lib().ph_surv_strata(ptr(hazard), N, qh.ctypes.data, K, ptr(require_cuda(cuts, "cuts")), ptr(group), ptr(sizes), ptr(bad),
+                               ptr(ws), stream()), "ph_surv_strata")
+
+
+def surv_table(survtime, event, group, G, times, at_risk, observed, censored, npoints):
+    """lifelines' event table per group (ph_surv_table) of survtime, event f32 [N] and group int32 [N] with G groups, into the
+    caller's device tensors times f32 [N], at_risk / observed / censored int32 [N, G] and npoints int32 [2] (slots, rows left
+    out); the rows from npoints[0] on stay unwritten.  Nothing is read back."""
+    survtime, event = _f32(survtime).reshape(-1), _f32(event).reshape(-1)
+    N, G = survtime.shape[0], int(G)
+    nbytes = lib().ph_surv_table_workspace_bytes(N, G)
+    if nbytes == 0 or event.shape[0] != N:
+        raise ValueError("surv_table: survtime and event [N] with 2 <= N <= 1048576, 1 <= G <= 8 (got %d, %d, G = %d)"
+                         % (N, event.shape[0], G))
+    _i32_out(group, N, "group")
+    if times.dtype != torch.float32 or times.numel() != N or not times.is_contiguous():
+        raise ValueError("surv_table: times is a contiguous float32 tensor of %d entries" % N)
+    for name, t in (("at_risk", at_risk), ("observed", observed), ("censored", censored)):
+        _i32_out(t, N * G, name)
+    _i32_out(npoints, 2, "npoints")
+    ws = torch.empty(nbytes, device=survtime.device, dtype=torch.uint8)
+    check(lib().ph_surv_table(ptr(survtime), ptr(event), ptr(group), N, G, ptr(require_cuda(times, "times")), ptr(at_risk),
+                              ptr(observed), ptr(censored), ptr(npoints), ptr(ws), stream()), "ph_surv_table")
+
+
+def surv_logrank_km(at_risk, observed, npoints, G, pairs, stat, surv):
+    """The log-rank sums (O - E, V) of the group pairs `pairs` (a host sequence of (a, b)) into stat float64 [P, 2] and the
+    Kaplan-Meier estimate of every group at every slot into surv float64 [N, G] (ph_surv_logrank_km), from the table of
+    `surv_table` on the device.  Nothing is read back."""
+    import numpy as np
+    G = int(G)
+    ph = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    P = ph.shape[0]
+    N = at_risk.numel() // max(G, 1)
+    nbytes = lib().ph_surv_logrank_km_workspace_bytes(N, G, P)
+    if nbytes == 0 or (P and (ph.min() < 0 or ph.max() >= G or bool((ph[:, 0] == ph[:, 1]).any()))):
+        raise ValueError("surv_logrank_km: 2 <= N <= 1048576, 1 <= G <= 8, at most 28 pairs of two different groups in [0, G) "
+                         "(got N = %d, G = %d, pairs %r)" % (N, G, ph.tolist()))
+    _i32_out(at_risk, N * G, "at_risk"); _i32_out(observed, N * G, "observed"); _i32_out(npoints, 2, "npoints")
+    for name, t, n in (("stat", stat, 2 * P), ("surv", surv, N * G)):
+        if t.dtype != torch.float64 or t.numel() != n or not t.is_contiguous():
+            raise ValueError("surv_logrank_km: %s is a contiguous float64 tensor of %d entries" % (name, n))
+    ws = torch.empty(nbytes, device=at_risk.device, dtype=torch.uint8)
+    check(lib().ph_surv_logrank_km(ptr(at_risk), ptr(observed), ptr(npoints), N, G, ph.ctypes.data if P else None, P,
+                                   ptr(require_cuda(stat, "stat")) if P else None, ptr(require_cuda(surv, "surv")), ptr(ws),
+                                   stream()), "ph_surv_logrank_km")
+
+
 def confusion_counts(pred, grade, out=None):
     """int64 [C, C] device tensor: row = true grade, column = arg-max of the row of pred (first maximum), ph_confusion_counts."""
     pred, grade = _pred_grade(pred, grade, "confusion_counts")
