@@ -11,6 +11,7 @@
 // The scores are log-probabilities (negative): nothing here relies on their sign.
 #include "ph_common.h"
 #include "ph_kernels.h"
+#include "ph_pairscan.h"
 
 namespace {
 
@@ -24,95 +25,87 @@ constexpr int QUANT_THREADS = 256;
 constexpr int QUANT_MAX_GROUP = 4096;     // PH_QUANTILE_MAX_GROUP: one group's column in LDS (16 KiB)
 constexpr int QUANT_WAVE_MAX_BLOCKS = 1 << 16;
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+// Element i of a ranking problem (ph_rank_counts, ph_roc_points): cls >= 0 - score pred[i][cls], label grade[i] == cls,
+// M = N; cls == -1 - pair i = n * C + c with score pred[i] and label grade[n] == c, M = N * C (micro).
+struct RocElem {
+  float s;
+  int lab;                     // 1 positive, 0 negative
+  unsigned int bad;            // a score that is not finite; once per row, a label outside [0, C) (it makes no pair positive)
+};
+
+__device__ __forceinline__ RocElem roc_elem(const float* __restrict__ pred, const int64_t* __restrict__ grade, int i, int C,
+                                            int cls) {
+  RocElem e;
+  int n, c;
+  if (cls >= 0) { n = i; c = cls; } else { n = i / C; c = i - n * C; }
+  e.s = pred[cls >= 0 ? (size_t)n * C + c : (size_t)i];       // (the micro load does not wait for the division)
+  const int64_t g = grade[n];
+  e.lab = g == (int64_t)c ? 1 : 0;
+  const bool count_label = cls >= 0 || c == 0;
+  e.bad = (isfinite(e.s) ? 0u : 1u) + ((count_label && (g < 0 || g >= (int64_t)C)) ? 1u : 0u);
+  return e;
+}
+
+// What a thread stages for element j: .x = the score of a positive j, .y = of a negative one.  A NaN compares false with
+// everything: the half that does not apply, the padding past the end and a NaN score all drop out of every count, so the
+// scan has no label test.
+__device__ __forceinline__ float2 roc_stage(const float* __restrict__ pred, const int64_t* __restrict__ grade, int j, int M,
+                                            int C, int cls) {
+  const float qnan = __builtin_nanf("");
+  float2 v = make_float2(qnan, qnan);
+  if (j < M) {
+    const RocElem e = roc_elem(pred, grade, j, C, cls);
+    if (e.lab) v.x = e.s; else v.y = e.s;
+  }
   return v;
 }
 
-// fixed-tree sum of RANK_TILE doubles (red[t] += red[t + o], o = 128 .. 1): the order tests/eval_emulation.py restates
-__device__ __forceinline__ double tile_tree_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int o = RANK_TILE >> 1; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-// Pair i = n * C + c has score pred[i] and label (grade[n] == c).  Thread = pair i; the j pairs stream through LDS in tiles.
-// For a positive i:  ge_all = #{j: s_j >= s_i}, ge_pos = the positives among them, below = #{j negative: s_j < s_i},
-// equal = #{j negative: s_j == s_i}.  counts[0..3] += P, concordant, tied, bad (64-bit integer atomics: exact, independent of the
-// order); part[block] = the tile-tree sum of ge_pos / ge_all over the block's positives (0.0 for every other thread).
-// A NaN score compares false everywhere and is counted in `bad`, as is a label outside [0, C) (which makes no pair positive).
+// Thread = pair i of the micro problem.  For a positive i:  ge_all = #{j: s_j >= s_i}, ge_pos = the positives among them,
+// below = #{j negative: s_j < s_i}, equal = #{j negative: s_j == s_i}.  counts[0..3] += P, concordant, tied, bad (64-bit
+// integer atomics: exact, independent of the order); part[block] = the fixed-tree sum (block_sum_tree: the order
+// tests/eval_emulation.py restates) of ge_pos / ge_all over the block's positives (0.0 for every other thread).
 __global__ __launch_bounds__(RANK_TILE) void rank_counts_kernel(const float* __restrict__ pred, const int64_t* __restrict__ grade,
                                                                 int M, int C, unsigned long long* __restrict__ counts,
                                                                 double* __restrict__ part) {
-  __shared__ float2 sj[RANK_TILE];       // .x = the score of a positive pair j, .y = of a negative one; the other half NaN
+  __shared__ float2 sj[RANK_TILE];
   __shared__ double red[RANK_TILE];
-  const int tid = threadIdx.x;
-  const int i = blockIdx.x * RANK_TILE + tid;
-  const bool live = i < M;
-  const float qnan = __builtin_nanf("");
+  const int i = blockIdx.x * RANK_TILE + threadIdx.x;
   float si = 0.f;
   bool pos = false;
   unsigned int bad = 0;
-  if (live) {
+  if (i < M) {
     si = pred[i];
     const int n = i / C, c = i - n * C;
     const int64_t g = grade[n];
     pos = g == (int64_t)c;
     bad = (isfinite(si) ? 0u : 1u) + ((c == 0 && (g < 0 || g >= (int64_t)C)) ? 1u : 0u);
   }
-  // A NaN compares false with everything: the half of sj[j] that does not apply, the padding of the last tile and a NaN
-  // score all drop out of every count, so the inner loop has a fixed length and no label test.
   unsigned int ge_pos = 0, ge_neg = 0, below = 0, equal = 0;
-  for (int j0 = 0; j0 < M; j0 += RANK_TILE) {
-    const int j = j0 + tid;
-    float2 v = make_float2(qnan, qnan);
-    if (j < M) {
-      const int n = j / C;
-      const float s = pred[j];
-      if (grade[n] == (int64_t)(j - n * C)) v.x = s; else v.y = s;
-    }
-    __syncthreads();
-    sj[tid] = v;
-    __syncthreads();
-    if (!pos) continue;        // (no early exit: every thread takes part in the barriers)
-#pragma unroll 8
-    for (int jj = 0; jj < RANK_TILE; ++jj) {
-      const float2 w = sj[jj];
-      ge_pos += w.x >= si ? 1u : 0u;
-      ge_neg += w.y >= si ? 1u : 0u;
-      below += w.y < si ? 1u : 0u;
-      equal += w.y == si ? 1u : 0u;
-    }
-  }
+  pair_scan<RANK_TILE>(
+      M, i, pos, [&](int j) { return roc_stage(pred, grade, j, M, C, -1); }, [&](int t, float2 v) { sj[t] = v; },
+      [&](int jj, int) {
+        const float2 w = sj[jj];
+        ge_pos += w.x >= si ? 1u : 0u;
+        ge_neg += w.y >= si ? 1u : 0u;
+        below += w.y < si ? 1u : 0u;
+        equal += w.y == si ? 1u : 0u;
+      });
   const unsigned int ge_all = ge_pos + ge_neg;
   // ge_all >= 1 for a finite positive (j = i); a NaN positive has ge_all = 0: its term is left out (the flag reports it)
   const double term = (pos && ge_all > 0) ? (double)ge_pos / (double)ge_all : 0.0;
-  const double tsum = tile_tree_sum(term, red);
-  if (tid == 0) part[blockIdx.x] = tsum;
-  const int lane = tid & 63;
-  const unsigned long long a = wave_sum_u64(pos ? 1ull : 0ull), b = wave_sum_u64(below), c = wave_sum_u64(equal),
-                           d = wave_sum_u64(bad);
-  if (lane == 0) {
-    if (a) atomicAdd(&counts[0], a);
-    if (b) atomicAdd(&counts[1], b);
-    if (c) atomicAdd(&counts[2], c);
-    if (d) atomicAdd(&counts[3], d);
-  }
+  const double tsum = block_sum_tree<RANK_TILE, double>(term, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = tsum;
+  const unsigned long long tot[4] = {wave_sum_u64(pos ? 1ull : 0ull), wave_sum_u64(below), wave_sum_u64(equal),
+                                     wave_sum_u64(bad)};       // (the four sums first: their shuffles overlap)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) lane0_atomic_add(&counts[k], tot[k]);
 }
 
-// One workgroup: thread t adds part[t], part[t + 256], ... in that order, then the tile tree.  Fixed order: two runs agree bitwise.
+// One workgroup: the blocks' parts in the fixed order of strided_tree_sum.
 __global__ __launch_bounds__(RANK_TILE) void rank_finish_kernel(const double* __restrict__ part, int nblocks,
                                                                 double* __restrict__ ap_sum) {
   __shared__ double red[RANK_TILE];
-  double v = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += RANK_TILE) v += part[b];
-  const double s = tile_tree_sum(v, red);
+  const double s = strided_tree_sum<RANK_TILE>(part, nblocks, 1, 0, red);
   if (threadIdx.x == 0) ap_sum[0] = s;
 }
 
@@ -121,7 +114,7 @@ __global__ __launch_bounds__(RANK_TILE) void rank_finish_kernel(const double* __
 // s_i = pred[n][g]; the rows j stream through LDS in tiles of 256 rows x C columns (staged once for all classes) and the
 // thread reads column g of each: w = sj[jj][g], positive when gj[jj] == g.  The last tile is padded with NaN scores, which
 // drop out of every comparison.  acc[c][0..3] collects P, concordant, tied, bad of the block per class in LDS (32-bit: at
-// most 256 * 2^20 per block), then 64-bit atomics into counts; part[block][c] = the tile tree over the block's terms of class c.
+// most 256 * 2^20 per block), then 64-bit atomics into counts; part[block][c] = the fixed tree over the block's terms of class c.
 __global__ __launch_bounds__(RANK_TILE) void rank_counts_classes_kernel(const float* __restrict__ pred,
                                                                         const int64_t* __restrict__ grade, int N, int C,
                                                                         unsigned long long* __restrict__ counts,
@@ -152,31 +145,27 @@ __global__ __launch_bounds__(RANK_TILE) void rank_counts_classes_kernel(const fl
   }
   const bool pos = g >= 0;
   unsigned int ge_pos = 0, ge_all = 0, below = 0, equal = 0;
-  const int tile_words = RANK_TILE * C;
-  for (int j0 = 0; j0 < N; j0 += RANK_TILE) {
-    __syncthreads();
-    const int rows = min(RANK_TILE, N - j0);
-    for (int k = tid; k < tile_words; k += RANK_TILE) sj[k] = k < rows * C ? pred[(size_t)j0 * C + k] : qnan;
-    {
-      int lab = -1;
-      if (tid < rows) {
-        const int64_t v = grade[j0 + tid];
-        if (v >= 0 && v < (int64_t)C) lab = (int)v;
-      }
-      gj[tid] = lab;
-    }
-    __syncthreads();
-    if (!pos) continue;        // (no early exit: every thread takes part in the barriers)
-#pragma unroll 8
-    for (int jj = 0; jj < RANK_TILE; ++jj) {
-      const float w = sj[jj * C + g];
-      const bool p = gj[jj] == g;
-      ge_all += w >= si ? 1u : 0u;
-      ge_pos += (p && w >= si) ? 1u : 0u;
-      below += (!p && w < si) ? 1u : 0u;
-      equal += (!p && w == si) ? 1u : 0u;
-    }
-  }
+  // A thread fetches the label of row j.  The row's C scores (a run-time count: not for registers) go from global memory to
+  // LDS in put, as part of the tile's RANK_TILE * C consecutive words.
+  pair_scan<RANK_TILE>(
+      N, n, pos,
+      [&](int j) {
+        const int64_t v = j < N ? grade[j] : (int64_t)-1;
+        return make_int2((v >= 0 && v < (int64_t)C) ? (int)v : -1, j - tid);
+      },
+      [&](int t, int2 v) {               // v.x = the label, v.y = j0
+        gj[t] = v.x;
+        const int words = min(RANK_TILE, N - v.y) * C;
+        for (int k = t; k < RANK_TILE * C; k += RANK_TILE) sj[k] = k < words ? pred[(size_t)v.y * C + k] : qnan;
+      },
+      [&](int jj, int) {
+        const float w = sj[jj * C + g];
+        const bool p = gj[jj] == g, ge = w >= si;        // (& of evaluated flags: the scan stays free of branches)
+        ge_all += ge ? 1u : 0u;
+        ge_pos += (p & ge) ? 1u : 0u;
+        below += (!p & (w < si)) ? 1u : 0u;
+        equal += (!p & (w == si)) ? 1u : 0u;
+      });
   if (pos) {
     if (below) atomicAdd(&acc[g * 4 + 1], below);
     if (equal) atomicAdd(&acc[g * 4 + 2], equal);
@@ -184,49 +173,23 @@ __global__ __launch_bounds__(RANK_TILE) void rank_counts_classes_kernel(const fl
   // ge_all >= 1 for a positive whose score is not a NaN (j = n); a NaN positive has ge_all = 0: its term is left out
   const double term = (pos && ge_all > 0) ? (double)ge_pos / (double)ge_all : 0.0;
   for (int c = 0; c < C; ++c) {
-    const double tsum = tile_tree_sum(g == c ? term : 0.0, red);
+    const double tsum = block_sum_tree<RANK_TILE, double>(g == c ? term : 0.0, red);
     if (tid == 0) part[(size_t)blockIdx.x * C + c] = tsum;
-    __syncthreads();           // red is rewritten for the next class
   }
   if (tid < C * 4 && acc[tid]) atomicAdd(&counts[tid], (unsigned long long)acc[tid]);
 }
 
-// Workgroup c: the fixed-order finish of rank_finish_kernel over part[b][c], b = 0 .. nblocks - 1.
+// Workgroup c: the finish of rank_finish_kernel over part[b][c], b = 0 .. nblocks - 1.
 __global__ __launch_bounds__(RANK_TILE) void rank_finish_classes_kernel(const double* __restrict__ part, int nblocks, int C,
                                                                         double* __restrict__ ap_sum) {
   __shared__ double red[RANK_TILE];
-  const int c = blockIdx.x;
-  double v = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += RANK_TILE) v += part[(size_t)b * C + c];
-  const double s = tile_tree_sum(v, red);
-  if (threadIdx.x == 0) ap_sum[c] = s;
+  const double s = strided_tree_sum<RANK_TILE>(part, nblocks, C, blockIdx.x, red);
+  if (threadIdx.x == 0) ap_sum[blockIdx.x] = s;
 }
 
-// ---- ph_roc_points.  Element i of the selected problem: cls >= 0 - score pred[i][cls], label
-// grade[i] == cls, M = N; cls == -1 - pair i = n * C + c of rank_counts_kernel, M = N * C.
-struct RocElem {
-  float s;
-  int lab;                     // 1 positive, 0 negative
-  unsigned int bad;
-};
-
-__device__ __forceinline__ RocElem roc_elem(const float* __restrict__ pred, const int64_t* __restrict__ grade, int i, int C,
-                                            int cls) {
-  RocElem e;
-  int n, c;
-  if (cls >= 0) { n = i; c = cls; } else { n = i / C; c = i - n * C; }
-  e.s = pred[(size_t)n * C + c];
-  const int64_t g = grade[n];
-  e.lab = g == (int64_t)c ? 1 : 0;
-  const bool count_label = cls >= 0 || c == 0;       // a label outside [0, C) once per row
-  e.bad = (isfinite(e.s) ? 0u : 1u) + ((count_label && (g < 0 || g >= (int64_t)C)) ? 1u : 0u);
-  return e;
-}
-
-// Pass 1, thread = element i, the j elements in LDS tiles (.x = the score of a positive j, .y = of a negative one, the other
-// half and the padding NaN).  tp_i / fp_i = #{positive / negative j: s_j >= s_i}; i represents its score when its score is
-// not a NaN and no j < i has an equal one.  rep[i] = s_i for a representative, NaN otherwise; tpfp[i] = (tp_i, fp_i).
-// npoints[0] += representatives, npoints[1] += bad (integer atomics: independent of the order).
+// ---- ph_roc_points: distinct-value placement (ph_pairscan.h) of the scores of the selected problem.
+// Pass 1, thread = element i: tp_i / fp_i = #{positive / negative j: s_j >= s_i}; rep[i] = s_i where i represents its score,
+// NaN otherwise; tpfp[i] = (tp_i, fp_i).  npoints[0] += representatives, npoints[1] += bad.
 __global__ __launch_bounds__(RANK_TILE) void roc_count_kernel(const float* __restrict__ pred, const int64_t* __restrict__ grade,
                                                               int M, int C, int cls, float* __restrict__ rep,
                                                               int2* __restrict__ tpfp, int* __restrict__ npoints) {
@@ -243,58 +206,36 @@ __global__ __launch_bounds__(RANK_TILE) void roc_count_kernel(const float* __res
     bad = e.bad;
   }
   unsigned int tp = 0, fp = 0, before = 0;
-  for (int j0 = 0; j0 < M; j0 += RANK_TILE) {
-    const int j = j0 + tid;
-    float2 v = make_float2(qnan, qnan);
-    if (j < M) {
-      const RocElem e = roc_elem(pred, grade, j, C, cls);
-      if (e.lab) v.x = e.s; else v.y = e.s;
-    }
-    __syncthreads();
-    sj[tid] = v;
-    __syncthreads();
-    const int lim = i - j0;                           // the elements jj < lim of this tile come before i
-#pragma unroll 8
-    for (int jj = 0; jj < RANK_TILE; ++jj) {
-      const float2 w = sj[jj];
-      tp += w.x >= si ? 1u : 0u;
-      fp += w.y >= si ? 1u : 0u;
-      before += (jj < lim && (w.x == si || w.y == si)) ? 1u : 0u;
-    }
-  }
-  const bool is_rep = live && si == si && before == 0;
+  pair_scan<RANK_TILE>(
+      M, i, true, [&](int j) { return roc_stage(pred, grade, j, M, C, cls); }, [&](int t, float2 v) { sj[t] = v; },
+      [&](int jj, int lim) {
+        const float2 w = sj[jj];
+        tp += w.x >= si ? 1u : 0u;
+        fp += w.y >= si ? 1u : 0u;
+        before += equal_before(w.x == si || w.y == si, jj, lim);
+      });
+  const bool is_rep = live && represents(si, before);
   if (live) {
     rep[i] = is_rep ? si : qnan;
     tpfp[i] = make_int2((int)tp, (int)fp);
   }
-  const unsigned long long r = wave_sum_u64(is_rep ? 1ull : 0ull), b = wave_sum_u64(bad);
-  if ((tid & 63) == 0) {
-    if (r) atomicAdd(&npoints[0], (int)r);
-    if (b) atomicAdd(&npoints[1], (int)b);
-  }
+  wave_atomic_add(&npoints[0], is_rep ? 1 : 0);
+  wave_atomic_add(&npoints[1], (int)bad);
 }
 
-// Pass 2: the slot of a representative = the number of representatives with a larger score (distinct scores: a permutation
-// of 0 .. points - 1), where it leaves its threshold and counts.
+// Pass 2: a representative leaves its threshold and counts in its slot, the number of representatives with a LARGER score.
 __global__ __launch_bounds__(RANK_TILE) void roc_place_kernel(const float* __restrict__ rep, const int2* __restrict__ tpfp, int M,
                                                               int* __restrict__ fps, int* __restrict__ tps,
                                                               float* __restrict__ thr) {
   __shared__ float sj[RANK_TILE];
-  const int tid = threadIdx.x;
-  const int i = blockIdx.x * RANK_TILE + tid;
+  const int i = blockIdx.x * RANK_TILE + threadIdx.x;
   const float qnan = __builtin_nanf("");
   const float si = i < M ? rep[i] : qnan;
   const bool is_rep = si == si;
   unsigned int slot = 0;
-  for (int j0 = 0; j0 < M; j0 += RANK_TILE) {
-    const int j = j0 + tid;
-    __syncthreads();
-    sj[tid] = j < M ? rep[j] : qnan;
-    __syncthreads();
-    if (!is_rep) continue;     // (no early exit: every thread takes part in the barriers)
-#pragma unroll 8
-    for (int jj = 0; jj < RANK_TILE; ++jj) slot += sj[jj] > si ? 1u : 0u;
-  }
+  pair_scan<RANK_TILE>(
+      M, i, is_rep, [&](int j) { return j < M ? rep[j] : qnan; }, [&](int t, float v) { sj[t] = v; },
+      [&](int jj, int) { slot += rep_beyond<true>(sj[jj], si); });
   if (is_rep && slot < (unsigned int)M) {
     const int2 c = tpfp[i];
     thr[slot] = si;

@@ -168,6 +168,11 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline unsigned nblk(size_t n, int t = 256) { return (unsigned)((n + t - 1) / t); }   // workgroups of t threads over n elements

@@ -130,12 +130,6 @@ __device__ __forceinline__ void slic_try(SlicBest<DT>& best, int l, uint32_t c0,
   if (d < best.d) { best.d = d; best.l = l; }
 }
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <typename DT>
 __global__ __launch_bounds__(256) void slic_assign_kernel(const uint32_t* __restrict__ lab, const u32x2* __restrict__ cen,
                                                           unsigned long long* __restrict__ sums, int16_t* __restrict__ labels,

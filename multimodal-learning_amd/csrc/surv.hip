@@ -4,7 +4,7 @@
 // CL_utils/KD_losses.py:20-22) and the concordance counts behind the evaluation's C-index (utils.py:424-425).
 #include "ph_common.h"
 #include "ph_kernels.h"
-#include "ph_reduce.h"
+#include "ph_pairscan.h"
 
 namespace {
 
@@ -230,11 +230,10 @@ __global__ void ema_update_dev_kernel(float* __restrict__ ema, const float* __re
 // (t_i < t_j, or t_i == t_j and e_j = 0); concordant iff h_i > h_j; tied iff h_i == h_j.  Thread = row i, the j rows
 // stream through LDS in tiles.  Integer counts, added with 64-bit integer atomics: exact, so the result does not depend
 // on the order of the rows or of the additions.  counts[v*3 + {0,1,2}] = comparable, concordant, tied.
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+// A time past the end is staged as a NaN: it is comparable with nothing, as is a NaN time among the rows.
+struct CidxStage {
+  float t, e, h[3];
+};
 
 __global__ __launch_bounds__(CIDX_TILE) void cindex_counts_kernel(const float* __restrict__ t, const float* __restrict__ e,
                                                                   const float* __restrict__ h0, const float* __restrict__ h1,
@@ -250,40 +249,40 @@ __global__ __launch_bounds__(CIDX_TILE) void cindex_counts_kernel(const float* _
   float hi[3] = {0.f, 0.f, 0.f};
   for (int v = 0; v < nvec; ++v) hi[v] = live ? hv[v][i] : 0.f;
   unsigned int comp = 0, conc[3] = {0u, 0u, 0u}, tie[3] = {0u, 0u, 0u};
-  for (int j0 = 0; j0 < N; j0 += CIDX_TILE) {
-    const int j = j0 + tid;
-    __syncthreads();
-    if (j < N) {
-      st[tid] = t[j];
-      se[tid] = e[j];
-      for (int v = 0; v < nvec; ++v) sh[v][tid] = hv[v][j];
-    }
-    __syncthreads();
-    const int nj = min(CIDX_TILE, N - j0);
-    if (!ev) continue;       // (no early exit: every thread takes part in the barriers)
-    for (int jj = 0; jj < nj; ++jj) {
-      const float tj = st[jj];
-      const bool cmp = ti < tj || (ti == tj && se[jj] <= 0.5f);
-      if (!cmp) continue;
-      ++comp;
-      for (int v = 0; v < nvec; ++v) {
-        const float hj = sh[v][jj];
-        conc[v] += hi[v] > hj;
-        tie[v] += hi[v] == hj;
-      }
-    }
-  }
-  const int lane = tid & 63;
-  unsigned long long r = wave_sum_u64(comp);
-  if (lane == 0 && r) {
-    for (int v = 0; v < nvec; ++v) atomicAdd(&counts[v * 3 + 0], r);
-  }
+  pair_scan<CIDX_TILE>(
+      N, i, ev,
+      [&](int j) {
+        CidxStage s = {__builtin_nanf(""), 0.f, {0.f, 0.f, 0.f}};
+        if (j < N) {
+          s.t = t[j];
+          s.e = e[j];
+#pragma unroll                   // (constant indices: the staged values stay in registers)
+          for (int v = 0; v < 3; ++v)
+            if (v < nvec) s.h[v] = hv[v][j];
+        }
+        return s;
+      },
+      [&](int k, const CidxStage& s) {
+        st[k] = s.t;
+        se[k] = s.e;
+#pragma unroll
+        for (int v = 0; v < 3; ++v) sh[v][k] = s.h[v];
+      },
+      [&](int jj, int) {
+        const float tj = st[jj];
+        const bool cmp = ti < tj || (ti == tj && se[jj] <= 0.5f);
+        if (!cmp) return;
+        ++comp;
+        for (int v = 0; v < nvec; ++v) {
+          const float hj = sh[v][jj];
+          conc[v] += hi[v] > hj;
+          tie[v] += hi[v] == hj;
+        }
+      });
   for (int v = 0; v < nvec; ++v) {
-    const unsigned long long a = wave_sum_u64(conc[v]), b = wave_sum_u64(tie[v]);
-    if (lane == 0) {
-      if (a) atomicAdd(&counts[v * 3 + 1], a);
-      if (b) atomicAdd(&counts[v * 3 + 2], b);
-    }
+    wave_atomic_add(&counts[v * 3 + 0], comp);
+    wave_atomic_add(&counts[v * 3 + 1], conc[v]);
+    wave_atomic_add(&counts[v * 3 + 2], tie[v]);
   }
 }
 

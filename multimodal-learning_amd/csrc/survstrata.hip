@@ -7,7 +7,7 @@
 // No sort anywhere: ranks and slots are exact integer counts from all-pairs passes over LDS tiles of 256, as ph_roc_points has
 // them; every workgroup walks the tiles b, b + gridDim.x, .. of its side (at most SURV_MAX_BLOCKS workgroups).
 #include "ph_common.h"
-#include "ph_reduce.h"
+#include "ph_pairscan.h"
 
 namespace {
 
@@ -60,18 +60,12 @@ __global__ __launch_bounds__(SURV_TILE) void strata_rank_kernel(const float* __r
     const bool live = i < N;
     const float hv = live ? hazard[i] : qnan;
     int rank = 0;
-    for (int j0 = 0; j0 < N; j0 += SURV_TILE) {
-      const int j = j0 + tid;
-      __syncthreads();
-      sj[tid] = j < N ? hazard[j] : qnan;
-      __syncthreads();
-      const int lim = i - j0;                           // the rows jj < lim of this tile come before i
-#pragma unroll 8
-      for (int jj = 0; jj < SURV_TILE; ++jj) {
-        const float w = sj[jj];
-        rank += (w < hv ? 1 : 0) + ((jj < lim && w == hv) ? 1 : 0);
-      }
-    }
+    pair_scan<SURV_TILE>(
+        N, i, true, [&](int j) { return j < N ? hazard[j] : qnan; }, [&](int t, float v) { sj[t] = v; },
+        [&](int jj, int lim) {
+          const float w = sj[jj];
+          rank += (w < hv ? 1 : 0) + (int)equal_before(w == hv, jj, lim);
+        });
     if (live && hv == hv) {
 #pragma unroll
       for (int k = 0; k < SURV_MAX_K; ++k) {
@@ -80,8 +74,7 @@ __global__ __launch_bounds__(SURV_TILE) void strata_rank_kernel(const float* __r
         if (rank == sel.hi[k]) picked[2 * k + 1] = hv;
       }
     }
-    const unsigned long long m = __ballot(live && hv != hv);
-    if ((tid & 63) == 0 && m != 0ull) atomicAdd(&nan[0], (int)__popcll(m));
+    wave_atomic_add(&nan[0], (live && hv != hv) ? 1 : 0);
   }
 }
 
@@ -128,50 +121,44 @@ __global__ __launch_bounds__(SURV_TILE) void strata_group_kernel(const float* __
 // ---- ph_surv_table.  A row takes part when its group lies in [0, G) and its time is not a NaN.
 __device__ __forceinline__ bool surv_row_ok(float t, int g, int G) { return g >= 0 && g < G && t == t; }
 
-// Pass 1, thread = row i: i represents its time when no EARLIER row has an equal one.  rep[i] = t_i for a representative, NaN
-// otherwise; npoints[0] += representatives, npoints[1] += the rows that take part in nothing (integer atomics).
+// the time of row j where it takes part, NaN where it does not or lies past the end
+__device__ __forceinline__ float surv_time(const float* __restrict__ survtime, const int* __restrict__ group, int j, int N, int G) {
+  if (j < N) {
+    const float t = survtime[j];
+    if (surv_row_ok(t, group[j], G)) return t;
+  }
+  return __builtin_nanf("");
+}
+
+// Distinct-value placement (ph_pairscan.h) of the times.  Pass 1, thread = row i: rep[i] = t_i where i represents its time, NaN
+// otherwise; npoints[0] += representatives, npoints[1] += the rows that take part in nothing.
 __global__ __launch_bounds__(SURV_TILE) void surv_rep_kernel(const float* __restrict__ survtime, const int* __restrict__ group, int N,
                                                              int G, float* __restrict__ rep, int* __restrict__ npoints) {
   __shared__ float sj[SURV_TILE];
-  const int tid = threadIdx.x;
-  const float qnan = __builtin_nanf("");
   for (int i0 = blockIdx.x * SURV_TILE; i0 < N; i0 += gridDim.x * SURV_TILE) {
-    const int i = i0 + tid;
+    const int i = i0 + threadIdx.x;
     const bool live = i < N;
-    float ti = qnan;
-    if (live) {
-      const float t = survtime[i];
-      if (surv_row_ok(t, group[i], G)) ti = t;
-    }
+    const float ti = surv_time(survtime, group, i, N, G);
     unsigned int before = 0;
-    for (int j0 = 0; j0 < N; j0 += SURV_TILE) {
-      const int j = j0 + tid;
-      float v = qnan;
-      if (j < N) {
-        const float t = survtime[j];
-        if (surv_row_ok(t, group[j], G)) v = t;
-      }
-      __syncthreads();
-      sj[tid] = v;
-      __syncthreads();
-      const int lim = i - j0;
-#pragma unroll 8
-      for (int jj = 0; jj < SURV_TILE; ++jj) before += (jj < lim && sj[jj] == ti) ? 1u : 0u;
-    }
-    const bool is_rep = ti == ti && before == 0;
-    if (live) rep[i] = is_rep ? ti : qnan;
-    const unsigned long long r = __ballot(is_rep), b = __ballot(live && ti != ti);
-    if ((tid & 63) == 0) {
-      if (r) atomicAdd(&npoints[0], (int)__popcll(r));
-      if (b) atomicAdd(&npoints[1], (int)__popcll(b));
-    }
+    pair_scan<SURV_TILE>(
+        N, i, true, [&](int j) { return surv_time(survtime, group, j, N, G); }, [&](int t, float v) { sj[t] = v; },
+        [&](int jj, int lim) { before += equal_before(sj[jj] == ti, jj, lim); });
+    const bool is_rep = represents(ti, before);
+    if (live) rep[i] = is_rep ? ti : __builtin_nanf("");
+    wave_atomic_add(&npoints[0], is_rep ? 1 : 0);
+    wave_atomic_add(&npoints[1], (live && ti != ti) ? 1 : 0);
   }
 }
 
-// Pass 2, thread = representative i: its slot = the number of representatives with a SMALLER time (distinct times: a
-// permutation of 0 .. points - 1), and the three counts of its time over all rows j per group.  Row j carries one 8-bit field
-// per group in a 64-bit word (wo: 1 in the field of its group when it has an event, wc: when it has none); the selected
-// words of SURV_CHUNK rows are added packed (a field reaches at most 128) and then unpacked into the 32-bit counters.
+// Pass 2, thread = representative i: its slot = the number of representatives with a SMALLER time, and the three counts of
+// its time over all rows j per group.  Row j carries one 8-bit field per group in a 64-bit word (wo: 1 in the field of its
+// group when it has an event, wc: when it has none); the selected words of SURV_CHUNK rows are added packed (a field
+// reaches at most 128) and then unpacked into the 32-bit counters.
+struct SurvStage {             // what row j brings: its time and its rep entry (NaN: none), wo and wc
+  float t, r;
+  unsigned long long wo, wc;
+};
+
 __global__ __launch_bounds__(SURV_TILE) void surv_place_kernel(const float* __restrict__ survtime, const float* __restrict__ event,
                                                                const int* __restrict__ group, const float* __restrict__ rep, int N,
                                                                int G, float* __restrict__ times, int* __restrict__ at_risk,
@@ -187,43 +174,43 @@ __global__ __launch_bounds__(SURV_TILE) void surv_place_kernel(const float* __re
     unsigned int slot = 0, cge[SURV_MAX_G], cob[SURV_MAX_G], cce[SURV_MAX_G];
 #pragma unroll
     for (int g = 0; g < SURV_MAX_G; ++g) cge[g] = cob[g] = cce[g] = 0;
-    for (int j0 = 0; j0 < N; j0 += SURV_TILE) {
-      const int j = j0 + tid;
-      float t = qnan, r = qnan;
-      unsigned long long wo = 0ull, wc = 0ull;
-      if (j < N) {
-        const float tj = survtime[j];
-        const int gj = group[j];
-        r = rep[j];
-        if (surv_row_ok(tj, gj, G)) {
-          t = tj;
-          const unsigned long long w = 1ull << (8 * gj);
-          if (event[j] > 0.f) wo = w; else wc = w;
-        }
-      }
-      __syncthreads();
-      st[tid] = t; sr[tid] = r; swo[tid] = wo; swc[tid] = wc;
-      __syncthreads();
-      if (!is_rep) continue;   // (no early exit: every thread takes part in the barriers)
-      for (int c0 = 0; c0 < SURV_TILE; c0 += SURV_CHUNK) {
-        unsigned long long age = 0ull, aob = 0ull, ace = 0ull;
+    pair_tiles<SURV_TILE>(
+        N, is_rep,
+        [&](int j) {
+          SurvStage s = {qnan, qnan, 0ull, 0ull};
+          if (j < N) {
+            const float tj = survtime[j];
+            const int gj = group[j];
+            s.r = rep[j];
+            if (surv_row_ok(tj, gj, G)) {
+              s.t = tj;
+              const unsigned long long w = 1ull << (8 * gj);
+              if (event[j] > 0.f) s.wo = w; else s.wc = w;
+            }
+          }
+          return s;
+        },
+        [&](int t, const SurvStage& s) { st[t] = s.t; sr[t] = s.r; swo[t] = s.wo; swc[t] = s.wc; },
+        [&](int) {
+          for (int c0 = 0; c0 < SURV_TILE; c0 += SURV_CHUNK) {
+            unsigned long long age = 0ull, aob = 0ull, ace = 0ull;
 #pragma unroll 8
-        for (int jj = c0; jj < c0 + SURV_CHUNK; ++jj) {
-          const float tj = st[jj];
-          const unsigned long long o = swo[jj], c = swc[jj];
-          age += tj >= ti ? (o | c) : 0ull;
-          aob += tj == ti ? o : 0ull;
-          ace += tj == ti ? c : 0ull;
-          slot += sr[jj] < ti ? 1u : 0u;
-        }
+            for (int jj = c0; jj < c0 + SURV_CHUNK; ++jj) {
+              const float tj = st[jj];
+              const unsigned long long o = swo[jj], c = swc[jj];
+              age += tj >= ti ? (o | c) : 0ull;
+              aob += tj == ti ? o : 0ull;
+              ace += tj == ti ? c : 0ull;
+              slot += rep_beyond<false>(sr[jj], ti);
+            }
 #pragma unroll
-        for (int g = 0; g < SURV_MAX_G; ++g) {
-          cge[g] += (unsigned int)(age >> (8 * g)) & 0xffu;
-          cob[g] += (unsigned int)(aob >> (8 * g)) & 0xffu;
-          cce[g] += (unsigned int)(ace >> (8 * g)) & 0xffu;
-        }
-      }
-    }
+            for (int g = 0; g < SURV_MAX_G; ++g) {
+              cge[g] += (unsigned int)(age >> (8 * g)) & 0xffu;
+              cob[g] += (unsigned int)(aob >> (8 * g)) & 0xffu;
+              cce[g] += (unsigned int)(ace >> (8 * g)) & 0xffu;
+            }
+          }
+        });
     if (is_rep && slot < (unsigned int)N) {
       times[slot] = ti;
       const size_t row = (size_t)slot * G;
@@ -289,7 +276,7 @@ __global__ __launch_bounds__(SURV_TILE) void surv_terms_kernel(const int* __rest
   }
 }
 
-// One workgroup.  stat[p] = per pair and sum: thread t adds part[t], part[t + 256], .. in that order, then the fixed tree.
+// One workgroup.  stat[p] = per pair and sum, the tiles' parts in the fixed order of strided_tree_sum.
 // tpre[tile][g] = the product of the tiles before `tile`, multiplied in tile order by thread g.
 __global__ __launch_bounds__(SURV_TILE) void surv_finish_kernel(const double* __restrict__ part, const double* __restrict__ tprod,
                                                                 const int* __restrict__ npoints, int N, int G, int P,
@@ -298,9 +285,7 @@ __global__ __launch_bounds__(SURV_TILE) void surv_finish_kernel(const double* __
   const int tid = threadIdx.x;
   const int np = surv_points(npoints, N), tiles = (np + SURV_TILE - 1) / SURV_TILE;
   for (int w = 0; w < 2 * P; ++w) {
-    double v = 0.0;
-    for (int b = tid; b < tiles; b += SURV_TILE) v += part[(size_t)b * 2 * P + w];
-    const double s = block_sum_tree<SURV_TILE>(v, red);
+    const double s = strided_tree_sum<SURV_TILE>(part, tiles, 2 * P, w, red);
     if (tid == 0) stat[w] = s;
   }
   if (tid < G) {

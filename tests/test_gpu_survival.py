@@ -378,6 +378,33 @@ def test_cindex_counts_with_ties_vs_numpy_n4096():
         assert tuple(int(x) for x in got[v]) == _np_counts(t, e, hs[v]), v
 
 
+def _cindex_tied_case(N, seed, with_nan=False):
+    rs = np.random.RandomState(seed)
+    t = rs.randint(1, 6, N).astype(np.float32)                      # five distinct times, three hazard levels: heavy ties
+    e = (rs.rand(N) > 0.4).astype(np.float32)
+    e[0] = 1.0                                                      # (an event in every case, N = 2 included)
+    hs = [rs.randint(0, 3, N).astype(np.float32) for _ in range(3)]
+    if with_nan:
+        t[N // 3] = np.nan
+        hs[0][N // 2] = hs[2][N - 1] = np.nan
+    return t, e, hs
+
+
+@pytest.mark.parametrize("N,with_nan", [(2, False), (255, False), (256, False), (257, False), (513, False), (257, True)])
+def test_cindex_counts_at_the_tile_edges_vs_numpy(N, with_nan):
+    """One row, one short, one more than the 256-row tile, two tiles and a row: the rows past the end are staged as NaN
+    times and must count in nothing.  A NaN time or hazard among the rows is comparable / concordant / tied with nothing
+    either (every comparison with it is false, in numpy as on the device)."""
+    import multimodal_learning_amd as m
+    t, e, hs = _cindex_tied_case(N, 11 + N, with_nan)
+    got = m.ops.cindex_counts(torch.from_numpy(t).cuda(), torch.from_numpy(e).cuda(), [torch.from_numpy(h).cuda() for h in hs])
+    got = got.cpu().numpy()
+    want = [_np_counts(t, e, h) for h in hs]
+    assert want[0][0] > 0
+    for v in range(3):
+        assert tuple(int(x) for x in got[v]) == want[v], (v, got[v], want[v])
+
+
 def test_cindex_counts_independent_of_row_order_n100000():
     import multimodal_learning_amd as m
     rs = np.random.RandomState(5)
