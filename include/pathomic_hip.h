@@ -779,6 +779,63 @@ int ph_surv_logrank_km(const int32_t* at_risk, const int32_t* observed, const in
                        int P, double* stat, double* surv, void* workspace, ph_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Between the batch body and the test pass of the stage-2 trainers' train(): the epoch bookkeeping,
+ * the MIA-2023 per-sample stores and the similarity audit over them - all on the device, no float atomics, every float64 sum
+ * in a fixed order (two runs agree bitwise).
+ *
+ * ph_epoch_record_add: ONE launch (capturable in a HIP graph) that adds a step into a persistent record of
+ * PH_EPOCHREC_WORDS 8-byte words, which the caller zeroes with a memset at epoch start and reads once at epoch end:
+ *   words [0, 16)   float64: sum k of the device scalars.  scalars (HOST array of n_scalars DEVICE pointers to one float32
+ *                   each) and modes (HOST int32 [n_scalars]) are read at the call; scalar k is read on the device when the
+ *                   stream gets there, widened to float64 and added - in call order, so the sum equals Python's
+ *                   `acc += t.item()` bit for bit.  PH_REC_ADD: always (a NaN propagates).  PH_REC_ADD_POSITIVE: only when the
+ *                   value is > 0.0 (`if loss_div > 0.0:`, MICCAI-2022 train_test_path_multi_distill.py:320-324) - 0.0, -0.0, a
+ *                   negative value and a NaN are not added.
+ *   words [16, 32)  float64: the elementwise sum of wvec f32 [n_w] (`loss_weights += scale`, :305).
+ *   words [32, 34)  float64: the sum over the calls of mean(row0) and mean(row1), f32 [n_row] each (row1 may be NULL, both
+ *                   may be): the row added in float64 (element t, t + 256, .. per thread, then a fixed tree), divided by
+ *                   n_row ("MIA 2023/stage2_unimodal_student/train_test_path_multi_distill.py":380-383, :475-476).
+ *   word 34         int64: rows of pred f32 [B][C] whose arg-max (the FIRST maximum, as ph_confusion_counts) equals grade[b];
+ *   word 35         int64: rows whose label lies outside [0, C) - left out of word 34;   word 37: int64, the rows seen (+= B).
+ *   word 36         int64: the calls (steps).
+ *   words [40, 56)  int64: how often scalar k was added (under PH_REC_ADD_POSITIVE: the calls whose value passed the test).
+ * pred and grade are both NULL or both given.  0 <= n_scalars, n_w <= 16; with pred 1 <= B <= 1048576, 1 <= C <= 16; with
+ * row0 1 <= n_row <= 1048576.  A call with nothing to add is refused.
+ *
+ * ph_store_rows: store[index[b]] = rows[b] for the B rows of rows f32 [B][D] (softmax == 1: softmax over the row first,
+ * float32, max-subtracted), store f32 [n][D], index int64 [B].  An index outside [0, n) is skipped and counted in
+ * skipped int64 [1] (+=; the caller zeroes it).  Among equal indices of one batch the HIGHEST position b wins, as numpy's
+ * a[index] = rows.  1 <= B <= 65536, 1 <= D <= 4096, 1 <= n <= 2^31.  One launch, capturable.
+ *
+ * ph_sim_audit: evaluate_feature / evaluate_logits (:162-196) over F f32 [n][Df] (teacher) and P f32 [n][Dp] (student),
+ * labels int64 [n] (NULL: one class).  With S_f, S_p the cosine similarity matrices (rows scaled by 1 / |row|, the norm from a
+ * float64 sum of squares; a zero row has similarity 0 with everything, as sklearn's normalize):
+ *   sums double [5]   = sum of S_f over the intra-class ordered pairs, over the inter-class ones, the same two of S_p,
+ *                       and sum |S_f - S_p| over all n^2 pairs (the difference in float32, as numpy's);
+ *   counts int64 [2]  = intra-class pairs, inter-class pairs.  Pairs are ordered and include the diagonal (np.equal).
+ * The host divides (no inter-class pair: 0 / 0 = NaN, numpy's mean of an empty selection).  No n x n matrix: workgroup
+ * (tile of 64 rows i, range of j tiles) streams tiles of 64 rows j, both Gram tiles by exact-f32 MFMA 32x32x2 over zero-padded
+ * chunks of 32 columns, class test and sums in the epilogue, per-workgroup float64 partials added in a fixed order.
+ * 1 <= n <= 65536, 1 <= Df, Dp <= 512; workspace (256-byte aligned): ph_sim_audit_workspace_bytes (0 for a refused shape).
+ * One memset and three launches whatever n is; no host read.
+ *
+ * All return PH_EINVAL for a NULL pointer (where not stated optional), a misaligned pointer or a size outside the stated
+ * range before any HIP call; nothing is written then.
+ * ---------------------------------------------------------------------------------------------- */
+#define PH_EPOCHREC_WORDS 56
+#define PH_EPOCHREC_MAX_SCALARS 16
+#define PH_REC_ADD 0
+#define PH_REC_ADD_POSITIVE 1
+int ph_epoch_record_add(void* record, const float* const* scalars, const int32_t* modes, int n_scalars, const float* wvec,
+                        int n_w, const float* pred, const int64_t* grade, int B, int C, const float* row0, const float* row1,
+                        int n_row, ph_stream_t stream);
+int ph_store_rows(const float* rows, const int64_t* index, int B, int D, float* store, int64_t n, int softmax,
+                  int64_t* skipped, ph_stream_t stream);
+size_t ph_sim_audit_workspace_bytes(int n, int Df, int Dp);
+int ph_sim_audit(const float* F, const float* P, const int64_t* labels, int n, int Df, int Dp, double* sums, int64_t* counts,
+                 void* workspace, ph_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * In-library kernel timer for bench.py's `roofline` object: HIP events around every MFMA kernel launch on the
  * launch stream.  Classes: 0 first-generation tap-conv Cout=64 (dgrad parity classes), 1 first-generation tap-conv
  * Cout>=128 stride 1 (1x1, dgrad parity classes), 2 tap-conv stride 2, 3 wgrad, 4 stem forward, 5 stem wgrad,

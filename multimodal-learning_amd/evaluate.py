@@ -742,3 +742,26 @@ def test_teacher_patches(opt, model, loader, device, agg=None, sync=None, avg="m
         patient_result.update(_patient_grading(loader, agg, tuple(zip(names, d)), avg, curves))
         print("Patient level (%s):" % (agg,), *patient_result["metrics_fuse"])
     return patch_result, patient_result
+
+
+def feature_audit_device(fuse, path, labels):
+    """`evaluate_feature` of the MIA-2023 trainer ("MIA 2023/stage2_unimodal_student/train_test_path_multi_distill.py":172-188)
+    over two device stores [n, Df] (teacher) and [n, Dp] (student) and the int labels [n]: the intra-class and inter-class
+    mean cosine similarity of either, and the mean |S_f - S_p| - without an n x n matrix (ph_sim_audit, DESIGN.md section 30;
+    one memset, three launches, one host read).  -> dict(teacher_intra, teacher_inter, student_intra, student_inter,
+    similarity_diff, intra_pairs, inter_pairs); a single class gives NaN for the inter-class means, as numpy's mean of an
+    empty selection.  1 <= n <= 65536, 1 <= D <= 512, else ValueError."""
+    from . import epoch
+    if labels is None:
+        raise ValueError("feature_audit_device: labels [n]")
+    labels = torch.as_tensor(labels)
+    if labels.is_floating_point():
+        raise ValueError("feature_audit_device: integer labels")
+    return epoch.audit_means(epoch.sim_audit(fuse, path, labels.to(fuse.device)))
+
+
+def logit_audit_device(fuse_pred, path_pred):
+    """`evaluate_logits` (:191-196): the mean absolute difference of the two cosine similarity matrices of the prediction
+    stores (the reference's third argument is unused there).  -> float."""
+    from . import epoch
+    return float(epoch.audit_means(epoch.sim_audit(fuse_pred, path_pred, None))["similarity_diff"])

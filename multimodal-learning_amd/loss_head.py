@@ -185,7 +185,7 @@ class FusedDistillLossFn(torch.autograd.Function):
                   "ph_gk_finish")                                     # x len(KD list) = 4 (:61)
         w, total, scaled = fin[5:10], fin[10], fin[11:16]
         H.out = dict(loss_cls=scaled[2], loss_div1=scaled[0], loss_div2=scaled[1], loss_kd1=scaled[3], loss_kd2=scaled[4],
-                     scale=fin[16:21], logit_path=logits, pred_path=pred)
+                     scale=fin[16:21], logit_path=logits, pred_path=pred, terms=Lb)
         ctx.H, ctx.feat, ctx.dl, ctx.G, ctx.w, ctx.crd_saved = H, feat, dl, G, w, [c[0] for c in done]
         return total
 

@@ -498,6 +498,35 @@ def distill_loss_plan(opt, variant, sync=None):
     return LossPlan(kl, feat, "gk" if gk else "sum", calls if ranked else 0, unused, True, report, False)
 
 
+EpochEndPlan = collections.namedtuple("EpochEndPlan", "measure use_patches add_to_average may_save")
+
+# (patch window, checkpoint window) of the three trainers' epoch ends, and the divisor of the averaged metrics
+EPOCH_END_WINDOWS = {"miccai2022": (10, 10), "mia2022": (20, 20), "mia2023": (20, 20)}
+EPOCH_AVERAGE_OVER = 3.0                               # MICCAI :404, v2 :584, MIA-2023 :534
+
+
+def epoch_end_plan(opt, epoch, variant):
+    """What the three trainers' train() decides after the last batch of `epoch` from the options alone (EpochEndPlan) - pure,
+    like distill_loss_plan.  Lines: MICCAI-2022/train_test_path_multi_distill.py | "MIA 2022/train_test_path_multi_distill_v2.py"
+    | "MIA 2023/stage2_unimodal_student/train_test_path_multi_distill.py".
+      measure         `opt.measure or epoch == niter + niter_decay - 1` (:348 | :527 | :478): the test pass and everything below
+                      run only then.  (The loop's last epoch is niter + niter_decay, :228: without opt.measure the ONE measured
+                      epoch is the one before it.)
+      use_patches     the nine-patch loader replaces the plain one: epoch > niter + niter_decay - 10 (:360) | - 20 (:539 | :489)
+      add_to_average  epoch > niter_decay - 3 (:368 | :547 | :497); the sum is divided by 3.0 whatever the count (:404 | :584 | :534)
+      may_save        the best-checkpoint test runs: epoch > niter_decay - 10 (:387) | - 20 (:566 | :516) - note niter_decay
+                      alone, not niter + niter_decay.
+    What depends on the epoch's numbers stays with the caller: the early stop (`task == "grad"` and the SUM loss_epoch <
+    opt.patience, :383 | :562 | :512, tested BEFORE the checkpoint) and whether the mean metric beats best_acc."""
+    if variant not in EPOCH_END_WINDOWS:
+        raise ValueError("variant must be 'miccai2022', 'mia2022' or 'mia2023'")
+    patch_w, save_w = EPOCH_END_WINDOWS[variant]
+    total = opt.niter + opt.niter_decay
+    measure = bool(opt.measure) or epoch == total - 1
+    return EpochEndPlan(measure, measure and epoch > total - patch_w, measure and epoch > opt.niter_decay - 3,
+                        measure and epoch > opt.niter_decay - save_w)
+
+
 # ----------------------------------------------------------------------------------------- the hot loop
 def _backward_and_update(step, loss):
     """The end of a step (train_test_path_multi_distill.py:326-329): backward, the replicas' gradient sum, fused update + EMA."""
@@ -554,6 +583,8 @@ class DistillStep:
         self.sampler = None       # optional ContrastIndexSampler: draws sample_idx when the batch carries None
         self.loader = None        # optional augment.ResidentTileLoader: step(None) takes its batches from it
         self._loader_bt = self._sample_idx_buf = self._capture_pre = None
+        self.record = None        # optional epoch.EpochRecord: every step ends with its launch (eager and captured alike)
+        self.stores = None        # optional epoch.FeatureStores (mia2023): the per-sample stores, filled inside the step
         self._e_dev = None        # the epoch weight (mia2022) / re-weighting switch (mia2023) as a persistent device scalar
         self._mo_init = None
         self._lh_const = {}       # loss_head._const: small constant device vectors by value (not part of state_dict)
@@ -737,9 +768,32 @@ class DistillStep:
             self._stamp(6)
             o = Hc.out
             extra = {k: o[k] for k in ("rows_div1", "rows_kd1", "w1", "w2") if k in o}       # (the MIA-2023 body's per-sample values)
-            return self._result(loss, o["loss_cls"], [o["loss_div1"], o["loss_div2"], o["loss_kd1"], o["loss_kd2"]], o["scale"],
-                                (o["logit_path"], o["pred_path"], path_feat), teachers, extra)
+            res = self._result(loss, o["loss_cls"], [o["loss_div1"], o["loss_div2"], o["loss_kd1"], o["loss_kd2"]], o["scale"],
+                               (o["logit_path"], o["pred_path"], path_feat), teachers, extra)
+            if self.record is None and self.stores is None:
+                return res
+            # the head's UNSCALED terms: `terms` [div1, div2, CE, kd1, kd2] of the MICCAI / MIA-2022 head (the CRD terms before
+            # the MIA-2022 epoch weight), the reported ones of the MIA-2023 head
+            if "terms" in o:
+                t = o["terms"]
+                kd1, kd2 = (t[3] * e, t[4] * e) if self.variant == "mia2022" else (t[3], t[4])
+                return self._recorded(res, t[0], t[1], kd1, kd2, grade, index)
+            return self._recorded(res, o["loss_div1"], o["loss_div2"], o["loss_kd1"], o["loss_kd2"], grade, index)
         return self._generic_loss(e, r1, r2, grade, index, sample_idx, bnorm, path_feat, logit_path, pred_path, teachers)
+
+    def _recorded(self, res, div1, div2, kd1, kd2, grade, index):
+        """The end of a step with `step.record` / `step.stores` attached: what the trainers accumulate per batch, taken from
+        the terms as the body computed them - loss_div = div1 + div2 unscaled (train_test_path_multi_distill.py:266 / :268 /
+        :270; a term the branch lacks is an exact zero), loss_kd = opt.beta * (kd1 + kd2) (:315) - handed to the record in
+        one launch, and the MIA-2023 stores' four scatters.  The two values join the result as `rec_loss_div`, `rec_loss_kd`."""
+        if self.record is not None:
+            with torch.no_grad():
+                res["rec_loss_div"] = (div1 + div2).detach().reshape(())
+                res["rec_loss_kd"] = (self.opt.beta * (kd1 + kd2)).detach().reshape(())
+            self.record.add(res, res["rec_loss_div"], res["rec_loss_kd"], grade)
+        if self.stores is not None:
+            self.stores.add(res, index)
+        return res
 
     @staticmethod
     def _result(loss, loss_cls, terms, scale, student, teachers, extra=None):
@@ -839,11 +893,13 @@ class DistillStep:
 
         # ---- 6. report (the plan's convention)
         student = (logit_path, pred_path, path_feat)
+        rec = ((lambda res: res) if self.record is None and self.stores is None else
+               (lambda res: self._recorded(res, div1, div2, kd1, kd2, grade, index)))
         if plan.report == "scaled":
-            return self._result(loss, loss_cls, scaled, scale, student, teachers)
+            return rec(self._result(loss, loss_cls, scaled, scale, student, teachers))
         if plan.report == "unscaled_rows":
-            return self._result(loss, loss_cls, [div1, div2, kd1, kd2], scale, student, teachers,
-                                dict(rows_div1=rows_div1.detach(), rows_kd1=rows_kd1.detach(), w1=w1.detach(), w2=w2.detach()))
+            return rec(self._result(loss, loss_cls, [div1, div2, kd1, kd2], scale, student, teachers,
+                                    dict(rows_div1=rows_div1.detach(), rows_kd1=rows_kd1.detach(), w1=w1.detach(), w2=w2.detach())))
         # "baseline": the KL terms as computed, beta * criterion.  Under data parallelism rkd / pkt / similarity are losses of the
         # GLOBAL batch (distiller_zoo).  The value that entered backward() is what the criterion returns - this replica's part of
         # the global loss with the summed gradient behind it (rkd), or the global loss itself (pkt, similarity: every replica
@@ -855,7 +911,7 @@ class DistillStep:
             w = float(self.sync.world_size)
             loss = loss - b * (kd - kd / w)
             kd = kd / w
-        return self._result(loss, loss_cls, [div1, div2, b * kd, z], scale, student, teachers)
+        return rec(self._result(loss, loss_cls, [div1, div2, b * kd, z], scale, student, teachers))
 
     def _add_reg(self, loss):
         """+ opt.lambda_reg * define_reg(opt, model) (train_test_path_multi_distill.py:312-313)."""
