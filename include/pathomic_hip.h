@@ -819,9 +819,38 @@ int ph_surv_logrank_km(const int32_t* at_risk, const int32_t* observed, const in
  * 1 <= n <= 65536, 1 <= Df, Dp <= 512; workspace (256-byte aligned): ph_sim_audit_workspace_bytes (0 for a refused shape).
  * One memset and three launches whatever n is; no host read.
  *
+ * ph_stage1_record_add: the same for the stage-1 teacher step.  ONE launch of ONE workgroup
+ * (capturable) that adds a step into a persistent record of PH_STAGE1REC_WORDS 8-byte words, zeroed by the caller with a
+ * memset at epoch start and read once at epoch end:
+ *   words [0, 16)   float64: sum k of the device scalars - scalars / modes / n_scalars exactly as ph_epoch_record_add takes
+ *                   them, by the same device routine: widened to float64, added in call order, PH_REC_ADD / PH_REC_ADD_POSITIVE.
+ *   words [16, 32)  int64: how often scalar k was added.
+ *   words [32, 35)  int64: per head h < n_heads the rows of pred_h f32 [B][C] whose arg-max (the FIRST maximum, as word 34 of
+ *                   the stage-2 record and ph_confusion_counts) equals grade[b], int64 [B].  Exactly the first n_heads of
+ *                   pred0..pred2 are given, the others NULL; grade is given iff n_heads > 0.
+ *   word 35         int64: rows whose label lies outside [0, C) - counted ONCE per row and left out of every head's count.
+ *   word 36         int64: the calls (steps);   word 37: int64, the rows seen (+= B when heads or survival rows are given).
+ *   word 38         int64: the CURSOR of the survival store = the rows appended since the memset.
+ *   word 39         int64: overflow = the rows dropped because the store was full.
+ *   words [40, 48)  spare (left zero).
+ * Survival rows: h_fuse, h_path, h_omic, censor, survtime f32 [B] and store f32 [5][cap] - all six pointers given, or none.
+ * Row b of the step goes to column cursor + b of the store (store[k * cap + cursor + b], k in the order above) while that is
+ * < cap; the rows that do not fit are dropped and counted in word 39; nothing is written at or past cap, whatever word 38
+ * holds.  The cursor lives in the record: the memset rewinds it, and a replayed graph appends at the right place without any
+ * per-step host value.  Every thread reads the cursor before a workgroup barrier and thread 0 advances it after it - one
+ * workgroup, so no ordering between blocks is relied on.
+ * 0 <= n_scalars <= 16, 0 <= n_heads <= 3; with heads or survival rows 1 <= B <= 65536; with heads 1 <= C <= 16; with survival
+ * rows 1 <= cap <= 1048576 (the range of ph_cindex_counts).  record 8-byte aligned, grade 8-byte, every float pointer 4-byte.
+ * A call with nothing to add, or with the survival pointers given only in part, is refused.
+ *
  * All return PH_EINVAL for a NULL pointer (where not stated optional), a misaligned pointer or a size outside the stated
  * range before any HIP call; nothing is written then.
  * ---------------------------------------------------------------------------------------------- */
+#define PH_STAGE1REC_WORDS 48
+int ph_stage1_record_add(void* record, const float* const* scalars, const int32_t* modes, int n_scalars, const float* pred0,
+                         const float* pred1, const float* pred2, int n_heads, const int64_t* grade, int B, int C,
+                         const float* h_fuse, const float* h_path, const float* h_omic, const float* censor,
+                         const float* survtime, float* store, int cap, ph_stream_t stream);
 #define PH_EPOCHREC_WORDS 56
 #define PH_EPOCHREC_MAX_SCALARS 16
 #define PH_REC_ADD 0

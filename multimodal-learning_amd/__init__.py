@@ -17,7 +17,7 @@ from .networks_new import (define_net, define_optimizer, define_reg, define_sche
 from .kd_loss import DistillKL
 from .CL_utils import CRDLoss, ContrastLoss_v2, Embed, Normalize, ContrastMemory_v3
 from .train_step import (AEKD_loss, momentum_AEKD_loss, update_ema_variables, DistillStep, FusedAdam, FusedAdagrad, FlatParams,
-                         TeacherStage1Step, epoch_end_plan)
+                         TeacherStage1Step, epoch_end_plan, teacher_epoch_end_plan)
 from . import dist
 from . import mia2023
 from . import sampler
@@ -29,13 +29,13 @@ from . import superpixel
 from . import augment
 from .options import stage2_opt
 from . import epoch
-from .epoch import EpochRecord, FeatureStores
+from .epoch import EpochRecord, FeatureStores, Stage1Record
 from . import trainers
-from .trainers import train
+from .trainers import train, train_teacher
 
 __all__ = ["build", "lib", "set_precision", "get_precision", "init_net", "init_max_weights", "count_parameters",
            "ResNet", "ResNet18", "ResNet34", "BasicBlock", "BilinearFusion", "PolynomialFusion", "define_net", "define_optimizer", "define_reg",
            "define_scheduler", "define_act_layer", "define_bifusion", "MaxNet", "PathomicNet", "get_resnet",
            "DistillKL", "CRDLoss", "ContrastLoss_v2", "Embed", "Normalize", "ContrastMemory_v3", "AEKD_loss", "momentum_AEKD_loss",
            "update_ema_variables", "DistillStep", "FusedAdam", "FusedAdagrad", "FlatParams", "TeacherStage1Step", "dist", "stage2_opt",
-           "epoch_end_plan", "EpochRecord", "FeatureStores", "train"]
+           "epoch_end_plan", "EpochRecord", "FeatureStores", "train", "teacher_epoch_end_plan", "Stage1Record", "train_teacher"]

@@ -91,6 +91,7 @@ SIGNATURES = {
     "ph_surv_logrank_km_workspace_bytes": (sz, [i32, i32, i32]),
     "ph_surv_logrank_km": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     "ph_epoch_record_add": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp]),
+    "ph_stage1_record_add": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
     "ph_store_rows": (i32, [vp, vp, i32, i32, vp, i64, i32, vp, vp]),
     "ph_sim_audit_workspace_bytes": (sz, [i32, i32, i32]),
     "ph_sim_audit": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),

@@ -4,6 +4,9 @@
 //   ph_epoch_record_add  one capturable launch per step that adds the step's device scalars, the GK-Refine weight vector, the
 //                        count of correct predictions and the mean query weights into a persistent record of float64 sums and
 //                        int64 counts; read once per epoch,
+//   ph_stage1_record_add the same for the stage-1 teacher step: the scalars, the correct counts of up to
+//                        three heads, and under survival the step's five per-sample columns appended to a device store at a
+//                        cursor that lives in the record,
 //   ph_store_rows        `store[index] = rows` (optionally softmax(rows, 1)) of the MIA-2023 per-sample stores,
 //   ph_sim_audit         evaluate_feature / evaluate_logits (:162-196) over two stores without an n x n matrix: both cosine
 //                        Gram tiles by exact-f32 MFMA 32x32x2 (the tiles of zoo_rkd.hip), class test and sums in the epilogue.
@@ -20,6 +23,8 @@ constexpr int ER_THREADS = 256;
 constexpr int ER_MAX_SCALARS = PH_EPOCHREC_MAX_SCALARS;
 constexpr int ER_MAX_B = 1 << 20;
 constexpr int ER_MAX_C = 16;
+constexpr int S1_MAX_B = 1 << 16;     // rows of one ph_stage1_record_add call (three 20-bit counts share a word)
+constexpr int S1_MAX_CAP = 1 << 20;   // columns of the survival store: the range of ph_cindex_counts
 constexpr int SR_MAX_B = 1 << 16;
 constexpr int SR_MAX_D = 4096;
 constexpr int SA_T = 64;            // rows of an i / j tile
@@ -34,6 +39,27 @@ struct ErScalars {
   int mode[ER_MAX_SCALARS];
 };
 
+// The scalar rule of both records, one copy: thread k < ns reads scalar k, widens it to float64 and adds it to sums[k]; added[k]
+// counts the additions.  PH_REC_ADD: a NaN propagates; PH_REC_ADD_POSITIVE: `if v > 0.0: acc += v` - false for 0.0, -0.0,
+// negatives and a NaN.
+__device__ __forceinline__ void rec_add_scalars(double* sums, long long* added, const ErScalars& sc, int ns, int tid) {
+  if (tid < ns) {
+    const float v = *sc.p[tid];
+    if (sc.mode[tid] == PH_REC_ADD || v > 0.0f) { sums[tid] += (double)v; added[tid] += 1; }
+  }
+}
+
+// The FIRST maximum of a row of C values (a strict `>` scan from column 0, as ph_confusion_counts; a NaN never wins).
+__device__ __forceinline__ int first_argmax(const float* __restrict__ row, int C) {
+  float best = row[0];
+  int arg = 0;
+  for (int c = 1; c < C; ++c) {
+    const float v = row[c];
+    if (v > best) { best = v; arg = c; }
+  }
+  return arg;
+}
+
 // One workgroup.  Record words (8 bytes each): [0, 16) scalar sums, [16, 32) weight-vector sums, [32, 34) sums of the row
 // means (float64); [34] correct, [35] bad labels, [36] steps, [37] rows seen (int64); [38, 40) spare; [40, 56) additions per
 // scalar (int64).
@@ -47,22 +73,12 @@ __global__ __launch_bounds__(ER_THREADS) void epoch_record_add_kernel(double* re
   __shared__ unsigned long long redu[ER_THREADS];
   const int tid = threadIdx.x;
   long long* reci = reinterpret_cast<long long*>(rec);
-  if (tid < ns) {
-    const float v = *sc.p[tid];
-    // PH_REC_ADD: a NaN propagates; PH_REC_ADD_POSITIVE: `if v > 0.0: acc += v` - false for 0.0, -0.0, negatives and a NaN
-    if (sc.mode[tid] == PH_REC_ADD || v > 0.0f) { rec[tid] += (double)v; reci[40 + tid] += 1; }
-  }
+  rec_add_scalars(rec, reci + 40, sc, ns, tid);
   if (tid >= 64 && tid < 64 + nw) rec[16 + tid - 64] += (double)wvec[tid - 64];
   if (pred) {                                   // (uniform over the workgroup: the trees below contain barriers)
     unsigned long long ok = 0, bad = 0;
     for (int n = tid; n < B; n += ER_THREADS) {
-      const float* row = pred + (size_t)n * C;
-      float best = row[0];
-      int arg = 0;
-      for (int c = 1; c < C; ++c) {
-        const float v = row[c];
-        if (v > best) { best = v; arg = c; }    // the FIRST maximum, as ph_confusion_counts
-      }
+      const int arg = first_argmax(pred + (size_t)n * C, C);
       const int64_t g = grade[n];
       if (g < 0 || g >= (int64_t)C) ++bad; else if (g == (int64_t)arg) ++ok;
     }
@@ -83,6 +99,52 @@ __global__ __launch_bounds__(ER_THREADS) void epoch_record_add_kernel(double* re
     if (tid == 0) rec[32 + k] += s / (double)nrow;
   }
   if (tid == 0) reci[36] += 1;
+}
+
+struct S1Heads { const float* p[3]; };
+struct S1Cols { const float* p[5]; };
+
+// One workgroup (a step's rows are few, and a single workgroup needs no ordering between blocks: every thread reads the cursor,
+// a barrier follows, and only then does thread 0 advance it).  Record words (8 bytes each): [0, 16) scalar sums (float64);
+// [16, 32) additions per scalar; [32, 35) correct rows of head 0 / 1 / 2; [35] bad labels; [36] steps; [37] rows seen;
+// [38] the store cursor = rows appended so far; [39] overflow = rows dropped because the store was full (int64); [40, 48) spare.
+__global__ __launch_bounds__(ER_THREADS) void stage1_record_add_kernel(double* rec, ErScalars sc, int ns, S1Heads hd, int nh,
+                                                                       const int64_t* __restrict__ grade, int B, int C,
+                                                                       S1Cols cols, float* __restrict__ store, int cap) {
+  __shared__ unsigned long long redu[ER_THREADS];
+  const int tid = threadIdx.x;
+  long long* reci = reinterpret_cast<long long*>(rec);
+  const long long cur = reci[38];               // read by every thread BEFORE the barrier, written by thread 0 after it
+  __syncthreads();
+  rec_add_scalars(rec, reci + 16, sc, ns, tid);
+  if (nh > 0) {                                 // (uniform over the workgroup: the trees below contain barriers)
+    unsigned long long ok = 0, bad = 0;         // three 20-bit fields: B <= 65536 rows per call
+    for (int n = tid; n < B; n += ER_THREADS) {
+      const int64_t g = grade[n];
+      if (g < 0 || g >= (int64_t)C) { ++bad; continue; }          // once, whatever the number of heads
+      for (int h = 0; h < nh; ++h)
+        if ((int64_t)first_argmax(hd.p[h] + (size_t)n * C, C) == g) ok += 1ull << (20 * h);
+    }
+    const unsigned long long t = block_sum_tree<ER_THREADS>(ok, redu), tb = block_sum_tree<ER_THREADS>(bad, redu);
+    if (tid == 0) {
+      for (int h = 0; h < nh; ++h) reci[32 + h] += (long long)((t >> (20 * h)) & 0xfffffull);
+      reci[35] += (long long)tb;
+    }
+  }
+  if (store) {
+    // rows [0, fit) of the step land at [cur, cur + fit); nothing is written at or past cap, whatever the cursor holds
+    const long long room = (cur >= 0 && cur < (long long)cap) ? (long long)cap - cur : 0;
+    const int fit = room < (long long)B ? (int)room : B;
+    for (int n = tid; n < fit; n += ER_THREADS) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) store[(size_t)k * cap + (size_t)(cur + n)] = cols.p[k][n];
+    }
+    if (tid == 0) { reci[38] = cur + fit; reci[39] += B - fit; }
+  }
+  if (tid == 0) {
+    if (nh > 0 || store) reci[37] += B;
+    reci[36] += 1;
+  }
 }
 
 // One wave per source row b.  The row is written unless its index is out of range (counted) or a LATER row of the batch
@@ -276,6 +338,43 @@ int ph_epoch_record_add(void* record, const float* const* scalars, const int32_t
   }
   hipLaunchKernelGGL(epoch_record_add_kernel, dim3(1), dim3(ER_THREADS), 0, st, static_cast<double*>(record), sc, n_scalars,
                      wvec, n_w, pred, grade, B, C, row0, row1, n_row);
+  PH_LAUNCH_CHECK();
+  return PH_OK;
+}
+
+int ph_stage1_record_add(void* record, const float* const* scalars, const int32_t* modes, int n_scalars, const float* pred0,
+                         const float* pred1, const float* pred2, int n_heads, const int64_t* grade, int B, int C,
+                         const float* h_fuse, const float* h_path, const float* h_omic, const float* censor,
+                         const float* survtime, float* store, int cap, hipStream_t st) {
+  static_assert(PH_STAGE1REC_WORDS >= 40, "the header's record is the kernel's");
+  if (!record || !aligned(record, 8)) return PH_EINVAL;
+  if (n_scalars < 0 || n_scalars > ER_MAX_SCALARS || n_heads < 0 || n_heads > 3) return PH_EINVAL;
+  if (n_scalars > 0 && (!scalars || !modes)) return PH_EINVAL;
+  const float* heads[3] = {pred0, pred1, pred2};
+  for (int h = 0; h < 3; ++h)                                              // exactly the first n_heads are given
+    if ((heads[h] != nullptr) != (h < n_heads) || !aligned(heads[h], 4)) return PH_EINVAL;
+  if ((grade != nullptr) != (n_heads > 0) || !aligned(grade, 8)) return PH_EINVAL;
+  const void* surv[6] = {h_fuse, h_path, h_omic, censor, survtime, store};
+  int given = 0;
+  for (int k = 0; k < 6; ++k) {
+    if (surv[k]) ++given;
+    if (!aligned(surv[k], 4)) return PH_EINVAL;
+  }
+  if (given != 0 && given != 6) return PH_EINVAL;                          // all of them, or none
+  if ((n_heads > 0 || given) && (B < 1 || B > S1_MAX_B)) return PH_EINVAL;
+  if (n_heads > 0 && (C < 1 || C > ER_MAX_C)) return PH_EINVAL;
+  if (given && (cap < 1 || cap > S1_MAX_CAP)) return PH_EINVAL;
+  if (n_scalars == 0 && n_heads == 0 && !given) return PH_EINVAL;          // nothing to add
+  ErScalars sc;
+  for (int k = 0; k < ER_MAX_SCALARS; ++k) { sc.p[k] = nullptr; sc.mode[k] = 0; }
+  for (int k = 0; k < n_scalars; ++k) {
+    if (!scalars[k] || !aligned(scalars[k], 4) || (modes[k] != PH_REC_ADD && modes[k] != PH_REC_ADD_POSITIVE)) return PH_EINVAL;
+    sc.p[k] = scalars[k]; sc.mode[k] = modes[k];
+  }
+  S1Heads hd{{pred0, pred1, pred2}};
+  S1Cols cols{{h_fuse, h_path, h_omic, censor, survtime}};
+  hipLaunchKernelGGL(stage1_record_add_kernel, dim3(1), dim3(ER_THREADS), 0, st, static_cast<double*>(record), sc, n_scalars, hd,
+                     n_heads, grade, B, C, cols, store, cap);
   PH_LAUNCH_CHECK();
   return PH_OK;
 }

@@ -1,7 +1,8 @@
 """What train() of the three stage-2 trainers keeps between the batch body and the test pass, on the device (DESIGN.md
 section 30; csrc/epochrec.hip): the epoch bookkeeping as one launch at the end of every step - eager or inside the captured
 graph - and one device-to-host copy per epoch (`EpochRecord`), the MIA-2023 per-sample stores (`FeatureStores`) and the
-similarity audit over them (`sim_audit`, behind evaluate.feature_audit_device / logit_audit_device).
+similarity audit over them (`sim_audit`, behind evaluate.feature_audit_device / logit_audit_device).  The stage-1
+trainers' counterpart is `Stage1Record` at the end of this file.
 
 The reference reads every one of these values on the host each step (MICCAI-2022 train_test_path_multi_distill.py:305,
 :317-324, :340; "MIA 2023/stage2_unimodal_student/train_test_path_multi_distill.py":338-342, :380-383, :423, :435-442, :459)."""
@@ -181,3 +182,135 @@ class FeatureStores:
             if getattr(self, name) is None:
                 setattr(self, name, torch.zeros(self.n_data, src.shape[1], device=self.device, dtype=torch.float32))
             store_rows(getattr(self, name), index, src, self.skipped, softmax=sm)
+
+
+# ------------------------------------------------------------------------------------------------ stage 1
+S1_WORDS = 48                       # PH_STAGE1REC_WORDS
+S1_MAX_B, S1_MAX_CAP = 65536, 1 << 20
+S1_COLUMNS = ("h_fuse", "h_path", "h_omic", "censor", "survtime")
+
+
+def stage1_record_add(buf, scalars=(), modes=(), heads=(), grade=None, cols=None, store=None):
+    """ph_stage1_record_add on the current stream: `scalars` / `modes` as in record_add, `heads` up to three float32 [B, C]
+    predictions against `grade` int64 [B], `cols` the five float32 [B] survival columns (S1_COLUMNS) appended to `store`
+    float32 [5, cap] at the cursor the record keeps.  A refused argument is a ValueError; nothing is launched then."""
+    ns = len(scalars)
+    if ns != len(modes) or ns > 16 or len(heads) > 3:
+        raise ValueError("stage1_record_add: up to 16 scalars with one mode each, up to three heads")
+    for t in scalars:
+        if _f32c(t, "scalar").numel() != 1:
+            raise ValueError("stage1_record_add: every scalar is a one-element tensor")
+    sp = (C.c_void_p * max(ns, 1))(*[t.data_ptr() for t in scalars])
+    md = (C.c_int32 * max(ns, 1))(*[int(m_) for m_ in modes])
+    B = Cc = cap = 0
+    if heads:
+        B, Cc = heads[0].shape if heads[0].dim() == 2 else (0, 0)
+        for h in heads:
+            if _f32c(h, "head").dim() != 2 or tuple(h.shape) != (B, Cc):
+                raise ValueError("stage1_record_add: every head is float32 [B, C]")
+        if grade is None or grade.dtype != torch.int64 or grade.numel() != B or not grade.is_contiguous():
+            raise ValueError("stage1_record_add: heads [B, C] float32 with grade int64 [B]")
+        require_cuda(grade, "grade")
+    elif grade is not None:
+        raise ValueError("stage1_record_add: grade without a head")
+    if (cols is None) != (store is None):
+        raise ValueError("stage1_record_add: the five survival columns and the store, or neither")
+    if cols is not None:
+        if len(cols) != 5:
+            raise ValueError("stage1_record_add: five survival columns %s" % (S1_COLUMNS,))
+        cols = [_f32c(c, "column").reshape(-1) for c in cols]
+        n = cols[0].numel()
+        if any(c.numel() != n for c in cols) or (heads and n != B):
+            raise ValueError("stage1_record_add: the survival columns have one length, the heads' B")
+        if _f32c(store, "store").dim() != 2 or store.shape[0] != 5:
+            raise ValueError("stage1_record_add: store float32 [5, cap]")
+        B, cap = n, store.shape[1]
+    hp = [ptr(h) for h in heads] + [None] * (3 - len(heads))
+    cp = [ptr(c) for c in cols] if cols is not None else [None] * 5
+    if max(B, Cc, cap) >= 2 ** 31:
+        raise ValueError("stage1_record_add: sizes beyond int32")
+    rc = lib().ph_stage1_record_add(ptr(buf), C.cast(sp, C.c_void_p) if ns else None, C.cast(md, C.c_void_p) if ns else None, ns,
+                                    hp[0], hp[1], hp[2], len(heads), ptr(grade) if heads else None, B, Cc, cp[0], cp[1], cp[2],
+                                    cp[3], cp[4], ptr(store), cap, stream())
+    if rc == -22:
+        raise ValueError("stage1_record_add: at most 16 scalars and 3 heads, 1 <= B <= %d, 1 <= C <= 16, 1 <= cap <= %d, and "
+                         "something to add (got B %d, C %d, cap %d)" % (S1_MAX_B, S1_MAX_CAP, B, Cc, cap))
+    check(rc, "ph_stage1_record_add")
+
+
+class Stage1Record:
+    """The epoch sums of a TeacherStage1Step on the device.  `step.record = Stage1Record(step, n_rows)` makes every step - eager,
+    masking or replayed from either captured graph - end with one ph_stage1_record_add; `reset()` is a memset on the stream at
+    epoch start (it also rewinds the survival store's cursor), `read()` the one device-to-host copy of the epoch.  Attach it
+    before the graph is captured (before the third step).  `n_rows`: the rows an epoch offers (the survival store's columns).
+
+    What is added, in the order of "MIA 2022/train_test_tSVD.py":455-467 (MICCAI-2022/train_test_MT.py:224-233 and MIA-2023
+    train_test_MT_SP_Masking.py:310-325 agree where they have the term): loss, the fuse / path / omic branch loss (the NLL
+    value under grading, the Cox term under survival: the reference's other addend is the Python integer 0), and only when
+    > 0.0 loss_tsvd, loss_CRD, loss_pred_KD, loss_pred_KD_masking.  On a step that ran the t-SVD auxiliary update the two
+    nuclear norms follow (:392, :409 - `avg_path_TNN += path_TNN` without a test, under conditions that are always true (:379,
+    :400), so both are added whatever tSVD_mode is; update_aux's source is absent from the reference, its TNN is a float32
+    device scalar here and is widened like every other scalar)."""
+    SCALARS = ("loss", "loss_fuse", "loss_path", "loss_omic", "loss_tsvd", "loss_CRD", "loss_KD", "loss_pred_KD_masking",
+               "avg_path_TNN", "avg_omic_TNN")
+    MODES = (REC_ADD,) * 4 + (REC_ADD_POSITIVE,) * 4 + (REC_ADD,) * 2
+
+    def __init__(self, step, n_rows):
+        if step.sync is not None:
+            raise NotImplementedError("Stage1Record under data parallelism (the replicas' records are not summed)")
+        self.surv = bool(step.surv)
+        self.n_rows = int(n_rows)
+        if self.surv and not 1 <= self.n_rows <= S1_MAX_CAP:
+            raise ValueError("Stage1Record: 1 <= n_rows <= %d (the range of ph_cindex_counts), got %d" % (S1_MAX_CAP, self.n_rows))
+        self.buf = torch.zeros(S1_WORDS, device=step.device, dtype=torch.int64)
+        self.store = torch.zeros(5, self.n_rows, device=step.device, dtype=torch.float32) if self.surv else None
+        self.rows_host = 0
+
+    def reset(self):
+        self.buf.zero_()
+        self.rows_host = 0
+
+    def count_rows(self, n):
+        self.rows_host += int(n)
+
+    def add(self, out, grade, tnns=None, survtime=None, censor=None):
+        """The end of a step: `out` the step's result, `tnns` (path_TNN, omic_TNN) on a step that ran the auxiliary update."""
+        branch = ("loss_cox_fuse", "loss_cox_path", "loss_cox_omic") if self.surv else ("loss_nll_fuse", "loss_nll_path",
+                                                                                        "loss_nll_omic")
+        sc = [out[k] for k in ("loss",) + branch + ("loss_tsvd", "loss_CRD", "loss_pred_KD", "loss_pred_KD_masking")]
+        if tnns is not None:
+            sc += list(tnns)
+        sc = [t.reshape(1) for t in sc]
+        if self.surv:
+            cols = [out["pred"], out["pred_path"], out["pred_omic"], censor, survtime]
+            stage1_record_add(self.buf, sc, self.MODES[:len(sc)], cols=cols, store=self.store)
+        else:
+            if grade.dtype != torch.int64:
+                grade = grade.long()
+            stage1_record_add(self.buf, sc, self.MODES[:len(sc)], heads=(out["pred"], out["pred_path"], out["pred_omic"]),
+                              grade=grade)
+
+    def read(self):
+        w = self.buf.cpu().numpy()
+        f = w.view(np.float64)
+        if int(w[39]):
+            raise RuntimeError("Stage1Record: %d survival rows did not fit the store of %d columns" % (int(w[39]), self.n_rows))
+        d = {name + "_epoch" if name.startswith("loss") else name: float(f[k]) for k, name in enumerate(self.SCALARS)}
+        d.update({name + "_added": int(w[16 + k]) for k, name in enumerate(self.SCALARS)})
+        d.update(grad_acc_epoch=int(w[32]), grad_path_epoch=int(w[33]), grad_omic_epoch=int(w[34]), bad_labels=int(w[35]),
+                 steps=int(w[36]), rows=int(w[37]), stored=int(w[38]), overflow=int(w[39]))
+        return d
+
+    def cindex(self):
+        """The epoch's three C-indices (fuse, path, omic; CIndex_lifeline, :523-525) from the device store: one
+        ph_cindex_counts launch over its first `rows_host` columns - the host's own count of the batch sizes."""
+        from . import ops, utils
+        if not self.surv:
+            raise ValueError("Stage1Record.cindex belongs to the survival task")
+        n = self.rows_host
+        if not 2 <= n <= min(self.n_rows, S1_MAX_CAP):
+            raise ValueError("Stage1Record.cindex: 2 <= rows <= %d (the store's columns; the range of ph_cindex_counts), got %d"
+                             % (min(self.n_rows, S1_MAX_CAP), n))
+        col = [self.store[k, :n] for k in range(5)]
+        counts = ops.cindex_counts(col[4], col[3], col[:3]).cpu().numpy()
+        return tuple(utils.cindex_from_counts(c) for c in counts)

@@ -527,6 +527,28 @@ def epoch_end_plan(opt, epoch, variant):
                         measure and epoch > opt.niter_decay - save_w)
 
 
+TeacherEpochEndPlan = collections.namedtuple("TeacherEpochEndPlan", "measure use_patches may_save")
+TEACHER_PATCH_WINDOW, TEACHER_SAVE_AFTER = 15, 15
+
+
+def teacher_epoch_end_plan(opt, epoch, variant):
+    """What the three stage-1 trainers' train() decides after the last batch of `epoch` from the options alone - pure, like
+    epoch_end_plan.  The three agree; lines: MICCAI-2022/train_test_MT.py | "MIA 2022/train_test_tSVD.py" |
+    "MIA 2023/stage1_multi_modal_teacher/train_test_MT_SP_Masking.py".
+      measure      `opt.measure or epoch == niter + niter_decay - 1` (:269 | :509 | :358): the test pass and everything below run
+                   only then (the loop's last epoch is niter + niter_decay: without opt.measure the ONE measured epoch is the
+                   one before it).
+      use_patches  the nine-patch loader replaces the plain one: epoch > niter + niter_decay - 15 (:288 | :533 | :378).  The
+                   reference rebinds `test_loader` for good; the window reaches the last epoch, so that changes nothing.
+      may_save     the best-checkpoint test runs: epoch > 15 (:295 | :540 | :385) - the epoch itself, not a distance to the end.
+    Both are False on an epoch that is not measured.  Whether the test metric beats best_acc stays with the caller."""
+    if variant not in EPOCH_END_WINDOWS:
+        raise ValueError("variant must be 'miccai2022', 'mia2022' or 'mia2023'")
+    total = opt.niter + opt.niter_decay
+    measure = bool(opt.measure) or epoch == total - 1
+    return TeacherEpochEndPlan(measure, measure and epoch > total - TEACHER_PATCH_WINDOW, measure and epoch > TEACHER_SAVE_AFTER)
+
+
 # ----------------------------------------------------------------------------------------- the hot loop
 def _backward_and_update(step, loss):
     """The end of a step (train_test_path_multi_distill.py:326-329): backward, the replicas' gradient sum, fused update + EMA."""
@@ -1295,6 +1317,7 @@ class TeacherStage1Step:
             self.path_TNN = self.omic_TNN = None
             self._batch_idx = 0
         self.optimizer = define_optimizer(opt, module_list if self.crd_on else self.model)      # :86-94
+        self.module_list = module_list      # (what the reference's train() returns first)
         self.scheduler = define_scheduler(opt, self.optimizer)
         # a fusion gate that is off leaves linear_h_k / linear_z_k unread (fusion.py:45-46,52-53): they stay in the optimiser's
         # list as in the reference, where their .grad stays None and the update skips them - unless the regulariser reaches
@@ -1316,6 +1339,7 @@ class TeacherStage1Step:
         flat = self.optimizer.flat
         self.optimizer.ema_range = (0, flat.offsets[n_model] if n_model < len(flat.offsets) else flat.numel)
         self._want_graph = False
+        self.record = None        # optional epoch.Stage1Record: every step ends with its launch (eager and captured alike)
         self._g_sets = StepGraphs(self.device, "stage-1", self._IN_NAMES, (self.model, self.ema_model))
         self._g_scal = self._g_ring = None      # the graph path's CRD weight | tau | mu of the penalty on the device
         self._ema_side = self._tsvd_side = None      # side streams, created on first use
@@ -1450,6 +1474,8 @@ class TeacherStage1Step:
                 self.mu = mu_pen                                                                 # :413
             self._batch_idx = bidx + 1
         self.iter_num += 1
+        if self.record is not None:
+            self.record.count_rows(x_path.shape[0])      # the host's own row count (a replayed launch calls no Python)
         return out
 
     _IN_NAMES = ("x_path", "ema_x_path", "x_omic", "grade", "index", "sample_idx")
@@ -1543,7 +1569,8 @@ class TeacherStage1Step:
             loss_pred_KD = torch.zeros((), device=dev)
         if not self.surv:
             nll = lambda p: ops.NLLFn.apply(p, grade, B)      # noqa: E731
-            loss_nll = nll(pred_path) + nll(pred_omic) + nll(pred)                              # :208-212
+            nll_path, nll_omic, nll_fuse = nll(pred_path), nll(pred_omic), nll(pred)
+            loss_nll = nll_path + nll_omic + nll_fuse                                           # :208-212
             loss = opt.lambda_nll * loss_nll + loss_CRD + loss_pred_KD + loss_masking           # :217-218; MIA-2023 :303-304
         loss_reg = torch.zeros((), device=dev)
         if opt.reg_type != "none":      # :209 - the shipped stage-1 command keeps the default `omic` (options.py:132)
@@ -1623,4 +1650,9 @@ class TeacherStage1Step:
             out.update(loss_cox=surv_terms[6], loss_cox_fuse=surv_terms[0], loss_cox_path=surv_terms[1],
                        loss_cox_omic=surv_terms[2], loss_kd_fuse=surv_terms[3], loss_kd_path=surv_terms[4],
                        loss_kd_omic=surv_terms[5])
+        else:
+            out.update(loss_nll_fuse=nll_fuse.detach(), loss_nll_path=nll_path.detach(), loss_nll_omic=nll_omic.detach())
+        if self.record is not None:
+            # the step's last launch; the nuclear norms are added only on a step that ran the auxiliary update (:392, :409)
+            self.record.add(out, grade, (self.path_TNN, self.omic_TNN) if self.tsvd_on and do_aux else None, survtime, censor)
         return out
